@@ -2,6 +2,8 @@
 """bench.py -- env-steps/s of the VLFM perception + value-map hot path on N MI355X GPUs of one node.
 
     python bench.py --gpus 1 --steps 30 --warmup 5
+    python bench.py --gpus 1 --steps 30 --warmup 5 --full     # + side legs (other sizes / configs, full step) + CPU baseline
+    python bench.py --gpus 1 --steps 30 --warmup 5 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
     python bench.py --gpus 8 --steps 30 --warmup 5            # re-executes itself under torch.distributed.run, 8 ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                 # what the driver does; same code path from there on
@@ -24,8 +26,10 @@ launch durations are HIP events on the dispatch itself, every n-th launch inside
   roofline_cfg5        the same row at BASELINE configs[4]'s per-GPU geometry (16 envs, 1280x720, full-map explored sync)
   roofline_depth_pass  the depth pass alone (4 H W bytes per observation)
   roofline_mfma        the ViT-g fc1 + GELU GEMM (csrc/gemm_f16.hip) against the dense f16 MFMA peak
-  small_batch / full_step   the reference's own geometries (configs[1], [2], [3], [4] per GPU) and the PCIe-inclusive rate
-  cpu_baseline         the oracle (NumPy + C restatement of the maps + the same ITC graph in fp32) on the host cores, bounded sample
+  small_batch / full_step   (--full only) the reference's own geometries (configs[1], [2], [3], [4] per GPU) and the PCIe-inclusive rate
+  cpu_baseline         (--full only) the oracle (NumPy + C restatement of the maps + the same ITC graph in fp32) on the host cores
+A plain run sets up, warms up, times the --steps steps, writes --dump-outputs if given and prints the line; everything after
+the headline (side legs, CPU baseline) runs only with --full.
 DESIGN.md section 5 has the prose; the full record of a run goes to --detail.
 """
 from __future__ import annotations
@@ -59,16 +63,23 @@ def parse_args(argv=None):
                          "their efficient regime at >= 64 (the 8/GPU, 16/GPU-HD and 1/GPU figures are reported alongside)")
     ap.add_argument("--preroll", type=int, default=150,
                     help="map-only steps every episode is advanced by before the warm-up (mid-episode map state)")
-    ap.add_argument("--no-small", action="store_true", help="skip the side measurements (small batches, config 5, PCIe)")
-    ap.add_argument("--no-full", action="store_true", help="skip the configs[2] full-step side runs")
-    ap.add_argument("--only-full", action="store_true", help="side runs: only the configs[2] full-step legs (tuning aid)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the side measurements (small batches, config 5, episode phases, PCIe, the "
+                         "configs[2] full-step legs) and the CPU baseline.  Off by default: a plain run only sets up, warms "
+                         "up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (f32 / f64, < 64 MB; the "
+                         "maps as a fixed seeded sample of cells + environment 0 in full), rank 0's environments")
+    ap.add_argument("--no-small", action="store_true", help="--full: skip the side measurements (small batches, config 5, PCIe)")
+    ap.add_argument("--no-full", action="store_true", help="--full: skip the configs[2] full-step side runs")
+    ap.add_argument("--only-full", action="store_true", help="--full side runs: only the configs[2] full-step legs (tuning aid)")
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--no-blip2", action="store_true", help="map kernels only (NOT the headline metric)")
     ap.add_argument("--no-obstacle", action="store_true")
     ap.add_argument("--sync-explored", action="store_true", help="config 5: value map synchronised with explored area")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-steps", type=int, default=2, help="BLIP-2 fp32 forwards timed on the host")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-steps", type=int, default=2, help="--full: BLIP-2 fp32 forwards timed on the host")
     ap.add_argument("--no-overlap", action="store_true", help="run the obstacle pipeline on the BLIP-2 stream")
     ap.add_argument("--kernel-event-every", type=int, default=5,
                     help="HIP events around every n-th launch of each map kernel in the timed region (roofline.achieved)")
@@ -543,6 +554,55 @@ def thread_cpu_seconds():
     return out
 
 
+DUMP_BUDGET = 64 << 20     # bytes, all files of --dump-outputs together
+DUMP_SAMPLE_CELLS = 1 << 20   # map cells sampled over all environments (fixed seed: the same cells in every run)
+
+
+def dump_outputs(sim, out_dir: str) -> dict:
+    """What a caller of BatchedEpisodes.step() receives after the last timed step, as DIR/<name>.npy (f32 / f64):
+    the per-environment BLIP-2 cosines, the frontiers (world xy, owning environment) and their values, and the maps --
+    confidence (f32), value (f64), obstacle / navigable / explored planes (0/1 as f32) -- as a seeded sample of cells over
+    all environments plus environment 0's confidence and value maps in full.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+
+    torch.cuda.synchronize(sim.device)
+    arrays = {}
+    cos = sim.last_cosines
+    if cos is not None:
+        cos = cos.detach().cpu().numpy() if torch.is_tensor(cos) else np.asarray(cos)
+        arrays["cosines"] = cos.astype(np.float64 if cos.dtype == np.float64 else np.float32)
+    if sim.last_frontier_values is not None:
+        arrays["frontier_values"] = np.asarray(sim.last_frontier_values, np.float64)
+    if sim.obstacles is not None and sim.obstacles.frontiers_ready:
+        xy, env_of = sim.obstacles.frontier_list()
+        arrays["frontiers_xy"] = np.asarray(xy, np.float64).reshape(-1, 2)
+        arrays["frontier_env"] = np.asarray(env_of, np.float64)
+    vm = sim.values
+    E, S = vm.n_envs, vm.size
+    n = min(DUMP_SAMPLE_CELLS, E * S * S)
+    cells = np.sort(np.random.default_rng(20240601).choice(E * S * S, size=n, replace=False))
+    idx = torch.from_numpy(cells).to(sim.device)
+    arrays["sample_cells"] = cells.astype(np.float64)   # flat (env, row, col) indices of the sampled cells
+    arrays["sample_confidence"] = vm.conf.reshape(-1)[idx].cpu().numpy()
+    arrays["sample_value"] = vm.value.reshape(E * S * S, -1)[idx].cpu().numpy()
+    arrays["env0_confidence"] = vm.conf[0].cpu().numpy()
+    arrays["env0_value"] = vm.value[0].cpu().numpy()
+    if sim.obstacles is not None:
+        om = sim.obstacles
+        for name, bits in (("obstacle", om.obstacle_bits), ("navigable", om.navigable_bits), ("explored", om.explored_bits)):
+            plane = om._unpack(bits)
+            arrays[f"sample_{name}"] = plane.reshape(-1)[idx].to(torch.float32).cpu().numpy()
+            del plane
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET, f"--dump-outputs would write {total} bytes (> {DUMP_BUDGET})"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -693,7 +753,9 @@ def main():
                           open(os.path.join(ROOT, "gpurun_out", "host_busy.json"), "w"))
             except OSError:
                 pass
-        if world == 1 and not args.no_small:
+        if args.dump_outputs:
+            dump_outputs(sim, args.dump_outputs)
+        if args.full and world == 1 and not args.no_small:
             side = side_legs(args, sim, device, common)
             # BASELINE configs[2] -- the reference's FULL ITMPolicyV2 step -- is its own top-level record; the legs are listed ONCE
             full = {k: side.pop(k) for k in [k for k in side if k.startswith("configs[2] full step")]}
@@ -704,7 +766,7 @@ def main():
                             "frontier selection / object goal + PointNav for every resident env, one GPU; parity of this object "
                             "against the single-environment ITMPolicyV2 restatement: tests/test_full_step_gpu.py",
                     "unit": "env-steps/s", **full}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, with_blip2=not args.no_blip2)
             except Exception as exc:  # noqa: BLE001 -- reported, never fatal for the headline line

@@ -229,3 +229,142 @@ def replay_two_cameras(make_map):
     conf = dense(g["conf_idx"], g["conf_val"], (1000, 1000), np.float32)
     assert np.array_equal(vm._map, conf)
     assert sha(np.asarray(vm._value_map, np.float64)) == str(g["value_sha"])
+
+
+# ---------------------------------------------------------------------------------------------- recorded reference outputs
+RECORD_ENV = "VLFM_RECORD_REFERENCE"   # =1: the differential tests write tests/golden/ref_<name>.json.gz from the live reference
+_DIGEST_MIN = 4096                     # arrays with at least this many elements are stored as SHA-256 digests
+
+
+def reference_present() -> bool:
+    from oracle.ref_shim import REFERENCE_ROOT
+
+    return os.path.isdir(os.path.join(REFERENCE_ROOT, "vlfm"))
+
+
+class Digest:
+    """A large array of the reference, as (dtype, shape, SHA-256 of its bytes)."""
+
+    def __init__(self, dtype, shape, digest):
+        self.dtype, self.shape, self.digest = np.dtype(dtype), tuple(shape), digest
+
+    def matches(self, a) -> bool:
+        a = np.asarray(a)
+        return a.dtype == self.dtype and a.shape == self.shape and sha(a) == self.digest
+
+
+def _encode(v, digests: bool = True):
+    import torch
+
+    if isinstance(v, torch.Tensor):
+        return {"pt": _encode(v.detach().cpu().numpy(), digests)}
+    if isinstance(v, Digest):
+        return {"sha": v.digest, "dtype": v.dtype.str, "shape": list(v.shape)}
+    if isinstance(v, np.ndarray):
+        if digests and v.size >= _DIGEST_MIN:
+            return {"sha": sha(v), "dtype": v.dtype.str, "shape": list(v.shape)}
+        flat = v.reshape(-1)
+        data = [str(x) for x in flat] if v.dtype.kind in "US" else (flat.astype(np.float64).tolist() if v.dtype.kind == "f"
+                                                                     else flat.tolist())
+        return {"nd": data, "dtype": v.dtype.str, "shape": list(v.shape)}
+    if isinstance(v, np.generic):
+        return {"np": _encode(np.asarray(v), digests)}
+    if isinstance(v, (list, tuple)):
+        return {"seq": [_encode(x, digests) for x in v], "tuple": isinstance(v, tuple)}
+    if isinstance(v, dict):
+        return {"map": [[k, _encode(x, digests)] for k, x in v.items()]}
+    if isinstance(v, float):
+        return {"f": repr(v)}                      # exact: float(repr(x)) == x, inf / nan included
+    if v is None or isinstance(v, (bool, int, str)):
+        return v
+    raise TypeError(f"cannot record {type(v).__name__}")
+
+
+def _decode(o):
+    import torch
+
+    if not isinstance(o, dict):
+        return o
+    if "pt" in o:
+        a = _decode(o["pt"])
+        return a if isinstance(a, Digest) else torch.from_numpy(a)
+    if "sha" in o:
+        return Digest(o["dtype"], o["shape"], o["sha"])
+    if "nd" in o:
+        dt = np.dtype(o["dtype"])
+        return np.asarray(o["nd"], dtype=np.float64 if dt.kind == "f" else None).astype(dt).reshape(o["shape"])
+    if "np" in o:
+        return _decode(o["np"])[()]
+    if "seq" in o:
+        seq = [_decode(x) for x in o["seq"]]
+        return tuple(seq) if o["tuple"] else seq
+    if "map" in o:
+        return {k: _decode(x) for k, x in o["map"]}
+    if "f" in o:
+        return float(o["f"])
+    raise ValueError(o)
+
+
+def same(want, got) -> bool:
+    """Exact equality of a reference output (live, or replayed: arrays, Digests, scalars, nested sequences) and ours."""
+    import torch
+
+    if isinstance(want, Digest):
+        return want.matches(got.detach().cpu().numpy() if isinstance(got, torch.Tensor) else got)
+    if isinstance(want, (list, tuple)) and isinstance(got, (list, tuple)):
+        return len(want) == len(got) and all(same(a, b) for a, b in zip(want, got))
+    if isinstance(want, (np.ndarray, torch.Tensor)) or isinstance(got, (np.ndarray, torch.Tensor)):
+        a = want.detach().cpu().numpy() if isinstance(want, torch.Tensor) else np.asarray(want)
+        b = got.detach().cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
+        return a.shape == b.shape and np.array_equal(a, b)
+    return want == got
+
+
+class ReferenceRecord:
+    """The reference's side of a differential test, live or replayed.  ``rec(fn)`` returns ``fn()`` -- a call into the reference --
+    where the reference tree exists, and the value that call returned when the record was made everywhere else, in call order.
+    Live runs check every value against the committed record (large arrays by SHA-256), so the record cannot drift from the
+    reference; ``VLFM_RECORD_REFERENCE=1`` (re)writes tests/golden/ref_<name>.json.gz instead."""
+
+    def __init__(self, name: str):
+        import gzip
+        import json
+
+        self.path = os.path.join(GOLDEN_DIR, f"ref_{name}.json.gz")
+        self.live = reference_present()
+        self.recording = self.live and os.environ.get(RECORD_ENV) == "1"
+        self.values = []
+        self.k = 0
+        if not self.recording:
+            if not os.path.isfile(self.path):
+                raise FileNotFoundError(f"{self.path}: recorded reference outputs missing (make them with {RECORD_ENV}=1 "
+                                        "where the reference tree exists)")
+            with gzip.open(self.path, "rt") as f:
+                self.values = json.load(f)
+
+    def __call__(self, fn, digest: bool = True):
+        """``digest=False`` stores every element (for values compared within a tolerance)."""
+        if not self.live:
+            assert self.k < len(self.values), f"{self.path}: more reference calls than recorded"
+            v = _decode(self.values[self.k])
+            self.k += 1
+            return v
+        v = fn()
+        if self.recording:
+            self.values.append(_encode(v, digest))
+        else:
+            assert self.k < len(self.values), f"{self.path}: more reference calls than recorded"
+            rec = _decode(self.values[self.k])
+            self.k += 1
+            assert same(rec, v), f"{self.path}: value {self.k - 1} differs from the live reference"
+        return v
+
+    def close(self) -> None:
+        import gzip
+        import json
+
+        if self.recording:
+            with gzip.open(self.path, "wt") as f:
+                json.dump(self.values, f, separators=(",", ":"))
+        else:
+            assert self.k == len(self.values), f"{self.path}: {len(self.values) - self.k} recorded reference calls left over"

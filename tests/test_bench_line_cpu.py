@@ -89,3 +89,11 @@ def test_detail_file_round_trip(tmp_path):
     rec = full_record()
     path = bench.write_detail(rec, str(tmp_path / "sub" / "bench_detail.json"))
     assert path and json.load(open(path))["roofline"]["hbm_kernels"] == rec["roofline"]["hbm_kernels"]
+
+
+def test_plain_run_is_lean_by_default():
+    """The side legs and the CPU baseline run only with --full; --dump-outputs is opt-in; --steps sets the timed steps."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "out", "--no-full"])
+    assert a.full is True and a.dump_outputs == "out" and a.no_full is True
