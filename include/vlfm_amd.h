@@ -537,6 +537,62 @@ int vlfm_obstacle_map_update_batched(const vlfm_fog_params* d_prm, int n, const 
 int vlfm_obstacle_status(const void* d_scratch, int n_envs, int map_size, int cap_pts, int cap_contours,
                          int32_t* h_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Map rendering: ValueMap.visualize (value_map.py:189-219 + img_utils.py:64-85) and ObstacleMap.visualize
+ * (obstacle_map.py:171-192) with the TrajectoryVisualizer overlay (traj_visualizer.py), for n frames at once, into a
+ * caller-given uint8 [n][S][S][3] buffer (BGR like the reference; rgb != 0 swaps B and R).
+ *
+ * d_frames [n][4] int32 per frame: (env slot, 1 = the slot's `_value_map` is f32 (normalise in f32) / 0 = f64,
+ *          explored plane index into d_explored or -1 = no explored mask, 0).
+ * Primitives: d_prim_off [n+1] int32 ranges into d_prims, one frame's primitives in drawing order; d_vtx [..][2] int64
+ *          16.16 vertices of VLFM_PRIM_POLYLINE.  d_prims = NULL: no primitives.
+ * d_path   [n_envs][S][stride] trajectory bit-planes in IMAGE coordinates (after the flip), or NULL.
+ * ------------------------------------------------------------------------------------------- */
+enum { VLFM_REDUCE_MAX = 0,        /* np.max(value, axis=-1) (value_map.py:192) */
+       VLFM_REDUCE_EXPLORE = 1,    /* np.where(v[..., 0] > t, v[..., 0], max) (ITMPolicyV3, itm_policy.py:275-287) */
+       VLFM_REDUCE_PLANE = 2 };    /* d_plane [n][S][S] f64: reduced on the host by any other reduce_fn */
+enum { VLFM_PRIM_CIRCLE_FILL = 0,  /* cv2.circle(thickness < 0): midpoint fill; x0,y0 centre, x1 radius */
+       VLFM_PRIM_CIRCLE = 1,       /* cv2.circle(thickness 0 or 1): midpoint outline */
+       VLFM_PRIM_LINE = 2,         /* cv2.line(x0,y0 -> x1,y1, thickness >= 2): ThickLine with both caps */
+       VLFM_PRIM_POLYLINE = 3 };   /* cv2.circle(thickness > 1): EllipseEx's open PolyLine over n_vtx 16.16 vertices */
+#define VLFM_RENDER_FLIP_ROWS 1    /* drawn before the frame's vertical flip (ObstacleMap's frontier circles) */
+#define VLFM_RENDER_UNDER_PATH 2   /* drawn before the trajectory: pixels of the path plane keep the path colour */
+typedef struct {
+    int32_t frame;                 /* informational: the frame whose range holds this primitive */
+    int32_t kind;                  /* VLFM_PRIM_* */
+    int32_t flags;                 /* VLFM_RENDER_* */
+    int32_t thickness;
+    int32_t x0, y0, x1, y1;        /* image coordinates (x = column, y = row) */
+    int32_t vtx_off, n_vtx;        /* VLFM_PRIM_POLYLINE vertices in d_vtx */
+    uint8_t bgr[4];
+    int32_t reserved;
+} vlfm_render_prim;                /* 48 bytes */
+
+size_t vlfm_value_render_scratch_bytes(int n, int map_size);
+
+/* d_value [n_envs][S][S][channels] f64 (ValueMapBatch.value); d_explored [*][S][stride] or NULL. */
+int vlfm_value_map_render(const double* d_value, int n_envs, int map_size, int channels, const int32_t* d_frames, int n,
+                          int reduce_mode, double explore_thresh, const double* d_plane, const uint32_t* d_explored,
+                          const uint32_t* d_path, const int32_t* d_prim_off, const vlfm_render_prim* d_prims,
+                          const int64_t* d_vtx, int rgb, void* d_scratch, size_t scratch_bytes, uint8_t* d_out,
+                          void* stream);
+
+/* d_obstacle / d_navigable / d_explored [n_envs][S][stride]; pad_bgr = radius_padding_color packed b | g << 8 | r << 16. */
+int vlfm_obstacle_map_render(const uint32_t* d_obstacle, const uint32_t* d_navigable, const uint32_t* d_explored,
+                             int n_envs, int map_size, const int32_t* d_frames, int n, uint32_t pad_bgr,
+                             const uint32_t* d_path, const int32_t* d_prim_off, const vlfm_render_prim* d_prims,
+                             const int64_t* d_vtx, int rgb, uint8_t* d_out, void* stream);
+
+/* ORs m trajectory segments d_segs [m][5] int32 (env slot, x0, y0, x1, y1) into d_path [n_envs][S][stride] as
+ * cv2.line(mask, p0, p1, 255, thickness) draws them (traj_visualizer.py:60-80); thickness >= 2. */
+int vlfm_traj_append(uint32_t* d_path, int n_envs, int map_size, const int32_t* d_segs, int m, int thickness,
+                     void* stream);
+
+/* Host: the 16.16 vertices EllipseEx hands to PolyLine for cv2.circle(centre, radius, thickness > 1) -- ellipse2Poly
+ * over 0..360 from OpenCV's float sine table, snapped, duplicates dropped (the sector code of vlfm_fog_params_host).
+ * h_circles [n][3] (cx, cy, radius); vertices of circle i are h_xy[2*h_off[i] ..] with h_off [n+1]. */
+int vlfm_circle_polygon_host(const int32_t* h_circles, int n, int64_t* h_xy, int32_t* h_off, int capacity);
+
 #ifdef __cplusplus
 }
 #endif

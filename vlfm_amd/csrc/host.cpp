@@ -17,7 +17,7 @@ void set_last_error(const char* msg) { g_last_error = msg ? msg : ""; }
 }  // namespace vlfm
 
 extern "C" const char* vlfm_last_error(void) { return vlfm::g_last_error.c_str(); }
-extern "C" int vlfm_abi_version(void) { return 8; }
+extern "C" int vlfm_abi_version(void) { return 9; }
 
 namespace {
 
@@ -142,6 +142,32 @@ extern "C" int vlfm_fog_params_host(const int32_t* h_agent_px, const double* h_a
         p.n_poly = m;
     }
     return VLFM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ cv2.circle outline
+extern "C" int vlfm_circle_polygon_host(const int32_t* h_circles, int n, int64_t* h_xy, int32_t* h_off, int capacity) {
+    if (!h_circles || !h_xy || !h_off || n < 0 || capacity < 0)
+        return vlfm::fail(VLFM_ERR_INVALID, "circle_polygon_host: bad argument");
+    int total = 0;
+    h_off[0] = 0;
+    for (int k = 0; k < n; k++) {
+        const int cx = h_circles[3 * k], cy = h_circles[3 * k + 1], r = h_circles[3 * k + 2];
+        if (r < 0) return vlfm::fail(VLFM_ERR_INVALID, "circle_polygon_host: negative radius");
+        const int m = ellipse_sector_polygon(cx, cy, r, 0.0, 360.0, h_xy + 2 * (size_t)total, capacity - total);
+        if (m < 0) return vlfm::fail(m, "circle_polygon_host: vertex capacity");
+        if (m == 1) {   // EllipseEx: a single vertex becomes a zero-length polyline at the centre
+            if (total + 2 > capacity) return vlfm::fail(VLFM_ERR_CAPACITY, "circle_polygon_host: vertex capacity");
+            for (int i = 0; i < 2; i++) {
+                h_xy[2 * (size_t)(total + i)] = (int64_t)cx << 16;
+                h_xy[2 * (size_t)(total + i) + 1] = (int64_t)cy << 16;
+            }
+            total += 2;
+        } else {
+            total += m;
+        }
+        h_off[k + 1] = total;
+    }
+    return total;
 }
 
 // ------------------------------------------------------------------------------------------------ confidence template

@@ -23,7 +23,7 @@ vlfm_amd/distributed.py); the only collective is the metric all-reduce in bench.
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -195,12 +195,15 @@ class BatchedEpisodes:
                  pointnav=None, world: str = "rooms", object_maps: bool = False,
                  sightings: Optional["ScriptedSightings"] = None, scripted_masks: bool = False,
                  coco_threshold: float = 0.8, non_coco_threshold: float = 0.4, pointnav_stop_radius: float = 0.9,
-                 object_map_erosion_size: float = 5, concurrent_vlm_max_envs: int = 0) -> None:
+                 object_map_erosion_size: float = 5, concurrent_vlm_max_envs: int = 0,
+                 render_trajectories: bool = False) -> None:
         self.device = require_gpu(device)
         # a rank waiting for its GPU must not hold a host core (bench.py `host`).  Effective only before the device's first
         # stream exists (bench.py sets it first thing); here it is best effort: a warning on failure, VLFM_HOST_WAIT=spin opts out
         _lib.try_host_wait_blocking(self.device)
         self.E, self.H, self.W, self.S = n_envs, height, width, map_size
+        # opt-in: record every step's pose in the maps' trajectory planes for render() (one small launch per map and step)
+        self.render_trajectories = render_trajectories
         self.fx, self.fy, self.fov = camera_intrinsics(width)
         self.episode_len = episode_len
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -623,6 +626,20 @@ class BatchedEpisodes:
         finally:
             self.blip2, self.detector, self.sam, self.selectors, self.pointnav, self.object_maps = saved
 
+    def render(self, env_ids: Optional[Sequence[int]] = None, rgb: bool = True) -> Dict[str, "torch.Tensor"]:
+        """The value and obstacle map frames of the chosen environments (all by default) as ValueMap.visualize /
+        ObstacleMap.visualize draw them: device uint8 [n, S, S, 3] tensors, RGB by default (BGR with ``rgb=False``).  The
+        agent's path and marker are drawn when the harness was built with ``render_trajectories=True``; the obstacle
+        frames carry the current frontier circles.  Not part of the timed step."""
+        env = list(range(self.E)) if env_ids is None else [int(e) for e in env_ids]
+        main = torch.cuda.current_stream(self.device)
+        if self.map_stream is not None:
+            main.wait_stream(self.map_stream)   # obstacle planes and trajectories are written on the map stream
+        out = {"value_map": self.values.render(env, rgb=rgb)}
+        if self.obstacles is not None:
+            out["obstacle_map"] = self.obstacles.render(env, rgb=rgb)
+        return out
+
     def frontier_stats(self):
         """(mean, max) number of frontiers per environment at the last step (what the obstacle pipeline is working on)."""
         if self.obstacles is None or not self.obstacles.frontiers_ready:
@@ -684,8 +701,12 @@ class BatchedEpisodes:
         main = torch.cuda.current_stream(self.device)
         side = self.map_stream if self.map_stream is not None else main
         # ---- mapping, part 1 (side stream): one depth pass feeds both maps, then the obstacle/frontier pipeline
+        if self.render_trajectories:   # BaseMap.update_agent_traj of both maps (base_objectnav_policy / itm_policy)
+            self.values.update_agent_traj(range(self.E), poses[:, :2], poses[:, 2])
         side.wait_stream(main)  # the previous step's value update consumed the column-max keys
         with torch.cuda.stream(side):
+            if self.render_trajectories and self.obstacles is not None:
+                self.obstacles.update_agent_traj(range(self.E), poses[:, :2], poses[:, 2])
             if self.obstacles is not None:
                 colmax = self.obstacles.ingest(depth, tf, MIN_DEPTH, MAX_DEPTH, self.fx, self.fy, want_colmax=True)
                 self.obstacles.update_after_ingest(tf, MAX_DEPTH, self.fov)

@@ -40,6 +40,21 @@ class BaseMap:
         self._last_camera_yaw = robot_heading
         self._camera_positions.append(robot_xy)
 
+    def _push_trajectory(self, batch, slot: int) -> None:
+        """Hands the positions of ``_camera_positions`` not yet drawn to the batch's device path plane (the reference's
+        TrajectoryVisualizer draws them on the next visualize(); traj_visualizer.py:49-50).  A shortened list, or a slot
+        reset underneath, starts the slot's trajectory over."""
+        n = len(self._camera_positions)
+        pushed = getattr(self, "_traj_pushed", 0)
+        if n < pushed or int(batch.traj.count[slot]) != pushed:
+            batch.traj.reset([slot])
+            pushed = 0
+        new = self._camera_positions[pushed:]
+        if new:
+            batch.update_agent_traj([slot] * len(new), new, [self._last_camera_yaw] * len(new))
+        batch.traj.yaw[slot] = self._last_camera_yaw
+        self._traj_pushed = n
+
     def _xy_to_px(self, points: np.ndarray) -> np.ndarray:
         """Metres (x forward, y left) -> integer (col, row) cells: the axes swap, ``rint`` rounds half to even, and the
         first coordinate is mirrored about the map size (base_map.py:44-46)."""

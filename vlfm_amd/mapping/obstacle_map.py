@@ -17,6 +17,7 @@ from typing import Any, List, Optional, Sequence, Union
 import numpy as np
 
 from .. import _lib
+from . import render as _render
 from .base_map import BaseMap, require_gpu
 from .value_map import INGEST_DTYPE, UploadRing, _stream_ptr, wait_stream
 
@@ -79,6 +80,8 @@ class ObstacleMapBatch:
         self._h_fr = torch.zeros((n_envs, self.READ_FRONTIERS, 2), dtype=torch.float64).pin_memory()
         self._h_counts = torch.zeros((n_envs, 4), dtype=torch.int32).pin_memory()
         self._h_status = torch.zeros((n_envs, 2), dtype=torch.int32).pin_memory()
+        self.traj = _render.TrajectoryPlanes(self.device, n_envs, size, pixels_per_meter)
+        self._render_ring = _render.PackedRing(self.device)
 
     # ------------------------------------------------------------------------------------------ state
     def reset(self, env_ids: Optional[Sequence[int]] = None) -> None:
@@ -94,6 +97,7 @@ class ObstacleMapBatch:
         self._dirty_obst[idx] = (0, self.size - 1, 0, self.size - 1)   # zeroed planes: everything is to be recomputed
         self._dirty_nav[idx] = (0, self.size - 1, 0, self.size - 1)
         self._bbox_host[idx] = (0, -1, 0, -1)
+        self.traj.reset(idx)
 
     @staticmethod
     def _union(into: np.ndarray, idx: np.ndarray, win: np.ndarray) -> None:
@@ -391,6 +395,49 @@ class ObstacleMapBatch:
                 raise RuntimeError("fill_small_holes scratch capacity exceeded (HOLE_CAP_PTS/HOLE_CAP_CONTOURS or the "
                                    "scatter journal)")
 
+    # ------------------------------------------------------------------------------------------ rendering
+    def update_agent_traj(self, env_ids: Sequence[int], xy, yaw) -> None:
+        """BaseMap.update_agent_traj for n slots (see ValueMapBatch.update_agent_traj)."""
+        self.traj.append(env_ids, xy, yaw)
+
+    def render(self, env_ids: Sequence[int], frontiers_px: Optional[Sequence[np.ndarray]] = None, out=None,
+               rgb: bool = False, padding_color=(100, 100, 100)):
+        """ObstacleMap.visualize (obstacle_map.py:171-192) for the slots ``env_ids`` -> uint8 [n,S,S,3] device tensor, BGR
+        (RGB with ``rgb``).  ``frontiers_px``: per requested slot the (F,2) pixel frontiers whose circles are drawn
+        (default: the slots' current frontiers, one read-back)."""
+        import torch
+
+        env = [int(e) for e in env_ids]
+        n, S = len(env), self.size
+        if any(not 0 <= e < self.n_envs for e in env):
+            raise IndexError("environment slot out of range")
+        out = _render.output(self.device, n, S, out)
+        if n == 0:
+            return out
+        if frontiers_px is None:
+            every = self.frontiers_px()
+            frontiers_px = [every[e] for e in env]
+        prims = []
+        for k, e in enumerate(env):
+            fr = np.asarray(frontiers_px[k], np.float64).reshape(-1, 2)
+            # obstacle_map.py:182-183: drawn before the flip, and before the trajectory
+            p = [_render.circle_prim(int(f[0]), int(f[1]), 5, 2, (200, 0, 0), _render.FLIP_ROWS | _render.UNDER_PATH)
+                 for f in fr]
+            prims.append(p + self.traj.agent_prims(e))
+        frames = np.array([[e, 0, e, 0] for e in env], np.int32)
+        buf, o_prims, o_vtx, any_prims = _render.pack(frames, prims)
+        pad = int(padding_color[0]) | int(padding_color[1]) << 8 | int(padding_color[2]) << 16
+        path = self.traj.plane
+        with torch.cuda.device(self.device):
+            d = self._render_ring.upload(buf)
+            base = d.data_ptr()
+            _lib.check(_lib.lib().vlfm_obstacle_map_render(
+                self.obstacle_bits.data_ptr(), self.navigable_bits.data_ptr(), self.explored_bits.data_ptr(),
+                self.n_envs, S, base, n, pad, path.data_ptr() if path is not None else None, base + 16 * n,
+                base + o_prims if any_prims else None, base + o_vtx, int(bool(rgb)), out.data_ptr(), _stream_ptr()),
+                "obstacle_map_render")
+        return out
+
 
 class ObstacleMap(BaseMap):
     """Drop-in for vlfm.mapping.obstacle_map.ObstacleMap."""
@@ -457,8 +504,12 @@ class ObstacleMap(BaseMap):
             self.frontiers = self._px_to_xy(self._frontiers_px)
 
     def visualize(self) -> np.ndarray:
-        vis = np.ones((self.size, self.size, 3), dtype=np.uint8) * 255
-        vis[self.explored_area == 1] = (200, 255, 200)
-        vis[self._navigable_map == 0] = self.radius_padding_color
-        vis[self._map == 1] = (0, 0, 0)
-        return vis[::-1].copy()
+        """The reference's image (obstacle_map.py:171-192), rendered on the device."""
+        return self.render_image()
+
+    def render_image(self, rgb: bool = False, host: bool = True):
+        """visualize() with the kernel's RGB switch (``rgb``) and, with ``host=False``, the device [S,S,3] tensor."""
+        self._push_trajectory(self._batch, 0)
+        fr = np.asarray(self._frontiers_px, np.float64).reshape(-1, 2)
+        img = self._batch.render([0], [fr], padding_color=self.radius_padding_color, rgb=rgb)[0]
+        return img.cpu().numpy() if host else img

@@ -20,6 +20,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from .. import _lib
+from . import render as _render
 from .base_map import BaseMap, require_gpu
 
 
@@ -245,6 +246,10 @@ class ValueMapBatch:
         self._written_stale = False  # an update ran without the explored plane since `_written` was last complete
         self._counters = None
         self._wp_out = self._wp_host = self._wp_cells = None
+        self.traj = _render.TrajectoryPlanes(self.device, n_envs, size, pixels_per_meter)
+        self._render_ring = _render.PackedRing(self.device)
+        self._render_scratch = None
+        self._render_plane_ring = None
 
     @property
     def value_is_f32(self) -> bool:
@@ -271,6 +276,7 @@ class ValueMapBatch:
             self.value[idx] = 0
             if self._written is not None:
                 self._written[idx] = 0
+        self.traj.reset(env_ids)
 
     def _rings(self, n: int):
         if self._ring is None or self._ring.nbytes < max(n, self.n_envs) * 256:
@@ -413,6 +419,83 @@ class ValueMapBatch:
             wait_stream()
         return self._wp_host[:m].numpy().copy()
 
+    # ------------------------------------------------------------------------------------------ rendering
+    def update_agent_traj(self, env_ids: Sequence[int], xy, yaw) -> None:
+        """BaseMap.update_agent_traj for n slots: xy [n,2] metres, yaw [n]; a slot may repeat (positions in order).  Only
+        the new path segments are rasterised (csrc/map_render.hip: traj_append_kernel)."""
+        self.traj.append(env_ids, xy, yaw)
+
+    def render(self, env_ids: Sequence[int], reduce: Any = "max", markers=None, explored: Any = "auto", out=None,
+               rgb: bool = False):
+        """ValueMap.visualize (value_map.py:189-219) for the slots ``env_ids`` -> uint8 [n,S,S,3] device tensor, BGR (RGB
+        with ``rgb``).
+
+        reduce: "max" (the default reduce_fn), ("explore", t) (ITMPolicyV3's visual reducer), or a reduced plane [n,S,S]
+            (host array or device tensor, f32 or f64: the dtype the normalisation runs in) for any other reduce_fn.
+        markers: rows (env slot, x, y, radius, thickness, b, g, r) drawn with cv2.circle after the trajectory, in order;
+            like the reference, a slot without trajectory positions draws none.
+        explored: "auto" = the synchronised obstacle map's plane (``explored_bits``) if any; None = no mask; or a
+            bit-packed plane tensor [n_envs or 1, S, ceil(S/32)] (cells outside it become 0, value_map.py:198-199)."""
+        import torch
+
+        env = [int(e) for e in env_ids]
+        n, S = len(env), self.size
+        if any(not 0 <= e < self.n_envs for e in env):
+            raise IndexError("environment slot out of range")
+        out = _render.output(self.device, n, S, out)
+        if n == 0:
+            return out
+        plane_ptr, thresh, mode = None, 0.0, _render.REDUCE_MAX
+        f32 = [int(self.value_dtype(e) == np.float32) for e in env]
+        keep = []
+        if isinstance(reduce, str) and reduce == "max":
+            pass
+        elif isinstance(reduce, tuple) and len(reduce) == 2 and reduce[0] == "explore":
+            mode, thresh = _render.REDUCE_EXPLORE, float(reduce[1])
+        else:
+            mode = _render.REDUCE_PLANE
+            is_t = torch.is_tensor(reduce)
+            dt = reduce.dtype if is_t else np.asarray(reduce).dtype
+            if dt not in (np.float32, np.float64, torch.float32, torch.float64):
+                raise TypeError(f"a reduced plane must be float32 or float64 (got {dt}): the normalisation runs in its dtype")
+            f32 = [int(dt in (np.float32, torch.float32))] * n
+            plane = (reduce.to(device=self.device, dtype=torch.float64) if is_t else
+                     torch.from_numpy(np.ascontiguousarray(np.asarray(reduce), np.float64)).to(self.device))
+            if tuple(plane.shape) != (n, S, S) and tuple(plane.shape) != (S, S) or (n != 1 and plane.dim() == 2):
+                raise ValueError(f"a reduced plane must be [{n}, {S}, {S}] (got {tuple(plane.shape)})")
+            plane = plane.reshape(n, S, S).contiguous()
+            keep.append(plane)
+            plane_ptr = plane.data_ptr()
+        if isinstance(explored, str) and explored == "auto":
+            explored = self.explored_bits
+        ex_ptr, ex_idx = None, [-1] * n
+        if explored is not None:
+            _render.check_planes(explored, self.device, self.n_envs, S, "explored")
+            ex_ptr = explored.data_ptr()
+            ex_idx = [0] * n if explored.shape[0] == 1 else env
+        frames = np.array([[e, f, x, 0] for e, f, x in zip(env, f32, ex_idx)], np.int32)
+        by_slot = _render.marker_prims(markers)
+        prims = []
+        for e in env:
+            p = self.traj.agent_prims(e)
+            if self.traj.count[e] > 0:   # value_map.py:206-217: markers only with a trajectory
+                p += by_slot.get(e, [])
+            prims.append(p)
+        buf, o_prims, o_vtx, any_prims = _render.pack(frames, prims)
+        need = _lib.lib().vlfm_value_render_scratch_bytes(n, S)
+        if self._render_scratch is None or self._render_scratch.numel() < need:
+            self._render_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        path = self.traj.plane
+        with torch.cuda.device(self.device):
+            d = self._render_ring.upload(buf)
+            base = d.data_ptr()
+            _lib.check(_lib.lib().vlfm_value_map_render(
+                self.value.data_ptr(), self.n_envs, S, self.channels, base, n, mode, thresh, plane_ptr, ex_ptr,
+                path.data_ptr() if path is not None else None, base + 16 * n, base + o_prims if any_prims else None,
+                base + o_vtx, int(bool(rgb)), self._render_scratch.data_ptr(), self._render_scratch.numel(),
+                out.data_ptr(), _stream_ptr()), "value_map_render")
+        return out
+
 
 def _explored_bits_of(obstacle_map, device):
     """Bit-packed explored area [1,S,ceil(S/32)] of an attached obstacle map: ours hands over its HBM plane; any other
@@ -436,6 +519,20 @@ PLAYING = os.environ.get("PLAY_VALUE_MAP", "0") == "1"
 RECORDING_DIR = "value_map_recordings"
 JSON_PATH = os.path.join(RECORDING_DIR, "data.json")
 KWARGS_JSON = os.path.join(RECORDING_DIR, "kwargs.json")
+
+
+def _default_reduce_fn(i):
+    return np.max(i, axis=-1)
+
+
+def explore_reduce_fn(thresh: float) -> Callable:
+    """ITMPolicyV3's visual reducer (itm_policy.py:275-287) as a host callable that ValueMap.visualize runs on the device."""
+    def visualize_value_map(arr: np.ndarray) -> np.ndarray:
+        first_channel = arr[:, :, 0]
+        return np.where(first_channel > thresh, first_channel, np.max(arr, axis=2))
+
+    visualize_value_map.device_reduce = ("explore", float(thresh))
+    return visualize_value_map
 
 
 class ValueMap(BaseMap):
@@ -537,18 +634,34 @@ class ValueMap(BaseMap):
         order = np.argsort([-v for v in values])  # the reference's own ordering call (value_map.py:183)
         return np.array([waypoints[i] for i in order]), [values[i] for i in order]
 
-    def visualize(self, markers=None, reduce_fn: Callable = lambda i: np.max(i, axis=-1), obstacle_map=None):
-        """Plain grey-scale rendering (the reference's OpenCV inferno/trajectory drawing is out of scope)."""
-        reduced = reduce_fn(self._value_map).copy()
-        if obstacle_map is not None:
-            reduced[obstacle_map.explored_area == 0] = 0
-        img = np.flipud(reduced)
-        zero = img == 0
-        top = float(img.max()) if img.size else 0.0
-        scaled = np.zeros(img.shape, np.uint8) if top <= 0 else (img / top * 255).astype(np.uint8)
-        rgb = np.stack([scaled] * 3, axis=-1)
-        rgb[zero] = (255, 255, 255)
-        return rgb
+    def visualize(self, markers: Optional[List[Tuple[np.ndarray, Dict[str, Any]]]] = None,
+                  reduce_fn: Callable = _default_reduce_fn, obstacle_map=None) -> np.ndarray:
+        """The reference's image (value_map.py:189-219), rendered on the device: the default reduce_fn (and a reducer
+        made by ``explore_reduce_fn``) runs there, any other callable is applied to ``_value_map`` on the host and its
+        plane uploaded."""
+        return self.render_image(markers, reduce_fn, obstacle_map)
+
+    def render_image(self, markers=None, reduce_fn: Callable = _default_reduce_fn, obstacle_map=None, rgb: bool = False,
+                     host: bool = True):
+        """visualize() with the kernel's RGB switch (``rgb``) and, with ``host=False``, the device [S,S,3] tensor."""
+        self._push_trajectory(self._batch, self._slot)
+        reduce: Any = "max"
+        if getattr(reduce_fn, "device_reduce", None) is not None:
+            reduce = reduce_fn.device_reduce
+        elif reduce_fn is not _default_reduce_fn:
+            reduce = np.asarray(reduce_fn(self._value_map)).copy()
+        explored = None if obstacle_map is None else _explored_bits_of(obstacle_map, self._batch.device)
+        rows = []
+        for pos, kw in markers or []:
+            extra = set(kw) - {"radius", "color", "thickness"}
+            if extra:
+                raise TypeError(f"marker keywords {sorted(extra)} are not supported by the device renderer")
+            px = _render.metric_to_pixel(pos, self.pixels_per_meter, self._episode_pixel_origin)
+            rows.append([self._slot, int(px[1]), int(px[0]), int(kw["radius"]), int(kw.get("thickness", 1)),
+                         *[int(c) for c in kw["color"]]])
+        img = self._batch.render([self._slot], reduce=reduce, markers=np.array(rows, np.int64).reshape(-1, 8),
+                                 explored=explored, rgb=rgb)[0]
+        return img.cpu().numpy() if host else img
 
 
 def replay_from_dir(recording_dir: str = RECORDING_DIR, device=None) -> ValueMap:

@@ -24,7 +24,7 @@ this class on the GPU maps and require identical modes, goals, stops, model-call
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Any, Callable, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -213,6 +213,7 @@ class ITMPolicyV2Step:
         if getattr(self, "_pointnav", None) is not None:
             self._pointnav.reset()
         self._last_goal = np.zeros(2)
+        self._last_frontiers = np.zeros((0, 2))
         self._num_steps = 0
         self._done_initializing = False
         self._called_stop = False
@@ -339,6 +340,7 @@ class ITMPolicyV2Step:
         base_objectnav_policy.py:107-150): value map, object map per camera, then initialise / explore / navigate."""
         nan = float("nan")
         frontiers = self._obstacle_map.frontiers
+        self._last_frontiers = frontiers   # what _get_policy_info draws (itm_policy.py:162)
         self._obstacle_map.update_agent_traj(robot_xy, yaw)
         self._update_value_map(value_cameras, robot_xy, yaw)
         dets = [self._update_object_map(*cam) for cam in object_cameras]
@@ -399,6 +401,45 @@ class ITMPolicyV2Step:
     def maps(self):
         return self._obstacle_map, self._value_map, self._object_map
 
+    # colours and sizes of BaseITMPolicy (itm_policy.py:27-31)
+    _target_object_color: Tuple[int, int, int] = (0, 255, 0)
+    _selected__frontier_color: Tuple[int, int, int] = (0, 255, 255)
+    _frontier_color: Tuple[int, int, int] = (0, 0, 255)
+    _circle_marker_thickness: int = 2
+    _circle_marker_radius: int = 5
+
+    @staticmethod
+    def _vis_reduce_fn(i: np.ndarray) -> np.ndarray:
+        return np.max(i, axis=-1)
+
+    def policy_maps(self) -> Dict[str, np.ndarray]:
+        """The "obstacle_map" / "value_map" RGB images of the last step as _get_policy_info builds them
+        (base_objectnav_policy.py:212-213, itm_policy.py:154-189): frontier markers, the last goal marked as selected
+        frontier or as target object, the policy's visual reducer; rendered on the device with the kernels' RGB switch."""
+        from .mapping.value_map import _default_reduce_fn
+
+        frontiers = self._last_frontiers
+        markers = [(f[:2], {"radius": self._circle_marker_radius, "thickness": self._circle_marker_thickness,
+                            "color": self._frontier_color}) for f in frontiers]
+        if not np.array_equal(self._last_goal, np.zeros(2)):
+            color = (self._selected__frontier_color if any(np.array_equal(self._last_goal, f) for f in frontiers)
+                     else self._target_object_color)
+            markers.append((self._last_goal, {"radius": self._circle_marker_radius,
+                                              "thickness": self._circle_marker_thickness, "color": color}))
+        reduce_fn = self._vis_reduce_fn
+        if reduce_fn is ITMPolicyV2Step._vis_reduce_fn:
+            reduce_fn = _default_reduce_fn
+        out = {}
+        if hasattr(self._obstacle_map, "render_image"):
+            out["obstacle_map"] = self._obstacle_map.render_image(rgb=True)
+        else:
+            out["obstacle_map"] = np.ascontiguousarray(self._obstacle_map.visualize()[..., ::-1])
+        if hasattr(self._value_map, "render_image"):
+            out["value_map"] = self._value_map.render_image(markers, reduce_fn=reduce_fn, rgb=True)
+        else:
+            out["value_map"] = np.ascontiguousarray(self._value_map.visualize(markers, reduce_fn=reduce_fn)[..., ::-1])
+        return out
+
 
 class ITMPolicyV3Step(ITMPolicyV2Step):
     """ITMPolicyV3 (itm_policy.py:270-318): two prompts ("target | exploration") -> a two-channel value map; a frontier is
@@ -408,6 +449,9 @@ class ITMPolicyV3Step(ITMPolicyV2Step):
     def __init__(self, exploration_thresh: float, *args: Any, **kwargs: Any) -> None:
         super().__init__(*args, **kwargs)
         self._exploration_thresh = exploration_thresh
+        from .mapping.value_map import explore_reduce_fn
+
+        self._vis_reduce_fn = explore_reduce_fn(exploration_thresh)   # itm_policy.py:275-287, on the device
 
     def _reduce_values(self, values: Sequence[Tuple[float, float]]) -> List[float]:
         use = 1 if max(v[0] for v in values) < self._exploration_thresh else 0
