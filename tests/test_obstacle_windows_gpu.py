@@ -1,5 +1,5 @@
 """-m gpu: the dirty-window forms of navigable_kernel / frontier_prepare_kernel (round 3) against the full-plane forms they
-replace (VLFM_FULL_PLANES=1 = NULL windows = the reference's full-map passes, obstacle_map.py:105-109,127,159-163): same
+replace (`full_planes = True` = NULL windows = the reference's full-map passes, obstacle_map.py:105-109,127,159-163): same
 obstacle / navigable / explored planes and the same frontiers at every step, through resets, explore=False calls, reveal-only
 calls and a camera whose reach window leaves the map.  (The golden fixtures and the oracle tests run on the windowed form and
 pin it against the reference; this file pins it against the other form on call patterns those do not contain.)"""

@@ -15,10 +15,6 @@
 
 namespace vlfm {
 
-#ifdef VLFM_PHASE_TIMING
-__device__ long long g_walk_ticks, g_walk_points, g_walk_calls;  // diagnostics: time inside follow_border (all scans)
-#endif
-
 struct Bits {            // read view
     const unsigned* w;
     int stride;          // words per row
@@ -280,13 +276,7 @@ __device__ inline void scan_external(const Bits& img, unsigned* traced, unsigned
             int n = 0;
             if (lane == 0) {
                 const int room = sink.cap_pts - sink.n_pts;
-#ifdef VLFM_PHASE_TIMING
-                const long long t0_ = wall_clock64();
-#endif
                 n = follow_border(img, traced, neg, x, y, method, sink.pts + sink.n_pts, room > 0 ? room : 0);
-#ifdef VLFM_PHASE_TIMING
-                g_walk_ticks += wall_clock64() - t0_; g_walk_points += n; g_walk_calls += 1;
-#endif
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             n = __shfl(n, 0, 64);

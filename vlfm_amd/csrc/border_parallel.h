@@ -1,8 +1,9 @@
 // border_parallel.h -- Suzuki-Abe border following by a whole workgroup (gfx950), for the padded LDS windows of bitmap.h.
 //
 // follow_border() is one lane executing a dependent chain: ~600 cycles per border pixel, i.e. 0.7 ms for the 2 300-pixel outline
-// of a mid-episode explored area, in explored_select_kernel and again in frontier_kernel (tools/phase_probe.py) -- while 1023 of
-// the 1024 lanes wait.  The walk is a deterministic map on STATES (pixel p, direction s_back to the pixel it was entered from):
+// of a mid-episode explored area, in explored_select_kernel and again in frontier_kernel (phase-timing build, removed; last in
+// 26e85ce) -- while 1023 of the 1024 lanes wait.  The walk is a deterministic map on STATES (pixel p, direction s_back to the
+// pixel it was entered from):
 //     f(p, s_back) = (p', s_back'),  p' = first set neighbour of p counter-clockwise after s_back,  s_back' = direction p' -> p.
 // f is injective (the predecessor of (p', s_back') is recovered by the clockwise search from p), so every valid state lies on a
 // cycle, and the border OpenCV traces from a start pixel i0 is exactly the cycle through state0 = (i0, direction to i1): the loop
@@ -20,17 +21,6 @@
 #include "bitmap.h"
 
 namespace vlfm {
-
-#ifdef VLFM_PHASE_TIMING
-__device__ long long g_walk_clk[16];   // one workgroup's stamps inside the parallel follower (the last call wins)
-__device__ int g_walk_block;
-#define WALK_STAMP(k)                                                                              \
-    do {                                                                                           \
-        if ((int)blockIdx.x == g_walk_block && threadIdx.x == 0) g_walk_clk[k] = wall_clock64();     \
-    } while (0)
-#else
-#define WALK_STAMP(k) do {} while (0)
-#endif
 
 // Barrier that also orders GLOBAL-memory traffic between the wavefronts of this workgroup.  They share one CU and its L1, so
 // workgroup scope is enough; __threadfence() is a device-scope release (L2 write-back on gfx950) and cost ~8 us per
@@ -108,7 +98,6 @@ __device__ inline void wg_build_walk_tables(const Bits& img, unsigned* lt, unsig
         auto h = [](const unsigned* q) { const unsigned c = q[0]; return c & ((c << 1) | (q[-1] >> 31)) & ((c >> 1) | (q[1] << 31)); };
         return r[0] & ~(h(r - pw) & h(r) & h(r + pw));
     };
-    WALK_STAMP(0);
     // a. border mask and (border pixels | states << 8) of every word; words are dealt round-robin so that a ragged row is
     //    everybody's problem (with contiguous chunks the thread that owned it took 30 us)
     int* wcount = T.wprefix;                            // packed counts now, ranks after the scan
@@ -133,7 +122,6 @@ __device__ inline void wg_build_walk_tables(const Bits& img, unsigned* lt, unsig
     for (int k = k0; k < k1; k++) { const int v = wcount[k]; nb += v & 255; ns += v >> 8; }
     int nb_ex, ns_ex, nb_tot, ns_tot;
     wg_scan2(nb, ns, sh, nb_ex, ns_ex, nb_tot, ns_tot);
-    WALK_STAMP(1);
     T.n_states = ns_tot;
     T.ok = nb_tot <= T.cap_bp && nb_tot <= T.cap_states && ns_tot <= T.cap_states && ns_tot > 0 && W <= T.cap_states;
     if (!T.ok) {
@@ -167,7 +155,6 @@ __device__ inline void wg_build_walk_tables(const Bits& img, unsigned* lt, unsig
         }
     }
     wg_sync_global();
-    WALK_STAMP(2);
     // d. successors: one border pixel per thread and step; the mask and rank of the successor's word come from LDS, only its
     //    first-state index is a global read
     for (int r = tid; r < nb_tot; r += nth) {
@@ -203,10 +190,6 @@ __device__ inline void wg_build_walk_tables(const Bits& img, unsigned* lt, unsig
         ln[ly * pw + lw] = 0u;
     }
     __syncthreads();
-    WALK_STAMP(3);
-#ifdef VLFM_PHASE_TIMING
-    if ((int)blockIdx.x == g_walk_block && threadIdx.x == 0) { g_walk_clk[12] = T.ok; g_walk_clk[13] = T.n_states; g_walk_clk[14] = nb_tot; }
-#endif
 }
 
 // follow_border_padded with a step budget: -1 when the border did not close within max_steps (labels written so far are a
@@ -284,13 +267,11 @@ __device__ inline int wg_follow_border(const Bits& img, const WalkTables& T, uns
     if (n_short >= 0) { __syncthreads(); return n_short; }
     const int id0 = sh[34], succ0 = sh[35], N = T.n_states;
     __syncthreads();
-    WALK_STAMP(4);
     // ---- list ranking: after the last round jump == id0 exactly for the states on state0's cycle, dist = steps to reach it
     unsigned* A = N <= T.lds_states ? T.ljd0 : T.jd0;
     unsigned* B = N <= T.lds_states ? T.ljd1 : T.jd1;
     for (int i = tid; i < N; i += nth) A[i] = i == id0 ? (unsigned)id0 : ((1u << 16) | (unsigned)T.next[i]);
     wg_sync_global();
-    WALK_STAMP(5);
     // a round: dist[i] += dist[jump[i]], jump[i] = jump[jump[i]] for every state.  The random reads of a thread's states are
     // issued eight at a time (the buffers may not alias, but the compiler cannot know: a plain loop serialises on them); the
     // ranking is complete as soon as state0's successor -- the farthest state of the cycle -- has reached state0.
@@ -315,7 +296,6 @@ __device__ inline int wg_follow_border(const Bits& img, const WalkTables& T, uns
         unsigned* t = A; A = B; B = t;
         if (succ0 == id0 || (int)(A[succ0] & 0xFFFFu) == id0) break;
     }
-    WALK_STAMP(6);
     if (succ0 != id0 && (int)(A[succ0] & 0xFFFFu) != id0) {   // the cycle did not close inside the tables: one lane walks it
         if (tid == 0) sh[33] = follow_border(img, traced, neg, x0, y0, method, out, cap);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -340,7 +320,6 @@ __device__ inline int wg_follow_border(const Bits& img, const WalkTables& T, uns
             if (pos < cap) out[pos] = make_int2(x, y);
         }
         wg_sync_global();
-        WALK_STAMP(7);
         return L;
     }
     // CHAIN_APPROX_SIMPLE: positions into B (free now), then an ordered compaction of the flagged ones
@@ -371,7 +350,6 @@ __device__ inline int wg_follow_border(const Bits& img, const WalkTables& T, uns
         }
     }
     wg_sync_global();
-    WALK_STAMP(7);
     return tot;
 }
 
@@ -513,9 +491,9 @@ __device__ inline void wg_scan_external(const Bits& img, unsigned* traced, unsig
 // =====================================================================================================================
 // Round 4: the follower with ALL its tables in LDS, every border of the image ranked at once.
 //
-// What the form above costs (tools/phase_probe.py, 256 environments): ~45 us to build the tables and ~47 us to rank ONE border of a
-// mid-episode explored area -- a chain of ~40 barrier-separated passes, each a round trip through L2 because the tables live in
-// global memory, over ~5 states per border pixel of which the traced border uses one.  This form:
+// What the form above costs (phase-timing build, removed; last in 26e85ce; 256 environments): ~45 us to build the tables and ~47 us
+// to rank ONE border of a mid-episode explored area -- a chain of ~40 barrier-separated passes, each a round trip through L2
+// because the tables live in global memory, over ~5 states per border pixel of which the traced border uses one.  This form:
 //   * STATES are (border pixel p, direction d of a BORDER-pixel neighbour): a traced border only ever visits border pixels (set
 //     pixels with a clear 8-neighbour; checked on 400 000 chain points of outer and hole borders), so states entered from an
 //     interior pixel are on no border -- ~3 states per border pixel instead of ~5.3.  A state whose successor pixel is not a
@@ -675,7 +653,6 @@ __device__ __forceinline__ void wg_build_rank_lds(const Bits& img, unsigned* lt,
         auto h = [](const unsigned* q) { const unsigned c = q[0]; return c & ((c << 1) | (q[-1] >> 31)) & ((c >> 1) | (q[1] << 31)); };
         return r[0] & ~(h(r - pw) & h(r) & h(r + pw));
     };
-    WALK_STAMP(0);
     // a. border mask; raster-order rank of every word's first border pixel (the per-word loops only count and copy: a word of a
     //    horizontal outline holds 32 border pixels, and anything heavier per pixel made its lane the critical path -- 36 us per pass)
     for (int k = tid; k < W; k += nth) { const int ly = k / wwords, lw = k - ly * wwords; lt[ly * pw + lw] = border_word(ly, lw); }
@@ -719,7 +696,6 @@ __device__ __forceinline__ void wg_build_rank_lds(const Bits& img, unsigned* lt,
     }
     if (tid == 0) T.rowrank[wrows] = (unsigned short)nb_tot;
     sync_pix<GPIX>();
-    WALK_STAMP(1);
     // b. ONE BORDER PIXEL PER LANE from here on: the directions that get a state (bits 22..29 of the pixel's entry), their count
     for (int r = tid; r < nb_tot; r += nth) {
         const int xy = T.pixxy[r], x = xy & 2047, ly = xy >> 11;
@@ -774,7 +750,6 @@ __device__ __forceinline__ void wg_build_rank_lds(const Bits& img, unsigned* lt,
     for (int i = tid; i < w32; i += nth) T.posflag[i] = 0u;
     if (tid == 0) T.pixbase[nb_tot] = (unsigned short)N;
     sync_pix<GPIX>();
-    WALK_STAMP(2);
     // c. successors: A = (next, 1), B = (self, 0) -- (DEAD, 0) for the fixed points.  The split form parks `next` in B first (the
     //    label planes are still border mask and ranks) and moves it over in a second pass.
     for (int r = tid; r < nb_tot; r += nth) {
@@ -829,7 +804,6 @@ __device__ __forceinline__ void wg_build_rank_lds(const Bits& img, unsigned* lt,
     }
     if (tid < 3) sh[36 + tid] = 0;
     __syncthreads();
-    WALK_STAMP(3);
     // e. rounds, in place
     const int cap_rounds = 33 - __builtin_clz((unsigned)N);
     const int cnt = (N + nth - 1) / nth;
@@ -855,7 +829,6 @@ __device__ __forceinline__ void wg_build_rank_lds(const Bits& img, unsigned* lt,
             __syncthreads();
         }
     }
-    WALK_STAMP(4);
     // f. cycle lengths into the heads' dm slots; the label planes are labels again
     unsigned* B = T.B;
     for (int i = tid; i < N; i += nth) {
@@ -866,10 +839,6 @@ __device__ __forceinline__ void wg_build_rank_lds(const Bits& img, unsigned* lt,
     for (int i = tid; i < 2 * plane_words; i += nth) lab0[i] = 0u;
     __syncthreads();
     T.ok = 1;
-    WALK_STAMP(5);
-#ifdef VLFM_PHASE_TIMING
-    if ((int)blockIdx.x == g_walk_block && threadIdx.x == 0) { g_walk_clk[12] = GPIX ? 3 : 2; g_walk_clk[13] = N; g_walk_clk[14] = nb_tot; }
-#endif
 }
 
 // One outer border from (x0, y0) out of the ranked tables.  All threads; returns the number of emitted points (uniform), or -1
@@ -1010,9 +979,7 @@ __device__ __forceinline__ void wg_scan_ranked(const Bits& img, const WalkLds& T
         if (!found) break;
         y = fy; x_done = fx;
         const int room = sink.cap_pts - sink.n_pts > 0 ? sink.cap_pts - sink.n_pts : 0;
-        if (sink.n_contours == 0) WALK_STAMP(6);
         int n = wg_emit_border_lds<GPIX>(img, T, traced, neg, fx, fy, method, sink.pts + sink.n_pts, room, sh);
-        if (sink.n_contours == 0) WALK_STAMP(7);
         if (n < 0) {
             if (tid == 0) sh[46] = follow_border(img, traced, neg, fx, fy, method, sink.pts + sink.n_pts, room);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1031,7 +998,6 @@ __device__ __forceinline__ void wg_scan_ranked(const Bits& img, const WalkLds& T
         sink.n_pts += n;
     }
     wg_sync_global();     // the points and the contour list (global memory) for whoever reads them next in this workgroup
-    WALK_STAMP(8);
     if (tid == 0) {
         if (n_fast) atomicAdd(&g_walk_paths[0], (unsigned long long)n_fast);
         if (n_serial) atomicAdd(&g_walk_paths[2], (unsigned long long)n_serial);

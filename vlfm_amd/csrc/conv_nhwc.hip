@@ -19,7 +19,6 @@
 // and write into one.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/vlfm_amd.h"
 #include "profile.h"
@@ -266,7 +265,7 @@ static int launch(ConvArgs a, int act, hipStream_t stream) {
 
 // The tile shapes (pixels x channels; 8 wavefronts each): the big ones have the best ratio of MFMA work to LDS traffic, the small ones
 // fill the chip when a layer has few pixels (7x10 and 14x20 feature maps) and waste less on narrow layers.
-struct TileCfg { int bm, bn; double rate; };      // rate: relative throughput of a CU running this shape (tools/conv_nhwc_probe.py sweep:
+struct TileCfg { int bm, bn; double rate; };      // rate: relative throughput of a CU running this shape (a tile sweep:
                                                   // with these the pick is within 1.3 % of the best shape summed over the probe layers)
 static const TileCfg kCfg[] = {{256, 256, 0.85}, {256, 128, 1.00}, {256, 64, 0.95}, {128, 128, 1.05},
                                {128, 64, 0.85},  {64, 128, 0.82},  {64, 64, 0.62}};
@@ -384,8 +383,7 @@ extern "C" int vlfm_conv_nhwc_f16(const void* d_x, const void* d_w, const void* 
     a.M = batch * a.Ho * a.Wo;
     a.ktiles_per_tap = cin / conv::GK;
     const int ktiles = (a.taps * cin + conv::GK - 1) / conv::GK;
-    int cfg = conv::pick_cfg(a.M, cout, ktiles);
-    if (const char* e = getenv("VLFM_CONV_CFG")) { const int v = atoi(e); if (v >= 0 && v < conv::kNumCfg) cfg = v; }   // tuning aid
+    const int cfg = conv::pick_cfg(a.M, cout, ktiles);
     return (cin % conv::GK) == 0 ? conv::launch_cfg<false>(a, cfg, act, (hipStream_t)stream)
                                  : conv::launch_cfg<true>(a, cfg, act, (hipStream_t)stream);
 }

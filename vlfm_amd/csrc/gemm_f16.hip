@@ -25,7 +25,6 @@
 // plain GEMM 1.0-1.1 PFLOP/s, i.e. 5-10 % BELOW hipBLASLt -- so only the fused fc1 uses it (vlfm_amd/vlm/ops.py:linear_gelu).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/vlfm_amd.h"
 #include "gelu_f16.h"
@@ -60,7 +59,7 @@ struct GemmArgs {
     int M, N, K;
     int tiles_m, tiles_n;
     int group_m;          // tile order of the ping-pong kernel: m-tiles per group (1 = plain n-fastest order)
-    int split_ragged;     // persistent kernel: split the tiles of a ragged last round into n-halves (0: diagnostic VLFM_GEMM_NO_SPLIT)
+    int split_ragged;     // persistent kernel: split the tiles of a ragged last round into n-halves (the launcher sets 1)
 };
 
 using lds_ptr = __attribute__((address_space(3))) unsigned char*;
@@ -530,12 +529,10 @@ extern "C" int vlfm_gemm_f16_nt(const void* d_x, const void* d_w, const void* d_
     a.x = (const _Float16*)d_x; a.w = (const _Float16*)d_w; a.bias = (const _Float16*)d_bias; a.c = (_Float16*)d_c;
     a.M = m; a.N = n; a.K = k;
     a.tiles_m = (m + GB - 1) / GB; a.tiles_n = (n + GB - 1) / GB;
-    // tile order of the persistent walk: groups of 4 m-tiles on every ViT shape (probe: 2-8 within 1 %, 1 and 16+ behind); the two
-    // diagnostic switches are read once per process
-    static const int env_group_m = [] { const char* e = getenv("VLFM_GEMM_GROUP_M"); return e ? atoi(e) : 0; }();
-    static const bool env_no_split = getenv("VLFM_GEMM_NO_SPLIT") != nullptr;
-    a.group_m = env_group_m >= 1 ? env_group_m : 4;
-    a.split_ragged = env_no_split ? 0 : 1;
+    // tile order of the persistent walk: groups of 4 m-tiles on every ViT shape (probe: 2-8 within 1 %, 1 and 16+ behind); the
+    // tiles of a ragged last round are split into n-halves
+    a.group_m = 4;
+    a.split_ragged = 1;
     if (epilogue == 0) return launch_gemm<EPI_BIAS>(a, (hipStream_t)stream);
     if (epilogue == 1) return launch_gemm<EPI_BIAS_GELU>(a, (hipStream_t)stream);
     return launch_gemm<EPI_ACCUM>(a, (hipStream_t)stream);

@@ -16,8 +16,8 @@
 // Synchronisation between the phases of a kernel is WORKGROUP scope everywhere (wg_sync_global, border_parallel.h): one workgroup owns
 // an environment and is its own consumer.  Round 4: the explored-selection and frontier kernels still used __threadfence() -- a
 // device-scope release, i.e. an L2 write-back -- at 17 phase boundaries; alone in the machine that costs a few microseconds, with 256
-// workgroups doing it at once the phases around global-memory hand-offs took 10 x as long (tools/phase_probe.py: window copy 4 -> 47 us,
-// offset + pick 6 -> 116 us, bad flags 14 -> 136 us at 1 -> 256 environments).
+// workgroups doing it at once the phases around global-memory hand-offs took 10 x as long (phase-timing build, removed; last in 26e85ce:
+// window copy 4 -> 47 us, offset + pick 6 -> 116 us, bad flags 14 -> 136 us at 1 -> 256 environments).
 // Dense work (dilations, masks, rasterisation, packing) is data-parallel over words/pixels; the order-dependent part
 // (Suzuki-Abe border chains) is followed by the WHOLE workgroup: successor tables + list ranking by pointer jumping
 // (border_parallel.h), with the one-lane walk of bitmap.h kept for short borders and as the fallback.  No MFMA; bit and
@@ -177,32 +177,6 @@ __global__ __launch_bounds__(1024) void find_contours_wg_kernel(const unsigned* 
         counts[plane * 3 + 2] = sink.overflow;
     }
 }
-
-// Optional phase timing (compile with -DVLFM_PHASE_TIMING; tools/phase_probe.py): workgroup 0's thread 0 stamps the
-// constant-rate 100 MHz counter at phase boundaries.  Zero cost when the macro is not defined.
-#ifdef VLFM_PHASE_TIMING
-__device__ long long g_phase_clock[3][16];
-__device__ int g_phase_block;              // the workgroup that stamps (vlfm_debug_phase_block)
-__device__ long long g_wg_first[3][1024];  // every workgroup's first and last stamp: which environment is the slow one?
-__device__ long long g_wg_last[3][1024];
-#define VLFM_PHASE(kernel_id, k)                                                                  \
-    do {                                                                                          \
-        __syncthreads();                                                                          \
-        if (threadIdx.x == 0) {                                                                   \
-            const long long t_ = wall_clock64();                                                  \
-            if ((int)blockIdx.x == g_phase_block) g_phase_clock[kernel_id][k] = t_;               \
-            if (blockIdx.x < 1024) { if ((k) == 0) g_wg_first[kernel_id][blockIdx.x] = t_; g_wg_last[kernel_id][blockIdx.x] = t_; } \
-        }                                                                                         \
-    } while (0)
-// the same without the barrier, for a stamp inside single-wavefront code
-#define VLFM_STAMP(kernel_id, k)                                                                  \
-    do {                                                                                          \
-        if ((int)blockIdx.x == g_phase_block && (threadIdx.x & 63) == 0) g_phase_clock[kernel_id][k] = wall_clock64(); \
-    } while (0)
-#else
-#define VLFM_PHASE(kernel_id, k) do {} while (0)
-#define VLFM_STAMP(kernel_id, k) do {} while (0)
-#endif
 
 // ================================================================================================ drawing helpers
 // Window view of a bit plane living in LDS: wn x wn cells, top-left = image cell (ox, oy); image is S x S.
@@ -607,7 +581,6 @@ __global__ __launch_bounds__(1024) void fog_of_war_kernel(const FogParams* __res
     if (tid < 16) sh_i[tid] = 0;
     __syncthreads();
 
-    VLFM_PHASE(0, 0);
     // ---- 1. cone sector (cv2.ellipse filled) into cone/par
     LdsBitmap bm;
     bm.solid = cone; bm.parity = par; bm.rows = S; bm.cols = S; bm.words = words;
@@ -622,7 +595,6 @@ __global__ __launch_bounds__(1024) void fog_of_war_kernel(const FogParams* __res
     __syncthreads();
     resolve_rows(bm, tid, nth);
     __syncthreads();
-    VLFM_PHASE(0, 1);
     // ---- 2. navigable window; obstacles_in_cone = cone & ~nav; visible = cone & nav
     for (int i = tid; i < plane_words; i += nth) {
         const int ly = i / words, lw = i - ly * words;
@@ -636,7 +608,6 @@ __global__ __launch_bounds__(1024) void fog_of_war_kernel(const FogParams* __res
         par[i] = 0u;
     }
     __syncthreads();
-    VLFM_PHASE(0, 2);
     // ---- 3. external contours (SIMPLE) of the obstacle blobs: wave 0 walks a padded copy
     for (int i = tid; i < pad_words; i += nth) {
         const int ly = i / pw - 1, lw = i % pw - 1;
@@ -661,7 +632,6 @@ __global__ __launch_bounds__(1024) void fog_of_war_kernel(const FogParams* __res
     if (sh_i[2]) { if (tid == 0) status[0] = 1; return; }
     if (tid == 0) { status[1] = n_obst; }
     if (n_obst == 0) return;  // "no obstacles in the cone": fog returned unchanged -> nothing revealed this step
-    VLFM_PHASE(0, 3);
     // ---- 4. shadow-casting points: convex blobs contribute their two angular extremes, the others every vertex.
     // One WAVEFRONT per blob (round 3; before: the whole workgroup per blob with three barriers each, and ONE lane evaluating
     // the f64 atan2 of every vertex of a convex blob in a serial loop).  The cuts of step 5 only clear bits, so the order in
@@ -719,7 +689,6 @@ __global__ __launch_bounds__(1024) void fog_of_war_kernel(const FogParams* __res
     __syncthreads();
     const int n_lines = sh_i[3];
     if (tid == 0) status[2] = n_lines;
-    VLFM_PHASE(0, 4);
     // ---- 5. cut the visible mask with 2-px lines from every point away from the agent (cv2.polylines, color 0).  End
     // points first (one f64 atan2 / cos / sin per LINE, not per task), then one (part, line) task per lane, PART-MAJOR so that
     // a wavefront runs one code path (edge / interior / end disc): the critical path becomes one edge + one interior + one
@@ -733,21 +702,16 @@ __global__ __launch_bounds__(1024) void fog_of_war_kernel(const FogParams* __res
     }
     __threadfence_block();
     __syncthreads();
-    VLFM_PHASE(0, 5);
     // tasks, part-major: [edge 0 .. 3, interior] x THICK_LINE_SEGS shares, then the two end discs
     constexpr int kCutTasks = 5 * THICK_LINE_SEGS + 2;
     for (int t = tid; t < n_lines * kCutTasks; t += nth) {
         const int p = t / n_lines, i = t - p * n_lines;
         const int part = p < 5 * THICK_LINE_SEGS ? p / THICK_LINE_SEGS : p - 5 * THICK_LINE_SEGS + 5;
         const int seg = p < 5 * THICK_LINE_SEGS ? p % THICK_LINE_SEGS : 0;
-#ifdef VLFM_CUT_SKIP   // diagnostic builds only (tools/phase_probe.py): leave parts out to see what each costs
-        if ((VLFM_CUT_SKIP >> part) & 1) continue;
-#endif
         const int4 ln = lines[i];
         thick_line2_clear(vis, W, ln.x + ox, ln.y + oy, ln.z, ln.w, part, seg, part < 5 ? THICK_LINE_SEGS : 1);
     }
     __syncthreads();
-    VLFM_PHASE(0, 6);
     // ---- 6. external contours of what is left; keep the one nearest the agent (|pointPolygonTest|, <= 3 px)
     for (int i = tid; i < pad_words; i += nth) {
         const int ly = i / pw - 1, lw = i % pw - 1;
@@ -795,7 +759,6 @@ __global__ __launch_bounds__(1024) void fog_of_war_kernel(const FogParams* __res
     if (sh_i[6]) { if (tid == 0) status[0] = 1; return; }
     const int best = sh_i[5];
     if (best < 0 || sh_i[7]) return;  // nothing visible / closest contour too far away
-    VLFM_PHASE(0, 7);
     // ---- 7. drawContours(fog, [visible_area], 0, 1, -1): fill the chosen outline (component + enclosed holes)
     {
         LdsBitmap fb;
@@ -812,7 +775,6 @@ __global__ __launch_bounds__(1024) void fog_of_war_kernel(const FogParams* __res
         resolve_rows(fb, tid, nth);
         __syncthreads();
     }
-    VLFM_PHASE(0, 8);
     // ---- 8. dilate 3x3 (obstacle_map.py:125), keep navigable cells (:127), OR into the explored plane (:126)
     unsigned* expl = mp.explored + eoff;
     for (int i = tid; i < plane_words; i += nth) {
@@ -840,7 +802,6 @@ __global__ __launch_bounds__(1024) void fog_of_war_kernel(const FogParams* __res
         if (lo && wi >= 0 && wi < mp.stride) atomicOr(&expl[(size_t)y * mp.stride + wi], lo & tail_mask(S, wi));
         if (hi && wi + 1 >= 0 && wi + 1 < mp.stride) atomicOr(&expl[(size_t)y * mp.stride + wi + 1], hi & tail_mask(S, wi + 1));
     }
-    VLFM_PHASE(0, 9);
     if (tid == 0) {
         int* bb = sc.bbox + (size_t)P.env * 4;
         atomicMin(&bb[0], max(oy, 0)); atomicMax(&bb[1], min(oy + wn - 1, S - 1));
@@ -875,7 +836,6 @@ __global__ __launch_bounds__(1024) void explored_select_kernel(const FogParams* 
     const int* bb = bbox + (size_t)P.env * 4;
     const int y_lo = max(bb[0] - 1, 0), y_hi = min(bb[1] + 1, S - 1);
     if (y_lo > y_hi) return;  // nothing explored yet
-    VLFM_PHASE(1, 0);
     // The border walk is a single-lane pointer chase: run it on an LDS copy of the explored window (everything ever revealed
     // lies inside the persistent bounding box) whenever image + two label planes fit; the global planes are the fallback.
     extern __shared__ __attribute__((aligned(16))) unsigned lds_win[];
@@ -897,7 +857,6 @@ __global__ __launch_bounds__(1024) void explored_select_kernel(const FogParams* 
         for (int i = tid + y_lo * stride; i < (y_hi + 1) * stride; i += nth) { traced[i] = 0u; neg[i] = 0u; }
     }
     wg_sync_global();   // (workgroup scope: the consumers are this workgroup's own wavefronts)
-    VLFM_PHASE(1, 1);
     int2* pts = sc.pts + (size_t)P.env * sc.cap_pts;
     int* cstart = sc.starts + (size_t)P.env * sc.cap_contours;
     int* clen = sc.lens + (size_t)P.env * sc.cap_contours;
@@ -916,7 +875,6 @@ __global__ __launch_bounds__(1024) void explored_select_kernel(const FogParams* 
         T.cap_bp = sc.cap_pts; T.cap_states = min(sc.walk_states, S * stride);
         T.wrows = wrows; T.wwords = wwords;
         wg_scan_external_lds(b, L_tr + pw + 1, L_ng + pw + 1, 2, sink, T, lds_win + 3 * wn, sc.lds_bytes - 12u * (unsigned)wn, sh_wg);
-        VLFM_STAMP(1, 2);
         const int npt = sink.n_pts < sc.cap_pts ? sink.n_pts : sc.cap_pts;
         for (int i = tid; i < npt; i += nth) { int2 q = pts[i]; q.x += w_lo * 32; q.y += y_lo; pts[i] = q; }  // -> image coords
         wg_sync_global();   // (workgroup scope: the consumers are this workgroup's own wavefronts)
@@ -940,11 +898,9 @@ __global__ __launch_bounds__(1024) void explored_select_kernel(const FogParams* 
             }
         }
         if (lane == 0) { sh_i[0] = sink.n_contours; sh_i[1] = sink.overflow; sh_i[2] = chosen; }
-        VLFM_STAMP(1, 3);
     }
     wg_sync_global();   // (workgroup scope: the consumers are this workgroup's own wavefronts)
     if (tid == 0) { status[0] = sh_i[1]; status[1] = sh_i[0]; status[2] = sh_i[2]; status[3] = 0; }
-    VLFM_PHASE(1, 4);
     if (sh_i[1] || sh_i[0] <= 1) return;
     // redraw the chosen outline filled on an empty plane (global-memory bitmaps; rare path)
     const int chosen = sh_i[2];
@@ -1063,11 +1019,9 @@ __global__ __launch_bounds__(1024) void frontier_kernel(const FogParams* __restr
     if (tid < 16) sh_i[tid] = 0;
     if (tid == 0) sh_i[0] = 1;
     __syncthreads();
-    VLFM_PHASE(2, 0);
     // ---- a. explored_d = dilate(explored, 5x5) & navigable ; unexplored = navigable & ~explored_d: full-plane, embarrassingly
     // parallel -> done for all environments at once by frontier_prepare_kernel (a single workgroup took ~125 us for it)
     unsigned ring_ok = 1;
-    VLFM_PHASE(2, 1);
     // ---- b. filter_out_small_unexplored.  Exact shortcut: when the border ring of `unexplored` is fully set, that one
     // component encloses every other one, RETR_EXTERNAL returns it alone and its contour area is (S-1)^2.
     ring_ok = ring_all_set(un, S, stride, tid, nth);
@@ -1136,7 +1090,6 @@ __global__ __launch_bounds__(1024) void frontier_kernel(const FogParams* __restr
         for (int i = tid; i < S * stride; i += nth) { traced[i] = 0u; neg[i] = 0u; }
         wg_sync_global();   // (workgroup scope: the consumers are this workgroup's own wavefronts)
     }
-    VLFM_PHASE(2, 2);
     // ---- c. border chain (CHAIN_APPROX_NONE) of the filtered explored mask
     const int* bb = bbox + (size_t)P.env * 4;
     {
@@ -1162,7 +1115,6 @@ __global__ __launch_bounds__(1024) void frontier_kernel(const FogParams* __restr
             for (int i = tid + y_lo * stride; i < (y_hi + 1) * stride; i += nth) { traced[i] = 0u; neg[i] = 0u; }
         }
         wg_sync_global();
-        VLFM_PHASE(2, 3);
         ContourSink sink;
         sink.pts = pts; sink.start = cstart; sink.len = clen; sink.cap_pts = sc.cap_pts; sink.cap_contours = sc.cap_contours;
         sink.n_pts = 0; sink.n_contours = 0; sink.overflow = 0;
@@ -1178,7 +1130,6 @@ __global__ __launch_bounds__(1024) void frontier_kernel(const FogParams* __restr
             T.wrows = wrows; T.wwords = wwords;
             wg_scan_external_lds(b, L_tr + pw + 1, L_ng + pw + 1, 1, sink, T, lds_win + 3 * wn, sc.lds_bytes - 12u * (unsigned)wn,
                                  sh_wg);
-            VLFM_STAMP(2, 4);
             const int npt = sink.n_pts < sc.cap_pts ? sink.n_pts : sc.cap_pts;
             for (int i = tid; i < npt; i += nth) { int2 q = pts[i]; q.x += w_lo * 32; q.y += y_lo; pts[i] = q; }
             if (tid == 0) { sh_i[5] = sink.n_contours; sh_i[6] = sink.n_pts; sh_i[7] = sink.overflow; }
@@ -1191,7 +1142,6 @@ __global__ __launch_bounds__(1024) void frontier_kernel(const FogParams* __restr
     wg_sync_global();   // (workgroup scope: the consumers are this workgroup's own wavefronts)
     const int nc = sh_i[5], npts_all = sh_i[6];
     if (sh_i[7]) { if (tid == 0) { out_n[0] = 0; out_n[1] = 1; } return; }
-    VLFM_PHASE(2, 5);
     // ---- d. a chain point is "bad" when no unexplored-navigable cell lies in its 3x3 neighbourhood
     //         (cv2.blur 3x3, BORDER_REFLECT_101, of 255*(navigable & ~filtered) is zero there)
     // the flags are consumed by a single lane below: keep them in LDS (the walk window is free again) when they fit
@@ -1228,7 +1178,6 @@ __global__ __launch_bounds__(1024) void frontier_kernel(const FogParams* __restr
         bad[i] = any ? 0 : 1;
     }
     wg_sync_global();   // (workgroup scope: the consumers are this workgroup's own wavefronts)
-    VLFM_PHASE(2, 6);
     // ---- e. frontier runs + arc-length midpoints.  Contours in OpenCV order (reverse discovery); the chain handed to
     // contour_to_frontiers is the contour rotated by one (interpolate_contour emits end points only).
     // Wavefront 0 lists the kept pieces, 64 chain positions at a time (a serial pass over a 2 300-point chain took 370 us);
@@ -1299,7 +1248,6 @@ __global__ __launch_bounds__(1024) void frontier_kernel(const FogParams* __restr
         if (lane == 0) { sh_i[8] = np; sh_i[9] = overflow; }
     }
     wg_sync_global();   // (workgroup scope: the consumers are this workgroup's own wavefronts)
-    VLFM_PHASE(2, 7);
     const int np = sh_i[8];
     // get_frontier_midpoint per piece.  The arc-length cumsum is sequential by definition (np.cumsum's rounding order), but
     // the segment lengths are not: all lanes compute them (f64 sqrt, chain indexing) into LDS, then one lane only adds.
@@ -1410,7 +1358,6 @@ __global__ __launch_bounds__(1024) void frontier_kernel(const FogParams* __restr
         }
         __syncthreads();
     }
-    VLFM_PHASE(2, 8);
     if (tid == 0) {
         out_n[0] = np < sc.cap_frontiers ? np : sc.cap_frontiers;
         // one flag for the whole explore pipeline of this environment: a capacity overflow in the fog-of-war or the
@@ -1644,33 +1591,6 @@ extern "C" int vlfm_obstacle_map_update_batched(const vlfm_fog_params* d_prm, in
     }
     return check_launch("frontier_kernel");
 }
-
-#ifdef VLFM_PHASE_TIMING
-extern "C" int vlfm_debug_phase_clocks(long long* h_out /* [3][16] */) {
-    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(vlfm::g_phase_clock), sizeof(long long) * 48) == hipSuccess ? VLFM_OK : VLFM_ERR_HIP;
-}
-extern "C" int vlfm_debug_phase_block(int block) {
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(vlfm::g_walk_block), &block, sizeof(int));
-    return hipMemcpyToSymbol(HIP_SYMBOL(vlfm::g_phase_block), &block, sizeof(int)) == hipSuccess ? VLFM_OK : VLFM_ERR_HIP;
-}
-extern "C" int vlfm_debug_wg_spans(long long* h_first /* [3][1024] */, long long* h_last) {
-    if (hipMemcpyFromSymbol(h_first, HIP_SYMBOL(vlfm::g_wg_first), sizeof(long long) * 3 * 1024) != hipSuccess) return VLFM_ERR_HIP;
-    return hipMemcpyFromSymbol(h_last, HIP_SYMBOL(vlfm::g_wg_last), sizeof(long long) * 3 * 1024) == hipSuccess ? VLFM_OK : VLFM_ERR_HIP;
-}
-extern "C" int vlfm_debug_parallel_walk_clocks(long long* h_out16) {
-    return hipMemcpyFromSymbol(h_out16, HIP_SYMBOL(vlfm::g_walk_clk), sizeof(long long) * 16) == hipSuccess ? VLFM_OK : VLFM_ERR_HIP;
-}
-extern "C" int vlfm_debug_walk_stats(long long* h_out /* ticks, points, calls; reset afterwards */) {
-    long long z = 0;
-    if (hipMemcpyFromSymbol(&h_out[0], HIP_SYMBOL(vlfm::g_walk_ticks), 8) != hipSuccess) return VLFM_ERR_HIP;
-    (void)hipMemcpyFromSymbol(&h_out[1], HIP_SYMBOL(vlfm::g_walk_points), 8);
-    (void)hipMemcpyFromSymbol(&h_out[2], HIP_SYMBOL(vlfm::g_walk_calls), 8);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(vlfm::g_walk_ticks), &z, 8);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(vlfm::g_walk_points), &z, 8);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(vlfm::g_walk_calls), &z, 8);
-    return VLFM_OK;
-}
-#endif
 
 extern "C" int vlfm_walk_path_counters(long long* h_out4, int reset) {
     // borders traced from the LDS tables / (unused) / by one lane after the tables declined; images whose tables were in LDS

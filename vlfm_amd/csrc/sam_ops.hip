@@ -346,11 +346,10 @@ extern "C" int vlfm_window_attention_masked_f32(const float* d_qkv, const float*
     const dim3 grid((unsigned)(windows * heads));
     const float sl = scale * 1.4426950408889634f;
     hipStream_t s = (hipStream_t)stream;
-    // the matrix-core form for the window sizes of TinyViT and Swin (7 x 7 and 14 x 14 tokens: 2 and 7 key tiles);
-    // VLFM_WINDOW_ATTENTION=valu keeps the vector form (A/B, tests)
-    static const bool use_mfma = [] { const char* e = getenv("VLFM_WINDOW_ATTENTION"); return !(e && e[0] == 'v'); }();
+    // the matrix-core form for the window sizes of TinyViT and Swin (7 x 7 and 14 x 14 tokens: 2 and 7 key tiles); the vector
+    // form below serves every other token count
     const int kt = (tokens + 31) / 32;
-    if (use_mfma && (kt == 2 || kt == 7)) {
+    if (kt == 2 || kt == 7) {
         VLFM_TIMED("window_attention_mfma_f32_kernel", stream);
         if (kt == 2) VLFM_KLAUNCH((sam::window_attention_mfma_f32_kernel<2>), grid, dim3(128), 0, s, d_qkv, d_bias_t, d_out, tokens, heads, sl, d_mask_t, windows_per_image);
         else VLFM_KLAUNCH((sam::window_attention_mfma_f32_kernel<7>), grid, dim3(256), 0, s, d_qkv, d_bias_t, d_out, tokens, heads, sl, d_mask_t, windows_per_image);

@@ -121,27 +121,6 @@ __device__ inline bool fuse_cell(const UpdateArgs& a, float nw, float old, const
     return true;
 }
 
-// Optional phase timing of the single-launch update (compile with -DVLFM_PHASE_TIMING; tools/vm_phase_probe.py): thread 0
-// of workgroup (0, 0) stamps the constant-rate 100 MHz counter at phase boundaries.  Zero cost otherwise.
-#ifdef VLFM_PHASE_TIMING
-__device__ long long g_vm_phase[16];
-__device__ long long g_vm_span[2048][2];     // first and last phase stamp of EVERY workgroup (observation-major): the imbalance
-#define VM_PHASE(k)                                                                                       \
-    do {                                                                                                  \
-        __syncthreads();                                                                                  \
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_vm_phase[k] = wall_clock64();        \
-        if (((k) == 0 || (k) == 7) && threadIdx.x == 0 && blockIdx.y * gridDim.x + blockIdx.x < 2048)       \
-            g_vm_span[blockIdx.y * gridDim.x + blockIdx.x][(k) == 7] = wall_clock64();                      \
-    } while (0)
-#define VM_STAMP(k)                                                                                       \
-    do {                                                                                                  \
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_vm_phase[k] = wall_clock64();        \
-    } while (0)
-#else
-#define VM_PHASE(k) do {} while (0)
-#define VM_STAMP(k) do {} while (0)
-#endif
-
 // The same tile with the template taps taken from LDS (single-launch kernel).  `quad` is the confidence table's
 // (T/2+1)^2 quadrant: the table depends on |row - T/2| and |col - T/2| only (value_map.py:343-351), and a tap is read only
 // where the visible bit -- which already contains the cone sector -- is set, so template[y][x] == quad[|y-T/2|][|x-T/2|] for
@@ -151,8 +130,9 @@ __device__ long long g_vm_span[2048][2];     // first and last phase stamp of EV
 // new confidence), 8 bytes -- and fused afterwards by fuse_list() with one lane per cell.  The tile sweep above was 14 dependent
 // [LDS phase -> issue map reads -> wait -> fuse -> store] round trips per wavefront (7 passes x 2 half tiles) with three quarters
 // of the lanes idle in each; at 256 observations, every CU waiting on the same memory system, those round trips were 26 of the
-// kernel's 56 us (tools/vm_phase_probe.py).  The list form is one or two round trips with every lane busy.  When the list is full
-// (more than `cap` cells: only a cone far wider than a camera's) a wavefront fuses its rows in place, the old way.
+// kernel's 56 us (measured with the phase-timing build, removed; last in 26e85ce).  The list form is one or two round trips with
+// every lane busy.  When the list is full (more than `cap` cells: only a cone far wider than a camera's) a wavefront fuses its
+// rows in place, the old way.
 constexpr unsigned LIST_SENTINEL = 0xFFFFFFFFu;
 
 template <int C_STATIC>
@@ -176,7 +156,6 @@ __device__ inline void fuse_tile_lds(const UpdateArgs& a, const vlfm_vm_pose& po
         const bool col_ok = (unsigned)mc < (unsigned)S;
         const int adelta = __double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[0], (double)x), 1024.0));
         const int bdelta = __double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[3], (double)x), 1024.0));
-        VM_STAMP(8);
 #pragma unroll 1
       for (int half = 0; half < 2; half++) {
         const int row_base = row_begin + half * R;
@@ -225,7 +204,6 @@ __device__ inline void fuse_tile_lds(const UpdateArgs& a, const vlfm_vm_pose& po
             }
             nw[k] = v;  // curr_map is f32 (value_map.py:316-317); 0 = the cell is not touched
         }
-        VM_STAMP(9);
         {   // nothing visible in this wavefront's 64 columns x R rows (three quarters of the cone's bounding box): no map
             // access at all -- the dummy reads of an all-idle wavefront would still cost it a full memory round trip
             bool any_on = false;
@@ -277,7 +255,6 @@ __device__ inline void fuse_tile_lds(const UpdateArgs& a, const vlfm_vm_pose& po
             old[k] = conf[cell[k]];
             if (C_STATIC == 1) oldv1[k] = value[cell[k]];
         }
-        VM_STAMP(10);
         // ---- phase C: fuse and write back
 #pragma unroll
         for (int k = 0; k < R; k++) {
@@ -323,7 +300,6 @@ __device__ inline void fuse_tile_lds(const UpdateArgs& a, const vlfm_vm_pose& po
             }
         }
       }
-        VM_STAMP(11);
     }
 }
 
@@ -331,7 +307,8 @@ __device__ inline void fuse_tile_lds(const UpdateArgs& a, const vlfm_vm_pose& po
 // The tile sweep evaluates source coordinates and four visibility taps for EVERY cell of the cone's destination bounding box --
 // ~40 instructions per cell for ~16 000-25 000 cells of which ~3 000 (the part of the cone the depth profile leaves visible) end
 // up with a confidence: 50 000 wavefront-instructions per observation, 25 us of pure VALU time on a CU that holds one workgroup
-// (tools/vm_phase_probe.py: "fuse tiles" 7 us for ONE pass of one workgroup at 1 environment, no memory system in the way).
+// (phase-timing build, removed; last in 26e85ce: "fuse tiles" 7 us for ONE pass of one workgroup at 1 environment, no memory
+// system in the way).
 // Here the window is cut into 4 x 4 blocks; a block is kept only if the source footprint of its cells (bounding box of the four
 // corner cells' coordinates -- exact: the fixed-point coordinate is a monotone function of the row plus a monotone function of
 // the column, so its extremes over a rectangle sit in the corners -- widened by the +1 taps) contains a visible bit.  The kept
@@ -622,7 +599,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
     unsigned wr0 = 0u;
     if (written && a.explored && my_word < plane_words) wr0 = written[my_word];
 
-    VM_PHASE(0);
     LdsBitmap bm;
     bm.solid = solid; bm.parity = parity; bm.rows = T; bm.cols = T; bm.words = words;
     for (int i = tid; i < 2 * T * words; i += nth) solid[i] = 0u;
@@ -685,21 +661,18 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
         vert[W + 1] = make_int2(T - 1, T - 1);
     }
     __syncthreads();
-    VM_PHASE(1);
     // the keys have been read: the last workgroup of this observation to get here zeroes them for the next depth ingest
     if (tid == 0) {
         __threadfence();
         sh_last = atomicAdd(&fx.counters[obs], 1) == G - 1;
     }
     raster_polygon_flat(bm, vert, n_vert, pref, sh_wave_tot, tid, nth);
-    VM_PHASE(2);
     if (sh_last) {
         unsigned* cmw = a.colmax + (size_t)obs * W;
         for (int i = tid; i < W; i += nth) cmw[i] = 0u;
         if (tid == 0) fx.counters[obs] = 0;
     }
     __syncthreads();
-    VM_PHASE(3);
     // resolve (one lane per row) fused with visible = (template > 0) & ~beyond-the-profile, and the source bounding box
     {
         int r_lo = T, r_hi = -1, c_lo = T, c_hi = -1;
@@ -728,7 +701,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
         }
     }
     __syncthreads();
-    VM_PHASE(4);
     if (tid == 0) {
         // destination (rotated) bounding box of everything that can receive a non-zero tap (see visible_mask_kernel)
         int4 m;
@@ -750,7 +722,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
         }
         sh_dbox = m;
     }
-    VM_PHASE(5);
     // ---- step 2: cells that hold a value but are not explored any more (value_map.py:369-375)
     if (written && a.explored) {
         const unsigned* explored = a.explored + (size_t)pose.env * S * ex_stride;
@@ -775,7 +746,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
         }
     }
     __syncthreads();
-    VM_PHASE(6);
     // ---- step 3: rotate + place + fuse, tiles g, g + G, ...
     int4 box = sh_dbox;
     box.x = __builtin_amdgcn_readfirstlane(box.x); box.y = __builtin_amdgcn_readfirstlane(box.y);
@@ -844,7 +814,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
         }
         __syncthreads();
         fuse_list<C_STATIC>(a, pose, list, min(sh_list_n, fx.list_cap), tid, nth, written);
-        VM_PHASE(7);
         return;
     }
     for (int t = t_lo + g * tiles_per_pass + tg; t <= t_hi; t += G * tiles_per_pass)
@@ -853,7 +822,6 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
         __syncthreads();
         fuse_list<C_STATIC>(a, pose, list, min(sh_list_n, fx.list_cap), tid, nth, written);
     }
-    VM_PHASE(7);
 }
 
 // ------------------------------------------------------------------------------------------------ sort_waypoints
@@ -936,15 +904,6 @@ extern "C" int vlfm_cone_template_build(const float* d_conf, const int64_t* d_po
     return check_launch("cone_template_kernel");
 }
 
-#ifdef VLFM_PHASE_TIMING
-extern "C" int vlfm_debug_vm_phase_clocks(long long* h_out /* [16] */) {
-    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(vlfm::g_vm_phase), sizeof(long long) * 16) == hipSuccess ? VLFM_OK : VLFM_ERR_HIP;
-}
-extern "C" int vlfm_debug_vm_span_clocks(long long* h_out /* [2048][2] */) {
-    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(vlfm::g_vm_span), sizeof(long long) * 4096) == hipSuccess ? VLFM_OK : VLFM_ERR_HIP;
-}
-#endif
-
 static int target_override_g() {
     static const int v = [] { const char* e = getenv("VLFM_VM_TARGET_WGS"); return e ? atoi(e) : 0; }();
     return v;
@@ -985,26 +944,23 @@ extern "C" int vlfm_value_map_update_fused_batched(uint32_t* d_colmax_keys, int 
                             (size_t)T * sizeof(int2);
     size_t lds = lds_base;
     if (lds > 150 * 1024) return fail(VLFM_ERR_CAPACITY, "value_map_update_fused_batched: template/width too large for LDS");
-    // the cell list takes what is left, up to 8192 entries (a 79-degree cone at 5 m marks ~3 000 cells; VLFM_VM_LIST=0: fuse in place)
-    static const int list_override = [] { const char* e = getenv("VLFM_VM_LIST"); return e ? atoi(e) : -1; }();
+    // the cell list takes what is left, up to 8192 entries (a 79-degree cone at 5 m marks ~3 000 cells)
     {
         size_t cap = (150 * 1024 - lds) / sizeof(uint2);
         if (cap > 8192) cap = 8192;
-        if (list_override >= 0 && (size_t)list_override < cap) cap = (size_t)list_override;
         if (cap < 1024) cap = 0;
         if (map_size >= 65535 || T >= 65536) cap = 0;   // a list entry packs (row << 16) | col of a MAP cell, 0xFFFFFFFF is the sentinel
         fx.list_cap = (int)cap;
         lds += cap * sizeof(uint2);
-        // block-sparse sweep: the column table + one list entry for EVERY 4 x 4 block of the window (VLFM_VM_BLOCKS=0: tile sweep)
-        static const int blocks_off = [] { const char* e = getenv("VLFM_VM_BLOCKS"); return e && atoi(e) == 0; }();
+        // block-sparse sweep: the column table + one list entry for EVERY 4 x 4 block of the window
         const int nb_side = (T + 3) / 4;
         const size_t extra = (size_t)T * sizeof(int2) + (size_t)nb_side * nb_side * 4;
         // ... when an observation has at most two workgroups: with more (small batches: G = CUs / n) the tile sweep split over
-        // G workgroups is the shorter chain (measured, tools/vm_phase_probe.py, old / new: 256 obs 56 / 38 us, 128 obs 37 / 35,
-        // 64 obs 27 / 36, 16 HD obs 31 / 40, 8 obs 23 / 29)
+        // G workgroups is the shorter chain (measured with the phase-timing build, removed; last in 26e85ce -- old / new: 256 obs
+        // 56 / 38 us, 128 obs 37 / 35, 64 obs 27 / 36, 16 HD obs 31 / 40, 8 obs 23 / 29)
         const int cu = target_override_g() > 0 ? target_override_g() : device_cu_count();
         const bool few_wgs = (cu + n - 1) / n <= 2;
-        if (!blocks_off && few_wgs && cap > 0 && lds + extra <= 150 * 1024 && T < 65536) {
+        if (few_wgs && cap > 0 && lds + extra <= 150 * 1024 && T < 65536) {
             fx.block_cap = nb_side * nb_side;
             lds += extra;
         }
@@ -1025,7 +981,8 @@ extern "C" int vlfm_value_map_update_fused_batched(uint32_t* d_colmax_keys, int 
     const int tiles = (T + ROWS_PER_TILE - 1) / ROWS_PER_TILE;
     // workgroups per observation: a 1024-thread workgroup fills a CU (register budget), so aim for one per CU over all
     // observations; more than ceil(tiles / 4) would leave workgroups without a tile
-    // (the device's CU count, asked once; VLFM_VM_TARGET_WGS -- read once per process -- is tools/vm_phase_probe.py's sweep knob)
+    // (the device's CU count, asked once; VLFM_VM_TARGET_WGS -- read once per process -- stands in for it, so that a test can run
+    // the block-sparse sweep and the tile sweep at one batch size)
     const int target = target_override_g() > 0 ? target_override_g() : device_cu_count();
     int G = (target + n - 1) / n;
     const int g_max = (tiles + FUSED_THREADS / 256 - 1) / (FUSED_THREADS / 256);

@@ -27,7 +27,6 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/vlfm_amd.h"
 #include "profile.h"
@@ -84,22 +83,14 @@ typedef short short4v __attribute__((__vector_size__(4 * sizeof(short))));
 typedef short short8v __attribute__((__vector_size__(8 * sizeof(short))));
 using half2_t = __attribute__((ext_vector_type(2))) _Float16;
 
-#ifdef PA_FREE_RUN     // timing experiment only (with PA_STUB=4): no waits, no barriers inside the item loop -- the memory side's issue rate alone
-#define PA_WAIT_VM(n) do {} while (0)
-#else
 #define PA_WAIT_VM(n) __builtin_amdgcn_s_waitcnt(0x0F70 | ((n) & 15) | (((n) >> 4) << 14))   /* vmcnt(n), n < 64 */
-#endif
 #define PA_WAIT_LGKM0() __builtin_amdgcn_s_waitcnt(0xC07F)
-#ifdef PA_FREE_RUN
-#define PA_BARRIER() asm volatile("" ::: "memory")
-#else
 #define PA_BARRIER()                               \
     do {                                           \
         asm volatile("" ::: "memory");             \
         __builtin_amdgcn_s_barrier();              \
         asm volatile("" ::: "memory");             \
     } while (0)
-#endif
 
 // reductions over the 16 lanes of a DPP row (quad swaps, then the two mirrors): every lane ends with the row's result
 #define PA_DPP(x, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, 0xF, 0xF, true))
@@ -123,24 +114,6 @@ __device__ inline half8_t tr_pair(const unsigned char* p0, const unsigned char* 
     return __builtin_bit_cast(half8_t, ab);
 }
 
-#ifndef PA_NO_STORES
-#define PA_NO_STORES 0   // diagnostic: the product without the row stores
-#endif
-#ifndef PA_STUB
-#define PA_STUB 0      // diagnostic builds (tools/vit_attn_stub_probe.py): 1 no MFMAs, 2 + no softmax, 3 + no odd-query passes, 4 + no sleeps
-#endif                 // (memory traffic and barriers only), 5 + no stores; 6 = the product without any vector memory operation
-// Optional stamps (diagnostic build -DVLFM_PHASE_TIMING, tools/vit_attn_phase_probe.py): wavefronts 0 and 4 of workgroup 0 record the
-// shader clock at the phase boundaries of every item they walk.
-#ifdef VLFM_PHASE_TIMING
-__device__ long long g_pa_clk[2][20][12];
-#define PA_STAMP(k)                                                                                              \
-    do {                                                                                                         \
-        if (blockIdx.x == 0 && (tid & 255) == 0 && n < 20) g_pa_clk[tid >> 8][n][k] = __builtin_readcyclecounter(); \
-    } while (0)
-#else
-#define PA_STAMP(k) do {} while (0)
-#endif
-
 __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _Float16* __restrict__ qkv,
                                                                               _Float16* __restrict__ out, int B, int H,
                                                                               float scale) {
@@ -155,22 +128,14 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
     const int nimg = B > xcd ? (B - xcd + 7) >> 3 : 0;      // images of this XCD: xcd, xcd + 8, ...
     if (t / H >= nimg) return;
     auto image_of = [&](int tt) { return xcd + 8 * (tt / H); };
-#ifdef PA_HEAD_MAJOR   // timing experiment only: qkv read as [B][H][3][S][88] (every K / V / Q block contiguous)
-    const int row_halfs = 3 * H * DH, row_bytes = 2 * DH, part_bytes = AT_S * 2 * DH;
-#else
     const int row_halfs = 3 * H * DH, row_bytes = 2 * row_halfs, part_bytes = 2 * H * DH;
-#endif
     // ---- zero the whole LDS once (over-read bytes must be finite)
     for (int i = tid; i < PA_LDS / 16; i += 64 * AT_WAVES) *reinterpret_cast<uint4*>(at_lds + 16 * i) = uint4{0, 0, 0, 0};
     PA_WAIT_LGKM0();
     PA_BARRIER();
     auto item_base = [&](int tt) {
         const int b = image_of(tt), h = tt % H;
-#ifdef PA_HEAD_MAJOR
-        return reinterpret_cast<const unsigned char*>(qkv) + (size_t)(b * H + h) * 3 * AT_S * DH * 2;
-#else
         return reinterpret_cast<const unsigned char*>(qkv) + ((size_t)b * AT_S * row_halfs + (size_t)h * DH) * 2;
-#endif
     };
     // LDS-DMA pieces go through inline asm: hipcc books a global_load_lds builtin as a FLAT operation that touches both memories and,
     // while one is pending, turns every LDS or vector-memory dependency into a wait for ZERO (the operand prefetch of the MFMA loops
@@ -180,7 +145,6 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
     // A vector-memory instruction blocks its wavefront at ISSUE while the CU's queue is full -- 104 KB issued back to back cost 6 000
     // cycles during which nothing else ran -- so the pieces are spread between the MFMAs at about the rate HBM drains them.
     auto dma16 = [&](const unsigned char* sbase, uint32_t voff, int dst) {
-        if (PA_STUB == 6) return;
         unsigned keep;
         const unsigned m0v = (unsigned)__builtin_amdgcn_readfirstlane((int)(size_t)(lds + dst));
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
@@ -213,14 +177,10 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
         int lane = threadIdx.x & 63;
         asm volatile("" : "+v"(lane));
         const int sg = 64 * i + lane, row = sg / 11, s = sg - 11 * row;
-        if (PA_STUB < 5 && !PA_NO_STORES && sg < 352) {
+        if (sg < 352) {
             const int b = image_of(tt), h = tt % H;
             const uint4 v = *reinterpret_cast<const uint4*>(at_lds + bo + (1 + 32 * wave) * PA_KROW + 16 * sg);
-#ifdef PA_CONTIG_OUT   // timing experiment only: head-major output (each (image, head) block of 257 rows contiguous)
-            *reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(out) + ((size_t)(b * H + h) * AT_S + 1 + 32 * wave) * (2 * DH) + 16 * sg) = v;
-#else
             *reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(out) + ((size_t)(b * AT_S + 1 + 32 * wave + row) * H + h) * (2 * DH) + 16 * s) = v;
-#endif
         }
     };
     const unsigned char* base = item_base(t);
@@ -248,7 +208,7 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
             }
             const float inv = 1.0f / lsum;
             const int b = image_of(tt), h = tt % H;
-            if (PA_STUB < 5 && lane < DH / 2)
+            if (lane < DH / 2)
                 *reinterpret_cast<half2_t*>(out + ((size_t)(b * AT_S) * H + h) * DH + 2 * lane) = half2_t{(_Float16)(o0 * inv), (_Float16)(o1 * inv)};
         }
     };
@@ -267,12 +227,9 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
         // would cut the MFMA loops into separate scheduling regions -- at the price of 90 KB of extra L2 traffic per workgroup)
         const unsigned char* base_n = has_next ? item_base(tn) : base;
         const int kb = (n & 1) * PA_KB, ob = PA_KB - kb;
-        PA_STAMP(0);
         // ---- A: K and Q of this item are in LDS (this wavefront's pieces: the last vector-memory operations of the previous item)
         PA_WAIT_VM(0);
-        PA_STAMP(1);
         PA_BARRIER();
-        PA_STAMP(2);
         // the B operand (Q^T) of the wavefront's 32 queries: lane (col, grp) = channels 16 kk + 8 grp .. of row 1 + 32 wave + col;
         // channels 88..95 (kk = 5, upper half) read 16 B of the next row: zeroed
         half8_t qf[AT_D / 16];
@@ -290,8 +247,7 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
 #pragma unroll                                                                // memory queue right behind barrier A
             for (int i = 0; i < 6; i++) store_out(t_prev, ob, i);
         }
-        if (PA_STUB < 3 && t_prev >= 0) merge_odd(t_prev, (n + 1) & 1);
-        PA_STAMP(3);
+        if (t_prev >= 0) merge_odd(t_prev, (n + 1) & 1);
         // ---- the odd query (row 0 of the Q image) against keys 32 wave .. 32 wave + 31 (+ key 256: every wavefront computes it, the last
         // one uses it) on the VALU, BETWEEN the MFMAs of QK^T below (one 16-byte slot per three contraction steps): lane (col, grp)
         // takes channels 48 grp .. of key 32 wave + col (the upper half has 40: its 6th slot is masked)
@@ -314,7 +270,6 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
                 os2 = __builtin_amdgcn_fdot2(half2_t{qv[2 * e], qv[2 * e + 1]}, half2_t{k2[2 * e], k2[2 * e + 1]}, os2, false);
             }
         };
-        PA_STAMP(4);
         // ---- S^T = K Q^T for the wavefront's 32 queries: 9 key tiles x 6 contraction steps; the 7 V pieces of this item in between
         f32x16_t acc[AT_KT];
 #pragma unroll
@@ -334,22 +289,17 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
 #pragma unroll
                         for (int u = 0; u < 3; u++) a_nxt[u] = *reinterpret_cast<const half8_t*>(kbase + 32 * (g0 + u) * PA_KROW + 32 * (kk + 1));
                     }
-#if PA_STUB == 0 || PA_STUB == 6
 #pragma unroll
                     for (int u = 0; u < 3; u++) acc[g0 + u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[u], qf[kk], acc[g0 + u], 0, 0, 0);
-#else
-                    if (g0 == 0 && kk == 0) acc[0][0] = (float)qf[0][0] + (float)qf[1][0] + (float)qf[2][0] + (float)qf[3][0] + (float)qf[4][0] + (float)qf[5][0];
-                    if (PA_STUB < 4) __builtin_amdgcn_s_sleep(4);
-#endif
 #pragma unroll
                     for (int u = 0; u < 3; u++) a_cur[u] = a_nxt[u];
                     const int step = 2 * g0 + kk;          // 0 .. 17
                     if (step >= 1 && step <= 13 && (step & 1)) v_piece(base, step >> 1);     // 7 pieces at steps 1, 3, .., 13
-                    if (PA_STUB < 3 && step % 3 == 0) odd_score_slot(step / 3);              // 6 slots at steps 0, 3, .., 15
+                    if (step % 3 == 0) odd_score_slot(step / 3);              // 6 slots at steps 0, 3, .., 15
                 }
             }
         }
-        if (PA_STUB < 3) {      // the odd query's 32 scores -> probabilities against the wavefront's own maximum (merged later)
+        {   // the odd query's 32 scores -> probabilities against the wavefront's own maximum (merged later)
             float s = os + __shfl_xor(os, 32, 64);
             const float s2 = os2 + __shfl_xor(os2, 32, 64);
             const bool last = wave == AT_WAVES - 1;
@@ -363,13 +313,12 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
             if (grp == 0) reinterpret_cast<float*>(at_lds + PA_PS_OFF)[32 * wave + col] = ps;    // read back (broadcast) by the odd query's P V
             if (lane == 0) { mine[96] = m; mine[97] = l + p2; mine[98] = p2; }
         }
-        PA_STAMP(5);
         // ---- C: every wavefront is done with K (and with the odd query's row, and has read its staged rows out of the other buffer)
         PA_BARRIER();
         // ---- softmax of the 32 main queries: accumulator register r of tile tt = key 32 tt + (r & 3) + 8 (r >> 2) + 4 grp
         float m = -__builtin_huge_valf();
 #pragma unroll
-        for (int tt = 0; tt < (PA_STUB >= 2 && PA_STUB < 6 ? 1 : AT_KT); tt++) {
+        for (int tt = 0; tt < AT_KT; tt++) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 if (32 * tt + (r & 3) + 8 * (r >> 2) + 4 * grp >= AT_S) acc[tt][r] = -__builtin_huge_valf();
@@ -385,26 +334,19 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
         half8_t pb[NCH];
 #pragma unroll
         for (int ch = 0; ch < NCH; ch++) {
-            if (PA_STUB < 2 || PA_STUB == 6 || ch == 0) {
 #pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const float p = __builtin_amdgcn_exp2f(fmaf(acc[ch >> 1][8 * (ch & 1) + j], c, mc));
-                    l += p;
-                    pb[ch][j] = (_Float16)p;
-                }
-            } else {
-                pb[ch] = pb[0];
+            for (int j = 0; j < 8; j++) {
+                const float p = __builtin_amdgcn_exp2f(fmaf(acc[ch >> 1][8 * (ch & 1) + j], c, mc));
+                l += p;
+                pb[ch][j] = (_Float16)p;
             }
             if (ch % 3 == 1) q_piece(base_n, kb, ch / 3);       // the 6 Q pieces of the next item -> this item's K buffer
         }
         l += __shfl_xor(l, 32, 64);
         // ---- B: V of this item is in LDS (this wavefront's pieces: older than the 6 Q pieces)
-        PA_STAMP(6);
         PA_WAIT_VM(6);
         PA_WAIT_LGKM0();
-        PA_STAMP(7);
         PA_BARRIER();
-        PA_STAMP(8);
         // ---- the odd query's share of P V runs BETWEEN the PV MFMAs below (two keys per 16-key chunk): lane = channel pair, its 32
         // probabilities are read back from LDS (one address per instruction: a broadcast)
         const int cp = min(lane, 47);
@@ -417,7 +359,6 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
             oo0[k & 1] = fmaf(pk, (float)vv[0], oo0[k & 1]);
             oo1[k & 1] = fmaf(pk, (float)vv[1], oo1[k & 1]);
         };
-        PA_STAMP(9);
         // ---- O^T = V^T P^T: per 16-key chunk three channel tiles; the A operand (32 channels x 16 keys) comes out of the row-major V
         // by two ds_read_b64_tr_b16: a 16-lane group addresses a [4 keys][16 channels] block (lane j: key j >> 2, channels 4 (j & 3) ..)
         // and lane j receives channel j of the 4 keys.  Keys behind the 8 operand elements: 16 ch + 4 grp + (0..3), then + 8.
@@ -440,29 +381,21 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
                     for (int dt = 0; dt < AT_D / 32; dt++)
                         v_nxt[dt] = tr_pair(vb + 16 * (ch + 1) * PA_VROW + 64 * dt, vb + 16 * (ch + 1) * PA_VROW + 64 * dt + 8 * PA_VROW);
                 }
-#if PA_STUB == 0 || PA_STUB == 6
 #pragma unroll
                 for (int dt = 0; dt < AT_D / 32; dt++) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v_cur[dt], pb[ch], o[dt], 0, 0, 0);
-#else
-                if (ch == 0) { o[0][0] = (float)pb[0][0]; }
-                if (PA_STUB < 4) __builtin_amdgcn_s_sleep(4);
-#endif
 #pragma unroll
                 for (int dt = 0; dt < AT_D / 32; dt++) v_cur[dt] = v_nxt[dt];
                 if (ch >= 2 && ch <= 12 && !(ch & 1)) k_piece(base_n, ob, (ch - 2) >> 1);     // the 6 K pieces of the next item
-                if (PA_STUB < 3 || PA_STUB == 6) {
-                    if (ch < 16) { odd_pv_key(2 * ch); odd_pv_key(2 * ch + 1); }
-                }
+                if (ch < 16) { odd_pv_key(2 * ch); odd_pv_key(2 * ch + 1); }
             }
         }
-        if (PA_STUB < 3 || PA_STUB == 6) {       // key 256 (p2 is zero except in the last wavefront), then the partial sums
+        {   // key 256 (p2 is zero except in the last wavefront), then the partial sums
             const half2_t vv = *reinterpret_cast<const half2_t*>(at_lds + PA_V_OFF + 256 * PA_VROW + 4 * cp);
             const float p2 = mine[98];
             oo0[0] = fmaf(p2, (float)vv[0], oo0[0]);
             oo1[0] = fmaf(p2, (float)vv[1], oo1[0]);
             if (lane < 48) *reinterpret_cast<float2*>(mine + 2 * lane) = float2{oo0[0] + oo0[1], oo1[0] + oo1[1]};
         }
-        PA_STAMP(10);
         // ---- normalise; the rows stay in registers (f16) until the next item's Q has been read out of the buffer that stages them
         {
             const float inv = 1.0f / l;
@@ -480,7 +413,6 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
             }
         }
         PA_WAIT_LGKM0();     // the partials are written before the next barrier A
-        PA_STAMP(11);
         t_prev = t;
         if (!has_next) break;
         t = tn;
@@ -494,7 +426,7 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
 #pragma unroll
     for (int i = 0; i < 6; i++) store_out(t_prev, (n & 1) * PA_KB, i);
     PA_BARRIER();
-    if (PA_STUB < 3) merge_odd(t_prev, n & 1);
+    merge_odd(t_prev, n & 1);
 }
 
 }  // namespace vlfm
@@ -521,9 +453,3 @@ extern "C" int vlfm_vit_attention_f16(const void* d_qkv, void* d_out, int batch,
                  (_Float16*)d_out, batch, heads, scale);
     return check_launch("vit_attention_kernel");
 }
-
-#ifdef VLFM_PHASE_TIMING
-extern "C" int vlfm_debug_attention_pers_clocks(long long* h_out480) {
-    return hipMemcpyFromSymbol(h_out480, HIP_SYMBOL(g_pa_clk), sizeof(long long) * 480) == hipSuccess ? VLFM_OK : VLFM_ERR_HIP;
-}
-#endif

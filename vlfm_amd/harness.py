@@ -296,20 +296,17 @@ class BatchedEpisodes:
         # runs each (profiles/r05_side_stream_priority.txt): 726-738 env-steps/s at priority 0 (other boxes: 845-849, i.e. the slow
         # mode is box- or run-dependent) against 819-828 at priority -1; at 64 environments the priority costs 7 % (746-767 -> 702-715:
         # there the forward is the shorter part and is the one being pushed aside), so it is not set below 128.
-        # VLFM_SIDE_PRIORITY overrides (diagnostic).
         full_step = detector is not None and object_maps
-        prio = int(os.environ["VLFM_SIDE_PRIORITY"]) if "VLFM_SIDE_PRIORITY" in os.environ else (-1 if n_envs >= 128 and full_step else 0)
+        prio = -1 if n_envs >= 128 and full_step else 0
         self.map_stream = torch.cuda.Stream(self.device, priority=prio) if overlap else None
         self.obj_stream = torch.cuda.Stream(self.device, priority=prio) if overlap else None
         # (the object stream alone at priority -1: 790-796; both: 819-828; the headline -- no detector -- keeps priority 0: -0.3 % with it)
-        # Optional (concurrent_vlm_max_envs > 0, VLFM_VLM_BESIDE): at small batches neither the detector (a HIP graph of ~1 700 short
+        # Optional (concurrent_vlm_max_envs > 0): at small batches neither the detector (a HIP graph of ~1 700 short
         # kernels for GroundingDINO) nor the BLIP-2 forward of 8 frames fills the chip, so the BLIP-2 forward can be enqueued FIRST,
         # on its own stream, with the detector beside it.  Measured in round 5 (profiles/r05_full_step_ab.txt): 323.6 -> 323.5
         # env-steps/s at 8 environments (YOLOv7-E6E), 184 -> 185 with GroundingDINO, 783 -> 672 at 64: no gain -- the 8-environment
         # step is bound by the host's launch rate and its read-backs, not by GPU occupancy -- so it is OFF by default; the
         # equivalence test (tests/test_full_step_gpu.py) keeps the path honest.
-        if os.environ.get("VLFM_VLM_BESIDE") is not None:      # diagnostic override (A/B runs): 0 = never, n = up to n environments
-            concurrent_vlm_max_envs = int(os.environ["VLFM_VLM_BESIDE"])
         self.vlm_stream = torch.cuda.Stream(self.device) if overlap and n_envs <= concurrent_vlm_max_envs else None
         self.last_cosines: Optional[torch.Tensor] = None
         self.last_frontier_values: Optional[np.ndarray] = None

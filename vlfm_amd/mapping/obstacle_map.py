@@ -65,15 +65,13 @@ class ObstacleMapBatch:
         # (y0, y1, x0, x1), empty when y1 < y0.  `_dirty_obst`: cells whose obstacle bit may have changed since `navigable`
         # was last recomputed (union of the reach windows of the frames ingested); `_dirty_nav`: cells whose `navigable` bit
         # may have changed since the last explore step.  A fresh slot starts with the whole map (first pass = the
-        # reference's full-map pass).  VLFM_FULL_PLANES=1 hands over NULL windows: the full-plane kernels, for A/B runs.
+        # reference's full-map pass).  `full_planes = True` hands over NULL windows: the full-plane kernels (tests compare the two).
         self._dirty_obst = np.tile(np.array([0, size - 1, 0, size - 1], np.int32), (n_envs, 1))
         self._dirty_nav = self._dirty_obst.copy()
         # host mirror of the device's bounding box of everything ever revealed (fog_of_war_kernel: agent cell +- (R + 2))
         self._bbox_host = np.tile(np.array([0, -1, 0, -1], np.int32), (n_envs, 1))
         self._ring_win = UploadRing(self.device, n_envs * 48, slots=8)
-        import os
-
-        self.full_planes = os.environ.get("VLFM_FULL_PLANES", "0") == "1"
+        self.full_planes = False
         # read-back path of the step: fixed-size staging + pinned host buffers, so a step never allocates and never
         # hands the runtime a pageable destination (which it would have to pin on the fly)
         self._d_fr_stage = torch.zeros((n_envs, self.READ_FRONTIERS, 2), dtype=torch.float64, device=self.device)

@@ -72,23 +72,6 @@ def x_is_contiguous_f16(t: torch.Tensor) -> bool:
     return t.dtype == torch.float16 and t.is_contiguous()
 
 
-def _default_hip_gemms() -> frozenset:
-    import os
-
-    v = os.environ.get("VLFM_VIT_GEMMS")
-    if v is None:
-        return frozenset(DEFAULT_HIP_GEMMS)
-    v = v.strip().lower()
-    if v == "all":
-        return frozenset(("qkv", "proj", "fc1", "fc2"))
-    if v in ("none", ""):
-        return frozenset()
-    names = frozenset(t.strip() for t in v.split(","))
-    if not names <= {"qkv", "proj", "fc1", "fc2"}:
-        raise ValueError(f"VLFM_VIT_GEMMS={v!r}: expected all, none or a comma list of qkv, proj, fc1, fc2")
-    return names
-
-
 class _VitBlock(nn.Module):
     def __init__(self, c: Blip2ITCConfig):
         super().__init__()
@@ -111,8 +94,8 @@ class _VitBlock(nn.Module):
         # went from 9.47 to 9.85 ms); 0 = always the library GEMM + a separate GELU pass
         self.hip_mlp_min_rows = 32 * 257
         # which of the block's four GEMMs run on csrc/gemm_f16.hip's 8-phase kernel once the GEMM has hip_mlp_min_rows rows (the
-        # others go to hipBLASLt): any of "qkv", "proj", "fc1", "fc2".  VLFM_VIT_GEMMS = all | none | a comma list overrides.
-        self.hip_gemms = _default_hip_gemms()
+        # others go to hipBLASLt): any of "qkv", "proj", "fc1", "fc2".
+        self.hip_gemms = frozenset(DEFAULT_HIP_GEMMS)
 
     def pack_heads(self, multiple: int = 32) -> None:
         """Inference-time repacking for the attention kernel: the 88-wide heads of ViT-g are zero-padded to the next
@@ -255,7 +238,7 @@ def _split_gemm(x16: torch.Tensor, pieces, bias: torch.Tensor, n_pieces: Optiona
     return o
 
 
-QFORMER_SPLIT_MIN_ROWS = int(os.environ.get("VLFM_QFORMER_SPLIT_MIN_ROWS", "2048"))   # rows (images x 32 queries) from which the Q-Former's f32 Linears go to csrc/gemm_f32.hip
+QFORMER_SPLIT_MIN_ROWS = 2048   # rows (images x 32 queries) from which the Q-Former's f32 Linears go to csrc/gemm_f32.hip
 
 
 def _qlinear(x: torch.Tensor, lin_w: torch.Tensor, lin_b, act=None, residual=None) -> torch.Tensor:
