@@ -13,7 +13,9 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(4096, 96, 96), (4096, 384, 96), (2500, 96, 384), (1200, 1536, 384), (3000, 2048, 256), (3000, 256, 2048),
           (6380, 1024, 256), (900, 256, 256), (777, 132, 64), (130, 36, 32),
           # the split form's 256-wide tile (N % 256 == 0 or N >= 640): full tiles, an n tail inside a wide tile, an m tail
-          (1000, 768, 192), (515, 2304, 96), (2049, 640, 64), (300, 1152, 384)]
+          (1000, 768, 192), (515, 2304, 96), (2049, 640, 64), (300, 1152, 384),
+          # the BLIP-2 Q-Former's Linears at 256 images (8192 query rows): attention / output, intermediate, output of the MLP
+          (8192, 768, 768), (8192, 3072, 768), (8192, 768, 3072)]
 
 
 def _err(got, ref64, scale):
@@ -86,8 +88,11 @@ def test_exact_form_is_a_k_ordered_fma_chain(gpu_device):
 def test_split_form_flags_operands_outside_f16_range(gpu_device):
     from vlfm_amd.vlm import ops
 
-    x = torch.randn(256, 64, device=gpu_device)
-    w = torch.randn(64, 64, device=gpu_device)
+    # seeded: at 3e-6 the hi part is f16-subnormal and so is lo', which leaves ~2e-6 of each x (not 2^-24).  The bound below then
+    # holds for ~99 % of random w (the error is that x error times sum_k w_k), so the data must not depend on which tests ran first
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(256, 64, generator=g).to(gpu_device)
+    w = torch.randn(64, 64, generator=g).to(gpu_device)
     flag = ops.gemm_f32_overflow_flag(gpu_device)
     flag.zero_()
     ops.linear_f32(x, w, precision="split")

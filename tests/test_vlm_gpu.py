@@ -81,7 +81,7 @@ def test_itc_head_vs_fp32_reference(gpu_device):
     from vlfm_amd.vlm import ops
 
     g = torch.Generator().manual_seed(0)
-    for (B, NQ, H, P) in [(5, 32, 768, 256), (2, 5, 24, 8), (1, 32, 768, 256)]:
+    for (B, NQ, H, P) in [(5, 32, 768, 256), (2, 5, 24, 8), (1, 32, 768, 256), (256, 32, 768, 256), (257, 32, 768, 256)]:
         q = torch.randn(B, NQ, H, generator=g)
         w = torch.randn(P, H, generator=g) * 0.05
         b = torch.randn(P, generator=g) * 0.1

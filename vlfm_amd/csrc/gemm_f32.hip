@@ -8,7 +8,8 @@
 //                saturated by one wavefront per SIMD, LDS and HBM are nearly idle -- what matters is never to stall the pipe.
 //   precision 1  SPLIT: every f32 operand a is written as hi + 2^-11 lo' with hi = f16(a), lo' = f16((a - hi) 2^11): the
 //                remainder a - hi is exact in f32 and has at most 13 significant bits, of which lo' keeps 11, so
-//                |a - (hi + 2^-11 lo')| <= 2^-24 |a| -- f32's own unit roundoff.  Then a b = hi_a hi_b + 2^-11 (hi_a lo'_b + lo'_a hi_b)
+//                |a - (hi + 2^-11 lo')| <= 2^-24 |a| -- f32's own unit roundoff -- for |a| >= 2^-14; below, hi and lo' are
+//                f16-subnormal and the bound is 2^-36 absolute instead (2e-6 relative at 3e-6).  Then a b = hi_a hi_b + 2^-11 (hi_a lo'_b + lo'_a hi_b)
 //                + O(2^-24 |a b|): THREE v_mfma_f32_32x32x16_f16 (exact 22-bit products, f32 accumulation) in place of eight
 //                32x32x2_f32, i.e. 16 / 3 = 5.3 x the matrix rate of the exact form (833 TFLOP/s-equivalent peak).  The two cross terms
 //                share one accumulator that is scaled by 2^-11 in the epilogue.  |a| >= 65504 cannot be represented: the kernel

@@ -76,6 +76,11 @@ constexpr int PA_PS_OFF = PA_PART_OFF + 2 * AT_WAVES * PA_PART * 4;   // 152 576
 constexpr int PA_LDS = PA_PS_OFF + AT_WAVES * 32 * 4;                 // 153 600
 constexpr int PA_KPIECES = 6, PA_VPIECES = 7, PA_QPIECES = 6, PA_KPITCH = 59, PA_VPITCH = 56;
 constexpr int PA_KSLOTS = AT_S * 11, PA_VSLOTS = AT_S * 12;
+// The vmcnt waits count instructions, so every q_piece and store_out instruction must move bytes in at least one lane of every
+// (wave, j): the first lane of the last Q piece of the last wavefront lies inside the image, and that of the last store inside the
+// wavefront's 352 slots.
+static_assert(32 * 11 * (AT_WAVES - 1) + 64 * (PA_QPIECES - 1) < PA_KSLOTS, "a Q piece with no active lane");
+static_assert(64 * 5 < 32 * 11, "a store_out instruction with no active lane");
 
 using lds_ptr = __attribute__((address_space(3))) unsigned char*;
 using gbl_ptr = const __attribute__((address_space(1))) unsigned char*;
