@@ -127,7 +127,8 @@ typedef struct {
  * In this mode a texel that falls off the map is only NOTED by the ingest (status word 1, bit 1): whether the reference
  * would have scattered it is decided by fill_small_holes, which promotes the note to VLFM_ERR_INDEX in status word 0
  * unless the frame has islands (their surviving texels are placed, and judged, again by the hole scatter).
- * Observations of one call must belong to distinct environment slots when a journal is used. */
+ * Observations of one call must belong to distinct environment slots when a journal is used -- or go through the *_rig_batched
+ * forms of the two follow-up calls below. */
 typedef struct {
     uint32_t* d_cells;    /* [n][capacity] */
     int32_t* d_count;     /* [n] */
@@ -186,6 +187,24 @@ int vlfm_depth_scatter_holes_batched(const vlfm_ingest_params* d_params, int n, 
                                      const float* d_depth /* [n][H][W]: read for island frames only; NULL = never */,
                                      void* stream);
 
+/* Camera rig: the same two calls when SEVERAL observations of the launch may belong to one slot (the robot's body cameras,
+ * reality_policies.py:113-138: the obstacle scatter is a pure OR, so the cameras of a step commute in the reference).  The
+ * speculative pass journals a bit for the ONE observation that set it first; if that observation turns out to be an island
+ * frame the undo would remove a bit a sibling frame legitimately placed (sequentially, the island frame would have been
+ * undone before the sibling ran).  d_slot_undone [n_envs] int32 (zeroed by the fill call) is set for every slot that had a
+ * frame undone; the scatter call then places the valid texels outside the filled area of EVERY frame of such a slot again,
+ * from d_depth (required).  Frames of slots without an island frame are read once, as in the single-camera form. */
+int vlfm_fill_small_holes_rig_batched(const uint32_t* d_hole_bits, const int32_t* d_status, int n, int height, int width,
+                                      double area_thresh, void* d_scratch, size_t scratch_bytes, int cap_pts,
+                                      int cap_contours, uint32_t* d_filled_bits, int32_t* d_counts,
+                                      const vlfm_ingest_params* d_params, uint32_t* d_obstacle, int map_size,
+                                      const vlfm_scatter_journal* journal, int32_t* d_slot_undone, int n_envs, void* stream);
+int vlfm_depth_scatter_holes_rig_batched(const vlfm_ingest_params* d_params, int n, int height, int width,
+                                         const uint32_t* d_hole_bits, const uint32_t* d_filled_bits,
+                                         const int32_t* d_hole_counts, uint32_t* d_obstacle, int map_size,
+                                         int pixels_per_meter, int32_t* d_status, const float* d_depth,
+                                         const int32_t* d_slot_undone, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * ValueMap.update_map for n observations (value_map.py:100-128 = :221-260 + :288-319 + :357-429) in ONE launch: every workgroup
  * rasterises the depth-profile polygon of its observation into LDS itself, so no visibility plane goes through HBM and no scratch
@@ -220,6 +239,43 @@ int vlfm_value_map_update_fused_batched(uint32_t* d_colmax_keys, int width, cons
                                         double min_depth, double max_depth, int use_max_confidence, int fusion_type,
                                         const uint32_t* d_explored_bits, uint32_t* d_written_bits, int32_t* d_counters,
                                         const float* d_conf_quadrant, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Camera rig: ValueMap.update_map for n observations of which SEVERAL may belong to one environment slot, in one launch.
+ * The observations of a slot are applied in the order given -- exactly the reference's sequential loop over its cameras
+ * (itm_policy.py:191-211; reality_policies.py:113-141), whose weighted fuse does not commute -- and different slots run
+ * concurrently.  The result equals n single-observation calls of vlfm_value_map_update_fused_batched bit for bit.
+ * Each observation brings its own optics (the reference passes min_depth / max_depth / fov per camera):
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float* d_template;         /* [T*T] masked confidence template of (fov, max_depth) (not read by the kernel today) */
+    const uint32_t* d_template_bits; /* [T][ceil(T/32)] its (> 0) bit plane */
+    const float* d_conf_quadrant;    /* [(T/2+1)^2] quadrant of the unmasked table */
+    const double* d_tan;             /* [W] tan table of (fov, W) */
+    float depth_scale;               /* f32(max_depth - min_depth) */
+    float depth_offset;              /* f32(min_depth) */
+    int32_t template_size;           /* T = 2*int(max_depth*ppm)+1 */
+    int32_t reserved;
+} vlfm_vm_optics;                    /* 48 bytes */
+
+/*   d_pose / d_optics [n]  GROUPED BY SLOT: the observations of a slot are consecutive and in application order;
+ *                          d_pose[i].reserved = the observation's row in d_colmax_keys, d_values and d_counters (its position
+ *                          in the caller's own list, so that keys written by a depth ingest need no reordering)
+ *   d_slots [n_slots][2]   int32 (first, count) into d_pose / d_optics, one entry per slot present in the call
+ *   max_template_size      the largest template_size among d_optics (sizes the workgroup's LDS).  d_optics is device data:
+ *                          the call cannot check it, a record with a larger template_size would overrun the LDS arrays
+ *   all observations share the image width (mixed widths: separate calls); the other arguments are those of
+ *   vlfm_value_map_update_fused_batched.  With d_explored_bits the (written & ~explored) clear runs once per slot before
+ *   its first camera (the plane does not change within the call, and fused cells are explored ones), the mask applies to
+ *   every camera.
+ * Scheduling: grid (G, n_slots); 8-row tile b of the MAP belongs to workgroup b mod G of its slot for the whole launch, so a
+ * map cell has one owner and no workgroup ever waits for another one. */
+int vlfm_value_map_update_rig_batched(uint32_t* d_colmax_keys, int width, const vlfm_vm_pose* d_pose,
+                                      const vlfm_vm_optics* d_optics, const int32_t* d_slots, int n_slots, int n,
+                                      int max_template_size, const double* d_values, float* d_conf, double* d_value,
+                                      int map_size, int channels, int pixels_per_meter, int use_max_confidence,
+                                      int fusion_type, const uint32_t* d_explored_bits, uint32_t* d_written_bits,
+                                      int32_t* d_counters, void* stream);
 
 /* ValueMap.sort_waypoints scoring (value_map.py:146-187 + img_utils.py:213-266): per waypoint and channel the
  * median of the positive cells inside the radius disc, -1 if none.

@@ -51,7 +51,13 @@ class ScatterJournal(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
-assert ctypes.sizeof(ScatterJournal) == 24
+class VmOptics(ctypes.Structure):
+    _fields_ = [("d_template", ctypes.c_void_p), ("d_template_bits", ctypes.c_void_p), ("d_conf_quadrant", ctypes.c_void_p),
+                ("d_tan", ctypes.c_void_p), ("depth_scale", ctypes.c_float), ("depth_offset", ctypes.c_float),
+                ("template_size", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(ScatterJournal) == 24 and ctypes.sizeof(VmOptics) == 48
 assert ctypes.sizeof(VmPose) == 64 and ctypes.sizeof(IngestParams) == 152 and ctypes.sizeof(FogParams) == 48 + 16 * FOG_MAX_POLY
 
 
@@ -118,6 +124,9 @@ def lib() -> ctypes.CDLL:
         L.vlfm_fill_small_holes_batched.argtypes = [vp, vp, ci, ci, ci, cd, vp, ctypes.c_size_t, ci, ci, vp, vp, vp, vp,
                                                     ci, vp, vp]
         L.vlfm_depth_scatter_holes_batched.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp]
+        L.vlfm_fill_small_holes_rig_batched.argtypes = [vp, vp, ci, ci, ci, cd, vp, ctypes.c_size_t, ci, ci, vp, vp, vp, vp,
+                                                        ci, vp, vp, ci, vp]
+        L.vlfm_depth_scatter_holes_rig_batched.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]
         L.vlfm_layernorm_bias_f16.argtypes = [vp, vp, vp, vp, vp, ci, ci, ctypes.c_float, vp]
         L.vlfm_vit_attention_f16.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_float, vp]
         L.vlfm_gemm_f16_nt.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
@@ -135,6 +144,8 @@ def lib() -> ctypes.CDLL:
         L.vlfm_conv_nhwc_f16.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
         L.vlfm_value_map_update_fused_batched.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, ci, ci, cd, cd,
                                                           ci, ci, vp, vp, vp, vp, vp]
+        L.vlfm_value_map_update_rig_batched.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp,
+                                                        vp, vp]
         L.vlfm_value_map_sort_waypoints_batched.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, vp, vp]
         L.vlfm_resample_coeffs_host.argtypes = [ci, ci, vp, vp, ci, ctypes.POINTER(ci)]
         L.vlfm_resample_coeffs_filter_host.argtypes = [ci, ci, ci, vp, vp, ci, ctypes.POINTER(ci)]

@@ -44,6 +44,10 @@ struct HoleArgs {
     unsigned* journal;              // [n][journal_cap]
     int* journal_count;             // [n]
     int journal_cap, S, stride;
+    // camera rig (several observations of one slot in the launch), or null: [n_envs] flag "a frame of this slot had its
+    // journalled bits taken back".  A sibling frame may have found one of those bits already set and journalled nothing for
+    // it, so hole_scatter_kernel places the valid texels of EVERY frame of a flagged slot again.
+    int* slot_undone;
 };
 
 __global__ __launch_bounds__(256) void fill_small_holes_kernel(HoleArgs a) {
@@ -173,6 +177,7 @@ __global__ __launch_bounds__(256) void fill_small_holes_kernel(HoleArgs a) {
                 const unsigned row = cell / (unsigned)a.S, col = cell % (unsigned)a.S;
                 atomicAnd(&grid[(size_t)row * a.stride + (col >> 5)], ~(1u << (col & 31)));
             }
+            if (a.slot_undone && tid == 0) atomicOr(&a.slot_undone[a.prm[obs].env], 1);
             __threadfence();
         }
     }
@@ -212,11 +217,11 @@ extern "C" size_t vlfm_hole_scratch_bytes(int n, int height, int width, int cap_
     return hole_layout(n, height, width, cap_pts, cap_contours).total;
 }
 
-extern "C" int vlfm_fill_small_holes_batched(const uint32_t* d_hole_bits, const int32_t* d_status, int n, int height,
-                                             int width, double area_thresh, void* d_scratch, size_t scratch_bytes,
-                                             int cap_pts, int cap_contours, uint32_t* d_filled_bits, int32_t* d_counts,
-                                             const vlfm_ingest_params* d_params, uint32_t* d_obstacle, int map_size,
-                                             const vlfm_scatter_journal* journal, void* stream) {
+static int fill_small_holes_impl(const uint32_t* d_hole_bits, const int32_t* d_status, int n, int height, int width,
+                                 double area_thresh, void* d_scratch, size_t scratch_bytes, int cap_pts, int cap_contours,
+                                 uint32_t* d_filled_bits, int32_t* d_counts, const vlfm_ingest_params* d_params,
+                                 uint32_t* d_obstacle, int map_size, const vlfm_scatter_journal* journal,
+                                 int32_t* d_slot_undone, void* stream) {
     if (n == 0) return VLFM_OK;
     if (!d_hole_bits || !d_status || !d_scratch || !d_filled_bits || !d_counts || n < 0 || height <= 0 || width <= 0 ||
         width > 2048 || cap_pts <= 0 || cap_contours <= 0)
@@ -235,6 +240,7 @@ extern "C" int vlfm_fill_small_holes_batched(const uint32_t* d_hole_bits, const 
     a.area_thresh = area_thresh;
     a.prm = nullptr; a.obstacle = nullptr; a.journal = nullptr; a.journal_count = nullptr; a.journal_cap = 0;
     a.S = map_size; a.stride = (map_size + 31) / 32;
+    a.slot_undone = d_slot_undone;
     if (journal && journal->d_cells && journal->d_count && journal->capacity > 0) {
         if (!d_params || !d_obstacle || map_size <= 0)
             return fail(VLFM_ERR_INVALID, "fill_small_holes_batched: a journal needs d_params, d_obstacle and map_size");
@@ -244,4 +250,29 @@ extern "C" int vlfm_fill_small_holes_batched(const uint32_t* d_hole_bits, const 
     VLFM_TIMED("fill_small_holes_kernel", stream);
     VLFM_KLAUNCH(fill_small_holes_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("fill_small_holes_kernel");
+}
+
+extern "C" int vlfm_fill_small_holes_batched(const uint32_t* d_hole_bits, const int32_t* d_status, int n, int height,
+                                             int width, double area_thresh, void* d_scratch, size_t scratch_bytes,
+                                             int cap_pts, int cap_contours, uint32_t* d_filled_bits, int32_t* d_counts,
+                                             const vlfm_ingest_params* d_params, uint32_t* d_obstacle, int map_size,
+                                             const vlfm_scatter_journal* journal, void* stream) {
+    return fill_small_holes_impl(d_hole_bits, d_status, n, height, width, area_thresh, d_scratch, scratch_bytes, cap_pts,
+                                 cap_contours, d_filled_bits, d_counts, d_params, d_obstacle, map_size, journal, nullptr, stream);
+}
+
+extern "C" int vlfm_fill_small_holes_rig_batched(const uint32_t* d_hole_bits, const int32_t* d_status, int n, int height,
+                                                 int width, double area_thresh, void* d_scratch, size_t scratch_bytes,
+                                                 int cap_pts, int cap_contours, uint32_t* d_filled_bits, int32_t* d_counts,
+                                                 const vlfm_ingest_params* d_params, uint32_t* d_obstacle, int map_size,
+                                                 const vlfm_scatter_journal* journal, int32_t* d_slot_undone, int n_envs,
+                                                 void* stream) {
+    if (n == 0) return VLFM_OK;
+    if (!d_slot_undone || n_envs <= 0 || !journal)
+        return fail(VLFM_ERR_INVALID, "fill_small_holes_rig_batched: needs a journal and d_slot_undone [n_envs]");
+    if (hipMemsetAsync(d_slot_undone, 0, (size_t)n_envs * sizeof(int32_t), (hipStream_t)stream) != hipSuccess)
+        return fail(VLFM_ERR_HIP, "fill_small_holes_rig_batched: memset failed");
+    return fill_small_holes_impl(d_hole_bits, d_status, n, height, width, area_thresh, d_scratch, scratch_bytes, cap_pts,
+                                 cap_contours, d_filled_bits, d_counts, d_params, d_obstacle, map_size, journal, d_slot_undone,
+                                 stream);
 }

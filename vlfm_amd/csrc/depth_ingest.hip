@@ -416,13 +416,20 @@ __global__ __launch_bounds__(CG * RL) void depth_ingest_kernel(IngestArgs a) { d
 // The zero texels that fill_small_holes left alone (holes of area >= hole_area_thresh), placed from the bit planes: the
 // depth images are not read again.  One thread per 32-texel word of (hole & ~filled); frames without a zero texel
 // (counts[3] == 0, the common case) cost one early exit per workgroup.
-__global__ __launch_bounds__(256) void hole_scatter_kernel(IngestArgs a, const int* counts) {
+// Camera rig (`slot_undone` [n_envs], else null): when a frame of a slot had its journalled bits taken back, a sibling frame of
+// the same launch may have found one of those bits set and journalled nothing for it -- sequentially the island frame would
+// have been undone before the sibling ran.  Every frame of a flagged slot therefore places its valid texels outside the
+// filled area again (for a frame without islands: all of them), which restores exactly the bits the sequential order keeps.
+__global__ __launch_bounds__(256) void hole_scatter_kernel(IngestArgs a, const int* counts, const int* slot_undone) {
     const int obs = blockIdx.y;
-    if (counts[(size_t)obs * 4 + 3] == 0) return;
+    const int c3 = counts[(size_t)obs * 4 + 3];
+    if (c3 == 0 && !slot_undone) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.H * a.hw) return;
     const vlfm_ingest_params p = a.prm[obs];
     if (!(p.scatter & 1) || (p.scatter & 2)) return;
+    const bool again = slot_undone && slot_undone[p.env] != 0;
+    if (c3 == 0 && !again) return;
     const unsigned hole = a.hole_bits[(size_t)obs * a.H * a.hw + i], filled = a.filled_bits[(size_t)obs * a.H * a.hw + i];
     unsigned w = hole & ~filled;
     const int v = i / a.hw, u0 = (i % a.hw) * 32;
@@ -431,7 +438,7 @@ __global__ __launch_bounds__(256) void hole_scatter_kernel(IngestArgs a, const i
     // its newly set bits were taken back by fill_small_holes_kernel, so every valid texel OUTSIDE the filled area is
     // placed again here, from the image (rows that cannot reach the height band are skipped).
     unsigned redo = 0u;
-    if ((counts[(size_t)obs * 4 + 3] & 2) && a.depth && row_may_hit(band, v, a.H)) {
+    if (((c3 & 2) || again) && a.depth && row_may_hit(band, v, a.H)) {
         redo = ~hole & ~filled;
         if (u0 + 32 > a.W) redo &= (a.W - u0 >= 32) ? 0xFFFFFFFFu : ((1u << (a.W - u0)) - 1u);
     }
@@ -472,11 +479,10 @@ extern "C" int vlfm_selftest_div_exact(const double* d_numerators, int n, double
     return check_launch("div_exact_check_kernel");
 }
 
-extern "C" int vlfm_depth_scatter_holes_batched(const vlfm_ingest_params* d_params, int n, int height, int width,
-                                                const uint32_t* d_hole_bits, const uint32_t* d_filled_bits,
-                                                const int32_t* d_hole_counts, uint32_t* d_obstacle, int map_size,
-                                                int pixels_per_meter, int32_t* d_status, const float* d_depth,
-                                                void* stream) {
+static int depth_scatter_holes_impl(const vlfm_ingest_params* d_params, int n, int height, int width,
+                                    const uint32_t* d_hole_bits, const uint32_t* d_filled_bits,
+                                    const int32_t* d_hole_counts, uint32_t* d_obstacle, int map_size, int pixels_per_meter,
+                                    int32_t* d_status, const float* d_depth, const int32_t* d_slot_undone, void* stream) {
     if (n == 0) return VLFM_OK;
     if (!d_params || !d_hole_bits || !d_filled_bits || !d_hole_counts || !d_obstacle || !d_status || n < 0 ||
         height <= 0 || width <= 0)
@@ -488,8 +494,28 @@ extern "C" int vlfm_depth_scatter_holes_batched(const vlfm_ingest_params* d_para
     a.ppm = (double)pixels_per_meter;
     VLFM_TIMED("hole_scatter_kernel", stream);
     VLFM_KLAUNCH(hole_scatter_kernel, dim3((a.H * a.hw + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, a,
-                 d_hole_counts);
+                 d_hole_counts, d_slot_undone);
     return check_launch("hole_scatter_kernel");
+}
+
+extern "C" int vlfm_depth_scatter_holes_batched(const vlfm_ingest_params* d_params, int n, int height, int width,
+                                                const uint32_t* d_hole_bits, const uint32_t* d_filled_bits,
+                                                const int32_t* d_hole_counts, uint32_t* d_obstacle, int map_size,
+                                                int pixels_per_meter, int32_t* d_status, const float* d_depth,
+                                                void* stream) {
+    return depth_scatter_holes_impl(d_params, n, height, width, d_hole_bits, d_filled_bits, d_hole_counts, d_obstacle, map_size,
+                                    pixels_per_meter, d_status, d_depth, nullptr, stream);
+}
+
+extern "C" int vlfm_depth_scatter_holes_rig_batched(const vlfm_ingest_params* d_params, int n, int height, int width,
+                                                    const uint32_t* d_hole_bits, const uint32_t* d_filled_bits,
+                                                    const int32_t* d_hole_counts, uint32_t* d_obstacle, int map_size,
+                                                    int pixels_per_meter, int32_t* d_status, const float* d_depth,
+                                                    const int32_t* d_slot_undone, void* stream) {
+    if (n > 0 && (!d_slot_undone || !d_depth))
+        return fail(VLFM_ERR_INVALID, "depth_scatter_holes_rig_batched: needs d_slot_undone and d_depth");
+    return depth_scatter_holes_impl(d_params, n, height, width, d_hole_bits, d_filled_bits, d_hole_counts, d_obstacle, map_size,
+                                    pixels_per_meter, d_status, d_depth, d_slot_undone, stream);
 }
 
 extern "C" int vlfm_depth_ingest_batched(const float* d_depth, int n, int height, int width,

@@ -824,6 +824,282 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
     }
 }
 
+// ------------------------------------------------------------------------------------------------ camera rig update
+// ValueMap.update_map for the cameras of a RIG: n observations in one launch, several of them per environment slot, applied in
+// the order the caller lists them (the reference's loop over `value_map_rgbd`, itm_policy.py:191-211, is sequential and the
+// weighted fuse does not commute).  grid = (G, slots in the call); the G workgroups of a slot walk the slot's observations in
+// order and each does per observation what value_map_update_fused_kernel does: keys -> profile polygon -> flattened raster
+// into LDS -> resolve -> block-sparse sweep -> cell list -> fuse_list.
+//   Ordering without waiting on another workgroup: the fuse is split by ABSOLUTE map rows -- 8-row tile b of the map belongs to
+// workgroup b mod G of the slot for the whole launch, whatever window a camera has -- so every cell a slot's cameras touch is
+// read and written by ONE workgroup, and camera k + 1 of that workgroup only has to see its own stores of camera k: a barrier
+// with workgroup-scope fences (the pattern of border_parallel.h's wg_sync_global).  No workgroup ever waits for another one, so
+// the launch cannot hang however few workgroups are resident.  The raster of every camera is repeated by the G workgroups
+// (LDS-only work, the G-fold redundancy of the single-camera kernel).
+//   Optics (template size, templates, tangent table, depth range) come per observation from vlfm_vm_optics; LDS is laid out for
+// the largest template of the call.
+//   Explored-synchronised mode: `explored` does not change within the call and fused cells are explored ones, so the
+// (written & ~explored) clear of value_map.py:369-375 is idempotent over the cameras: it runs once per slot, before the first
+// camera, over the rows each workgroup owns; the explored mask itself applies to every camera (fuse_list).
+struct RigArgs {
+    const vlfm_vm_optics* optics;   // [n] in the order of UpdateArgs::pose (grouped by slot)
+    const int2* slots;              // [gridDim.y] (first observation, count) into pose / optics
+    int quad_in_lds;                // the confidence quadrants are staged in LDS (else the taps read them through the caches:
+                                    // a template so large that quadrant + lists exceed the LDS, e.g. 8 m at 20 cells / m)
+};
+
+__device__ inline void rig_sync_global() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// UpdateArgs: T = the largest template size of the call (LDS layout); pose[i].reserved = the observation's row in colmax / values
+// / counters (its position in the caller's list); tan_tab, tmpl, tmpl_bits, depth_scale, depth_offset, half_t_* are not read.
+template <int C_STATIC>
+__global__ __launch_bounds__(FUSED_THREADS) void value_map_update_rig_kernel(UpdateArgs a, FusedExtra fx, RigArgs rg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int Tm = a.T, W = a.W, S = a.S;
+    const int words_m = (Tm + 31) >> 5;
+    const int n_vert = W + 2;
+    unsigned* solid = reinterpret_cast<unsigned*>(smem);
+    int2* vert = reinterpret_cast<int2*>(solid + 2 * Tm * words_m + ((2 * Tm * words_m) & 1));
+    int* pref = reinterpret_cast<int*>(vert + n_vert);
+    const int Qm = (Tm >> 1) + 1;
+    float* quad = reinterpret_cast<float*>(pref + n_vert + 1 + ((n_vert + 1) & 1));
+    int2* row_xy0 = reinterpret_cast<int2*>(quad + (rg.quad_in_lds ? Qm * Qm + ((Qm * Qm) & 1) : 0));
+    uint2* list = reinterpret_cast<uint2*>(row_xy0 + Tm);                 // [fx.list_cap]
+    int2* col_xy = reinterpret_cast<int2*>(list + fx.list_cap);          // [Tm]
+    unsigned* block_list = reinterpret_cast<unsigned*>(col_xy + Tm);     // [fx.block_cap] (first map row << 16) | window block column
+    __shared__ int sh_list_n, sh_block_n;
+    __shared__ int sh_wave_tot[FUSED_THREADS / 64];
+    __shared__ int sh_last;
+    __shared__ int sh_box[4];
+    __shared__ int4 sh_dbox;
+    const int g = blockIdx.x, G = gridDim.x;
+    const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const int first = __builtin_amdgcn_readfirstlane(rg.slots[blockIdx.y].x);
+    const int count = __builtin_amdgcn_readfirstlane(rg.slots[blockIdx.y].y);
+    const int env = __builtin_amdgcn_readfirstlane(a.pose[first].env);
+    const int ex_stride = (S + 31) >> 5;
+    unsigned* written = fx.written ? fx.written + (size_t)env * S * ex_stride : nullptr;
+
+    // ---- once per slot: cells that hold a value but are not explored any more, in the rows this workgroup owns
+    if (written && a.explored) {
+        const unsigned* explored = a.explored + (size_t)env * S * ex_stride;
+        float* conf = a.conf + (size_t)env * S * S;
+        const int C = C_STATIC > 0 ? C_STATIC : a.C;
+        double* value = a.value + (size_t)env * S * S * C;
+        const int plane_words = S * ex_stride, tile_words = ROWS_PER_TILE * ex_stride;
+        const int n_tiles = (S + ROWS_PER_TILE - 1) / ROWS_PER_TILE;
+        const int n_own = g < n_tiles ? (n_tiles - 1 - g) / G + 1 : 0;
+        for (int idx = tid; idx < n_own * tile_words; idx += nth) {
+            const int j = idx / tile_words;
+            const int i = (g + j * G) * tile_words + (idx - j * tile_words);
+            if (i >= plane_words) continue;
+            const unsigned wr = written[i];
+            if (!wr) continue;
+            unsigned dead = wr & ~explored[i];
+            if (!dead) continue;
+            atomicAnd(&written[i], ~dead);
+            const int row = i / ex_stride, c0 = (i - row * ex_stride) * 32;
+            while (dead) {
+                const int b = __builtin_ctz(dead);
+                dead &= dead - 1u;
+                const size_t cell = (size_t)row * S + c0 + b;
+                conf[cell] = 0.0f;
+                for (int c = 0; c < C; c++) value[cell * C + c] = __dmul_rn(value[cell * C + c], 0.0);   // (:375) a product: -0.0 stays
+            }
+        }
+    }
+
+    for (int k = 0; k < count; k++) {
+        // this workgroup's map stores of the previous camera (and of the clear above) before this camera's map loads; also
+        // fences the LDS arrays that are re-used
+        rig_sync_global();
+        vlfm_vm_pose pose;
+        {
+            const int* src = reinterpret_cast<const int*>(a.pose + first + k);
+            int* dst = reinterpret_cast<int*>(&pose);
+#pragma unroll
+            for (int u = 0; u < (int)(sizeof(vlfm_vm_pose) / 4); u++) dst[u] = __builtin_amdgcn_readfirstlane(src[u]);
+        }
+        vlfm_vm_optics op;
+        {
+            const int* src = reinterpret_cast<const int*>(rg.optics + first + k);
+            int* dst = reinterpret_cast<int*>(&op);
+#pragma unroll
+            for (int u = 0; u < (int)(sizeof(vlfm_vm_optics) / 4); u++) dst[u] = __builtin_amdgcn_readfirstlane(src[u]);
+        }
+        const int obs = pose.reserved;               // row of the keys, values and counter (fuse_list reads values through it)
+        const int T = op.template_size, words = (T + 31) >> 5, Q = (T >> 1) + 1;
+        unsigned* parity = solid + T * words;        // after the resolve: the visible plane
+        const float half_t_f = (float)(T / 2.0);
+        const double half_t_d = T / 2.0;
+
+        LdsBitmap bm;
+        bm.solid = solid; bm.parity = parity; bm.rows = T; bm.cols = T; bm.words = words;
+        for (int i = tid; i < 2 * T * words; i += nth) solid[i] = 0u;
+        if (tid == 0) { sh_box[0] = T; sh_box[1] = -1; sh_box[2] = T; sh_box[3] = -1; sh_list_n = 0; sh_block_n = 0; }
+        for (int x = tid; x < T; x += nth)   // the column part of cv::warpAffine's fixed-point coordinate
+            col_xy[x] = make_int2(__double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[0], (double)x), 1024.0)),
+                                  __double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[3], (double)x), 1024.0)));
+        for (int y = tid; y < T; y += nth)   // cv::warpAffine: X0 = round((M01 y + M02) * 1024) + 16, Y0 likewise (AB_BITS = 10)
+            row_xy0[y] = make_int2(
+                __double2int_rn(__dmul_rn(__dadd_rn(__dmul_rn(pose.inv_affine[1], (double)y), pose.inv_affine[2]), 1024.0)) + 16,
+                __double2int_rn(__dmul_rn(__dadd_rn(__dmul_rn(pose.inv_affine[4], (double)y), pose.inv_affine[5]), 1024.0)) + 16);
+        unsigned* cm = a.colmax + (size_t)obs * W;
+        for (int i = tid; i < W; i += nth) {
+            const unsigned key = cm[i];
+            const float raw = __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+            const float d = __fadd_rn(__fmul_rn(raw, op.depth_scale), op.depth_offset);      // f32 (value_map.py:234)
+            const float xr = __fadd_rn(__fmul_rn(d, a.ppm_f), half_t_f);                     // f32 (:248)
+            const double yl = __dadd_rn(__dmul_rn(__dmul_rn((double)d, op.d_tan[i]), a.ppm_d), half_t_d);  // f64 (:242,249)
+            vert[i + 1] = make_int2((int)(long long)yl, (int)(long long)xr);                 // astype(int): truncation
+        }
+        if (rg.quad_in_lds)
+            for (int i = tid; i < Q * Q; i += nth) quad[i] = op.d_conf_quadrant[i];
+        if (tid == 0) {
+            vert[0] = make_int2(0, T - 1);
+            vert[W + 1] = make_int2(T - 1, T - 1);
+        }
+        __syncthreads();
+        // the keys have been read: the last workgroup of the slot to get here zeroes them for the next depth ingest (a completion
+        // count per observation -- nobody waits on it)
+        if (tid == 0) {
+            __threadfence();
+            sh_last = atomicAdd(&fx.counters[obs], 1) == G - 1;
+        }
+        raster_polygon_flat(bm, vert, n_vert, pref, sh_wave_tot, tid, nth);
+        if (sh_last) {
+            for (int i = tid; i < W; i += nth) cm[i] = 0u;
+            if (tid == 0) fx.counters[obs] = 0;
+        }
+        __syncthreads();
+        // resolve (one lane per row) fused with visible = (template > 0) & ~beyond-the-profile, and the source bounding box
+        {
+            int r_lo = T, r_hi = -1, c_lo = T, c_hi = -1;
+            for (int y = tid; y < T; y += nth) {
+                unsigned carry = 0;
+                for (int w = 0; w < words; w++) {
+                    const int i = y * words + w;
+                    unsigned p = parity[i];
+                    p ^= p << 1; p ^= p << 2; p ^= p << 4; p ^= p << 8; p ^= p << 16;
+                    if (carry) p = ~p;
+                    carry = p >> 31;
+                    const unsigned v = op.d_template_bits[i] & ~(p | solid[i]);
+                    parity[i] = v;
+                    if (v) {
+                        r_lo = min(r_lo, y); r_hi = max(r_hi, y);
+                        c_lo = min(c_lo, w * 32 + __builtin_ctz(v)); c_hi = max(c_hi, w * 32 + 31 - __builtin_clz(v));
+                    }
+                }
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                r_lo = min(r_lo, __shfl_xor(r_lo, off, 64)); r_hi = max(r_hi, __shfl_xor(r_hi, off, 64));
+                c_lo = min(c_lo, __shfl_xor(c_lo, off, 64)); c_hi = max(c_hi, __shfl_xor(c_hi, off, 64));
+            }
+            if (lane == 0 && r_hi >= 0) {
+                atomicMin(&sh_box[0], r_lo); atomicMax(&sh_box[1], r_hi); atomicMin(&sh_box[2], c_lo); atomicMax(&sh_box[3], c_hi);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            // destination (rotated) bounding box of everything that can receive a non-zero tap (as in the single-camera kernel)
+            int4 m;
+            if (sh_box[1] < 0) {
+                m = make_int4(1, 0, 1, 0);
+            } else {
+                const double a0 = pose.inv_affine[0], a1 = pose.inv_affine[1], a2 = pose.inv_affine[2];
+                const double a3 = pose.inv_affine[3], a4 = pose.inv_affine[4], a5 = pose.inv_affine[5];
+                const double det = a0 * a4 - a1 * a3;
+                double xlo = 1e30, xhi = -1e30, ylo = 1e30, yhi = -1e30;
+                for (int c = 0; c < 4; c++) {
+                    const double sx = (c & 1) ? sh_box[3] + 1.0 : sh_box[2] - 1.0, sy = (c & 2) ? sh_box[1] + 1.0 : sh_box[0] - 1.0;
+                    const double dx = (a4 * (sx - a2) - a1 * (sy - a5)) / det, dy = (-a3 * (sx - a2) + a0 * (sy - a5)) / det;
+                    xlo = fmin(xlo, dx); xhi = fmax(xhi, dx); ylo = fmin(ylo, dy); yhi = fmax(yhi, dy);
+                }
+                if (!(fabs(det) > 1e-9) || !(xlo == xlo) || !(ylo == ylo)) { xlo = ylo = 0; xhi = yhi = T; }
+                m = make_int4(max(0, (int)floor(ylo) - 2), min(T - 1, (int)ceil(yhi) + 2), max(0, (int)floor(xlo) - 2),
+                              min(T - 1, (int)ceil(xhi) + 2));
+            }
+            sh_dbox = m;
+        }
+        __syncthreads();
+        int4 box = sh_dbox;
+        box.x = __builtin_amdgcn_readfirstlane(box.x); box.y = __builtin_amdgcn_readfirstlane(box.y);
+        box.z = __builtin_amdgcn_readfirstlane(box.z); box.w = __builtin_amdgcn_readfirstlane(box.w);
+        // window rows / columns of the box that lie on the map
+        const int y_lo = max(box.x, max(0, -pose.row0)), y_hi = min(min(box.y, T - 1), S - 1 - pose.row0);
+        const int bx_lo = max(box.z, max(0, -pose.col0)) / VB, bx_hi = min(min(box.w, T - 1), S - 1 - pose.col0) / VB;
+        if (box.z > box.w || y_lo > y_hi || bx_lo > bx_hi) continue;   // (workgroup-uniform)
+        // ---- which 4 x 4 blocks can hold a cell with a visible tap?  Block rows are cut on ABSOLUTE map rows (two per 8-row map
+        // tile), and only the tiles b = g (mod G) are this workgroup's
+        const int b_lo = (pose.row0 + y_lo) / ROWS_PER_TILE, b_hi = (pose.row0 + y_hi) / ROWS_PER_TILE;
+        const int b0 = b_lo + ((g - b_lo % G) + G) % G;
+        const int n_own = b0 > b_hi ? 0 : (b_hi - b0) / G + 1;
+        const int nbx = bx_hi - bx_lo + 1;
+        const int nblk = n_own * (ROWS_PER_TILE / VB) * nbx;
+        for (int i0 = 0; i0 < nblk; i0 += nth) {       // (wavefront-uniform trip count: the ballot below needs every lane)
+            const int i = i0 + tid;
+            bool act = false;
+            int m0 = 0, bx = 0;
+            if (i < nblk) {
+                const int r = i / nbx;
+                bx = bx_lo + (i - r * nbx);
+                m0 = (b0 + (r / (ROWS_PER_TILE / VB)) * G) * ROWS_PER_TILE + (r % (ROWS_PER_TILE / VB)) * VB;   // first map row
+                const int y0 = max(m0 - pose.row0, y_lo), y1 = min(m0 - pose.row0 + VB - 1, y_hi);
+                if (y0 <= y1) {
+                    const int x0 = bx * VB, x1 = min(x0 + VB - 1, T - 1);
+                    const int2 ra = row_xy0[y0], rb = row_xy0[y1], ca = col_xy[x0], cb = col_xy[x1];
+                    // fixed-point coordinate (>> 10 = the cell's first tap) in the four corners
+                    const int xa = ra.x + ca.x, xb = ra.x + cb.x, xc = rb.x + ca.x, xd = rb.x + cb.x;
+                    const int ya = ra.y + ca.y, yb = ra.y + cb.y, yc = rb.y + ca.y, yd = rb.y + cb.y;
+                    const int sx0 = min(min(xa, xb), min(xc, xd)) >> 10, sx1 = (max(max(xa, xb), max(xc, xd)) >> 10) + 1;
+                    const int sy0 = min(min(ya, yb), min(yc, yd)) >> 10, sy1 = (max(max(ya, yb), max(yc, yd)) >> 10) + 1;
+                    act = any_visible(parity, words, T, sx0, sx1, sy0, sy1);
+                }
+            }
+            const unsigned long long m = __ballot(act);
+            if (m == 0ull) continue;
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&sh_block_n, __popcll(m));
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (act) {
+                const int j = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                if (j < fx.block_cap) block_list[j] = ((unsigned)m0 << 16) | (unsigned)bx;
+            }
+        }
+        __syncthreads();
+        // ---- the cells of the listed blocks, four blocks per wavefront and round, one lane per cell
+        const int nb = min(sh_block_n, fx.block_cap);   // (block_cap covers every block a window can have: nothing is ever dropped)
+        for (int i0 = wave * 4; i0 < nb; i0 += (nth >> 6) * 4) {
+            const int bi = i0 + (lane >> 4);
+            const bool have = bi < nb;
+            const unsigned blk = block_list[have ? bi : 0];
+            const int mr = (int)(blk >> 16) + ((lane >> 2) & 3), x = (int)(blk & 0xFFFFu) * VB + (lane & 3);
+            const int y = mr - pose.row0, mc = pose.col0 + x;
+            const bool ok = have && y >= y_lo && y <= y_hi && x < T && (unsigned)mc < (unsigned)S;
+            const int2 rxy = row_xy0[ok ? y : 0], cxy = col_xy[x < T ? x : 0];
+            const float nwv = rg.quad_in_lds ? cell_new_confidence(parity, quad, T, words, rxy, cxy, ok)
+                                             : cell_new_confidence(parity, op.d_conf_quadrant, T, words, rxy, cxy, ok);
+            const unsigned long long m = __ballot(nwv != 0.0f);
+            if (m == 0ull) continue;
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&sh_list_n, __popcll(m));
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (nwv != 0.0f) {
+                const int j = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                const uint2 e = make_uint2(((unsigned)mr << 16) | (unsigned)mc, __float_as_uint(nwv));
+                if (j < fx.list_cap) list[j] = e;
+                else fuse_list<C_STATIC>(a, pose, &e, 1, 0, 1, written);    // list full (a cone far wider than a camera's): in place
+            }
+        }
+        __syncthreads();
+        fuse_list<C_STATIC>(a, pose, list, min(sh_list_n, fx.list_cap), tid, nth, written);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ sort_waypoints
 // One workgroup (256 threads) per (waypoint, channel).  Gathers the positive cells of the disc into LDS, then finds
 // the median by rank counting (n <= (2r+1)^2, r = 10 -> 441; O(n^2) compares spread over the workgroup).  The map is f64
@@ -994,6 +1270,70 @@ extern "C" int vlfm_value_map_update_fused_batched(uint32_t* d_colmax_keys, int 
     else
         VLFM_KLAUNCH(value_map_update_fused_kernel<0>, dim3(G, n), dim3(FUSED_THREADS), lds, (hipStream_t)stream, a, fx);
     return check_launch("value_map_update_fused_kernel");
+}
+
+extern "C" int vlfm_value_map_update_rig_batched(uint32_t* d_colmax_keys, int width, const vlfm_vm_pose* d_pose,
+                                                 const vlfm_vm_optics* d_optics, const int32_t* d_slots, int n_slots, int n,
+                                                 int max_template_size, const double* d_values, float* d_conf,
+                                                 double* d_value, int map_size, int channels, int pixels_per_meter,
+                                                 int use_max_confidence, int fusion_type, const uint32_t* d_explored_bits,
+                                                 uint32_t* d_written_bits, int32_t* d_counters, void* stream) {
+    static_assert(sizeof(vlfm_vm_optics) == 48, "vlfm_vm_optics layout");
+    if (n == 0) return VLFM_OK;
+    if (!d_colmax_keys || !d_pose || !d_optics || !d_slots || !d_values || !d_conf || !d_value || !d_counters || n < 0 ||
+        n_slots <= 0 || n_slots > n || width <= 0 || max_template_size <= 0 || map_size <= 0 || channels <= 0 ||
+        fusion_type < 0 || fusion_type > 2)
+        return fail(VLFM_ERR_INVALID, "value_map_update_rig_batched: bad argument");
+    if ((d_explored_bits == nullptr) != (d_written_bits == nullptr))
+        return fail(VLFM_ERR_INVALID, "value_map_update_rig_batched: d_explored_bits and d_written_bits go together");
+    if (map_size >= 65535 || n_slots > 65535)   // a list entry packs (row << 16) | col of a MAP cell; gridDim.y
+        return fail(VLFM_ERR_CAPACITY, "value_map_update_rig_batched: map or batch too large");
+    UpdateArgs a{};
+    a.colmax = reinterpret_cast<unsigned*>(d_colmax_keys); a.pose = d_pose; a.values = d_values;
+    a.conf = d_conf; a.value = d_value; a.explored = d_explored_bits;
+    a.W = width; a.T = max_template_size; a.S = map_size; a.C = channels;
+    a.ppm_f = (float)pixels_per_meter;
+    a.ppm_d = (double)pixels_per_meter;
+    a.use_max_conf = use_max_confidence; a.fusion = fusion_type;
+    FusedExtra fx{d_written_bits, d_counters, nullptr, 0, 0};
+    RigArgs rg{d_optics, reinterpret_cast<const int2*>(d_slots), 1};
+    const int T = max_template_size, words = (T + 31) >> 5;
+    const int n_vert = width + 2, Q = T / 2 + 1, nb_side = (T + VB - 1) / VB;
+    fx.block_cap = (nb_side + 4) * nb_side;   // block rows are cut on map rows: up to T/4 + 4 of them meet a window
+    size_t lds = (size_t)(2 * T * words + ((2 * T * words) & 1)) * 4 + (size_t)n_vert * sizeof(int2) +
+                 (size_t)(n_vert + 1 + ((n_vert + 1) & 1)) * sizeof(int) + (size_t)2 * T * sizeof(int2) +
+                 (size_t)fx.block_cap * 4;
+    // the confidence quadrant goes to LDS when it leaves room for a cell list of 4096 entries (T = 201: 41 of 150 KB)
+    const size_t quad_bytes = (size_t)(Q * Q + ((Q * Q) & 1)) * 4;
+    rg.quad_in_lds = lds + quad_bytes + 4096 * sizeof(uint2) <= 150 * 1024;
+    if (rg.quad_in_lds) lds += quad_bytes;
+    // the cell list takes what is left, up to 8192 entries (a 79-degree cone at 5 m marks ~3 000 cells); a cone with more
+    // cells than the list holds has the rest fused in place
+    size_t cap = lds + 1024 * sizeof(uint2) <= 150 * 1024 ? (150 * 1024 - lds) / sizeof(uint2) : 0;
+    if (cap == 0) return fail(VLFM_ERR_CAPACITY, "value_map_update_rig_batched: template/width too large for LDS");
+    if (cap > 8192) cap = 8192;
+    fx.list_cap = (int)cap;
+    lds += cap * sizeof(uint2);
+    if (lds > 64 * 1024) {   // beyond the default dynamic-LDS limit: opt in once per device and kernel
+        static LdsOptIn opt1, opt0;
+        const bool ok = channels == 1 ? opt1.ensure(reinterpret_cast<const void*>(value_map_update_rig_kernel<1>), 150 * 1024)
+                                      : opt0.ensure(reinterpret_cast<const void*>(value_map_update_rig_kernel<0>), 150 * 1024);
+        if (!ok) return fail(VLFM_ERR_HIP, "value_map_update_rig_batched: cannot opt in to large LDS");
+    }
+    // workgroups per slot: one 1024-thread workgroup fills a CU, so aim for one per CU over all slots; a window meets about
+    // T / 8 map tiles, and beyond a quarter of them (the single-camera kernel's bound) the repeated raster outweighs the split
+    const int tiles = (T + ROWS_PER_TILE - 1) / ROWS_PER_TILE;
+    const int target = target_override_g() > 0 ? target_override_g() : device_cu_count();
+    int G = (target + n_slots - 1) / n_slots;
+    const int g_max = (tiles + FUSED_THREADS / 256 - 1) / (FUSED_THREADS / 256);
+    if (G > g_max) G = g_max;
+    if (G < 1) G = 1;
+    VLFM_TIMED("value_map_update_rig_kernel", stream);
+    if (channels == 1)
+        VLFM_KLAUNCH(value_map_update_rig_kernel<1>, dim3(G, n_slots), dim3(FUSED_THREADS), lds, (hipStream_t)stream, a, fx, rg);
+    else
+        VLFM_KLAUNCH(value_map_update_rig_kernel<0>, dim3(G, n_slots), dim3(FUSED_THREADS), lds, (hipStream_t)stream, a, fx, rg);
+    return check_launch("value_map_update_rig_kernel");
 }
 
 extern "C" int vlfm_value_map_sort_waypoints_batched(const double* d_value, int map_size, int channels,

@@ -23,6 +23,7 @@ vlfm_amd/distributed.py); the only collective is the metric all-reduce in bench.
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -126,6 +127,56 @@ def ellipse_masks(ellipses, height: int, width: int, device) -> torch.Tensor:
     return (xx - cx) ** 2 / ax ** 2 + (yy - cy) ** 2 / ay ** 2 <= 1
 
 
+@dataclass(frozen=True)
+class Camera:
+    """One camera of a rig, mounted relative to the robot pose: yawed ``yaw`` radians to the left and moved ``forward`` /
+    ``left`` / ``up`` metres in the robot frame.  ``hfov`` (radians; None = the harness's 79 degrees) and the depth range are
+    the camera's own (reality/objectnav_env.py:184-228 hands min_depth / max_depth / fov per camera); ``obstacle`` / ``value``
+    say which map the camera feeds (the robot: several depth cameras for obstacles, one RGB-D camera for values)."""
+    yaw: float = 0.0
+    forward: float = 0.0
+    left: float = 0.0
+    up: float = 0.0
+    hfov: Optional[float] = None
+    min_depth: float = MIN_DEPTH
+    max_depth: float = MAX_DEPTH
+    obstacle: bool = True
+    value: bool = True
+
+    def offset_tf(self) -> np.ndarray:
+        """xyz_yaw_to_tf_matrix (geometry_utils.py:162-180) of the mounting offset."""
+        c, s = np.cos(self.yaw), np.sin(self.yaw)
+        return np.array([[c, -s, 0.0, self.forward], [s, c, 0.0, self.left], [0.0, 0.0, 1.0, self.up], [0.0, 0.0, 0.0, 1.0]])
+
+
+class CameraRig:
+    """The cameras every environment of a ``BatchedEpisodes(rig=...)`` carries, in the order they are applied to the maps
+    (the reference loops over its cameras sequentially and the value fuse does not commute).  ``designated`` is the camera whose
+    frames the single-camera stages use: the detector / segmenter / object maps (its RGB frame, depth frame and pose, like
+    object_map_rgbd on the robot; it keeps the harness's default optics) and the PointNav depth.  The reveal uses the robot pose."""
+
+    def __init__(self, cameras: Sequence[Camera], designated: int = 0) -> None:
+        self.cameras = list(cameras)
+        if any(not (c.obstacle or c.value) for c in self.cameras):
+            raise ValueError("a rig camera must feed the obstacle map, the value map or both")
+        self.obstacle_ids = [i for i, c in enumerate(self.cameras) if c.obstacle]
+        self.value_ids = [i for i, c in enumerate(self.cameras) if c.value]
+        if not self.obstacle_ids or not self.value_ids:
+            raise ValueError("a rig needs at least one obstacle camera and one value camera")
+        if not 0 <= designated < len(self.cameras):
+            raise ValueError("designated camera out of range")
+        self.designated = designated
+        self.offsets = np.stack([c.offset_tf() for c in self.cameras])          # [K,4,4]
+
+    def __len__(self) -> int:
+        return len(self.cameras)
+
+    def camera_tfs(self, robot_tf: np.ndarray) -> np.ndarray:
+        """camera -> episodic transforms [..., K, 4, 4] for robot -> episodic transforms [..., 4, 4]: robot_tf @ offset."""
+        robot_tf = np.asarray(robot_tf, np.float64)
+        return np.matmul(robot_tf[..., None, :, :], self.offsets)
+
+
 class RoomsRenderer:
     """Depth frames of the consistent rooms-and-pillars world (vlfm_amd/synthetic.py) for E environments at once, ray-cast ON
     THE DEVICE (f64, the arithmetic of synthetic.wall_profile / depth_from_profile batched over environments): environment
@@ -160,9 +211,32 @@ class RoomsRenderer:
         return self.painter(t, d) if self.painter is not None else d
 
     def _render_walls(self, t: int) -> torch.Tensor:
-        x, y = self.xy[t, :, 0][:, None, None], self.xy[t, :, 1][:, None, None]
-        c, s = self.cs[t, :, 0][:, None, None], self.cs[t, :, 1][:, None, None]
-        dx, dy = c - s * self.m, s + c * self.m                                                  # [E,W,1]
+        return self._cast(self.xy[t], self.cs[t], self.m, self.floor)
+
+    @torch.no_grad()
+    def render_cameras(self, tf: np.ndarray, hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None) -> torch.Tensor:
+        """[n,H,W] f32 normalised depth seen from n camera -> episodic transforms [n,4,4] (yaw about z; a camera is just another
+        pose for the ray caster): position tf[:, :2, 3], heading (cos, sin) = tf[:, :2, 0], height tf[:, 2, 3]; ``hfov`` [n]
+        per camera (None = the renderer's); ``min_depth`` / ``max_depth`` [n]: each camera's own range, which its frame is
+        normalised to (None = 0.5 / 5 m), so that a short-range camera sees a far wall as "beyond range", not nearer.  Walls only: the painter of scripted objects belongs to the robot's own frame."""
+        tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        xy, cs = torch.tensor(tf[:, :2, 3], **f64), torch.tensor(tf[:, :2, 0], **f64)
+        fx = np.full(len(tf), camera_intrinsics(self.W)[0]) if hfov is None else \
+            self.W / (2 * np.tan(np.asarray(hfov, np.float64) / 2))
+        m = -(torch.arange(self.W, **f64)[None, :] - self.W // 2) / torch.tensor(fx, **f64)[:, None]      # [n,W]
+        rows = (torch.arange(self.H, **f64) - self.H // 2)[None, :]
+        height = torch.tensor(tf[:, 2, 3], **f64)[:, None]
+        floor = torch.where(rows > 0, height * torch.tensor(fx, **f64)[:, None] / rows.clamp(min=1e-9),
+                            torch.full_like(rows, float("inf")).expand(len(tf), -1))                      # [n,H]
+        lo = None if min_depth is None else torch.tensor(np.asarray(min_depth, np.float64), **f64)[:, None, None]
+        hi = None if max_depth is None else torch.tensor(np.asarray(max_depth, np.float64), **f64)[:, None, None]
+        return self._cast(xy, cs, m[:, :, None], floor[:, :, None], lo, hi)
+
+    def _cast(self, xy: torch.Tensor, cs: torch.Tensor, m: torch.Tensor, floor: torch.Tensor, lo=None, hi=None) -> torch.Tensor:
+        x, y = xy[:, 0][:, None, None], xy[:, 1][:, None, None]
+        c, s = cs[:, 0][:, None, None], cs[:, 1][:, None, None]
+        dx, dy = c - s * m, s + c * m                                                            # [E,W,1]
         tiny = 1e-12
         dx = torch.where(dx.abs() < tiny, torch.full_like(dx, tiny), dx)
         dy = torch.where(dy.abs() < tiny, torch.full_like(dy, tiny), dy)
@@ -173,8 +247,12 @@ class RoomsRenderer:
         tmax = torch.minimum(torch.maximum(tx0, tx1), torch.maximum(ty0, ty1))
         hit = (tmax >= tmin.clamp(min=0.0)) & (tmin > 0.0)
         wall = torch.where(hit, tmin, torch.full_like(tmin, float("inf"))).amin(dim=2).float().double()   # f32 like the host path
-        d = torch.minimum(wall[:, None, :], self.floor)                                          # [E,H,W]
-        return ((d - MIN_DEPTH) / (MAX_DEPTH - MIN_DEPTH)).clamp(1e-3, 1.0).float()
+        d = torch.minimum(wall[:, None, :], floor)                                               # [E,H,W]
+        if lo is None and hi is None:
+            return ((d - MIN_DEPTH) / (MAX_DEPTH - MIN_DEPTH)).clamp(1e-3, 1.0).float()
+        lo = MIN_DEPTH if lo is None else lo
+        hi = MAX_DEPTH if hi is None else hi
+        return ((d - lo) / (hi - lo)).clamp(1e-3, 1.0).float()
 
     def prepare(self, t0: int, n: int) -> None:
         self.window = torch.stack([self.render((t0 + i) % self.L) for i in range(n)])
@@ -196,8 +274,19 @@ class BatchedEpisodes:
                  sightings: Optional["ScriptedSightings"] = None, scripted_masks: bool = False,
                  coco_threshold: float = 0.8, non_coco_threshold: float = 0.4, pointnav_stop_radius: float = 0.9,
                  object_map_erosion_size: float = 5, concurrent_vlm_max_envs: int = 0,
-                 render_trajectories: bool = False, emulate_jpeg: bool = False) -> None:
+                 render_trajectories: bool = False, emulate_jpeg: bool = False, rig: Optional[CameraRig] = None) -> None:
         self.device = require_gpu(device)
+        # rig: K cameras per environment (CameraRig) fused into the environment's maps by ONE ingest_cameras / update_cameras per
+        # step (step() -> _step_rig()); None = one camera at the robot pose, the step as it always was
+        self.rig = rig
+        if rig is not None:
+            if world != "rooms" or host_inputs or not obstacle:
+                raise ValueError("a camera rig needs the rooms world rendered on the device and the obstacle map")
+            dc = rig.cameras[rig.designated]
+            if (detector is not None or sam is not None or object_maps) and not (
+                    dc.hfov in (None, camera_intrinsics(width)[2]) and dc.min_depth == MIN_DEPTH and dc.max_depth == MAX_DEPTH):
+                raise ValueError("the designated camera feeds the detector / object-map stage, which runs with the harness's "
+                                 "own optics: give it the default hfov and depth range")
         # a rank waiting for its GPU must not hold a host core (bench.py `host`).  Effective only before the device's first
         # stream exists (bench.py sets it first thing); here it is best effort: a warning on failure, VLFM_HOST_WAIT=spin opts out
         _lib.try_host_wait_blocking(self.device)
@@ -331,6 +420,8 @@ class BatchedEpisodes:
         self.pointnav = pointnav
         self.prev_goals = np.zeros((n_envs, 2))
         self.last_actions = None
+        self.last_rig = None          # (frames, camera transforms, slots, camera indices) of the last rig step
+        self._rig_keys = None
         self.timers: Dict[str, List] = {}
 
     def reset(self) -> None:
@@ -688,12 +779,147 @@ class BatchedEpisodes:
                 "num_frontiers": int(len(n_fr[e])) if n_fr is not None else 0,
                 "best_frontier_value_last_step": best})
 
+    def _detect(self, rgb: torch.Tensor, t_ep: int):
+        """The detector on the frames ``rgb`` [E,H,W,3] of episode step ``t_ep`` (one frame per environment) -> per-environment
+        ObjectDetections, or None without a detector and without a scripted head."""
+        # YOLOv7 takes the frames alone; GroundingDINO is prompted (MP3D-style caption, habitat_policies.py:139-141)
+        scripted = self.sightings is not None and (self.detector is not None or self.object_maps is not None)
+        if self.detector is None:
+            d = None
+        elif self.detector_is_prompted:
+            d = self.detector.predict_batch(rgb, [self.gdino_caption])
+        elif scripted and self.scripted_through_nms and hasattr(self.detector, "in_hw"):
+            # the scripted head speaks THROUGH the detector's own post-processing: its candidates (a cluster of jittered boxes
+            # per sighting, the scripted confidence on the best one) are written into the network's raw prediction, and
+            # non_max_suppression / scale_coords / the rounding and normalisation of yolov7.py:91-110 produce the detections
+            d = self.detector.predict_batch(rgb, pred_hook=lambda pred, in_hw: self._inject_candidates(pred, in_hw, t_ep))
+            want = [0] * self.E
+            for sg in self._sightings_at(t_ep):
+                want[sg[0]] += 1
+            self.object_stats["head_mismatch"] = self.object_stats.get("head_mismatch", 0) + sum(
+                int(det.num_detections != w) for det, w in zip(d, want))
+            return d
+        else:
+            d = self.detector.predict_batch(rgb)
+        if scripted:
+            d = self._scripted_detections(t_ep)     # the scripted HEAD: the network above ran (and is timed), its random logits are not used
+        return d
+
+    def rig_observations(self, t_ep: int):
+        """The rig's observations of episode step ``t_ep``: (frames [E*K,H,W] device f32, camera transforms [E*K,4,4], slot of
+        each frame [E*K], camera index of each frame [E*K]) -- environment-major, cameras in rig order."""
+        K = len(self.rig)
+        tf = self.rig.camera_tfs(self.tf_table[t_ep]).reshape(self.E * K, 4, 4)
+        cam = np.tile(np.arange(K), self.E)
+        hf = np.array([self.fov if c.hfov is None else c.hfov for c in self.rig.cameras])[cam]
+        lo, hi = (np.array([getattr(c, a) for c in self.rig.cameras], np.float64)[cam] for a in ("min_depth", "max_depth"))
+        frames = self.rooms.render_cameras(tf, hf, lo, hi)
+        if self.rooms.painter is not None:     # scripted objects: in front of the DESIGNATED camera (the detector stage's frame)
+            d_idx = torch.from_numpy(np.arange(self.E) * K + self.rig.designated).to(self.device)
+            frames[d_idx] = self.rooms.painter(t_ep, frames[d_idx])
+        return frames, tf, np.repeat(np.arange(self.E), K), cam
+
+    def _step_rig(self) -> None:
+        """step() for a camera rig: K * E frames rendered, ONE depth pass over the obstacle cameras' frames (which also reduces
+        the column maxima of the value cameras among them), one obstacle pipeline call per slot from the robot pose, one BLIP-2
+        batch over the K_v * E value frames, ONE value-map launch in which each slot fuses its cameras in rig order."""
+        t_ep = self.t % self.episode_len
+        rig, E = self.rig, self.E
+        cams = rig.cameras
+        poses, tf_robot = self.pose_table[t_ep], self.tf_table[t_ep]
+        depth, tf, slot, cam = self.rig_observations(t_ep)
+        per = lambda f: np.array([f(c) for c in cams])[cam]   # noqa: E731
+        lo, hi = per(lambda c: c.min_depth), per(lambda c: c.max_depth)
+        hfov = per(lambda c: self.fov if c.hfov is None else c.hfov)
+        fx = self.W / (2 * np.tan(hfov / 2))
+        is_o, is_v = per(lambda c: c.obstacle), per(lambda c: c.value)
+        o_idx, v_idx = np.flatnonzero(is_o), np.flatnonzero(is_v)
+        v_only = np.flatnonzero(is_v & ~is_o)
+        self.last_rig = (depth, tf, slot, cam)
+        main = torch.cuda.current_stream(self.device)
+        side = self.map_stream if self.map_stream is not None else main
+        if self.render_trajectories:      # one pose per slot and step: the robot's, not one per camera
+            self.values.update_agent_traj(range(E), poses[:, :2], poses[:, 2])
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            if self.render_trajectories:
+                self.obstacles.update_agent_traj(range(E), poses[:, :2], poses[:, 2])
+            d_o = depth if len(o_idx) == len(slot) else depth[torch.from_numpy(o_idx).to(self.device)]
+            keys_o = self.obstacles.ingest_cameras(d_o, tf[o_idx], lo[o_idx], hi[o_idx], fx[o_idx], fx[o_idx], slot[o_idx],
+                                                   want_colmax=True)
+            # the reveal: the robot pose, the widest obstacle camera's range and field of view
+            self.obstacles.update_after_ingest(tf_robot, float(hi[o_idx].max()), float(hfov[o_idx].max()))
+            # key rows in value-camera order: rows of the shared pass for cameras that feed both maps, a column-max-only pass
+            # for the value-only ones; both key buffers are handed back zeroed, as a value update would
+            if self._rig_keys is None:
+                self._rig_keys = torch.zeros((len(v_idx), self.W), dtype=torch.int32, device=self.device)
+                row_o, row_v = {int(i): r for r, i in enumerate(o_idx)}, {int(i): r for r, i in enumerate(v_only)}
+                pick = lambda rows: [torch.tensor(x, dtype=torch.int64, device=self.device) for x in   # noqa: E731
+                                     ([r for r, i in enumerate(v_idx) if int(i) in rows],
+                                      [rows[int(i)] for i in v_idx if int(i) in rows])]
+                self._rig_gather = (pick(row_o), pick(row_v))
+            (dst_o, src_o), (dst_v, src_v) = self._rig_gather
+            if len(dst_o):
+                self._rig_keys[dst_o] = keys_o[src_o]
+            keys_o.zero_()
+            if len(v_only):
+                keys_v = self.values.column_max(depth[torch.from_numpy(v_only).to(self.device)])
+                self._rig_keys[dst_v] = keys_v[src_v]
+                keys_v.zero_()
+        # ---- perception: one batch over the value cameras' frames (the synthetic RGB pool has one frame per environment: the
+        # designated camera of environment e sees pool frame e, camera k pool frame (e + k - designated) mod E)
+        n_v = len(v_idx)
+        pool = self.rgb_pool[self.t % self.rgb_pool.shape[0]]
+        if self.emulate_jpeg:     # the transport hop on the pool frames: every camera's frame is one of them
+            from .vlm.transport import jpeg_roundtrip_batch
+
+            pool = jpeg_roundtrip_batch(pool, 90, out=self.jpeg_frames, scratch=self.jpeg_scratch)
+        # ---- detector / segmenter / object maps: ONE designated camera per environment, as object_map_rgbd on the robot
+        # (reality_policies.py:103-111) -- the single-camera stage on that camera's RGB frame, depth frame and pose
+        d_rows = np.arange(E) * len(rig) + rig.designated
+        dets = self._detect(pool, t_ep)
+        self.last_detections = dets
+        if self.object_maps is not None and dets is not None:
+            self._update_object_maps(dets, pool, depth[torch.from_numpy(d_rows).to(self.device)], tf[d_rows])
+        elif self.sam is not None:
+            sel = [e for e in range(E) if (self.t + e) % self.sam_every == 0]
+            if sel:
+                box = torch.tensor([[[0.3 * self.W, 0.3 * self.H, 0.7 * self.W, 0.8 * self.H]]] * len(sel))
+                self.last_masks = self.sam.segment_bboxes(pool[sel], box)
+        if self.blip2 is not None:
+            rgb = pool[torch.from_numpy((slot[v_idx] + cam[v_idx] - rig.designated) % E).to(self.device)]
+            prompts = [self.prompts[e] for e in slot[v_idx]]
+            cos = self.blip2.cosine_batch(rgb, prompts)
+        else:
+            cos = torch.from_numpy(self.stub_rng.uniform(0.15, 0.45, size=n_v)).to(self.device)
+        self.last_cosines = cos
+        with torch.cuda.stream(side):
+            wps, env_of = self.obstacles.frontier_list()
+        main.wait_stream(side)
+        self.values.update_cameras(cos.reshape(n_v, 1), None, tf[v_idx], lo[v_idx], hi[v_idx], hfov[v_idx], slot[v_idx],
+                                   colmax=self._rig_keys)
+        self.last_frontier_values = None
+        if len(wps):
+            self.last_frontier_values = self.values.waypoint_values(wps, env_of, 0.5)
+        if self.selectors is not None:
+            modes, goals, halt = self._decide(wps, env_of, self.last_frontier_values, poses, t_ep)
+            self.last_modes, self.last_goals = modes, goals
+            nav = depth[torch.from_numpy(np.arange(E) * len(rig) + rig.designated).to(self.device)]
+            self.last_actions = self._navigate(nav, modes, goals, halt, poses)
+            self.object_stats["env_steps"] += E
+            for m in modes:
+                self.object_stats["modes"][m] += 1
+        self._end_episodes(t_ep)
+        self.t += 1
+
     def step(self) -> None:
         if self.t and self.t % self.episode_len == 0:
             self.check()
             self._log_finished_episodes()
             self.episodes_done += 1
             self.reset()
+        if self.rig is not None:
+            return self._step_rig()
         k = self.t % self.depth_pool.shape[0]
         kr = self.t % self.rgb_pool.shape[0]
         if self.host_inputs:
@@ -731,30 +957,6 @@ class BatchedEpisodes:
         detector_first = self.detector is not None and self.object_maps is not None and self.obj_stream is not None
         dets = None
 
-        def detect():
-            # YOLOv7 takes the frames alone; GroundingDINO is prompted (MP3D-style caption, habitat_policies.py:139-141)
-            scripted = self.sightings is not None and (self.detector is not None or self.object_maps is not None)
-            if self.detector is None:
-                d = None
-            elif self.detector_is_prompted:
-                d = self.detector.predict_batch(rgb, [self.gdino_caption])
-            elif scripted and self.scripted_through_nms and hasattr(self.detector, "in_hw"):
-                # the scripted head speaks THROUGH the detector's own post-processing: its candidates (a cluster of jittered boxes
-                # per sighting, the scripted confidence on the best one) are written into the network's raw prediction, and
-                # non_max_suppression / scale_coords / the rounding and normalisation of yolov7.py:91-110 produce the detections
-                d = self.detector.predict_batch(rgb, pred_hook=lambda pred, in_hw: self._inject_candidates(pred, in_hw, t_ep))
-                want = [0] * self.E
-                for sg in self._sightings_at(t_ep):
-                    want[sg[0]] += 1
-                self.object_stats["head_mismatch"] = self.object_stats.get("head_mismatch", 0) + sum(
-                    int(det.num_detections != w) for det, w in zip(d, want))
-                return d
-            else:
-                d = self.detector.predict_batch(rgb)
-            if scripted:
-                d = self._scripted_detections(t_ep)     # the scripted HEAD: the network above ran (and is timed), its random logits are not used
-            return d
-
         def perceive():
             return (self.blip2.cosine_batch_graphed(rgb, self.prompts) if self.graph_blip2
                     else self.blip2.cosine_batch(rgb, self.prompts))
@@ -766,7 +968,7 @@ class BatchedEpisodes:
             with torch.cuda.stream(self.vlm_stream):
                 cos = perceive()
         if detector_first:
-            dets = detect()
+            dets = self._detect(rgb, t_ep)
         # ---- perception (main stream): one batched BLIP-2 ITC forward for all resident envs
         if cos is not None:
             pass
@@ -776,7 +978,7 @@ class BatchedEpisodes:
             cos = torch.from_numpy(self.stub_rng.uniform(0.15, 0.45, size=self.E)).to(self.device)
         self.last_cosines = cos
         if not detector_first:
-            dets = detect()
+            dets = self._detect(rgb, t_ep)
         self.last_detections = dets
         if self.object_maps is not None and dets is not None:
             if detector_first:

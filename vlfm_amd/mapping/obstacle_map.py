@@ -61,6 +61,8 @@ class ObstacleMapBatch:
         self.frontiers_ready = False
         self._explored_u8 = None
         self._journal_dirty = False   # the scatter journal holds entries no fill_small_holes launch has consumed
+        self._slot_undone = None      # [n_envs] ingest_cameras: slots in which an island frame was undone (set on the device)
+        self._rig_high = (0, 0)       # ingest_cameras: most observations / largest journal capacity seen (buffers keep that size)
         # Dirty windows (csrc/obstacle_map.hip: navigable_kernel / frontier_prepare_kernel), per slot, inclusive
         # (y0, y1, x0, x1), empty when y1 < y0.  `_dirty_obst`: cells whose obstacle bit may have changed since `navigable`
         # was last recomputed (union of the reach windows of the frames ingested); `_dirty_nav`: cells whose `navigable` bit
@@ -272,6 +274,130 @@ class ObstacleMapBatch:
                                                               self.pixels_per_meter, self.status.data_ptr(),
                                                               depth.data_ptr(), _stream_ptr()), "depth_scatter_holes")
         return keys
+
+    # ------------------------------------------------------------------------------------------ step, part 1: camera rig
+    @staticmethod
+    def rig_windows(env: np.ndarray, tf: np.ndarray, reach_px: np.ndarray, size: int, pixels_per_meter: int):
+        """Dirty windows of a rig ingest: per observation the reach window of ``_note_ingest`` (its own reach: cameras differ in
+        range and optics), then the UNION over the cameras of a slot.  Returns (distinct slots [m], windows [m, 4] int32,
+        inclusive (y0, y1, x0, x1); the whole map where a camera's window leaves it or its transform is not rigid)."""
+        S = size
+        R = tf[:, :3, :3]
+        rigid = np.abs(np.einsum("nij,nkj->nik", R, R) - np.eye(3)).reshape(len(tf), -1).max(axis=1) < 1e-9
+        cell = np.rint(tf[:, :2, 3] * pixels_per_meter) + S // 2
+        row, col = cell[:, 0], S - cell[:, 1]
+        r = np.ceil(np.asarray(reach_px, np.float64)) + 2
+        win = np.stack([row - r, row + r, col - r, col + r], axis=1)
+        inside = rigid & np.isfinite(win).all(axis=1) & (win[:, 0] >= 0) & (win[:, 1] <= S - 1) & (win[:, 2] >= 0) & \
+            (win[:, 3] <= S - 1)
+        win = np.where(inside[:, None], win, np.array([0, S - 1, 0, S - 1], np.float64)[None]).astype(np.int32)
+        order = np.argsort(env, kind="stable")
+        slots, first = np.unique(env[order], return_index=True)
+        w = win[order]
+        out = np.stack([np.minimum.reduceat(w[:, 0], first), np.maximum.reduceat(w[:, 1], first),
+                        np.minimum.reduceat(w[:, 2], first), np.maximum.reduceat(w[:, 3], first)], axis=1).astype(np.int32)
+        return slots.astype(np.int64), out
+
+    def ingest_cameras(self, depth, tf, min_depth, max_depth, fx, fy, env_ids: Sequence[int], want_colmax: bool = False):
+        """``ingest`` for the cameras of a rig: n observations of ONE image shape, ``env_ids`` [n] may repeat (several body
+        cameras per robot, reality_policies.py:113-138); ``min_depth`` / ``max_depth`` / ``fx`` / ``fy`` are scalars or
+        length-n arrays.  Returns the column-max key rows [n, W] (row i = observation i; what ``ValueMapBatch.update_cameras``
+        takes as ``colmax``) or None.
+
+        What follows it is ONE ordinary ``update_after_ingest(reveal pose, update_obstacles=True, explore=True)`` per slot
+        and no new kernel: the reference's K ``explore=False`` calls and its reveal-only call are, plane for plane, the OR of
+        the K cameras' obstacle cells (obstacle_map.py:98-101 is a pure OR), ``navigable`` recomputed from the final obstacle
+        plane (:104-108 is a function of that plane alone) and fog of war / frontiers once from the reveal pose (``explore=
+        False`` returns before anything else, :110-111).  tests/test_rig_gpu.py pins this with the om_multicam fixture.
+
+        fill_small_holes mode: the speculative pass journals a new bit for the one frame that set it first; when that frame
+        is an island frame its undo would take a bit a sibling frame placed legitimately, so the device flags the slot and
+        every frame of a flagged slot places its valid texels again (csrc/depth_holes.hip, csrc/depth_ingest.hip:
+        hole_scatter_kernel).  Frames of slots without an island frame are read once, as in ``ingest``.
+
+        A slot out of range is an AssertionError before anything is launched; an obstacle point off the map is reported by
+        ``check_status`` (IndexError), after which the obstacle planes hold the points placed so far, as after ``ingest``."""
+        import torch
+
+        from .value_map import per_observation, stack_rig_frames
+
+        depth = stack_rig_frames(depth)
+        if not torch.is_tensor(depth):
+            depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32)).to(self.device)
+        depth = depth.contiguous()
+        n, H, W = depth.shape
+        tf = np.asarray(tf, np.float64).reshape(n, 4, 4)
+        assert np.array_equal(tf[:, 3, :], np.tile([0.0, 0, 0, 1], (n, 1))), "camera transforms must be affine"
+        lo, hi = per_observation(min_depth, n), per_observation(max_depth, n)
+        fxs, fys = per_observation(fx, n), per_observation(fy, n)
+        env = np.asarray(env_ids, np.int64).reshape(-1)
+        assert env.shape == (n,), "one slot id per observation"
+        assert int(env.max()) < self.n_envs and int(env.min()) >= 0, "environment slot out of range"
+        prm = np.zeros(n, INGEST_DTYPE)
+        prm["tf"] = tf[:, :3, :].reshape(n, 12)
+        prm["depth_scale"], prm["depth_offset"], prm["depth_max"] = hi - lo, lo, hi
+        prm["fx"], prm["fy"] = fxs, fys
+        prm["min_height"], prm["max_height"] = self._min_height, self._max_height
+        prm["env"] = env
+        fill = self._hole_area_thresh != -1
+        prm["scatter"] = 1 | (4 if fill else 2)
+        reach = hi * np.sqrt(1.0 + (W / 2 / fxs) ** 2 + (H / 2 / fys) ** 2) * self.pixels_per_meter
+        slots, win = self.rig_windows(env, tf, reach, self.size, self.pixels_per_meter)
+        self._union(self._dirty_obst, slots, win)
+        rows = max(n, self.n_envs)
+        if self.status.shape[0] < rows:     # status words are per OBSERVATION: a rig has more of them than slots
+            grown = torch.zeros((rows, 2), dtype=torch.int32, device=self.device)
+            grown[:self.status.shape[0]] = self.status
+            self.status = grown
+            self._h_status = torch.zeros((rows, 2), dtype=torch.int32).pin_memory()
+        if self._ring_ingest.nbytes < n * INGEST_DTYPE.itemsize:
+            self._ring_ingest = UploadRing(self.device, n * INGEST_DTYPE.itemsize, slots=8)
+        keys = None
+        if want_colmax:
+            if self.colmax_keys is None or self.colmax_keys.shape != (rows, W):
+                self.colmax_keys = torch.zeros((rows, W), dtype=torch.int32, device=self.device)
+            keys = self.colmax_keys
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            d_prm = self._ring_ingest.upload(prm)
+            if not fill:   # every zero texel -> 1.0 (obstacle_map.py:87-89): atomicOr only, duplicates of a slot are safe
+                _lib.check(L.vlfm_depth_ingest_batched(depth.data_ptr(), n, H, W, d_prm.data_ptr(),
+                                                       keys.data_ptr() if keys is not None else None,
+                                                       self.obstacle_bits.data_ptr(), self.size, self.pixels_per_meter,
+                                                       self.status.data_ptr(), None, None, None, _stream_ptr()),
+                           "depth_ingest")
+                return keys[:n] if keys is not None else None
+            cap = int(min(self.size * self.size, (2 * int(np.ceil(reach.max())) + 3) ** 2))
+            # sized for the high-water mark: the number of observations changes when a slot drops out of a step, and a
+            # reallocation would re-zero every hole / scratch / journal buffer
+            self._rig_high = (max(n, self._rig_high[0]), max(cap, self._rig_high[1]))
+            holes, filled, scratch, counts, journal = self._hole_buffers(self._rig_high[0], H, W, self._rig_high[1])
+            if self._slot_undone is None:
+                self._slot_undone = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+            jref = ctypes.byref(journal)
+            if self._journal_dirty:
+                self._journal_count.zero_()
+            self._journal_dirty = True
+            _lib.check(L.vlfm_depth_ingest_batched(depth.data_ptr(), n, H, W, d_prm.data_ptr(),
+                                                   keys.data_ptr() if keys is not None else None,
+                                                   self.obstacle_bits.data_ptr(), self.size, self.pixels_per_meter,
+                                                   self.status.data_ptr(), holes.data_ptr(), None, jref, _stream_ptr()),
+                       "depth_ingest")
+            _lib.check(L.vlfm_fill_small_holes_rig_batched(holes.data_ptr(), self.status.data_ptr(), n, H, W,
+                                                           float(self._hole_area_thresh), scratch.data_ptr(),
+                                                           scratch.numel(), self.HOLE_CAP_PTS, self.HOLE_CAP_CONTOURS,
+                                                           filled.data_ptr(), counts.data_ptr(), d_prm.data_ptr(),
+                                                           self.obstacle_bits.data_ptr(), self.size, jref,
+                                                           self._slot_undone.data_ptr(), self.n_envs, _stream_ptr()),
+                       "fill_small_holes_rig")
+            self._journal_dirty = False
+            _lib.check(L.vlfm_depth_scatter_holes_rig_batched(d_prm.data_ptr(), n, H, W, holes.data_ptr(),
+                                                              filled.data_ptr(), counts.data_ptr(),
+                                                              self.obstacle_bits.data_ptr(), self.size,
+                                                              self.pixels_per_meter, self.status.data_ptr(),
+                                                              depth.data_ptr(), self._slot_undone.data_ptr(),
+                                                              _stream_ptr()), "depth_scatter_holes_rig")
+        return keys[:n] if keys is not None else None
 
     def _hole_buffers(self, n: int, H: int, W: int, journal_cap: int):
         import torch

@@ -107,6 +107,9 @@ INGEST_DTYPE = np.dtype([("tf", "<f8", (12,)), ("depth_scale", "<f4"), ("depth_o
                          ("reserved0", "<f4"), ("fx", "<f8"), ("fy", "<f8"), ("min_height", "<f8"),
                          ("max_height", "<f8"), ("env", "<i4"), ("scatter", "<i4")])
 assert VM_POSE_DTYPE.itemsize == 64 and INGEST_DTYPE.itemsize == 152
+VM_OPTICS_DTYPE = np.dtype([("d_template", "<u8"), ("d_template_bits", "<u8"), ("d_conf_quadrant", "<u8"), ("d_tan", "<u8"),
+                            ("depth_scale", "<f4"), ("depth_offset", "<f4"), ("template_size", "<i4"), ("reserved", "<i4")])
+assert VM_OPTICS_DTYPE.itemsize == 48
 
 
 class _ConeTemplates:
@@ -212,6 +215,59 @@ def pose_params(tf: np.ndarray, env_ids: Optional[Sequence[int]], size: int, ppm
     return out
 
 
+def group_rig(env_ids: Sequence[int], n_envs: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Host grouping of a camera-rig call: ``env_ids`` [n] may repeat and interleave slots.  Returns ``order`` [n] -- the
+    observations sorted by slot, the observations of one slot in the order they were listed (the reference applies its
+    cameras sequentially) -- and ``slots`` [n_slots, 2] int32 = (first, count) into that order, one row per slot present."""
+    env = np.asarray(env_ids, np.int64).reshape(-1)
+    assert env.size > 0, "a rig call needs at least one observation"
+    assert int(env.max()) < n_envs and int(env.min()) >= 0, "environment slot out of range"
+    order = np.argsort(env, kind="stable")
+    _, first, count = np.unique(env[order], return_index=True, return_counts=True)
+    return order, np.ascontiguousarray(np.stack([first, count], axis=1).astype(np.int32))
+
+
+def per_observation(x, n: int, dtype=np.float64) -> np.ndarray:
+    """A scalar or a length-n sequence -> [n] array (the per-camera min_depth / max_depth / fov / fx / fy of a rig call)."""
+    a = np.asarray(x, dtype)
+    if a.ndim == 0:
+        return np.full(n, a, dtype)
+    assert a.shape == (n,), f"expected a scalar or {n} values, got shape {a.shape}"
+    return np.ascontiguousarray(a)
+
+
+def rig_optics(min_depth, max_depth, fov, n: int, lookup: Callable) -> np.ndarray:
+    """vlfm_vm_optics records [n] (caller's order).  ``lookup(fov, max_depth)`` -> (template, template bits, quadrant, tangent
+    table, T): device addresses of that camera model's cached tables and its template size."""
+    lo, hi, fv = per_observation(min_depth, n), per_observation(max_depth, n), per_observation(fov, n)
+    out = np.zeros(n, VM_OPTICS_DTYPE)
+    out["depth_scale"] = (hi - lo).astype(np.float32)     # f32(max_depth - min_depth), the difference taken in f64
+    out["depth_offset"] = lo.astype(np.float32)
+    # one lookup per camera model, array ops over the observations (a 256-slot rig has a thousand of them per step)
+    models, inv = np.unique(fv + 1j * hi, return_inverse=True)      # (fov, max_depth) pairs as complex numbers: a 1-D sort
+    tab = np.array([lookup(float(m.real), float(m.imag)) for m in models], np.int64).reshape(len(models), 5)[inv.reshape(-1)]
+    out["d_template"], out["d_template_bits"], out["d_conf_quadrant"], out["d_tan"] = tab[:, 0], tab[:, 1], tab[:, 2], tab[:, 3]
+    out["template_size"] = tab[:, 4]
+    return out
+
+
+def stack_rig_frames(depth):
+    """The frames of one rig call as [n,H,W]: a tensor / array passes through; a list of frames must share one shape (the
+    tangent table and the key rows are per image width; cameras with other image sizes go into a call of their own)."""
+    if not isinstance(depth, (list, tuple)):
+        return depth
+    shapes = {tuple(d.shape[-2:]) for d in depth}
+    if len(shapes) != 1:
+        raise ValueError(f"the cameras of one rig call must share the image shape, got {sorted(shapes)}: "
+                         "use one call per image size")
+    import torch
+
+    if any(torch.is_tensor(d) for d in depth):
+        return torch.stack([d.reshape(d.shape[-2], d.shape[-1]) if torch.is_tensor(d) else
+                            torch.from_numpy(np.ascontiguousarray(d, np.float32)).to(depth[0].device) for d in depth])
+    return np.stack([np.asarray(d, np.float32).reshape(d.shape[-2], d.shape[-1]) for d in depth])
+
+
 class ValueMapBatch:
     """``n_envs`` value maps (+ confidence maps) resident in HBM, updated together."""
 
@@ -245,6 +301,7 @@ class ValueMapBatch:
         self._written = None   # [n_envs,S,ceil(S/32)] cells that ever received a confidence (explored-synchronised mode)
         self._written_stale = False  # an update ran without the explored plane since `_written` was last complete
         self._counters = None
+        self._rig_plans: Dict[Any, Dict[str, Any]] = {}   # update_cameras: per (env_ids, optics, width), see _rig_plan
         self._wp_out = self._wp_host = self._wp_cells = None
         self.traj = _render.TrajectoryPlanes(self.device, n_envs, size, pixels_per_meter)
         self._render_ring = _render.PackedRing(self.device)
@@ -382,6 +439,111 @@ class ValueMapBatch:
                 _lib.FUSION_TYPES[self.fusion_type], explored_ptr, written_ptr, self._counters.data_ptr(),
                 _TEMPLATES.quadrant(self.device, fov, max_depth, self.pixels_per_meter,
                                     self._min_confidence).data_ptr(), _stream_ptr()), "value_map_update_fused")
+
+    def update_cameras(self, values, depth, tf_camera_to_episodic, min_depth, max_depth, fov, env_ids: Sequence[int],
+                       colmax=None) -> None:
+        """ValueMap.update_map for the cameras of a rig in ONE launch (csrc/value_map.hip: value_map_update_rig_kernel).
+
+        n observations; ``env_ids`` [n] may repeat and interleave slots.  The observations of one slot are fused in the
+        order they are listed -- the reference loops over its cameras sequentially (itm_policy.py:191-211) and the weighted
+        fuse does not commute -- different slots run concurrently; the maps equal n single-camera ``update`` calls bit for
+        bit.  ``min_depth`` / ``max_depth`` / ``fov``: scalars or length-n arrays (each camera its own optics, as in
+        reality/objectnav_env.py:184-228).  ``depth`` [n,H,W] (or a list of frames of ONE shape: mixed image sizes raise
+        ValueError); ``colmax`` = the key rows [n,W] of a shared depth ingest, row i for observation i.
+
+        Errors as in ``update``: a camera outside the map or a slot out of range is an AssertionError raised before
+        anything is launched (``colmax`` keys handed in are zeroed); the maps are then unchanged, ``n_updates`` too."""
+        import torch
+
+        if torch.is_tensor(values):
+            d_vals = values.to(device=self.device, dtype=torch.float64).reshape(-1, self.channels).contiguous()
+        else:
+            d_vals = torch.from_numpy(
+                np.ascontiguousarray(np.asarray(values, np.float64).reshape(-1, self.channels))).to(self.device)
+        n = d_vals.shape[0]
+        try:
+            if colmax is None:
+                depth = stack_rig_frames(depth)
+            W = colmax.shape[-1] if colmax is not None else int(depth.shape[-1])
+            plan = self._rig_plan(env_ids, min_depth, max_depth, fov, n, W)
+            tf = np.asarray(tf_camera_to_episodic, np.float64).reshape(n, 4, 4)[plan["order"]]
+            if len(plan["groups"]) == 1:
+                pose = pose_params(tf, plan["env"], self.size, self.pixels_per_meter, plan["groups"][0][0])
+            else:                                               # the camera cell's window depends on the template size
+                pose = np.zeros(n, VM_POSE_DTYPE)
+                for T, idx in plan["groups"]:
+                    pose[idx] = pose_params(tf[idx], plan["env"][idx], self.size, self.pixels_per_meter, T)
+            pose["reserved"] = plan["order"]                    # row of the observation's keys / values / counter
+        except Exception:
+            if colmax is not None:
+                colmax.zero_()
+            raise
+        self.n_updates += plan["counts"]
+        if colmax is None:
+            if not torch.is_tensor(depth):
+                depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32)).to(self.device)
+            depth = depth.reshape(n, depth.shape[-2], depth.shape[-1]).contiguous()
+            assert depth.dtype == torch.float32
+            colmax = self.column_max(depth)
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            d_pose = self._rings(n).upload(pose)
+            explored_ptr = written_ptr = None
+            if self.explored_bits is None:
+                self._written_stale = True   # cells fused from here on are not recorded in the plane
+            else:
+                ex = self.explored_bits
+                assert ex.dtype == torch.int32 and ex.is_contiguous() and ex.shape[-2] == self.size
+                explored_ptr = ex.data_ptr()
+                if self._written is None or self._written_stale:   # (re)start from conf != 0, as update() does
+                    if self._written is None:
+                        self._written = torch.zeros((self.n_envs, self.size, (self.size + 31) // 32),
+                                                    dtype=torch.int32, device=self.device)
+                    _lib.check(L.vlfm_bits_pack((self.conf != 0).to(torch.uint8).contiguous().data_ptr(),
+                                                self._written.data_ptr(), self.n_envs, self.size, self.size,
+                                                _stream_ptr()), "bits_pack")
+                    self._written_stale = False
+                written_ptr = self._written.data_ptr()
+            if self._counters is None or self._counters.numel() < n:
+                self._counters = torch.zeros(max(n, self.n_envs), dtype=torch.int32, device=self.device)
+            static = plan["d_static"].data_ptr()
+            _lib.check(L.vlfm_value_map_update_rig_batched(
+                colmax.data_ptr(), W, d_pose.data_ptr(), static, static + n * VM_OPTICS_DTYPE.itemsize, plan["n_slots"], n,
+                plan["T_max"], d_vals.data_ptr(), self.conf.data_ptr(), self.value.data_ptr(),
+                self.size, self.channels, self.pixels_per_meter, int(self.use_max_confidence),
+                _lib.FUSION_TYPES[self.fusion_type], explored_ptr, written_ptr, self._counters.data_ptr(),
+                _stream_ptr()), "value_map_update_rig")
+
+    def _rig_plan(self, env_ids, min_depth, max_depth, fov, n: int, W: int) -> Dict[str, Any]:
+        """Everything of a rig call that does not depend on the poses: grouping by slot, the slot table and the optics records
+        (already on the device, behind one another in ``d_static``).  A rig has the same slots and optics step after step, so
+        the plan is kept per (env_ids, optics, width) and a step only builds and uploads its pose records."""
+        env = np.ascontiguousarray(np.asarray(env_ids, np.int32).reshape(-1))
+        assert env.shape == (n,), "one slot id per observation"
+        lo, hi, fv = per_observation(min_depth, n), per_observation(max_depth, n), per_observation(fov, n)
+        key = (n, W, env.tobytes(), lo.tobytes(), hi.tobytes(), fv.tobytes())
+        plan = self._rig_plans.get(key)
+        if plan is not None:
+            return plan
+        order, slots = group_rig(env, self.n_envs)
+
+        def lookup(fov_, max_depth_):
+            d_tmpl, d_bits, T = _TEMPLATES.template(self.device, fov_, max_depth_, self.pixels_per_meter, self._min_confidence)
+            d_quad = _TEMPLATES.quadrant(self.device, fov_, max_depth_, self.pixels_per_meter, self._min_confidence)
+            return (d_tmpl.data_ptr(), d_bits.data_ptr(), d_quad.data_ptr(),
+                    _TEMPLATES.tan_table(self.device, fov_, W).data_ptr(), T)
+
+        optics = rig_optics(lo, hi, fv, n, lookup)[order]
+        sizes = optics["template_size"]
+        static = np.concatenate([optics.view(np.uint8).reshape(-1), slots.view(np.uint8).reshape(-1)])
+        plan = dict(order=order.astype(np.int32), env=np.ascontiguousarray(env[order]), n_slots=len(slots),
+                    counts=np.bincount(env, minlength=self.n_envs), T_max=int(sizes.max()),
+                    groups=[(int(T), np.nonzero(sizes == T)[0]) for T in np.unique(sizes)],
+                    d_static=_bytes_to_device(static.tobytes(), self.device))
+        if len(self._rig_plans) >= 16:
+            self._rig_plans.clear()
+        self._rig_plans[key] = plan
+        return plan
 
     # ------------------------------------------------------------------------------------------ frontier scoring
     def waypoint_values(self, waypoints_xy: np.ndarray, env_of_waypoint: Sequence[int], radius: float) -> np.ndarray:
