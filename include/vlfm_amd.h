@@ -331,6 +331,18 @@ int vlfm_preprocess_rgb_batched(const uint8_t* d_rgb, int n, int height, int wid
 int vlfm_itc_head_batched(const float* d_proj, int batch, int n_query, int proj_dim,
                           const float* d_text, float* d_out, void* stream);
 
+/* Device: the ITC head of ONE image against T prompts.  d_proj [B][NQ][P] f32 as above, d_text_table [U][P] the unique
+ * L2-normalised text features, d_text_index [B][T] int32 rows of that table -> d_out [B][T],
+ * out[b][t] = max_q <proj[b][q], table[index[b][t]]> / max(|proj[b][q]|, 1e-12).  Every query row is read once: its norm
+ * and the T dot products come from one pass.  For each (b, t) the bits are those of vlfm_itc_head_batched on image b
+ * and that text row (same element order per lane, same shuffle tree).  NQ <= 64, U >= 1,
+ * 1 <= T <= VLFM_ITC_MAX_PROMPTS (one accumulator per prompt in registers, one wavefront of the 512-thread block per
+ * prompt for the max over queries).  An index outside [0, U) is never followed: that element of d_out is NaN (callers
+ * validate indices when they build the index array). */
+#define VLFM_ITC_MAX_PROMPTS 8
+int vlfm_itc_head_multi(const float* d_proj, int batch, int n_query, int proj_dim, const float* d_text_table, int n_text,
+                        const int32_t* d_text_index, int n_prompts, float* d_out, void* stream);
+
 /* y = LayerNorm(x + c) * gamma + beta over the last dimension of f16 rows [rows][dim] (f32 statistics); c = f32 [dim]
  * per-channel constant or NULL.  Used by the ViT-g blocks of BLIP-2 (blip2itm.py): the projection / fc2 GEMMs accumulate
  * straight into the residual stream and their bias vectors, summed per layer on the host once, enter through c -- the

@@ -152,6 +152,7 @@ def lib() -> ctypes.CDLL:
         L.vlfm_preprocess_sam_batched.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp]
         L.vlfm_preprocess_rgb_batched.argtypes = [vp, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, ci, ci, vp]
         L.vlfm_itc_head_batched.argtypes = [vp, ci, ci, ci, vp, vp, vp]
+        L.vlfm_itc_head_multi.argtypes = [vp, ci, ci, ci, vp, ci, vp, ci, vp, vp]
         cf = ctypes.c_float
         L.vlfm_resize_area_tab_host.argtypes = [ci, ci, vp, vp, vp, ci]
         L.vlfm_resize_area_batched.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp]

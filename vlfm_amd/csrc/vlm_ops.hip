@@ -388,6 +388,55 @@ __global__ __launch_bounds__(512) void itc_head_kernel(const float* __restrict__
     }
 }
 
+// One image against T prompts: text is a table [U][P] of unique features, idx [B][T] picks a row per (image, prompt).
+// Each query row is loaded once; its norm and the T dot products come from that one pass.  Per (b, t) the arithmetic is
+// itc_head_kernel's -- same lane-strided element order, same fmaf chains, same shuffle tree -- so the result is the same
+// bits.  An index outside the table is never followed: row 0 stands in for the loads and the result is NaN.
+template <int T>
+__global__ __launch_bounds__(512) void itc_head_multi_kernel(const float* __restrict__ proj, int NQ, int P,
+                                                             const float* __restrict__ text, int U,
+                                                             const int* __restrict__ idx, float* __restrict__ out) {
+    __shared__ float cos_q[T][64];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    const float* tp[T];
+    unsigned ok = 0;   // bit t: idx[b][t] is inside the table
+#pragma unroll
+    for (int t = 0; t < T; t++) {
+        const int u = idx[(size_t)b * T + t];
+        const bool in = u >= 0 && u < U;
+        ok |= (unsigned)in << t;
+        tp[t] = text + (size_t)(in ? u : 0) * P;
+    }
+    for (int q = wave; q < NQ; q += n_waves) {
+        const float* p = proj + ((size_t)b * NQ + q) * P;
+        float n2 = 0.0f, dt[T];
+#pragma unroll
+        for (int t = 0; t < T; t++) dt[t] = 0.0f;
+        for (int j = lane; j < P; j += 64) {
+            const float v = p[j];
+            n2 = fmaf(v, v, n2);
+#pragma unroll
+            for (int t = 0; t < T; t++) dt[t] = fmaf(v, tp[t][j], dt[t]);
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            n2 += __shfl_down(n2, off, 64);
+#pragma unroll
+            for (int t = 0; t < T; t++) dt[t] += __shfl_down(dt[t], off, 64);
+        }
+        if (lane == 0) {
+            const float nrm = fmaxf(sqrtf(n2), 1e-12f);  // F.normalize eps
+#pragma unroll
+            for (int t = 0; t < T; t++) cos_q[t][q] = dt[t] / nrm;
+        }
+    }
+    __syncthreads();
+    if (wave < T) {   // (T <= 8 = the block's wavefronts: one wavefront per prompt takes the max over the queries)
+        float c = lane < NQ ? cos_q[wave][lane] : -__builtin_huge_valf();
+        for (int off = 32; off > 0; off >>= 1) c = fmaxf(c, __shfl_down(c, off, 64));
+        if (lane == 0) out[(size_t)b * T + wave] = (ok >> wave) & 1u ? c : __builtin_nanf("");
+    }
+}
+
 }  // namespace vlfm
 
 using namespace vlfm;
@@ -555,6 +604,26 @@ extern "C" int vlfm_itc_head_batched(const float* d_proj, int batch, int n_query
     VLFM_KLAUNCH(itc_head_kernel, dim3(batch), dim3(512), 0, (hipStream_t)stream, d_proj, n_query, proj_dim,
                        d_text, d_out);
     return check_launch("itc_head_kernel");
+}
+
+extern "C" int vlfm_itc_head_multi(const float* d_proj, int batch, int n_query, int proj_dim, const float* d_text_table,
+                                   int n_text, const int32_t* d_text_index, int n_prompts, float* d_out, void* stream) {
+    if (!d_proj || !d_text_table || !d_text_index || !d_out || batch < 0 || n_query <= 0 || n_query > 64 || proj_dim <= 0 ||
+        n_text < 1 || n_prompts < 1 || n_prompts > VLFM_ITC_MAX_PROMPTS)
+        return fail(VLFM_ERR_INVALID, "itc_head_multi: bad argument (n_query <= 64, 1 <= n_prompts <= 8, n_text >= 1)");
+    if (batch == 0) return VLFM_OK;
+    VLFM_TIMED("itc_head_multi_kernel", stream);
+#define VLFM_ITC_MULTI(T)                                                                                              \
+    case T:                                                                                                            \
+        VLFM_KLAUNCH(itc_head_multi_kernel<T>, dim3(batch), dim3(512), 0, (hipStream_t)stream, d_proj, n_query,        \
+                     proj_dim, d_text_table, n_text, d_text_index, d_out);                                             \
+        break
+    switch (n_prompts) {
+        VLFM_ITC_MULTI(1); VLFM_ITC_MULTI(2); VLFM_ITC_MULTI(3); VLFM_ITC_MULTI(4);
+        VLFM_ITC_MULTI(5); VLFM_ITC_MULTI(6); VLFM_ITC_MULTI(7); VLFM_ITC_MULTI(8);
+    }
+#undef VLFM_ITC_MULTI
+    return check_launch("itc_head_multi_kernel");
 }
 
 extern "C" int vlfm_layernorm_bias_f16(const void* d_x, const float* d_channel_bias, const void* d_gamma, const void* d_beta,

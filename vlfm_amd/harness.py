@@ -264,6 +264,16 @@ class RoomsRenderer:
         return self.render(t)
 
 
+def episode_prompts(text_prompt: str, exploration_thresh: Optional[float], targets: Sequence[str]) -> List[List[str]]:
+    """The prompts BLIP-2 sees for each environment's target: ``text_prompt`` split at "|" and checked against the policy
+    (policy_step.split_text_prompt: several prompts need ``exploration_thresh``, a threshold needs two), ``target_object``
+    substituted as itm_policy.py:197 does.  Needs no device."""
+    from .policy_step import split_text_prompt, substitute_target
+
+    base = split_text_prompt(text_prompt, exploration_thresh)
+    return [substitute_target(base, t) for t in targets]
+
+
 class BatchedEpisodes:
     def __init__(self, n_envs: int, device=None, height: int = 480, width: int = 640, env_offset: int = 0,
                  blip2=None, use_blip2: bool = True, frame_pool: int = 4, map_size: int = 1000,
@@ -274,7 +284,15 @@ class BatchedEpisodes:
                  sightings: Optional["ScriptedSightings"] = None, scripted_masks: bool = False,
                  coco_threshold: float = 0.8, non_coco_threshold: float = 0.4, pointnav_stop_radius: float = 0.9,
                  object_map_erosion_size: float = 5, concurrent_vlm_max_envs: int = 0,
-                 render_trajectories: bool = False, emulate_jpeg: bool = False, rig: Optional[CameraRig] = None) -> None:
+                 render_trajectories: bool = False, emulate_jpeg: bool = False, rig: Optional[CameraRig] = None,
+                 text_prompt: str = PROMPT, exploration_thresh: Optional[float] = None) -> None:
+        # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
+        # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
+        self.env_ids = [env_offset + e for e in range(n_envs)]
+        self.targets = [TARGETS[i % len(TARGETS)] for i in self.env_ids]
+        self.prompt_lists = episode_prompts(text_prompt, exploration_thresh, self.targets)
+        self.C = len(self.prompt_lists[0]) if self.prompt_lists else len(text_prompt.split("|"))
+        self.exploration_thresh = exploration_thresh
         self.device = require_gpu(device)
         # rig: K cameras per environment (CameraRig) fused into the environment's maps by ONE ingest_cameras / update_cameras per
         # step (step() -> _step_rig()); None = one camera at the robot pose, the step as it always was
@@ -304,10 +322,9 @@ class BatchedEpisodes:
             self.jpeg_scratch = jpeg_roundtrip_scratch(n_envs, height, width, self.device)
         self.fx, self.fy, self.fov = camera_intrinsics(width)
         self.episode_len = episode_len
-        self.env_ids = [env_offset + e for e in range(n_envs)]
-        self.targets = [TARGETS[i % len(TARGETS)] for i in self.env_ids]
-        self.prompts = [PROMPT.replace("target_object", t.replace("|", "/")) for t in self.targets]
-        self.values = ValueMapBatch(n_envs, 1, map_size, use_max_confidence=False, device=self.device)
+        # one prompt: the environments' prompts as strings (what cosine_batch takes); several: per-environment lists
+        self.prompts = [p[0] for p in self.prompt_lists] if self.C == 1 else self.prompt_lists
+        self.values = ValueMapBatch(n_envs, self.C, map_size, use_max_confidence=False, device=self.device)
         self.n_frontiers = n_frontiers
         self.t = 0
         self.episodes_done = 0
@@ -408,6 +425,7 @@ class BatchedEpisodes:
         self.vlm_stream = torch.cuda.Stream(self.device) if overlap and n_envs <= concurrent_vlm_max_envs else None
         self.last_cosines: Optional[torch.Tensor] = None
         self.last_frontier_values: Optional[np.ndarray] = None
+        self.last_frontier_envs: Optional[np.ndarray] = None      # environment slot of each row of last_frontier_values
         # frontier selection of ITMPolicyV2 (stick-to-last rule, itm_policy.py:76-152), one selector per environment
         self.selectors = None
         if select_frontiers:
@@ -615,7 +633,15 @@ class BatchedEpisodes:
         (modes, goals [E,2] (nan = none), stop_no_frontier [E])."""
         goals = np.full((self.E, 2), np.nan)
         modes, halt = [], np.zeros(self.E, bool)
-        vals = np.asarray(vals, np.float64).reshape(-1) if vals is not None else np.zeros(0)
+        # (getattr: tests/test_host_logic.py calls this method on a bare stand-in object that carries only the attributes the
+        # single-prompt rules read; the constructor always sets the attribute)
+        thresh = getattr(self, "exploration_thresh", None)
+        if thresh is None:
+            vals = np.asarray(vals, np.float64).reshape(-1) if vals is not None else np.zeros(0)
+        else:
+            from .policy_step import explore_reduce_values
+
+            vals = np.asarray(vals, np.float64).reshape(-1, self.C) if vals is not None else np.zeros((0, self.C))
         bounds = np.searchsorted(env_of, np.arange(self.E + 1))
         ep_steps = self._episode_steps(t_ep)
         for e in range(self.E):
@@ -631,9 +657,13 @@ class BatchedEpisodes:
                 if hi <= lo:
                     halt[e] = True          # "No frontiers found during exploration, stopping." itm_policy.py:64-67
                     continue
-                order = np.argsort(-vals[lo:hi])       # sort_waypoints' descending order (value_map.py:183-186)
+                v = vals[lo:hi]
+                if thresh is not None:    # ITMPolicyV3._reduce_values over this environment's frontiers (through lists: the ONE
+                    # function the single-environment policy uses, which takes the reference's list of tuples)
+                    v = np.array(explore_reduce_values(v.tolist(), thresh), np.float64)
+                order = np.argsort(-v)       # sort_waypoints' descending order (value_map.py:183-186)
                 pts = wps[lo:hi]
-                goals[e], _ = self.selectors[e].choose(pts[order], [float(v) for v in vals[lo:hi][order]], pts, robot_xy)
+                goals[e], _ = self.selectors[e].choose(pts[order], [float(x) for x in v[order]], pts, robot_xy)
             else:
                 modes.append("navigate")
                 goals[e] = obj[:2]
@@ -732,7 +762,10 @@ class BatchedEpisodes:
         main = torch.cuda.current_stream(self.device)
         if self.map_stream is not None:
             main.wait_stream(self.map_stream)   # obstacle planes and trajectories are written on the map stream
-        out = {"value_map": self.values.render(env, rgb=rgb)}
+        if self.exploration_thresh is None:
+            out = {"value_map": self.values.render(env, rgb=rgb)}
+        else:     # the visual reducer ITMPolicyV3.__init__ installs (itm_policy.py:275-287)
+            out = {"value_map": self.values.render(env, reduce=("explore", float(self.exploration_thresh)), rgb=rgb)}
         if self.obstacles is not None:
             out["obstacle_map"] = self.obstacles.render(env, rgb=rgb)
         return out
@@ -765,9 +798,18 @@ class BatchedEpisodes:
         from .utils.log_saver import is_evaluated, log_episode
 
         n_fr = self.obstacles.frontiers_px() if self.obstacles is not None and self.obstacles.frontiers_ready else None
-        best = None
+        best = [None] * self.E
         if self.last_frontier_values is not None and len(self.last_frontier_values):
-            best = float(np.max(self.last_frontier_values))
+            if self.exploration_thresh is None:      # (single prompt: the batch-wide maximum, as it always was)
+                best = [float(np.max(self.last_frontier_values))] * self.E
+            else:     # V3's rule is per environment: the best value of ITS frontiers after ITS reduction
+                from .policy_step import explore_reduce_values
+
+                v, env_of = np.asarray(self.last_frontier_values).reshape(-1, self.C), np.asarray(self.last_frontier_envs)
+                for e in range(self.E):
+                    mine = v[env_of == e]
+                    if len(mine):
+                        best[e] = float(max(explore_reduce_values(mine.tolist(), self.exploration_thresh)))
         for e, env_id in enumerate(self.env_ids):
             episode_id = self.episodes_done * len(self.env_ids) + e
             scene = f"synthetic{env_id:04d}"
@@ -777,7 +819,7 @@ class BatchedEpisodes:
                 "target_object": self.targets[e], "num_steps": int(self.episode_len),
                 "final_pose": [float(v) for v in self.pose_table[(self.t - 1) % self.episode_len][e]],
                 "num_frontiers": int(len(n_fr[e])) if n_fr is not None else 0,
-                "best_frontier_value_last_step": best})
+                "best_frontier_value_last_step": best[e]})
 
     def _detect(self, rgb: torch.Tensor, t_ep: int):
         """The detector on the frames ``rgb`` [E,H,W,3] of episode step ``t_ep`` (one frame per environment) -> per-environment
@@ -889,16 +931,18 @@ class BatchedEpisodes:
         if self.blip2 is not None:
             rgb = pool[torch.from_numpy((slot[v_idx] + cam[v_idx] - rig.designated) % E).to(self.device)]
             prompts = [self.prompts[e] for e in slot[v_idx]]
-            cos = self.blip2.cosine_batch(rgb, prompts)
-        else:
+            cos = self.blip2.cosine_batch(rgb, prompts) if self.C == 1 else self.blip2.cosine_prompts_batch(rgb, prompts)
+        elif self.C == 1:
             cos = torch.from_numpy(self.stub_rng.uniform(0.15, 0.45, size=n_v)).to(self.device)
+        else:
+            cos = torch.from_numpy(self.stub_rng.uniform(0.15, 0.45, size=(n_v, self.C))).to(self.device)
         self.last_cosines = cos
         with torch.cuda.stream(side):
             wps, env_of = self.obstacles.frontier_list()
         main.wait_stream(side)
-        self.values.update_cameras(cos.reshape(n_v, 1), None, tf[v_idx], lo[v_idx], hi[v_idx], hfov[v_idx], slot[v_idx],
+        self.values.update_cameras(cos.reshape(n_v, self.C), None, tf[v_idx], lo[v_idx], hi[v_idx], hfov[v_idx], slot[v_idx],
                                    colmax=self._rig_keys)
-        self.last_frontier_values = None
+        self.last_frontier_values, self.last_frontier_envs = None, env_of
         if len(wps):
             self.last_frontier_values = self.values.waypoint_values(wps, env_of, 0.5)
         if self.selectors is not None:
@@ -958,6 +1002,9 @@ class BatchedEpisodes:
         dets = None
 
         def perceive():
+            if self.C > 1:      # every prompt of every environment from one vision forward -> [E, C]
+                return (self.blip2.cosine_prompts_batch_graphed(rgb, self.prompts) if self.graph_blip2
+                        else self.blip2.cosine_prompts_batch(rgb, self.prompts))
             return (self.blip2.cosine_batch_graphed(rgb, self.prompts) if self.graph_blip2
                     else self.blip2.cosine_batch(rgb, self.prompts))
 
@@ -974,8 +1021,10 @@ class BatchedEpisodes:
             pass
         elif self.blip2 is not None:
             cos = perceive()
-        else:
+        elif self.C == 1:
             cos = torch.from_numpy(self.stub_rng.uniform(0.15, 0.45, size=self.E)).to(self.device)
+        else:
+            cos = torch.from_numpy(self.stub_rng.uniform(0.15, 0.45, size=(self.E, self.C))).to(self.device)
         self.last_cosines = cos
         if not detector_first:
             dets = self._detect(rgb, t_ep)
@@ -1009,9 +1058,9 @@ class BatchedEpisodes:
         if vlm_beside:
             main.wait_stream(self.vlm_stream)          # the cosines; and the next step may not repaint the frames under the ViT
             cos.record_stream(main)
-        self.values.update(cos.reshape(self.E, 1), None, tf, MIN_DEPTH, MAX_DEPTH, self.fov, colmax=colmax)
+        self.values.update(cos.reshape(self.E, self.C), None, tf, MIN_DEPTH, MAX_DEPTH, self.fov, colmax=colmax)
         # ---- frontier scoring (ITMPolicyV2._sort_frontiers_by_value, radius 0.5 m)
-        self.last_frontier_values = None
+        self.last_frontier_values, self.last_frontier_envs = None, env_of
         if len(wps):
             self.last_frontier_values = self.values.waypoint_values(wps, env_of, 0.5)  # D2H sync: the policy needs it
         if self.selectors is not None:

@@ -268,9 +268,11 @@ class ITMPolicyV2Step:
         """``cameras`` = [(rgb, depth, tf, min_depth, max_depth, fov), ...].  One cosine per camera and per prompt
         ("|"-separated) with target_object substituted, the "|" of a multi-name category shown to BLIP-2 as "/"; ALL
         cosines are asked for first, then the maps are updated camera by camera (itm_policy.py:191-211)."""
-        shown = self._target_object.replace("|", "/")
-        prompts = [p.replace("target_object", shown) for p in self._text_prompt.split(PROMPT_SEPARATOR)]
-        cosines = [[self._itm.cosine(cam[0], p) for p in prompts] for cam in cameras]
+        prompts = substitute_target(self._text_prompt.split(PROMPT_SEPARATOR), self._target_object)
+        if hasattr(self._itm, "cosines"):     # all prompts of a camera from ONE vision forward (one call per camera: B = 1)
+            cosines = [list(self._itm.cosines(cam[0], prompts)) for cam in cameras]
+        else:                                 # any other client: the reference's one call per prompt
+            cosines = [[self._itm.cosine(cam[0], p) for p in prompts] for cam in cameras]
         for cos, (_, depth, tf, min_depth, max_depth, fov) in zip(cosines, cameras):
             self._value_map.update_map(np.array(cos), depth, tf, min_depth, max_depth, fov)
         self._value_map.update_agent_traj(robot_xy, heading)
@@ -441,6 +443,36 @@ class ITMPolicyV2Step:
         return out
 
 
+def explore_reduce_values(values: Sequence[Sequence[float]], exploration_thresh: float) -> List[float]:
+    """ITMPolicyV3._reduce_values (itm_policy.py:296-316) for ONE environment's frontiers: ``values`` = one (target value,
+    exploration value) per frontier; every frontier is scored by its exploration value iff the highest target value among
+    them is below ``exploration_thresh``, by its target value otherwise."""
+    use = 1 if max(v[0] for v in values) < exploration_thresh else 0
+    return [v[use] for v in values]
+
+
+def split_text_prompt(text_prompt: str, exploration_thresh: Optional[float] = None) -> List[str]:
+    """The prompts of a ``text_prompt`` ("|"-separated, itm_policy.py:23), checked against the policy they imply: more than
+    one value channel needs a reduction (value_map.py sort_waypoints: "Must provide a reduction function when using
+    multiple value channels") -- here V3's ``exploration_thresh`` -- and that threshold needs its two channels.  Needs no
+    device."""
+    prompts = text_prompt.split(PROMPT_SEPARATOR)
+    if exploration_thresh is None and len(prompts) > 1:
+        raise ValueError("Must provide a reduction function when using multiple value channels: "
+                         f"{len(prompts)} prompts need exploration_thresh")
+    if exploration_thresh is not None and len(prompts) < 2:
+        raise ValueError("exploration_thresh ranks frontiers by a second (exploration) channel: text_prompt needs at "
+                         "least two '|'-separated prompts")
+    return prompts
+
+
+def substitute_target(prompts: Sequence[str], target_object: str) -> List[str]:
+    """The prompts as BLIP-2 sees them for one target: ``target_object`` substituted, the "|" of a multi-name category
+    shown as "/" (itm_policy.py:197)."""
+    shown = target_object.replace("|", "/")
+    return [p.replace("target_object", shown) for p in prompts]
+
+
 class ITMPolicyV3Step(ITMPolicyV2Step):
     """ITMPolicyV3 (itm_policy.py:270-318): two prompts ("target | exploration") -> a two-channel value map; a frontier is
     scored by its target channel, unless no frontier's target value reaches ``exploration_thresh`` -- then every
@@ -454,8 +486,7 @@ class ITMPolicyV3Step(ITMPolicyV2Step):
         self._vis_reduce_fn = explore_reduce_fn(exploration_thresh)   # itm_policy.py:275-287, on the device
 
     def _reduce_values(self, values: Sequence[Tuple[float, float]]) -> List[float]:
-        use = 1 if max(v[0] for v in values) < self._exploration_thresh else 0
-        return [v[use] for v in values]
+        return explore_reduce_values(values, self._exploration_thresh)
 
     def _sort_frontiers_by_value(self, frontiers: np.ndarray):
         return self._value_map.sort_waypoints(frontiers, 0.5, reduce_fn=self._reduce_values)

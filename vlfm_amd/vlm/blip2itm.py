@@ -714,6 +714,7 @@ class BLIP2ITM:
             blk.pack_heads()
             blk.strict_hip_attention = bool(strict_hip_attention)
         self._text_cache: Dict[str, torch.Tensor] = {}
+        self._prompt_cache: Dict[tuple, tuple] = {}
         self._proj_t = None
         self.two_stream_min = None    # e.g. 64: run batches of at least that many images as two halves on two streams
         self._side_stream = None
@@ -813,10 +814,9 @@ class BLIP2ITM:
         g.replay()
         return static_out
 
-    @torch.inference_mode()
-    def cosine_batch(self, images_u8: torch.Tensor, txts: Sequence[str]) -> torch.Tensor:
-        """images_u8: [B,H,W,3] uint8 RGB on device; txts: one prompt per image (or a single shared prompt).
-        Returns [B] fp32 cosines on device (no host sync)."""
+    def _query_feats(self, images_u8: torch.Tensor) -> torch.Tensor:
+        """[B,H,W,3] u8 -> the Q-Former's query outputs [B,NQ,H] f32: preprocessing, ViT-g and Q-Former, the part of the forward
+        that does not depend on the text (``cosine_batch`` and ``cosine_prompts_batch`` share it)."""
         from . import ops
 
         B = images_u8.shape[0]
@@ -840,6 +840,16 @@ class BLIP2ITM:
             q = torch.cat([q_lo, q_hi]).contiguous()
         else:
             q = self.model.query_features(self.model.vision_tokens(pix)).float().contiguous()
+        return q
+
+    @torch.inference_mode()
+    def cosine_batch(self, images_u8: torch.Tensor, txts: Sequence[str]) -> torch.Tensor:
+        """images_u8: [B,H,W,3] uint8 RGB on device; txts: one prompt per image (or a single shared prompt).
+        Returns [B] fp32 cosines on device (no host sync)."""
+        from . import ops
+
+        B = images_u8.shape[0]
+        q = self._query_feats(images_u8)
         if len(txts) == 1:
             text = self.text_feature(txts[0])[None].expand(B, -1).contiguous()
         else:
@@ -849,6 +859,57 @@ class BLIP2ITM:
             self._proj_t = (self.model.vision_projection.weight.float().t().contiguous(),
                             self.model.vision_projection.bias.float().contiguous())
         return ops.itc_head(q, self._proj_t[0], self._proj_t[1], text)
+
+    def _prompt_tensors(self, prompts, B: int):
+        """(text table [U,P], index [B,T] int32) of a prompt structure, built and uploaded once per structure (the index is
+        validated there): a steady-state step finds both in the cache and uploads nothing.  Never evicted, like ``_text_cache``."""
+        from . import ops
+
+        key = (B, tuple(prompts) if isinstance(prompts[0], str) else tuple(tuple(p) for p in prompts))
+        hit = self._prompt_cache.get(key)
+        if hit is None:
+            unique, rows = prompt_table(prompts, B)
+            table = torch.stack([self.text_feature(t) for t in unique]).contiguous()
+            hit = self._prompt_cache[key] = (table, ops.itc_text_index(rows, len(unique), self.device), key)
+        return hit
+
+    @torch.inference_mode()
+    def cosine_prompts_batch(self, images_u8: torch.Tensor, prompts) -> torch.Tensor:
+        """images_u8: [B,H,W,3] uint8 RGB on device; prompts: ONE list of T prompts shared by all images, or B lists of T
+        prompts.  Returns [B,T] fp32 cosines on device (no host sync): one vision forward -- the image side of ITC does
+        not depend on the text -- and one head launch for all T prompts; column t carries what ``cosine_batch`` gives
+        for the t-th prompts."""
+        from . import ops
+
+        B = images_u8.shape[0]
+        q = self._query_feats(images_u8)
+        table, index, _ = self._prompt_tensors(prompts, B)
+        if self._proj_t is None:
+            self._proj_t = (self.model.vision_projection.weight.float().t().contiguous(),
+                            self.model.vision_projection.bias.float().contiguous())
+        return ops.itc_head_multi(q, self._proj_t[0], self._proj_t[1], table, index)
+
+    def cosine_prompts_batch_graphed(self, images_u8: torch.Tensor, prompts) -> torch.Tensor:
+        """``cosine_prompts_batch`` replayed from a captured HIP graph, one per (shape, prompt structure) key, as
+        ``cosine_batch_graphed``: the table and the index are the cached tensors of that structure, static under replay."""
+        table, index, structure = self._prompt_tensors(prompts, images_u8.shape[0])
+        key = (tuple(images_u8.shape), structure)
+        if not hasattr(self, "_prompt_graphs"):
+            self._prompt_graphs = {}
+        if key not in self._prompt_graphs:
+            static_in = images_u8.clone()
+            for _ in range(2):  # warm-up outside capture: coefficient tables, text features, hipBLASLt workspaces
+                self.cosine_prompts_batch(static_in, prompts)
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                static_out = self.cosine_prompts_batch(static_in, prompts)
+            # (the graph holds the addresses of the table and the index: they live as long as it does)
+            self._prompt_graphs[key] = (g, static_in, static_out, table, index)
+        g, static_in, static_out = self._prompt_graphs[key][:3]
+        static_in.copy_(images_u8)
+        g.replay()
+        return static_out
 
     def check_numerics(self) -> None:
         """Raise if a split-precision f32 GEMM of the Q-Former met an operand outside f16's range since the last check (its result is
@@ -866,6 +927,28 @@ class BLIP2ITM:
         """blip2itm.py:37-54: one RGB frame (H,W,3) u8 + prompt -> Python float."""
         img = torch.from_numpy(np.ascontiguousarray(image)).to(self.device)[None]
         return float(self.cosine_batch(img, [txt])[0].item())
+
+    def cosines(self, image: np.ndarray, prompts: Sequence[str]) -> List[float]:
+        """One RGB frame against every prompt of ``prompts``: what ``[cosine(image, p) for p in prompts]`` returns, from one
+        vision forward."""
+        img = torch.from_numpy(np.ascontiguousarray(image)).to(self.device)[None]
+        return [float(v) for v in self.cosine_prompts_batch(img, list(prompts))[0].tolist()]
+
+
+def prompt_table(prompts, n_images: int):
+    """A prompt structure -- one list of T prompts shared by all images, or ``n_images`` lists of T prompts -> (the unique
+    prompts in order of first appearance, index rows [n_images][T] into them).  Needs no device."""
+    if len(prompts) == 0:
+        raise ValueError("at least one prompt is needed")
+    per = [list(prompts)] * n_images if isinstance(prompts[0], str) else [list(p) for p in prompts]
+    if len(per) != n_images:
+        raise ValueError(f"{len(per)} prompt lists for {n_images} images")
+    T = len(per[0]) if per else 0
+    if any(len(p) != T for p in per) or (per and T == 0):
+        raise ValueError("every image needs the same number (>= 1) of prompts")
+    unique: Dict[str, int] = {}
+    rows = [[unique.setdefault(t, len(unique)) for t in p] for p in per]
+    return list(unique), rows
 
 
 class BLIP2ITMClient:
@@ -889,3 +972,11 @@ class BLIP2ITMClient:
 
             image = jpeg_roundtrip(image)  # server_wrapper.py:57-68
         return self._model.cosine(image, txt)
+
+    def cosines(self, image: np.ndarray, prompts: Sequence[str]) -> List[float]:
+        """``[cosine(image, p) for p in prompts]`` from one vision forward (and one transport hop when it is emulated)."""
+        if self._emulate_jpeg:
+            from .transport import jpeg_roundtrip
+
+            image = jpeg_roundtrip(image)
+        return self._model.cosines(image, prompts)

@@ -86,6 +86,41 @@ def itc_head(query_feats: torch.Tensor, proj_t: torch.Tensor, proj_bias: torch.T
     return out
 
 
+ITC_MAX_PROMPTS = 8     # VLFM_ITC_MAX_PROMPTS (include/vlfm_amd.h)
+
+
+def itc_text_index(rows, n_text: int, device) -> torch.Tensor:
+    """[B][T] rows of a text table with ``n_text`` rows -> the int32 device index tensor ``itc_head_multi`` takes, validated
+    HERE, once, where it is built (the kernel never follows an index outside the table, but answers NaN for it)."""
+    idx = np.asarray(rows, np.int64)
+    if idx.ndim != 2 or idx.shape[1] < 1 or idx.shape[1] > ITC_MAX_PROMPTS:
+        raise ValueError(f"text index must be [B, T] with 1 <= T <= {ITC_MAX_PROMPTS}, got shape {idx.shape}")
+    if n_text < 1 or (idx.size and (idx.min() < 0 or idx.max() >= n_text)):
+        raise ValueError(f"text index outside the table of {n_text} row(s)")
+    return torch.from_numpy(idx.astype(np.int32)).to(device)
+
+
+def itc_head_multi(query_feats: torch.Tensor, proj_t: torch.Tensor, proj_bias: torch.Tensor, text_table: torch.Tensor,
+                   text_index: torch.Tensor) -> torch.Tensor:
+    """query_feats [B,NQ,H] f32, proj_t [H,P], proj_bias [P], text_table [U,P] unique text features, text_index [B,T]
+    int32 rows of the table (``itc_text_index``) -> [B,T] cosines: ONE projection (the ``addmm`` of ``itc_head``, so both
+    heads see the same tensor) and ONE epilogue launch for all T prompts of every image."""
+    B, NQ, Hd = query_feats.shape
+    P = proj_t.shape[1]
+    for t in (query_feats, proj_t, proj_bias, text_table):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    assert text_index.is_cuda and text_index.dtype == torch.int32 and text_index.is_contiguous()
+    assert proj_t.shape[0] == Hd and text_table.dim() == 2 and text_table.shape[1] == P
+    assert text_index.dim() == 2 and text_index.shape[0] == B
+    U, T = text_table.shape[0], text_index.shape[1]
+    proj = torch.addmm(proj_bias, query_feats.view(B * NQ, Hd), proj_t)
+    out = torch.empty((B, T), dtype=torch.float32, device=query_feats.device)
+    with torch.cuda.device(query_feats.device):
+        _lib.check(_lib.lib().vlfm_itc_head_multi(proj.data_ptr(), B, NQ, P, text_table.data_ptr(), U,
+                                                 text_index.data_ptr(), T, out.data_ptr(), _stream()), "itc_head_multi")
+    return out
+
+
 SAM_MEAN = (123.675, 116.28, 103.53)   # Sam.pixel_mean / pixel_std [ext segment_anything / mobile_sam build_sam]
 SAM_STD = (58.395, 57.12, 57.375)
 
