@@ -676,6 +676,36 @@ size_t vlfm_jpeg_scratch_bytes(int n, int H, int W);               /* 0 for inva
 int vlfm_jpeg_roundtrip_batched(const uint8_t* d_in, uint8_t* d_out, int n, int H, int W, const uint16_t* h_tables,
                                 void* d_scratch, size_t scratch_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * JPEG encoder (ABI 12): the files Pillow's save(format="JPEG", quality=q, subsampling="4:2:0") writes through
+ * libjpeg-turbo, byte for byte, for n frames at once: baseline, one interleaved scan, the standard Huffman tables of
+ * Annex K, no restart markers (csrc/jpeg_entropy.hip; tests/jpeg_huff_ref.py is the NumPy form).
+ *
+ * vlfm_jpeg_header_host: the 623 bytes in front of the scan (SOI, APP0 JFIF 1.01, two DQT, SOF0, four DHT, SOS) for
+ *   (quality, H, W); *len = 623 always, VLFM_ERR_CAPACITY if cap is less.
+ * vlfm_jpeg_encode_bound: a capacity no frame of H x W can exceed, whatever its content and tables; 0 for sizes the encoder
+ *   does not take.  Derivation: a block costs at most one DC code of 11 bits + 11 amplitude bits and, for each of its 63
+ *   AC coefficients, a 16-bit run/size code + 10 amplitude bits (a ZRL or EOB code replaces >= 1 such coefficient and is
+ *   shorter): 1660 bits.  bound = 623 + 2 * ceil(6 * ceil(H/16) * ceil(W/16) * 1660 / 8) + 2: the header, the scan with
+ *   its last byte padded and every byte stuffed, EOI.
+ * vlfm_jpeg_encode_scratch_bytes: the scratch the call below needs (coefficients, block bit offsets, the unstuffed stream at
+ *   the bound, 0xFF counts); 0 for invalid sizes.
+ * vlfm_jpeg_encode_batched: d_in uint8 [n][H][W][3] device frames packed back to back; rgb_order 0 reads slot 2 of a pixel
+ *   as R (what cv2.imencode does with the frame the reference hands it: the convention of vlfm_jpeg_roundtrip_batched),
+ *   1 reads slot 0 as R (Image.fromarray(rgb).save).  Frame i's file goes to d_out + i * capacity, its full length to
+ *   d_lengths[i].  A frame longer than capacity is cut at capacity -- no byte outside its own slot is written, the other
+ *   frames are complete, the call still returns VLFM_OK and d_lengths[i] > capacity tells.  Bytes of a slot behind the
+ *   file's end are left as they were.  h_tables, d_scratch alignment and the argument checks as for the round trip; in
+ *   addition frames whose scan could pass 2^32 bits (6 * ceil(H/16) * ceil(W/16) * 1660 >= 2^32, about 10 000 x 10 000
+ *   pixels) are refused: bit offsets and lengths are 32-bit.  Seven kernel launches on `stream`, no synchronisation.
+ * ------------------------------------------------------------------------------------------- */
+int vlfm_jpeg_header_host(int quality, int H, int W, uint8_t* h_out, size_t cap, size_t* len);
+size_t vlfm_jpeg_encode_bound(int H, int W);
+size_t vlfm_jpeg_encode_scratch_bytes(int n, int H, int W);
+int vlfm_jpeg_encode_batched(const uint8_t* d_in, int n, int H, int W, int rgb_order, const uint16_t* h_tables,
+                             uint8_t* d_out, size_t capacity, uint32_t* d_lengths, void* d_scratch, size_t scratch_bytes,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,9 @@
 //                         limit.  Decoded Y, Cb, Cr samples go to the scratch planes.
 //   jpeg_upsample_kernel  one thread per 16-pixel output run: h2v2 fancy chroma upsampling and YCbCr -> RGB, 3 x 16 B stores.
 //
+// The encoder (jpeg_entropy.hip) uses jpeg_code_kernel<true, *>: the same kernel stopped after quantisation, storing the
+// quantised coefficients of every block of the scan instead of decoding them.
+//
 // Upsampling output rows 16k-1 and 16k needs a decoded chroma row of the neighbouring MCU row; the plane pass makes that a
 // read of the scratch plane instead of a recomputed halo (why, and what the planes cost in bytes).
 //
@@ -147,6 +150,16 @@ struct Geometry {
 
 __device__ __forceinline__ uint32_t byte_of(const uint32_t* w, int i) { return (w[i >> 2] >> (8 * (i & 3))) & 0xffu; }
 
+// jutils.c jpeg_natural_order: the natural (row-major) index of the k-th coefficient in zigzag order
+__device__ const uint8_t kNaturalOrder[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
+                                              12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                                              35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
+                                              58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// kEncode = false: the round trip (decoded planes to `scratch`).  kEncode = true: the encoder's coefficient pass, which
+// stops after quantisation and stores every block of the scan as 64 int16 in zigzag order, blocks in scan order (MCUs
+// row-major; Y00 Y01 Y10 Y11 Cb Cr), to `scratch`; kRgb then reads slot 0 of a pixel as R instead of slot 2.
+template <bool kEncode, bool kRgb>
 __global__ void __launch_bounds__(THREADS) jpeg_code_kernel(const uint8_t* __restrict__ in, QuantTables qt, Geometry g,
                                                             uint8_t* __restrict__ scratch) {
     __shared__ uint4 px4[16 * TILE_ROW_BYTES / 16];   // 16 interleaved sample rows of the tile
@@ -199,7 +212,8 @@ __global__ void __launch_bounds__(THREADS) jpeg_code_kernel(const uint8_t* __res
         for (int i = 0; i < 6; ++i) w[i] = pxw[(lrow * TILE_ROW_BYTES + bc * 24) / 4 + i];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const int B = byte_of(w, 3 * i), G = byte_of(w, 3 * i + 1), R = byte_of(w, 3 * i + 2);
+            const int B = byte_of(w, 3 * i + (kRgb ? 2 : 0)), G = byte_of(w, 3 * i + 1);
+            const int R = byte_of(w, 3 * i + (kRgb ? 0 : 2));
             v[i] = ((fix16(0.299) * R + fix16(0.587) * G + fix16(0.114) * B + ONE_HALF) >> 16) - 128;
         }
     } else {
@@ -221,7 +235,8 @@ __global__ void __launch_bounds__(THREADS) jpeg_code_kernel(const uint8_t* __res
             for (int i = 0; i < 12; ++i) w[i] = pxw[((2 * li + rr) * TILE_ROW_BYTES + bc * 48) / 4 + i];
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int B = byte_of(w, 3 * i), G = byte_of(w, 3 * i + 1), R = byte_of(w, 3 * i + 2);
+                const int B = byte_of(w, 3 * i + (kRgb ? 2 : 0)), G = byte_of(w, 3 * i + 1);
+                const int R = byte_of(w, 3 * i + (kRgb ? 0 : 2));
                 s[i >> 1] += (cr_r * R + cr_g * G + cr_b * B + CBCR_OFFSET + ONE_HALF - 1) >> 16;
             }
         }
@@ -248,14 +263,41 @@ __global__ void __launch_bounds__(THREADS) jpeg_code_kernel(const uint8_t* __res
             int q = (int)((float)num * qrcp[tab][i * 8 + c]);   // off by at most one (num < 2^18): corrected below
             const int rest = num - q * d;
             q += rest < 0 ? -1 : rest >= d ? 1 : 0;
-            v[i] = (v[i] < 0 ? -q : q) * (d >> 3);
+            v[i] = (v[i] < 0 ? -q : q) * (kEncode ? 1 : d >> 3);
         }
-        idct8<CONST_BITS - PASS1_BITS>(v);
+        if (!kEncode) idct8<CONST_BITS - PASS1_BITS>(v);
 #pragma unroll
         for (int i = 0; i < 8; ++i) cb[i * CSTRIDE + c] = v[i];
     }
     __syncthreads();
 
+    if (kEncode) {
+        // ---- zigzag positions 8r .. 8r+7 of block b: one 16-byte store.  jccoefct.c compress_data: a luma block past the
+        // last real block column ceil(W/8) or row ceil(H/8) is a dummy -- AC all zero, DC that of the block coded just
+        // before it in its MCU (itself possibly a dummy; the first block of an MCU is always real).
+        const int u = b < 16 ? (b & 7) >> 1 : (b - 16) & 3;            // MCU of the tile
+        const int mx = x0 / 16 + u;
+        if (mx >= g.mw) return;
+        const int k = b < 16 ? (b >> 3) * 2 + (b & 1) : 4 + ((b - 16) >> 2);
+        const int bh = (g.H + 7) >> 3, bw = (g.W + 7) >> 3;
+        int src = k;
+        if (b < 16)
+            while (src > 0 && (2 * m + (src >> 1) >= bh || 2 * mx + (src & 1) >= bw)) --src;
+        const int* sb = src == k ? cb : coef + ((src >> 1) * 8 + 2 * u + (src & 1)) * CBLOCK;
+        uint32_t w[4];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int nat = kNaturalOrder[8 * r + j];
+            int c = sb[(nat >> 3) * CSTRIDE + (nat & 7)];
+            if (src != k && 8 * r + j > 0) c = 0;
+            if (j & 1) w[j >> 1] |= (uint32_t)(c & 0xffff) << 16;
+            else w[j >> 1] = (uint32_t)(c & 0xffff);
+        }
+        int16_t* dst = reinterpret_cast<int16_t*>(scratch) +
+                       ((((size_t)f * g.mh + m) * g.mw + mx) * 6 + k) * 64 + 8 * r;
+        *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+        return;
+    }
     // ---- row r of block b: IDCT pass 2, range limit, 8 samples to the scratch plane.
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = cb[r * CSTRIDE + i];
@@ -358,6 +400,29 @@ __global__ void __launch_bounds__(256) jpeg_upsample_kernel(const uint8_t* __res
     }
 }
 
+// The encoder's coefficient pass (jpeg_entropy.hip calls it): 768 bytes per MCU to d_coef.
+int launch_coefficients(const uint8_t* d_in, int n, int H, int W, int rgb_order, const uint16_t* h_tables, int16_t* d_coef,
+                        hipStream_t st) {
+    Geometry g;
+    g.n = n; g.H = H; g.W = W;
+    g.mh = (H + 15) / 16; g.mw = (W + 15) / 16;
+    g.tiles_x = (g.mw + TILE_MCUS - 1) / TILE_MCUS;
+    g.ch = (H + 1) / 2; g.cw = (W + 1) / 2;
+    g.vec_in = (3 * (size_t)W) % 16 == 0 && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0;
+    g.vec_out = 0;
+    QuantTables qt;
+    for (int i = 0; i < 128; ++i) qt.q[i >> 6][i & 63] = h_tables[i];
+    const size_t code_blocks = (size_t)n * g.mh * g.tiles_x;
+    if (code_blocks > 0x7fffffff) return fail(VLFM_ERR_INVALID, "jpeg_encode_batched: batch too large for one launch");
+    auto kernel = rgb_order ? jpeg_code_kernel<true, true> : jpeg_code_kernel<true, false>;
+    {
+        VLFM_TIMED("jpeg_coef_kernel", st);
+        VLFM_KLAUNCH(kernel, dim3((unsigned)code_blocks), dim3(THREADS), 0, st, d_in, qt, g,
+                     reinterpret_cast<uint8_t*>(d_coef));
+    }
+    return check_launch("jpeg_coef_kernel");
+}
+
 }  // namespace jpeg
 }  // namespace vlfm
 
@@ -432,7 +497,8 @@ extern "C" int vlfm_jpeg_roundtrip_batched(const uint8_t* d_in, uint8_t* d_out, 
     hipStream_t st = (hipStream_t)stream;
     {
         VLFM_TIMED("jpeg_code_kernel", st);
-        VLFM_KLAUNCH(jpeg_code_kernel, dim3((unsigned)code_blocks), dim3(THREADS), 0, st, d_in, qt, g, scratch);
+        auto kernel = jpeg_code_kernel<false, false>;
+        VLFM_KLAUNCH(kernel, dim3((unsigned)code_blocks), dim3(THREADS), 0, st, d_in, qt, g, scratch);
     }
     if (int rc = check_launch("jpeg_code_kernel")) return rc;
     {

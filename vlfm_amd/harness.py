@@ -770,6 +770,15 @@ class BatchedEpisodes:
             out["obstacle_map"] = self.obstacles.render(env, rgb=rgb)
         return out
 
+    def render_jpeg(self, env_ids: Optional[Sequence[int]] = None, quality: int = 90) -> Dict[str, List[bytes]]:
+        """``render()`` as JPEG files: for each map the frames of the chosen environments (all by default), every one the
+        bytes ``Image.fromarray(frame).save(format="JPEG", quality=quality, subsampling="4:2:0")`` writes for the RGB frame
+        ``render()`` returns, encoded on the device (transport.jpeg_encode_batch_bytes) so that only the files cross to
+        the host.  Not part of the timed step."""
+        from .vlm.transport import jpeg_encode_batch_bytes
+
+        return {name: jpeg_encode_batch_bytes(frames.contiguous(), quality, "rgb") for name, frames in self.render(env_ids).items()}
+
     def frontier_stats(self):
         """(mean, max) number of frontiers per environment at the last step (what the obstacle pipeline is working on)."""
         if self.obstacles is None or not self.obstacles.frontiers_ready:

@@ -102,3 +102,144 @@ def jpeg_roundtrip_batch(images_u8, quality: int = 90, out=None, scratch=None):
                                                           scratch.data_ptr(), scratch.numel(), _stream()),
                    "jpeg_roundtrip_batched")
     return out
+
+
+JPEG_HEADER_BYTES = 623
+
+
+def jpeg_header(quality: int, height: int, width: int) -> bytes:
+    """The 623 bytes in front of the scan of every quality-q height x width file ``jpeg_encode_batch`` writes."""
+    from .. import _lib
+
+    import ctypes
+
+    buf, n = np.zeros(JPEG_HEADER_BYTES, np.uint8), ctypes.c_size_t(0)
+    _lib.check(_lib.lib().vlfm_jpeg_header_host(int(quality), int(height), int(width), buf.ctypes.data, buf.size,
+                                                ctypes.byref(n)), "jpeg_header_host")
+    return buf[:n.value].tobytes()
+
+
+def jpeg_encode_bound(height: int, width: int) -> int:
+    """A per-frame capacity that no height x width frame exceeds, whatever its content (0: not a size the encoder takes)."""
+    from .. import _lib
+
+    return int(_lib.lib().vlfm_jpeg_encode_bound(int(height), int(width)))
+
+
+def jpeg_encode_scratch(n: int, height: int, width: int, device) -> "torch.Tensor":
+    """A device buffer that ``jpeg_encode_batch(..., scratch=)`` accepts for n frames of height x width."""
+    import torch
+
+    from .. import _lib
+
+    return torch.empty(int(_lib.lib().vlfm_jpeg_encode_scratch_bytes(n, height, width)), dtype=torch.uint8, device=device)
+
+
+def jpeg_encode_batch(images_u8, quality: int = 90, channel_order: str = "bgr", capacity=None, out=None, lengths=None,
+                      scratch=None):
+    """Baseline 4:2:0 JPEG files of a whole batch on the GPU: a contiguous [n,H,W,3] uint8 device tensor to
+    ``(out [n, capacity] uint8, lengths [n] int32)``, both on the device.  ``out[i, :lengths[i]]`` is, byte for byte, the
+    file Pillow's ``save(format="JPEG", quality=q, subsampling="4:2:0")`` writes for frame i (csrc/jpeg_entropy.hip).
+
+    ``channel_order="bgr"`` reads slot 2 of a pixel as R: what ``cv2.imencode`` does with the RGB frame the reference hands
+    it (server_wrapper.py:57-61) and the convention of ``jpeg_roundtrip_batch``; ``"rgb"`` reads slot 0 as R
+    (``Image.fromarray(rgb).save``).  ``capacity`` is the bytes per frame slot, by default ``jpeg_encode_bound(H, W)``, which
+    no frame exceeds.  With a smaller one, a frame that does not fit is cut at ``capacity`` and its ``lengths[i]`` (the full
+    length) says so; the other frames are complete.  Bytes of a slot behind the file's end are not written.
+
+    Runs on the current stream, with no synchronisation and no host copy.  ``out`` (contiguous uint8 [n, capacity]),
+    ``lengths`` (contiguous int32 [n]) and ``scratch`` (``jpeg_encode_scratch``) may be passed in; otherwise they come from
+    PyTorch's caching allocator.  Raises ValueError for a wrong dtype, rank, channel count or device, a non-contiguous
+    tensor, a quality outside 1..100, an unknown channel order, a capacity below 1, a frame the encoder does not take
+    (larger than 65500 on a side, or than about 10 000 x 10 000 pixels), or an ``out`` / ``lengths`` / ``scratch`` that does
+    not fit."""
+    import torch
+
+    from .. import _lib
+    from .ops import _stream
+
+    x = images_u8
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError("jpeg_encode_batch expects a [n,H,W,3] uint8 tensor")
+    if x.device.type != "cuda":
+        raise ValueError("jpeg_encode_batch expects a tensor on a GPU")
+    if not x.is_contiguous():
+        raise ValueError("jpeg_encode_batch expects a contiguous tensor")
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise ValueError(f"quality must be an integer in 1..100, got {quality!r}")
+    if channel_order not in ("bgr", "rgb"):
+        raise ValueError(f"channel_order must be 'bgr' or 'rgb', got {channel_order!r}")
+    n, h, w, _ = x.shape
+    if n == 0 or h == 0 or w == 0:
+        raise ValueError(f"jpeg_encode_batch expects a non-empty batch, got shape {tuple(x.shape)}")
+    if h > 65500 or w > 65500:
+        raise ValueError("JPEG frames are at most 65500 pixels on a side")
+    bound = jpeg_encode_bound(h, w)
+    if bound == 0:
+        raise ValueError(f"a {h} x {w} frame is too large for the encoder's 32-bit bit offsets")
+    if capacity is None:
+        capacity = bound if out is None else (out.shape[1] if isinstance(out, torch.Tensor) and out.dim() == 2 else bound)
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or int(capacity) < 1:
+        raise ValueError(f"capacity must be a positive integer, got {capacity!r}")
+    capacity = int(capacity)
+    if out is None:
+        out = torch.empty((n, capacity), dtype=torch.uint8, device=x.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, capacity)
+          or out.device != x.device or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {capacity}) on the input's device")
+    if lengths is None:
+        lengths = torch.empty(n, dtype=torch.int32, device=x.device)
+    elif (not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,)
+          or lengths.device != x.device or not lengths.is_contiguous()):
+        raise ValueError(f"lengths must be a contiguous int32 tensor of shape ({n},) on the input's device")
+    need = int(_lib.lib().vlfm_jpeg_encode_scratch_bytes(n, h, w))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=x.device)   # (the caching allocator: no device allocation)
+    elif (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint8 or scratch.device != x.device
+          or not scratch.is_contiguous() or scratch.numel() < need or scratch.data_ptr() % 16):
+        raise ValueError(f"scratch must be a contiguous, 16-byte aligned uint8 device tensor of at least {need} bytes")
+
+    def span(t):
+        return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+
+    bufs = [("the input", x), ("out", out), ("lengths", lengths), ("scratch", scratch)]
+    for i, (na, a) in enumerate(bufs):
+        for nb_, b in bufs[i + 1:]:
+            (a0, a1), (b0, b1) = span(a), span(b)
+            if a0 < b1 and b0 < a1:
+                raise ValueError(f"{nb_} must not overlap {na}")
+    tables = jpeg_quant_tables(int(quality))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().vlfm_jpeg_encode_batched(x.data_ptr(), n, h, w, int(channel_order == "rgb"),
+                                                       tables.ctypes.data, out.data_ptr(), capacity, lengths.data_ptr(),
+                                                       scratch.data_ptr(), scratch.numel(), _stream()),
+                   "jpeg_encode_batched")
+    return out, lengths
+
+
+def jpeg_encode_batch_bytes(images_u8, quality: int = 90, channel_order: str = "bgr", capacity=None, out=None,
+                            lengths=None, scratch=None):
+    """``jpeg_encode_batch`` brought to the host as one ``bytes`` per frame.  One synchronisation: the lengths come first,
+    then only the used prefix of every slot is copied.  Raises ValueError naming the frames that did not fit ``capacity``."""
+    import torch
+
+    dev_out, dev_len = jpeg_encode_batch(images_u8, quality, channel_order, capacity, out, lengths, scratch)
+    lens = dev_len.cpu().numpy().astype(np.int64)           # (waits for the encoder)
+    cap = dev_out.shape[1]
+    over = [i for i in range(lens.size) if lens[i] > cap]
+    if over:
+        raise ValueError(f"frames {over} did not fit the capacity of {cap} bytes (they take "
+                         f"{[int(lens[i]) for i in over]})")
+    # one gather of the used prefixes, one copy
+    starts = np.concatenate([[0], np.cumsum(lens)])
+    idx = torch.from_numpy(np.concatenate([np.arange(l, dtype=np.int64) + i * cap for i, l in enumerate(lens)]))
+    flat = dev_out.view(-1)[idx.to(dev_out.device)].cpu().numpy().tobytes()
+    return [flat[starts[i]:starts[i + 1]] for i in range(lens.size)]
+
+
+def image_to_str_batch(images_u8, quality: int = 90):
+    """``image_to_str(frame, quality)`` of server_wrapper.py:57-61 for every frame of a [n,H,W,3] uint8 device tensor: the
+    base64 text of ``cv2.imencode(".jpg", frame, [IMWRITE_JPEG_QUALITY, quality])``, which reads the frame as BGR."""
+    import base64
+
+    return [base64.b64encode(b).decode() for b in jpeg_encode_batch_bytes(images_u8, quality, "bgr")]
