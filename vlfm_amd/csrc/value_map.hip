@@ -91,6 +91,20 @@ struct UpdateArgs {
 };
 
 constexpr int ROWS_PER_TILE = 8;
+
+// cv::warpAffine's fixed-point source coordinate (AB_BITS = 10) of window cell (x, y) is row_coord(y) + col_coord(x):
+// X0 = round((M01 y + M02) * 1024) + 16 plus adelta = round(M00 x * 1024), Y0 / bdelta likewise.
+__device__ __forceinline__ int2 col_coord(const vlfm_vm_pose& pose, int x) {
+    return make_int2(__double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[0], (double)x), 1024.0)),
+                     __double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[3], (double)x), 1024.0)));
+}
+
+__device__ __forceinline__ int2 row_coord(const vlfm_vm_pose& pose, int y) {
+    return make_int2(
+        __double2int_rn(__dmul_rn(__dadd_rn(__dmul_rn(pose.inv_affine[1], (double)y), pose.inv_affine[2]), 1024.0)) + 16,
+        __double2int_rn(__dmul_rn(__dadd_rn(__dmul_rn(pose.inv_affine[4], (double)y), pose.inv_affine[5]), 1024.0)) + 16);
+}
+
 // The fusion arithmetic of one cell (value_map.py:377-429).  Returns false when the cell is left untouched.
 template <int C>
 __device__ inline bool fuse_cell(const UpdateArgs& a, float nw, float old, const double* oldv, const double* vals,
@@ -154,8 +168,8 @@ __device__ inline void fuse_tile_lds(const UpdateArgs& a, const vlfm_vm_pose& po
         if (x - lane > box.w || x - lane + 63 < box.z) continue;  // wave-uniform: segment outside the cone's columns
         const int mc = pose.col0 + x;
         const bool col_ok = (unsigned)mc < (unsigned)S;
-        const int adelta = __double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[0], (double)x), 1024.0));
-        const int bdelta = __double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[3], (double)x), 1024.0));
+        const int2 cxy = col_coord(pose, x);
+        const int adelta = cxy.x, bdelta = cxy.y;
 #pragma unroll 1
       for (int half = 0; half < 2; half++) {
         const int row_base = row_begin + half * R;
@@ -557,6 +571,157 @@ __device__ inline void raster_polygon_flat(const LdsBitmap& bm, const int2* vert
 
 constexpr int FUSED_THREADS = 1024;   // 16 wavefronts: the raster's items are spread thin, then 4 tiles are fused at a time
 
+// ---- the stages of one observation that the single-camera and the rig kernel share.  They take values and pointers; what
+// differs between the two kernels (block enumeration, list decoding, where the quadrant and the optics live) stays in the kernels.
+
+// a structure that is the same for every lane, read into scalar registers (the pose's six f64 coefficients alone would
+// otherwise pin 12 vector registers through the whole fuse loop)
+template <typename R>
+__device__ __forceinline__ R load_uniform(const R* p) {
+    static_assert(sizeof(R) % 4 == 0, "dword-sized record");
+    R r;
+    const int* src = reinterpret_cast<const int*>(p);
+    int* dst = reinterpret_cast<int*>(&r);
+#pragma unroll
+    for (int u = 0; u < (int)(sizeof(R) / 4); u++) dst[u] = __builtin_amdgcn_readfirstlane(src[u]);
+    return r;
+}
+
+// one vertex of the depth-profile polygon from a column-max key
+__device__ __forceinline__ int2 profile_vertex(unsigned key, double tangent, float depth_scale, float depth_offset, float ppm_f,
+                                               double ppm_d, float half_t_f, double half_t_d) {
+    const float raw = __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+    const float d = __fadd_rn(__fmul_rn(raw, depth_scale), depth_offset);                      // f32 (value_map.py:234)
+    const float xr = __fadd_rn(__fmul_rn(d, ppm_f), half_t_f);                                 // f32 (:248)
+    const double yl = __dadd_rn(__dmul_rn(__dmul_rn((double)d, tangent), ppm_d), half_t_d);    // f64 (:242,249)
+    return make_int2((int)(long long)yl, (int)(long long)xr);                                  // astype(int): truncation
+}
+
+// The vertices are in LDS (the caller's barrier is behind it): raster the polygon, and the last of the G workgroups that read
+// the W keys `cm` hands them back zeroed for the next depth ingest (a completion count -- nobody waits on it).  Ends in a barrier.
+__device__ __forceinline__ void raster_and_return_keys(const LdsBitmap& bm, const int2* vert, int n_vert, int* pref,
+                                                       int* wave_tot, unsigned* cm, int W, int* counter, int G, int* sh_last,
+                                                       int tid, int nth) {
+    if (tid == 0) {
+        __threadfence();
+        *sh_last = atomicAdd(counter, 1) == G - 1;
+    }
+    raster_polygon_flat(bm, vert, n_vert, pref, wave_tot, tid, nth);
+    if (*sh_last) {
+        for (int i = tid; i < W; i += nth) cm[i] = 0u;
+        if (tid == 0) *counter = 0;
+    }
+    __syncthreads();
+}
+
+// resolve (one lane per row) fused with visible = (template > 0) & ~beyond-the-profile, which replaces the parity plane, and
+// the source bounding box sh_box = (row lo, row hi, col lo, col hi) (preset to T, -1, T, -1)
+__device__ __forceinline__ void resolve_visible(unsigned* parity, const unsigned* solid, const unsigned* tmpl_bits, int T,
+                                                int words, int* sh_box, int tid, int nth) {
+    int r_lo = T, r_hi = -1, c_lo = T, c_hi = -1;
+    for (int y = tid; y < T; y += nth) {
+        unsigned carry = 0;
+        for (int w = 0; w < words; w++) {
+            const int i = y * words + w;
+            unsigned p = parity[i];
+            p ^= p << 1; p ^= p << 2; p ^= p << 4; p ^= p << 8; p ^= p << 16;
+            if (carry) p = ~p;
+            carry = p >> 31;
+            const unsigned v = tmpl_bits[i] & ~(p | solid[i]);
+            parity[i] = v;
+            if (v) {
+                r_lo = min(r_lo, y); r_hi = max(r_hi, y);
+                c_lo = min(c_lo, w * 32 + __builtin_ctz(v)); c_hi = max(c_hi, w * 32 + 31 - __builtin_clz(v));
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        r_lo = min(r_lo, __shfl_xor(r_lo, off, 64)); r_hi = max(r_hi, __shfl_xor(r_hi, off, 64));
+        c_lo = min(c_lo, __shfl_xor(c_lo, off, 64)); c_hi = max(c_hi, __shfl_xor(c_hi, off, 64));
+    }
+    if ((tid & 63) == 0 && r_hi >= 0) {
+        atomicMin(&sh_box[0], r_lo); atomicMax(&sh_box[1], r_hi); atomicMin(&sh_box[2], c_lo); atomicMax(&sh_box[3], c_hi);
+    }
+}
+
+// destination (rotated) bounding box (row lo, row hi, col lo, col hi) of everything that can receive a non-zero tap from the
+// source box sh_box (see visible_mask_kernel); empty = (1, 0, 1, 0)
+__device__ __forceinline__ int4 destination_box(const vlfm_vm_pose& pose, const int* sh_box, int T) {
+    if (sh_box[1] < 0) return make_int4(1, 0, 1, 0);
+    const double a0 = pose.inv_affine[0], a1 = pose.inv_affine[1], a2 = pose.inv_affine[2];
+    const double a3 = pose.inv_affine[3], a4 = pose.inv_affine[4], a5 = pose.inv_affine[5];
+    const double det = a0 * a4 - a1 * a3;
+    double xlo = 1e30, xhi = -1e30, ylo = 1e30, yhi = -1e30;
+    for (int k = 0; k < 4; k++) {
+        const double sx = (k & 1) ? sh_box[3] + 1.0 : sh_box[2] - 1.0, sy = (k & 2) ? sh_box[1] + 1.0 : sh_box[0] - 1.0;
+        const double dx = (a4 * (sx - a2) - a1 * (sy - a5)) / det, dy = (-a3 * (sx - a2) + a0 * (sy - a5)) / det;
+        xlo = fmin(xlo, dx); xhi = fmax(xhi, dx); ylo = fmin(ylo, dy); yhi = fmax(yhi, dy);
+    }
+    if (!(fabs(det) > 1e-9) || !(xlo == xlo) || !(ylo == ylo)) { xlo = ylo = 0; xhi = yhi = T; }
+    return make_int4(max(0, (int)floor(ylo) - 2), min(T - 1, (int)ceil(yhi) + 2), max(0, (int)floor(xlo) - 2),
+                     min(T - 1, (int)ceil(xhi) + 2));
+}
+
+__device__ __forceinline__ int4 uniform_box(int4 box) {
+    return make_int4(__builtin_amdgcn_readfirstlane(box.x), __builtin_amdgcn_readfirstlane(box.y),
+                     __builtin_amdgcn_readfirstlane(box.z), __builtin_amdgcn_readfirstlane(box.w));
+}
+
+// word i (value `wr`) of an environment's `written` plane: the cells that hold a value but are not explored any more are cleared
+// (value_map.py:369-375)
+template <int C_STATIC>
+__device__ __forceinline__ void clear_unexplored_word(const UpdateArgs& a, int env, unsigned* written, int i, unsigned wr) {
+    if (!wr) return;
+    const int S = a.S, ex_stride = (S + 31) >> 5;
+    const int C = C_STATIC > 0 ? C_STATIC : a.C;
+    unsigned dead = wr & ~a.explored[(size_t)env * S * ex_stride + i];
+    if (!dead) return;
+    float* conf = a.conf + (size_t)env * S * S;
+    double* value = a.value + (size_t)env * S * S * C;
+    atomicAnd(&written[i], ~dead);
+    const int row = i / ex_stride, c0 = (i - row * ex_stride) * 32;
+    while (dead) {
+        const int b = __builtin_ctz(dead);
+        dead &= dead - 1u;
+        const size_t cell = (size_t)row * S + c0 + b;
+        conf[cell] = 0.0f;
+        // `_value_map[explored_area == 0] *= 0` (:375): a product, so a negative value leaves -0.0
+        for (int c = 0; c < C; c++) value[cell * C + c] = __dmul_rn(value[cell * C + c], 0.0);
+    }
+}
+
+// Can the 4 x 4 block of window cells with corner rows ra, rb and corner columns ca, cb (their row_coord / col_coord) hold a cell
+// with a visible tap?  The fixed-point coordinate (>> 10 = the cell's first tap) is monotone in the row and in the column, so
+// the footprint's extremes sit in the four corners; widened by the +1 taps.
+__device__ __forceinline__ bool block_sees_visible(const unsigned* vis, int words, int T, int2 ra, int2 rb, int2 ca, int2 cb) {
+    const int xa = ra.x + ca.x, xb = ra.x + cb.x, xc = rb.x + ca.x, xd = rb.x + cb.x;
+    const int ya = ra.y + ca.y, yb = ra.y + cb.y, yc = rb.y + ca.y, yd = rb.y + cb.y;
+    const int sx0 = min(min(xa, xb), min(xc, xd)) >> 10, sx1 = (max(max(xa, xb), max(xc, xd)) >> 10) + 1;
+    const int sy0 = min(min(ya, yb), min(yc, yd)) >> 10, sy1 = (max(max(ya, yb), max(yc, yd)) >> 10) + 1;
+    return any_visible(vis, words, T, sx0, sx1, sy0, sy1);
+}
+
+// Ballot-compacted append to an LDS list counted by *count: one LDS atomic per wavefront reserves the slots of its lanes that
+// `want` one.  Every lane of the wavefront calls it; returns the lane's slot, or -1 for a lane that wants none.
+__device__ __forceinline__ int compact_slot(bool want, int* count, int lane) {
+    const unsigned long long m = __ballot(want);
+    if (m == 0ull) return -1;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(count, __popcll(m));
+    base = __builtin_amdgcn_readfirstlane(base);
+    return want ? base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) : -1;
+}
+
+// map cell (mr, mc) receives the new confidence nw: into slot k of the cell list, or -- list full (a cone far wider than a
+// camera's) -- fused in place
+template <int C_STATIC>
+__device__ __forceinline__ void list_append_or_fuse(const UpdateArgs& a, const vlfm_vm_pose& pose, uint2* list, int cap, int k,
+                                                    int mr, int mc, float nw, unsigned* written) {
+    const uint2 e = make_uint2(((unsigned)mr << 16) | (unsigned)mc, __float_as_uint(nw));
+    if (k < cap) list[k] = e;
+    else fuse_list<C_STATIC>(a, pose, &e, 1, 0, 1, written);
+}
+
 template <int C_STATIC>
 __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(UpdateArgs a, FusedExtra fx) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -581,15 +746,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
     const int obs = blockIdx.y, g = blockIdx.x, G = gridDim.x;
     const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63;
 
-    // the pose is the same for every lane: keep its 16 dwords in scalar registers (the six f64 coefficients alone would
-    // otherwise pin 12 vector registers through the whole fuse loop)
-    vlfm_vm_pose pose;
-    {
-        const int* src = reinterpret_cast<const int*>(a.pose + obs);
-        int* dst = reinterpret_cast<int*>(&pose);
-#pragma unroll
-        for (int u = 0; u < (int)(sizeof(vlfm_vm_pose) / 4); u++) dst[u] = __builtin_amdgcn_readfirstlane(src[u]);
-    }
+    vlfm_vm_pose pose = load_uniform(a.pose + obs);
     pose.reserved = obs;  // fuse_tile reads the observation's values through it
     const int ex_stride = (S + 31) >> 5;
     // step 2's first loads are independent of everything else: issue them before the raster so that they travel under it
@@ -603,15 +760,10 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
     bm.solid = solid; bm.parity = parity; bm.rows = T; bm.cols = T; bm.words = words;
     for (int i = tid; i < 2 * T * words; i += nth) solid[i] = 0u;
     if (tid == 0) { sh_box[0] = T; sh_box[1] = -1; sh_box[2] = T; sh_box[3] = -1; sh_list_n = 0; sh_block_n = 0; }
-    if (fx.block_cap > 0)
-        for (int x = tid; x < T; x += nth)   // the column part of cv::warpAffine's fixed-point coordinate (fuse_tile_lds: adelta, bdelta)
-            col_xy[x] = make_int2(__double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[0], (double)x), 1024.0)),
-                                  __double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[3], (double)x), 1024.0)));
-    for (int y = tid; y < T; y += nth)   // cv::warpAffine: X0 = round((M01 y + M02) * 1024) + 16, Y0 likewise (AB_BITS = 10)
-        row_xy0[y] = make_int2(
-            __double2int_rn(__dmul_rn(__dadd_rn(__dmul_rn(pose.inv_affine[1], (double)y), pose.inv_affine[2]), 1024.0)) + 16,
-            __double2int_rn(__dmul_rn(__dadd_rn(__dmul_rn(pose.inv_affine[4], (double)y), pose.inv_affine[5]), 1024.0)) + 16);
-    const unsigned* cm = a.colmax + (size_t)obs * W;
+    if (fx.block_cap > 0)   // (the tile sweep takes the column part per lane: fuse_tile_lds)
+        for (int x = tid; x < T; x += nth) col_xy[x] = col_coord(pose, x);
+    for (int y = tid; y < T; y += nth) row_xy0[y] = row_coord(pose, y);
+    unsigned* cm = a.colmax + (size_t)obs * W;
     // Loads in issue order keys + tangents, THEN the quadrant: the vertex arithmetic below only has to wait for the first two
     // (memory returns in order), and the quadrant's ten loads per lane travel under it.
     constexpr int KPT = 2;   // keys per lane held in registers (W <= 2048 with 1024 lanes); wider images loop below
@@ -633,14 +785,8 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
 #pragma unroll
     for (int u = 0; u < KPT; u++) {
         const int i = tid + u * nth;
-        if (i < W) {
-            const unsigned key = key_r[u];
-            const float raw = __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-            const float d = __fadd_rn(__fmul_rn(raw, a.depth_scale), a.depth_offset);
-            const float xr = __fadd_rn(__fmul_rn(d, a.ppm_f), a.half_t_f);
-            const double yl = __dadd_rn(__dmul_rn(__dmul_rn((double)d, tan_r[u]), a.ppm_d), a.half_t_d);
-            vert[i + 1] = make_int2((int)(long long)yl, (int)(long long)xr);
-        }
+        if (i < W)
+            vert[i + 1] = profile_vertex(key_r[u], tan_r[u], a.depth_scale, a.depth_offset, a.ppm_f, a.ppm_d, a.half_t_f, a.half_t_d);
     }
 #pragma unroll
     for (int u = 0; u < QPT; u++) {
@@ -648,108 +794,24 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
         if (i < Q * Q) quad[i] = quad_r[u];
     }
     for (int i = tid + QPT * nth; i < Q * Q; i += nth) quad[i] = fx.quad[i];
-    for (int i = tid + KPT * nth; i < W; i += nth) {
-        const unsigned key = cm[i];
-        const float raw = __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-        const float d = __fadd_rn(__fmul_rn(raw, a.depth_scale), a.depth_offset);        // f32 (value_map.py:234)
-        const float xr = __fadd_rn(__fmul_rn(d, a.ppm_f), a.half_t_f);                   // f32 (:248)
-        const double yl = __dadd_rn(__dmul_rn(__dmul_rn((double)d, a.tan_tab[i]), a.ppm_d), a.half_t_d);  // f64 (:242,249)
-        vert[i + 1] = make_int2((int)(long long)yl, (int)(long long)xr);                 // astype(int): truncation
-    }
+    for (int i = tid + KPT * nth; i < W; i += nth)
+        vert[i + 1] = profile_vertex(cm[i], a.tan_tab[i], a.depth_scale, a.depth_offset, a.ppm_f, a.ppm_d, a.half_t_f, a.half_t_d);
     if (tid == 0) {
         vert[0] = make_int2(0, T - 1);
         vert[W + 1] = make_int2(T - 1, T - 1);
     }
     __syncthreads();
-    // the keys have been read: the last workgroup of this observation to get here zeroes them for the next depth ingest
-    if (tid == 0) {
-        __threadfence();
-        sh_last = atomicAdd(&fx.counters[obs], 1) == G - 1;
-    }
-    raster_polygon_flat(bm, vert, n_vert, pref, sh_wave_tot, tid, nth);
-    if (sh_last) {
-        unsigned* cmw = a.colmax + (size_t)obs * W;
-        for (int i = tid; i < W; i += nth) cmw[i] = 0u;
-        if (tid == 0) fx.counters[obs] = 0;
-    }
+    raster_and_return_keys(bm, vert, n_vert, pref, sh_wave_tot, cm, W, &fx.counters[obs], G, &sh_last, tid, nth);
+    resolve_visible(parity, solid, a.tmpl_bits, T, words, sh_box, tid, nth);
     __syncthreads();
-    // resolve (one lane per row) fused with visible = (template > 0) & ~beyond-the-profile, and the source bounding box
-    {
-        int r_lo = T, r_hi = -1, c_lo = T, c_hi = -1;
-        for (int y = tid; y < T; y += nth) {
-            unsigned carry = 0;
-            for (int w = 0; w < words; w++) {
-                const int i = y * words + w;
-                unsigned p = parity[i];
-                p ^= p << 1; p ^= p << 2; p ^= p << 4; p ^= p << 8; p ^= p << 16;
-                if (carry) p = ~p;
-                carry = p >> 31;
-                const unsigned v = a.tmpl_bits[i] & ~(p | solid[i]);
-                parity[i] = v;
-                if (v) {
-                    r_lo = min(r_lo, y); r_hi = max(r_hi, y);
-                    c_lo = min(c_lo, w * 32 + __builtin_ctz(v)); c_hi = max(c_hi, w * 32 + 31 - __builtin_clz(v));
-                }
-            }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            r_lo = min(r_lo, __shfl_xor(r_lo, off, 64)); r_hi = max(r_hi, __shfl_xor(r_hi, off, 64));
-            c_lo = min(c_lo, __shfl_xor(c_lo, off, 64)); c_hi = max(c_hi, __shfl_xor(c_hi, off, 64));
-        }
-        if (lane == 0 && r_hi >= 0) {
-            atomicMin(&sh_box[0], r_lo); atomicMax(&sh_box[1], r_hi); atomicMin(&sh_box[2], c_lo); atomicMax(&sh_box[3], c_hi);
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        // destination (rotated) bounding box of everything that can receive a non-zero tap (see visible_mask_kernel)
-        int4 m;
-        if (sh_box[1] < 0) {
-            m = make_int4(1, 0, 1, 0);
-        } else {
-            const double a0 = pose.inv_affine[0], a1 = pose.inv_affine[1], a2 = pose.inv_affine[2];
-            const double a3 = pose.inv_affine[3], a4 = pose.inv_affine[4], a5 = pose.inv_affine[5];
-            const double det = a0 * a4 - a1 * a3;
-            double xlo = 1e30, xhi = -1e30, ylo = 1e30, yhi = -1e30;
-            for (int k = 0; k < 4; k++) {
-                const double sx = (k & 1) ? sh_box[3] + 1.0 : sh_box[2] - 1.0, sy = (k & 2) ? sh_box[1] + 1.0 : sh_box[0] - 1.0;
-                const double dx = (a4 * (sx - a2) - a1 * (sy - a5)) / det, dy = (-a3 * (sx - a2) + a0 * (sy - a5)) / det;
-                xlo = fmin(xlo, dx); xhi = fmax(xhi, dx); ylo = fmin(ylo, dy); yhi = fmax(yhi, dy);
-            }
-            if (!(fabs(det) > 1e-9) || !(xlo == xlo) || !(ylo == ylo)) { xlo = ylo = 0; xhi = yhi = T; }
-            m = make_int4(max(0, (int)floor(ylo) - 2), min(T - 1, (int)ceil(yhi) + 2), max(0, (int)floor(xlo) - 2),
-                          min(T - 1, (int)ceil(xhi) + 2));
-        }
-        sh_dbox = m;
-    }
+    if (tid == 0) sh_dbox = destination_box(pose, sh_box, T);
     // ---- step 2: cells that hold a value but are not explored any more (value_map.py:369-375)
-    if (written && a.explored) {
-        const unsigned* explored = a.explored + (size_t)pose.env * S * ex_stride;
-        float* conf = a.conf + (size_t)pose.env * S * S;
-        const int C = C_STATIC > 0 ? C_STATIC : a.C;
-        double* value = a.value + (size_t)pose.env * S * S * C;
-        for (int i = my_word; i < plane_words; i += G * nth) {
-            const unsigned wr = i == my_word ? wr0 : written[i];
-            if (!wr) continue;
-            unsigned dead = wr & ~explored[i];
-            if (!dead) continue;
-            atomicAnd(&written[i], ~dead);
-            const int row = i / ex_stride, c0 = (i - row * ex_stride) * 32;
-            while (dead) {
-                const int b = __builtin_ctz(dead);
-                dead &= dead - 1u;
-                const size_t cell = (size_t)row * S + c0 + b;
-                conf[cell] = 0.0f;
-                // `_value_map[explored_area == 0] *= 0` (:375): a product, so a negative value leaves -0.0
-                for (int c = 0; c < C; c++) value[cell * C + c] = __dmul_rn(value[cell * C + c], 0.0);
-            }
-        }
-    }
+    if (written && a.explored)
+        for (int i = my_word; i < plane_words; i += G * nth)
+            clear_unexplored_word<C_STATIC>(a, pose.env, written, i, i == my_word ? wr0 : written[i]);
     __syncthreads();
     // ---- step 3: rotate + place + fuse, tiles g, g + G, ...
-    int4 box = sh_dbox;
-    box.x = __builtin_amdgcn_readfirstlane(box.x); box.y = __builtin_amdgcn_readfirstlane(box.y);
-    box.z = __builtin_amdgcn_readfirstlane(box.z); box.w = __builtin_amdgcn_readfirstlane(box.w);
+    const int4 box = uniform_box(sh_dbox);
     if (box.z > box.w) return;
     // four wavefronts per 8-row tile (fuse_tile's shape), FUSED_THREADS / 256 tiles in flight per workgroup; only tiles
     // inside the cone's destination rows are dealt out
@@ -771,23 +833,10 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
             if (b < nblk) {
                 by = by_lo + b / nbx; bx = bx_lo + b % nbx;
                 const int y0 = by * VB, y1 = min(y0 + VB - 1, T - 1), x0 = bx * VB, x1 = min(x0 + VB - 1, T - 1);
-                const int2 ra = row_xy0[y0], rb = row_xy0[y1], ca = col_xy[x0], cb = col_xy[x1];
-                // fixed-point coordinate (>> 10 = the cell's first tap) in the four corners
-                const int xa = ra.x + ca.x, xb = ra.x + cb.x, xc = rb.x + ca.x, xd = rb.x + cb.x;
-                const int ya = ra.y + ca.y, yb = ra.y + cb.y, yc = rb.y + ca.y, yd = rb.y + cb.y;
-                const int sx0 = min(min(xa, xb), min(xc, xd)) >> 10, sx1 = (max(max(xa, xb), max(xc, xd)) >> 10) + 1;
-                const int sy0 = min(min(ya, yb), min(yc, yd)) >> 10, sy1 = (max(max(ya, yb), max(yc, yd)) >> 10) + 1;
-                act = any_visible(parity, words, T, sx0, sx1, sy0, sy1);
+                act = block_sees_visible(parity, words, T, row_xy0[y0], row_xy0[y1], col_xy[x0], col_xy[x1]);
             }
-            const unsigned long long m = __ballot(act);
-            if (m == 0ull) continue;
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&sh_block_n, __popcll(m));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (act) {
-                const int k = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                if (k < fx.block_cap) block_list[k] = ((unsigned)by << 16) | (unsigned)bx;
-            }
+            const int k = compact_slot(act, &sh_block_n, lane);
+            if ((unsigned)k < (unsigned)fx.block_cap) block_list[k] = ((unsigned)by << 16) | (unsigned)bx;
         }
         __syncthreads();
         // ---- 3b: the cells of the listed blocks, four blocks per wavefront and round, one lane per cell
@@ -800,17 +849,8 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_fused_kernel(U
             const int mr = pose.row0 + y, mc = pose.col0 + x;
             const bool ok = have && y < T && x < T && (unsigned)mr < (unsigned)S && (unsigned)mc < (unsigned)S;
             const float nwv = cell_new_confidence(parity, quad, T, words, row_xy0[y < T ? y : 0], col_xy[x < T ? x : 0], ok);
-            const unsigned long long m = __ballot(nwv != 0.0f);
-            if (m == 0ull) continue;
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&sh_list_n, __popcll(m));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (nwv != 0.0f) {
-                const int k = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                const uint2 e = make_uint2(((unsigned)mr << 16) | (unsigned)mc, __float_as_uint(nwv));
-                if (k < fx.list_cap) list[k] = e;
-                else fuse_list<C_STATIC>(a, pose, &e, 1, 0, 1, written);    // list full (a cone far wider than a camera's): in place
-            }
+            const int k = compact_slot(nwv != 0.0f, &sh_list_n, lane);
+            if (k >= 0) list_append_or_fuse<C_STATIC>(a, pose, list, fx.list_cap, k, mr, mc, nwv, written);
         }
         __syncthreads();
         fuse_list<C_STATIC>(a, pose, list, min(sh_list_n, fx.list_cap), tid, nth, written);
@@ -886,30 +926,13 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_rig_kernel(Upd
 
     // ---- once per slot: cells that hold a value but are not explored any more, in the rows this workgroup owns
     if (written && a.explored) {
-        const unsigned* explored = a.explored + (size_t)env * S * ex_stride;
-        float* conf = a.conf + (size_t)env * S * S;
-        const int C = C_STATIC > 0 ? C_STATIC : a.C;
-        double* value = a.value + (size_t)env * S * S * C;
         const int plane_words = S * ex_stride, tile_words = ROWS_PER_TILE * ex_stride;
         const int n_tiles = (S + ROWS_PER_TILE - 1) / ROWS_PER_TILE;
         const int n_own = g < n_tiles ? (n_tiles - 1 - g) / G + 1 : 0;
         for (int idx = tid; idx < n_own * tile_words; idx += nth) {
             const int j = idx / tile_words;
             const int i = (g + j * G) * tile_words + (idx - j * tile_words);
-            if (i >= plane_words) continue;
-            const unsigned wr = written[i];
-            if (!wr) continue;
-            unsigned dead = wr & ~explored[i];
-            if (!dead) continue;
-            atomicAnd(&written[i], ~dead);
-            const int row = i / ex_stride, c0 = (i - row * ex_stride) * 32;
-            while (dead) {
-                const int b = __builtin_ctz(dead);
-                dead &= dead - 1u;
-                const size_t cell = (size_t)row * S + c0 + b;
-                conf[cell] = 0.0f;
-                for (int c = 0; c < C; c++) value[cell * C + c] = __dmul_rn(value[cell * C + c], 0.0);   // (:375) a product: -0.0 stays
-            }
+            if (i < plane_words) clear_unexplored_word<C_STATIC>(a, env, written, i, written[i]);
         }
     }
 
@@ -917,20 +940,8 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_rig_kernel(Upd
         // this workgroup's map stores of the previous camera (and of the clear above) before this camera's map loads; also
         // fences the LDS arrays that are re-used
         rig_sync_global();
-        vlfm_vm_pose pose;
-        {
-            const int* src = reinterpret_cast<const int*>(a.pose + first + k);
-            int* dst = reinterpret_cast<int*>(&pose);
-#pragma unroll
-            for (int u = 0; u < (int)(sizeof(vlfm_vm_pose) / 4); u++) dst[u] = __builtin_amdgcn_readfirstlane(src[u]);
-        }
-        vlfm_vm_optics op;
-        {
-            const int* src = reinterpret_cast<const int*>(rg.optics + first + k);
-            int* dst = reinterpret_cast<int*>(&op);
-#pragma unroll
-            for (int u = 0; u < (int)(sizeof(vlfm_vm_optics) / 4); u++) dst[u] = __builtin_amdgcn_readfirstlane(src[u]);
-        }
+        const vlfm_vm_pose pose = load_uniform(a.pose + first + k);
+        const vlfm_vm_optics op = load_uniform(rg.optics + first + k);
         const int obs = pose.reserved;               // row of the keys, values and counter (fuse_list reads values through it)
         const int T = op.template_size, words = (T + 31) >> 5, Q = (T >> 1) + 1;
         unsigned* parity = solid + T * words;        // after the resolve: the visible plane
@@ -941,22 +952,11 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_rig_kernel(Upd
         bm.solid = solid; bm.parity = parity; bm.rows = T; bm.cols = T; bm.words = words;
         for (int i = tid; i < 2 * T * words; i += nth) solid[i] = 0u;
         if (tid == 0) { sh_box[0] = T; sh_box[1] = -1; sh_box[2] = T; sh_box[3] = -1; sh_list_n = 0; sh_block_n = 0; }
-        for (int x = tid; x < T; x += nth)   // the column part of cv::warpAffine's fixed-point coordinate
-            col_xy[x] = make_int2(__double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[0], (double)x), 1024.0)),
-                                  __double2int_rn(__dmul_rn(__dmul_rn(pose.inv_affine[3], (double)x), 1024.0)));
-        for (int y = tid; y < T; y += nth)   // cv::warpAffine: X0 = round((M01 y + M02) * 1024) + 16, Y0 likewise (AB_BITS = 10)
-            row_xy0[y] = make_int2(
-                __double2int_rn(__dmul_rn(__dadd_rn(__dmul_rn(pose.inv_affine[1], (double)y), pose.inv_affine[2]), 1024.0)) + 16,
-                __double2int_rn(__dmul_rn(__dadd_rn(__dmul_rn(pose.inv_affine[4], (double)y), pose.inv_affine[5]), 1024.0)) + 16);
+        for (int x = tid; x < T; x += nth) col_xy[x] = col_coord(pose, x);
+        for (int y = tid; y < T; y += nth) row_xy0[y] = row_coord(pose, y);
         unsigned* cm = a.colmax + (size_t)obs * W;
-        for (int i = tid; i < W; i += nth) {
-            const unsigned key = cm[i];
-            const float raw = __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-            const float d = __fadd_rn(__fmul_rn(raw, op.depth_scale), op.depth_offset);      // f32 (value_map.py:234)
-            const float xr = __fadd_rn(__fmul_rn(d, a.ppm_f), half_t_f);                     // f32 (:248)
-            const double yl = __dadd_rn(__dmul_rn(__dmul_rn((double)d, op.d_tan[i]), a.ppm_d), half_t_d);  // f64 (:242,249)
-            vert[i + 1] = make_int2((int)(long long)yl, (int)(long long)xr);                 // astype(int): truncation
-        }
+        for (int i = tid; i < W; i += nth)
+            vert[i + 1] = profile_vertex(cm[i], op.d_tan[i], op.depth_scale, op.depth_offset, a.ppm_f, a.ppm_d, half_t_f, half_t_d);
         if (rg.quad_in_lds)
             for (int i = tid; i < Q * Q; i += nth) quad[i] = op.d_conf_quadrant[i];
         if (tid == 0) {
@@ -964,71 +964,12 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_rig_kernel(Upd
             vert[W + 1] = make_int2(T - 1, T - 1);
         }
         __syncthreads();
-        // the keys have been read: the last workgroup of the slot to get here zeroes them for the next depth ingest (a completion
-        // count per observation -- nobody waits on it)
-        if (tid == 0) {
-            __threadfence();
-            sh_last = atomicAdd(&fx.counters[obs], 1) == G - 1;
-        }
-        raster_polygon_flat(bm, vert, n_vert, pref, sh_wave_tot, tid, nth);
-        if (sh_last) {
-            for (int i = tid; i < W; i += nth) cm[i] = 0u;
-            if (tid == 0) fx.counters[obs] = 0;
-        }
+        raster_and_return_keys(bm, vert, n_vert, pref, sh_wave_tot, cm, W, &fx.counters[obs], G, &sh_last, tid, nth);
+        resolve_visible(parity, solid, op.d_template_bits, T, words, sh_box, tid, nth);
         __syncthreads();
-        // resolve (one lane per row) fused with visible = (template > 0) & ~beyond-the-profile, and the source bounding box
-        {
-            int r_lo = T, r_hi = -1, c_lo = T, c_hi = -1;
-            for (int y = tid; y < T; y += nth) {
-                unsigned carry = 0;
-                for (int w = 0; w < words; w++) {
-                    const int i = y * words + w;
-                    unsigned p = parity[i];
-                    p ^= p << 1; p ^= p << 2; p ^= p << 4; p ^= p << 8; p ^= p << 16;
-                    if (carry) p = ~p;
-                    carry = p >> 31;
-                    const unsigned v = op.d_template_bits[i] & ~(p | solid[i]);
-                    parity[i] = v;
-                    if (v) {
-                        r_lo = min(r_lo, y); r_hi = max(r_hi, y);
-                        c_lo = min(c_lo, w * 32 + __builtin_ctz(v)); c_hi = max(c_hi, w * 32 + 31 - __builtin_clz(v));
-                    }
-                }
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                r_lo = min(r_lo, __shfl_xor(r_lo, off, 64)); r_hi = max(r_hi, __shfl_xor(r_hi, off, 64));
-                c_lo = min(c_lo, __shfl_xor(c_lo, off, 64)); c_hi = max(c_hi, __shfl_xor(c_hi, off, 64));
-            }
-            if (lane == 0 && r_hi >= 0) {
-                atomicMin(&sh_box[0], r_lo); atomicMax(&sh_box[1], r_hi); atomicMin(&sh_box[2], c_lo); atomicMax(&sh_box[3], c_hi);
-            }
-        }
+        if (tid == 0) sh_dbox = destination_box(pose, sh_box, T);
         __syncthreads();
-        if (tid == 0) {
-            // destination (rotated) bounding box of everything that can receive a non-zero tap (as in the single-camera kernel)
-            int4 m;
-            if (sh_box[1] < 0) {
-                m = make_int4(1, 0, 1, 0);
-            } else {
-                const double a0 = pose.inv_affine[0], a1 = pose.inv_affine[1], a2 = pose.inv_affine[2];
-                const double a3 = pose.inv_affine[3], a4 = pose.inv_affine[4], a5 = pose.inv_affine[5];
-                const double det = a0 * a4 - a1 * a3;
-                double xlo = 1e30, xhi = -1e30, ylo = 1e30, yhi = -1e30;
-                for (int c = 0; c < 4; c++) {
-                    const double sx = (c & 1) ? sh_box[3] + 1.0 : sh_box[2] - 1.0, sy = (c & 2) ? sh_box[1] + 1.0 : sh_box[0] - 1.0;
-                    const double dx = (a4 * (sx - a2) - a1 * (sy - a5)) / det, dy = (-a3 * (sx - a2) + a0 * (sy - a5)) / det;
-                    xlo = fmin(xlo, dx); xhi = fmax(xhi, dx); ylo = fmin(ylo, dy); yhi = fmax(yhi, dy);
-                }
-                if (!(fabs(det) > 1e-9) || !(xlo == xlo) || !(ylo == ylo)) { xlo = ylo = 0; xhi = yhi = T; }
-                m = make_int4(max(0, (int)floor(ylo) - 2), min(T - 1, (int)ceil(yhi) + 2), max(0, (int)floor(xlo) - 2),
-                              min(T - 1, (int)ceil(xhi) + 2));
-            }
-            sh_dbox = m;
-        }
-        __syncthreads();
-        int4 box = sh_dbox;
-        box.x = __builtin_amdgcn_readfirstlane(box.x); box.y = __builtin_amdgcn_readfirstlane(box.y);
-        box.z = __builtin_amdgcn_readfirstlane(box.z); box.w = __builtin_amdgcn_readfirstlane(box.w);
+        const int4 box = uniform_box(sh_dbox);
         // window rows / columns of the box that lie on the map
         const int y_lo = max(box.x, max(0, -pose.row0)), y_hi = min(min(box.y, T - 1), S - 1 - pose.row0);
         const int bx_lo = max(box.z, max(0, -pose.col0)) / VB, bx_hi = min(min(box.w, T - 1), S - 1 - pose.col0) / VB;
@@ -1051,24 +992,11 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_rig_kernel(Upd
                 const int y0 = max(m0 - pose.row0, y_lo), y1 = min(m0 - pose.row0 + VB - 1, y_hi);
                 if (y0 <= y1) {
                     const int x0 = bx * VB, x1 = min(x0 + VB - 1, T - 1);
-                    const int2 ra = row_xy0[y0], rb = row_xy0[y1], ca = col_xy[x0], cb = col_xy[x1];
-                    // fixed-point coordinate (>> 10 = the cell's first tap) in the four corners
-                    const int xa = ra.x + ca.x, xb = ra.x + cb.x, xc = rb.x + ca.x, xd = rb.x + cb.x;
-                    const int ya = ra.y + ca.y, yb = ra.y + cb.y, yc = rb.y + ca.y, yd = rb.y + cb.y;
-                    const int sx0 = min(min(xa, xb), min(xc, xd)) >> 10, sx1 = (max(max(xa, xb), max(xc, xd)) >> 10) + 1;
-                    const int sy0 = min(min(ya, yb), min(yc, yd)) >> 10, sy1 = (max(max(ya, yb), max(yc, yd)) >> 10) + 1;
-                    act = any_visible(parity, words, T, sx0, sx1, sy0, sy1);
+                    act = block_sees_visible(parity, words, T, row_xy0[y0], row_xy0[y1], col_xy[x0], col_xy[x1]);
                 }
             }
-            const unsigned long long m = __ballot(act);
-            if (m == 0ull) continue;
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&sh_block_n, __popcll(m));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (act) {
-                const int j = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                if (j < fx.block_cap) block_list[j] = ((unsigned)m0 << 16) | (unsigned)bx;
-            }
+            const int j = compact_slot(act, &sh_block_n, lane);
+            if ((unsigned)j < (unsigned)fx.block_cap) block_list[j] = ((unsigned)m0 << 16) | (unsigned)bx;
         }
         __syncthreads();
         // ---- the cells of the listed blocks, four blocks per wavefront and round, one lane per cell
@@ -1083,17 +1011,8 @@ __global__ __launch_bounds__(FUSED_THREADS) void value_map_update_rig_kernel(Upd
             const int2 rxy = row_xy0[ok ? y : 0], cxy = col_xy[x < T ? x : 0];
             const float nwv = rg.quad_in_lds ? cell_new_confidence(parity, quad, T, words, rxy, cxy, ok)
                                              : cell_new_confidence(parity, op.d_conf_quadrant, T, words, rxy, cxy, ok);
-            const unsigned long long m = __ballot(nwv != 0.0f);
-            if (m == 0ull) continue;
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&sh_list_n, __popcll(m));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (nwv != 0.0f) {
-                const int j = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                const uint2 e = make_uint2(((unsigned)mr << 16) | (unsigned)mc, __float_as_uint(nwv));
-                if (j < fx.list_cap) list[j] = e;
-                else fuse_list<C_STATIC>(a, pose, &e, 1, 0, 1, written);    // list full (a cone far wider than a camera's): in place
-            }
+            const int j = compact_slot(nwv != 0.0f, &sh_list_n, lane);
+            if (j >= 0) list_append_or_fuse<C_STATIC>(a, pose, list, fx.list_cap, j, mr, mc, nwv, written);
         }
         __syncthreads();
         fuse_list<C_STATIC>(a, pose, list, min(sh_list_n, fx.list_cap), tid, nth, written);
@@ -1180,9 +1099,48 @@ extern "C" int vlfm_cone_template_build(const float* d_conf, const int64_t* d_po
     return check_launch("cone_template_kernel");
 }
 
-static int target_override_g() {
-    static const int v = [] { const char* e = getenv("VLFM_VM_TARGET_WGS"); return e ? atoi(e) : 0; }();
-    return v;
+// ---- what the launchers of the single-camera and the rig kernel share
+static UpdateArgs map_update_args(uint32_t* d_colmax_keys, int width, int template_size, const vlfm_vm_pose* d_pose,
+                                  const double* d_values, float* d_conf, double* d_value, int map_size, int channels,
+                                  int pixels_per_meter, int use_max_confidence, int fusion_type,
+                                  const uint32_t* d_explored_bits) {
+    UpdateArgs a{};
+    a.colmax = reinterpret_cast<unsigned*>(d_colmax_keys); a.pose = d_pose; a.values = d_values;
+    a.conf = d_conf; a.value = d_value; a.explored = d_explored_bits;
+    a.W = width; a.T = template_size; a.S = map_size; a.C = channels;
+    a.ppm_f = (float)pixels_per_meter;
+    a.ppm_d = (double)pixels_per_meter;
+    a.use_max_conf = use_max_confidence; a.fusion = fusion_type;
+    return a;
+}
+
+// the head of both LDS layouts: the two bit planes, the polygon's vertices and the raster's prefix sums (each padded to 8 bytes)
+static size_t raster_lds_bytes(int T, int width) {
+    const int words = (T + 31) >> 5, n_vert = width + 2;
+    return (size_t)(2 * T * words + ((2 * T * words) & 1)) * 4 + (size_t)n_vert * sizeof(int2) +
+           (size_t)(n_vert + 1 + ((n_vert + 1) & 1)) * sizeof(int);
+}
+
+static size_t quadrant_lds_bytes(int T) {
+    const int Q = T / 2 + 1;
+    return (size_t)(Q * Q + ((Q * Q) & 1)) * 4;
+}
+
+// the device's CU count, asked once; VLFM_VM_TARGET_WGS -- read once per process -- stands in for it, so that a test can run the
+// block-sparse sweep and the tile sweep at one batch size
+static int target_wgs() {
+    static const int override_g = [] { const char* e = getenv("VLFM_VM_TARGET_WGS"); return e ? atoi(e) : 0; }();
+    return override_g > 0 ? override_g : device_cu_count();
+}
+
+// workgroups per observation (per slot of a rig): a 1024-thread workgroup fills a CU (register budget), so aim for one per CU
+// over all of them; more than ceil(tiles / 4) would leave workgroups of the tile sweep without a tile, and in the rig kernel
+// -- a window meets about T / 8 map tiles -- the repeated raster outweighs the split beyond that
+static int workgroups_per_item(int items, int T) {
+    const int tiles = (T + ROWS_PER_TILE - 1) / ROWS_PER_TILE;
+    const int g_max = (tiles + FUSED_THREADS / 256 - 1) / (FUSED_THREADS / 256);
+    const int G = (target_wgs() + items - 1) / items;
+    return G > g_max ? g_max : G < 1 ? 1 : G;
 }
 
 extern "C" int vlfm_value_map_update_fused_batched(uint32_t* d_colmax_keys, int width, const double* d_tan,
@@ -1200,24 +1158,16 @@ extern "C" int vlfm_value_map_update_fused_batched(uint32_t* d_colmax_keys, int 
         return fail(VLFM_ERR_INVALID, "value_map_update_fused_batched: bad argument");
     if ((d_explored_bits == nullptr) != (d_written_bits == nullptr))
         return fail(VLFM_ERR_INVALID, "value_map_update_fused_batched: d_explored_bits and d_written_bits go together");
-    UpdateArgs a;
-    a.colmax = reinterpret_cast<unsigned*>(d_colmax_keys); a.tan_tab = d_tan; a.tmpl = d_template;
-    a.tmpl_bits = d_template_bits; a.pose = d_pose; a.values = d_values;
-    a.conf = d_conf; a.value = d_value; a.explored = d_explored_bits;
-    a.W = width; a.T = template_size; a.S = map_size; a.C = channels;
+    UpdateArgs a = map_update_args(d_colmax_keys, width, template_size, d_pose, d_values, d_conf, d_value, map_size, channels,
+                                   pixels_per_meter, use_max_confidence, fusion_type, d_explored_bits);
+    a.tan_tab = d_tan; a.tmpl = d_template; a.tmpl_bits = d_template_bits;
     a.depth_scale = (float)(max_depth - min_depth);
     a.depth_offset = (float)min_depth;
-    a.ppm_f = (float)pixels_per_meter;
     a.half_t_f = (float)(template_size / 2.0);
-    a.ppm_d = (double)pixels_per_meter;
     a.half_t_d = template_size / 2.0;
-    a.use_max_conf = use_max_confidence; a.fusion = fusion_type;
     FusedExtra fx{d_written_bits, d_counters, d_conf_quadrant, 0, 0};
-    const int T = template_size, words = (T + 31) >> 5;
-    const int n_vert = width + 2, Q = T / 2 + 1;
-    const size_t lds_base = (size_t)(2 * T * words + ((2 * T * words) & 1)) * 4 + (size_t)n_vert * sizeof(int2) +
-                            (size_t)(n_vert + 1 + ((n_vert + 1) & 1)) * sizeof(int) + (size_t)(Q * Q + ((Q * Q) & 1)) * 4 +
-                            (size_t)T * sizeof(int2);
+    const int T = template_size;
+    const size_t lds_base = raster_lds_bytes(T, width) + quadrant_lds_bytes(T) + (size_t)T * sizeof(int2);
     size_t lds = lds_base;
     if (lds > 150 * 1024) return fail(VLFM_ERR_CAPACITY, "value_map_update_fused_batched: template/width too large for LDS");
     // the cell list takes what is left, up to 8192 entries (a 79-degree cone at 5 m marks ~3 000 cells)
@@ -1234,8 +1184,7 @@ extern "C" int vlfm_value_map_update_fused_batched(uint32_t* d_colmax_keys, int 
         // ... when an observation has at most two workgroups: with more (small batches: G = CUs / n) the tile sweep split over
         // G workgroups is the shorter chain (measured with the phase-timing build, removed; last in 26e85ce -- old / new: 256 obs
         // 56 / 38 us, 128 obs 37 / 35, 64 obs 27 / 36, 16 HD obs 31 / 40, 8 obs 23 / 29)
-        const int cu = target_override_g() > 0 ? target_override_g() : device_cu_count();
-        const bool few_wgs = (cu + n - 1) / n <= 2;
+        const bool few_wgs = (target_wgs() + n - 1) / n <= 2;
         if (few_wgs && cap > 0 && lds + extra <= 150 * 1024 && T < 65536) {
             fx.block_cap = nb_side * nb_side;
             lds += extra;
@@ -1254,16 +1203,7 @@ extern "C" int vlfm_value_map_update_fused_batched(uint32_t* d_colmax_keys, int 
             lds = lds_base;
         }
     }
-    const int tiles = (T + ROWS_PER_TILE - 1) / ROWS_PER_TILE;
-    // workgroups per observation: a 1024-thread workgroup fills a CU (register budget), so aim for one per CU over all
-    // observations; more than ceil(tiles / 4) would leave workgroups without a tile
-    // (the device's CU count, asked once; VLFM_VM_TARGET_WGS -- read once per process -- stands in for it, so that a test can run
-    // the block-sparse sweep and the tile sweep at one batch size)
-    const int target = target_override_g() > 0 ? target_override_g() : device_cu_count();
-    int G = (target + n - 1) / n;
-    const int g_max = (tiles + FUSED_THREADS / 256 - 1) / (FUSED_THREADS / 256);
-    if (G > g_max) G = g_max;
-    if (G < 1) G = 1;
+    const int G = workgroups_per_item(n, T);
     VLFM_TIMED("value_map_update_fused_kernel", stream);
     if (channels == 1)
         VLFM_KLAUNCH(value_map_update_fused_kernel<1>, dim3(G, n), dim3(FUSED_THREADS), lds, (hipStream_t)stream, a, fx);
@@ -1288,23 +1228,15 @@ extern "C" int vlfm_value_map_update_rig_batched(uint32_t* d_colmax_keys, int wi
         return fail(VLFM_ERR_INVALID, "value_map_update_rig_batched: d_explored_bits and d_written_bits go together");
     if (map_size >= 65535 || n_slots > 65535)   // a list entry packs (row << 16) | col of a MAP cell; gridDim.y
         return fail(VLFM_ERR_CAPACITY, "value_map_update_rig_batched: map or batch too large");
-    UpdateArgs a{};
-    a.colmax = reinterpret_cast<unsigned*>(d_colmax_keys); a.pose = d_pose; a.values = d_values;
-    a.conf = d_conf; a.value = d_value; a.explored = d_explored_bits;
-    a.W = width; a.T = max_template_size; a.S = map_size; a.C = channels;
-    a.ppm_f = (float)pixels_per_meter;
-    a.ppm_d = (double)pixels_per_meter;
-    a.use_max_conf = use_max_confidence; a.fusion = fusion_type;
+    const UpdateArgs a = map_update_args(d_colmax_keys, width, max_template_size, d_pose, d_values, d_conf, d_value, map_size,
+                                         channels, pixels_per_meter, use_max_confidence, fusion_type, d_explored_bits);
     FusedExtra fx{d_written_bits, d_counters, nullptr, 0, 0};
     RigArgs rg{d_optics, reinterpret_cast<const int2*>(d_slots), 1};
-    const int T = max_template_size, words = (T + 31) >> 5;
-    const int n_vert = width + 2, Q = T / 2 + 1, nb_side = (T + VB - 1) / VB;
+    const int T = max_template_size, nb_side = (T + VB - 1) / VB;
     fx.block_cap = (nb_side + 4) * nb_side;   // block rows are cut on map rows: up to T/4 + 4 of them meet a window
-    size_t lds = (size_t)(2 * T * words + ((2 * T * words) & 1)) * 4 + (size_t)n_vert * sizeof(int2) +
-                 (size_t)(n_vert + 1 + ((n_vert + 1) & 1)) * sizeof(int) + (size_t)2 * T * sizeof(int2) +
-                 (size_t)fx.block_cap * 4;
+    size_t lds = raster_lds_bytes(T, width) + (size_t)2 * T * sizeof(int2) + (size_t)fx.block_cap * 4;
     // the confidence quadrant goes to LDS when it leaves room for a cell list of 4096 entries (T = 201: 41 of 150 KB)
-    const size_t quad_bytes = (size_t)(Q * Q + ((Q * Q) & 1)) * 4;
+    const size_t quad_bytes = quadrant_lds_bytes(T);
     rg.quad_in_lds = lds + quad_bytes + 4096 * sizeof(uint2) <= 150 * 1024;
     if (rg.quad_in_lds) lds += quad_bytes;
     // the cell list takes what is left, up to 8192 entries (a 79-degree cone at 5 m marks ~3 000 cells); a cone with more
@@ -1320,14 +1252,7 @@ extern "C" int vlfm_value_map_update_rig_batched(uint32_t* d_colmax_keys, int wi
                                       : opt0.ensure(reinterpret_cast<const void*>(value_map_update_rig_kernel<0>), 150 * 1024);
         if (!ok) return fail(VLFM_ERR_HIP, "value_map_update_rig_batched: cannot opt in to large LDS");
     }
-    // workgroups per slot: one 1024-thread workgroup fills a CU, so aim for one per CU over all slots; a window meets about
-    // T / 8 map tiles, and beyond a quarter of them (the single-camera kernel's bound) the repeated raster outweighs the split
-    const int tiles = (T + ROWS_PER_TILE - 1) / ROWS_PER_TILE;
-    const int target = target_override_g() > 0 ? target_override_g() : device_cu_count();
-    int G = (target + n_slots - 1) / n_slots;
-    const int g_max = (tiles + FUSED_THREADS / 256 - 1) / (FUSED_THREADS / 256);
-    if (G > g_max) G = g_max;
-    if (G < 1) G = 1;
+    const int G = workgroups_per_item(n_slots, T);
     VLFM_TIMED("value_map_update_rig_kernel", stream);
     if (channels == 1)
         VLFM_KLAUNCH(value_map_update_rig_kernel<1>, dim3(G, n_slots), dim3(FUSED_THREADS), lds, (hipStream_t)stream, a, fx, rg);

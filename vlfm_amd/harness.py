@@ -870,6 +870,64 @@ class BatchedEpisodes:
             frames[d_idx] = self.rooms.painter(t_ep, frames[d_idx])
         return frames, tf, np.repeat(np.arange(self.E), K), cam
 
+    # ---- the pieces step() and _step_rig() share; each enqueues on the stream that is current when it is called
+    def _transported(self, rgb: torch.Tensor) -> torch.Tensor:
+        """The step's RGB frames after the JPEG transport hop, when it is emulated (main stream: every reader of the previous
+        step's transported frames ran on it or was joined back into it)."""
+        if not self.emulate_jpeg:
+            return rgb
+        from .vlm.transport import jpeg_roundtrip_batch
+
+        return jpeg_roundtrip_batch(rgb, 90, out=self.jpeg_frames, scratch=self.jpeg_scratch)
+
+    def _open_step(self, poses):
+        """(main, side) streams of a step, the side stream joined to the main one (the previous step's value update consumed
+        the column-max keys), after BaseMap.update_agent_traj of both maps (base_objectnav_policy / itm_policy)."""
+        main = torch.cuda.current_stream(self.device)
+        side = self.map_stream if self.map_stream is not None else main
+        if self.render_trajectories:      # one pose per slot and step: the robot's
+            self.values.update_agent_traj(range(self.E), poses[:, :2], poses[:, 2])
+        side.wait_stream(main)
+        if self.render_trajectories and self.obstacles is not None:
+            with torch.cuda.stream(side):
+                self.obstacles.update_agent_traj(range(self.E), poses[:, :2], poses[:, 2])
+        return main, side
+
+    def _cosines(self, rgb: torch.Tensor, prompts, graphed: bool = False) -> torch.Tensor:
+        """One batched BLIP-2 ITC forward: [n] cosines for one prompt per frame, [n, C] for C prompts per frame (every prompt
+        of every frame from one vision forward); ``graphed``: replayed from a captured graph."""
+        if self.C == 1:
+            return self.blip2.cosine_batch_graphed(rgb, prompts) if graphed else self.blip2.cosine_batch(rgb, prompts)
+        return (self.blip2.cosine_prompts_batch_graphed(rgb, prompts) if graphed
+                else self.blip2.cosine_prompts_batch(rgb, prompts))
+
+    def _stub_cosines(self, n: int) -> torch.Tensor:
+        """What stands in for the cosines of ``n`` frames without a model."""
+        return torch.from_numpy(self.stub_rng.uniform(0.15, 0.45, size=n if self.C == 1 else (n, self.C))).to(self.device)
+
+    def _fixed_box_sam(self, rgb: torch.Tensor) -> None:
+        """(legacy leg without object maps: MobileSAM on one fixed box for every ``sam_every``-th environment-step)"""
+        sel = [e for e in range(self.E) if (self.t + e) % self.sam_every == 0]
+        if sel:
+            box = torch.tensor([[[0.3 * self.W, 0.3 * self.H, 0.7 * self.W, 0.8 * self.H]]] * len(sel))
+            self.last_masks = self.sam.segment_bboxes(rgb[sel], box)
+
+    def _score_and_act(self, wps, env_of, poses, t_ep: int, nav_depth) -> None:
+        """After the value update: frontier scoring (ITMPolicyV2._sort_frontiers_by_value, radius 0.5 m), the policy's decision,
+        navigation on the frames ``nav_depth()`` [E,H,W], the end of the episodes; the step is over."""
+        self.last_frontier_values, self.last_frontier_envs = None, env_of
+        if len(wps):
+            self.last_frontier_values = self.values.waypoint_values(wps, env_of, 0.5)  # D2H sync: the policy needs it
+        if self.selectors is not None:
+            modes, goals, halt = self._decide(wps, env_of, self.last_frontier_values, poses, t_ep)
+            self.last_modes, self.last_goals = modes, goals
+            self.last_actions = self._navigate(nav_depth(), modes, goals, halt, poses)
+            self.object_stats["env_steps"] += self.E
+            for m in modes:
+                self.object_stats["modes"][m] += 1
+        self._end_episodes(t_ep)
+        self.t += 1
+
     def _step_rig(self) -> None:
         """step() for a camera rig: K * E frames rendered, ONE depth pass over the obstacle cameras' frames (which also reduces
         the column maxima of the value cameras among them), one obstacle pipeline call per slot from the robot pose, one BLIP-2
@@ -887,14 +945,8 @@ class BatchedEpisodes:
         o_idx, v_idx = np.flatnonzero(is_o), np.flatnonzero(is_v)
         v_only = np.flatnonzero(is_v & ~is_o)
         self.last_rig = (depth, tf, slot, cam)
-        main = torch.cuda.current_stream(self.device)
-        side = self.map_stream if self.map_stream is not None else main
-        if self.render_trajectories:      # one pose per slot and step: the robot's, not one per camera
-            self.values.update_agent_traj(range(E), poses[:, :2], poses[:, 2])
-        side.wait_stream(main)
+        main, side = self._open_step(poses)
         with torch.cuda.stream(side):
-            if self.render_trajectories:
-                self.obstacles.update_agent_traj(range(E), poses[:, :2], poses[:, 2])
             d_o = depth if len(o_idx) == len(slot) else depth[torch.from_numpy(o_idx).to(self.device)]
             keys_o = self.obstacles.ingest_cameras(d_o, tf[o_idx], lo[o_idx], hi[o_idx], fx[o_idx], fx[o_idx], slot[o_idx],
                                                    want_colmax=True)
@@ -917,14 +969,10 @@ class BatchedEpisodes:
                 keys_v = self.values.column_max(depth[torch.from_numpy(v_only).to(self.device)])
                 self._rig_keys[dst_v] = keys_v[src_v]
                 keys_v.zero_()
-        # ---- perception: one batch over the value cameras' frames (the synthetic RGB pool has one frame per environment: the
-        # designated camera of environment e sees pool frame e, camera k pool frame (e + k - designated) mod E)
+        # ---- the transport hop on the pool frames: every camera's frame is one of them (the synthetic RGB pool has one frame
+        # per environment: the designated camera of environment e sees pool frame e, camera k pool frame (e + k - designated) mod E)
         n_v = len(v_idx)
-        pool = self.rgb_pool[self.t % self.rgb_pool.shape[0]]
-        if self.emulate_jpeg:     # the transport hop on the pool frames: every camera's frame is one of them
-            from .vlm.transport import jpeg_roundtrip_batch
-
-            pool = jpeg_roundtrip_batch(pool, 90, out=self.jpeg_frames, scratch=self.jpeg_scratch)
+        pool = self._transported(self.rgb_pool[self.t % self.rgb_pool.shape[0]])
         # ---- detector / segmenter / object maps: ONE designated camera per environment, as object_map_rgbd on the robot
         # (reality_policies.py:103-111) -- the single-camera stage on that camera's RGB frame, depth frame and pose
         d_rows = np.arange(E) * len(rig) + rig.designated
@@ -933,37 +981,20 @@ class BatchedEpisodes:
         if self.object_maps is not None and dets is not None:
             self._update_object_maps(dets, pool, depth[torch.from_numpy(d_rows).to(self.device)], tf[d_rows])
         elif self.sam is not None:
-            sel = [e for e in range(E) if (self.t + e) % self.sam_every == 0]
-            if sel:
-                box = torch.tensor([[[0.3 * self.W, 0.3 * self.H, 0.7 * self.W, 0.8 * self.H]]] * len(sel))
-                self.last_masks = self.sam.segment_bboxes(pool[sel], box)
+            self._fixed_box_sam(pool)
+        # ---- perception: one batch over the value cameras' frames
         if self.blip2 is not None:
             rgb = pool[torch.from_numpy((slot[v_idx] + cam[v_idx] - rig.designated) % E).to(self.device)]
-            prompts = [self.prompts[e] for e in slot[v_idx]]
-            cos = self.blip2.cosine_batch(rgb, prompts) if self.C == 1 else self.blip2.cosine_prompts_batch(rgb, prompts)
-        elif self.C == 1:
-            cos = torch.from_numpy(self.stub_rng.uniform(0.15, 0.45, size=n_v)).to(self.device)
+            cos = self._cosines(rgb, [self.prompts[e] for e in slot[v_idx]])
         else:
-            cos = torch.from_numpy(self.stub_rng.uniform(0.15, 0.45, size=(n_v, self.C))).to(self.device)
+            cos = self._stub_cosines(n_v)
         self.last_cosines = cos
         with torch.cuda.stream(side):
             wps, env_of = self.obstacles.frontier_list()
         main.wait_stream(side)
         self.values.update_cameras(cos.reshape(n_v, self.C), None, tf[v_idx], lo[v_idx], hi[v_idx], hfov[v_idx], slot[v_idx],
                                    colmax=self._rig_keys)
-        self.last_frontier_values, self.last_frontier_envs = None, env_of
-        if len(wps):
-            self.last_frontier_values = self.values.waypoint_values(wps, env_of, 0.5)
-        if self.selectors is not None:
-            modes, goals, halt = self._decide(wps, env_of, self.last_frontier_values, poses, t_ep)
-            self.last_modes, self.last_goals = modes, goals
-            nav = depth[torch.from_numpy(np.arange(E) * len(rig) + rig.designated).to(self.device)]
-            self.last_actions = self._navigate(nav, modes, goals, halt, poses)
-            self.object_stats["env_steps"] += E
-            for m in modes:
-                self.object_stats["modes"][m] += 1
-        self._end_episodes(t_ep)
-        self.t += 1
+        self._score_and_act(wps, env_of, poses, t_ep, lambda: depth[torch.from_numpy(d_rows).to(self.device)])
 
     def step(self) -> None:
         if self.t and self.t % self.episode_len == 0:
@@ -982,58 +1013,33 @@ class BatchedEpisodes:
             depth, rgb = self.rooms.frame(self.t % self.episode_len), self.rgb_pool[kr]
         else:
             depth, rgb = self.depth_pool[k], self.rgb_pool[kr]
-        if self.emulate_jpeg:
-            # (main stream: every reader of the previous step's transported frames ran on it or was joined back into it)
-            from .vlm.transport import jpeg_roundtrip_batch
-
-            rgb = jpeg_roundtrip_batch(rgb, 90, out=self.jpeg_frames, scratch=self.jpeg_scratch)
-        poses, tf = self.pose_table[self.t % self.episode_len], self.tf_table[self.t % self.episode_len]
-        main = torch.cuda.current_stream(self.device)
-        side = self.map_stream if self.map_stream is not None else main
+        rgb = self._transported(rgb)
+        t_ep = self.t % self.episode_len
+        poses, tf = self.pose_table[t_ep], self.tf_table[t_ep]
         # ---- mapping, part 1 (side stream): one depth pass feeds both maps, then the obstacle/frontier pipeline
-        if self.render_trajectories:   # BaseMap.update_agent_traj of both maps (base_objectnav_policy / itm_policy)
-            self.values.update_agent_traj(range(self.E), poses[:, :2], poses[:, 2])
-        side.wait_stream(main)  # the previous step's value update consumed the column-max keys
+        main, side = self._open_step(poses)
         with torch.cuda.stream(side):
-            if self.render_trajectories and self.obstacles is not None:
-                self.obstacles.update_agent_traj(range(self.E), poses[:, :2], poses[:, 2])
             if self.obstacles is not None:
                 colmax = self.obstacles.ingest(depth, tf, MIN_DEPTH, MAX_DEPTH, self.fx, self.fy, want_colmax=True)
                 self.obstacles.update_after_ingest(tf, MAX_DEPTH, self.fov)
             else:
                 colmax = self.values.column_max(depth)
-        t_ep = self.t % self.episode_len
         # ---- detector (main stream).  With the object maps switched on it goes FIRST: its read-back is the step's first host
         # synchronisation anyway, and what follows it -- MobileSAM on the surviving boxes and one ObjectPointCloudMap.update_map per
         # mask, each a few small kernels and two host read-backs -- then runs on its own stream WHILE the BLIP-2 forward occupies the
         # GPU (17 ms of mostly idle GPU per 128-environment step before).  No result depends on the order: BLIP-2 sees the frames only.
         detector_first = self.detector is not None and self.object_maps is not None and self.obj_stream is not None
-        dets = None
-
-        def perceive():
-            if self.C > 1:      # every prompt of every environment from one vision forward -> [E, C]
-                return (self.blip2.cosine_prompts_batch_graphed(rgb, self.prompts) if self.graph_blip2
-                        else self.blip2.cosine_prompts_batch(rgb, self.prompts))
-            return (self.blip2.cosine_batch_graphed(rgb, self.prompts) if self.graph_blip2
-                    else self.blip2.cosine_batch(rgb, self.prompts))
-
-        cos = None
+        dets = cos = None
         vlm_beside = detector_first and self.vlm_stream is not None and self.blip2 is not None
         if vlm_beside:
             self.vlm_stream.wait_stream(main)          # (the frames of this step are complete on the main stream)
             with torch.cuda.stream(self.vlm_stream):
-                cos = perceive()
+                cos = self._cosines(rgb, self.prompts, self.graph_blip2)
         if detector_first:
             dets = self._detect(rgb, t_ep)
         # ---- perception (main stream): one batched BLIP-2 ITC forward for all resident envs
-        if cos is not None:
-            pass
-        elif self.blip2 is not None:
-            cos = perceive()
-        elif self.C == 1:
-            cos = torch.from_numpy(self.stub_rng.uniform(0.15, 0.45, size=self.E)).to(self.device)
-        else:
-            cos = torch.from_numpy(self.stub_rng.uniform(0.15, 0.45, size=(self.E, self.C))).to(self.device)
+        if cos is None:
+            cos = self._cosines(rgb, self.prompts, self.graph_blip2) if self.blip2 is not None else self._stub_cosines(self.E)
         self.last_cosines = cos
         if not detector_first:
             dets = self._detect(rgb, t_ep)
@@ -1047,11 +1053,7 @@ class BatchedEpisodes:
             else:
                 self._update_object_maps(dets, rgb, depth, tf)
         elif self.sam is not None:
-            # (legacy leg without object maps: MobileSAM on one fixed box for every ``sam_every``-th environment-step)
-            sel = [e for e in range(self.E) if (self.t + e) % self.sam_every == 0]
-            if sel:
-                box = torch.tensor([[[0.3 * self.W, 0.3 * self.H, 0.7 * self.W, 0.8 * self.H]]] * len(sel))
-                self.last_masks = self.sam.segment_bboxes(rgb[sel], box)
+            self._fixed_box_sam(rgb)
         # ---- frontiers back to the host (the policy needs them); waits for the side stream only, so the host-side
         # prologue of the value update overlaps the GPU's BLIP-2 work
         if self.obstacles is not None and self.obstacles.frontiers_ready:
@@ -1068,16 +1070,4 @@ class BatchedEpisodes:
             main.wait_stream(self.vlm_stream)          # the cosines; and the next step may not repaint the frames under the ViT
             cos.record_stream(main)
         self.values.update(cos.reshape(self.E, self.C), None, tf, MIN_DEPTH, MAX_DEPTH, self.fov, colmax=colmax)
-        # ---- frontier scoring (ITMPolicyV2._sort_frontiers_by_value, radius 0.5 m)
-        self.last_frontier_values, self.last_frontier_envs = None, env_of
-        if len(wps):
-            self.last_frontier_values = self.values.waypoint_values(wps, env_of, 0.5)  # D2H sync: the policy needs it
-        if self.selectors is not None:
-            modes, goals, halt = self._decide(wps, env_of, self.last_frontier_values, poses, t_ep)
-            self.last_modes, self.last_goals = modes, goals
-            self.last_actions = self._navigate(depth, modes, goals, halt, poses)
-            self.object_stats["env_steps"] += self.E
-            for m in modes:
-                self.object_stats["modes"][m] += 1
-        self._end_episodes(t_ep)
-        self.t += 1
+        self._score_and_act(wps, env_of, poses, t_ep, lambda: depth)

@@ -199,45 +199,69 @@ class ObstacleMapBatch:
                env_ids: Optional[Sequence[int]] = None, update_obstacles: bool = True):
         """obstacle_map.py:86-101 for n observations: one pass over the depth images (shared with the value map's
         column maximum when ``want_colmax``).  Returns the column-max key buffer (or None)."""
+        n = depth.shape[0]
+        env = np.arange(n) if env_ids is None else np.asarray(env_ids)
+        L = _lib.lib()
+
+        def prepare(tf, reach, cap):
+            if update_obstacles:
+                self._note_ingest(np.asarray(env, np.int64), tf, float(reach.max()))
+                # the speculative pass journals the bits it sets per observation; two observations of one slot in the same
+                # launch would hide each other's first-time bits (the reference's multi-camera loop is sequential anyway)
+                assert self._hole_area_thresh == -1 or len(np.unique(env)) == n, "one observation per environment slot and call"
+            return n, cap
+
+        def fill_holes(*args):
+            _lib.check(L.vlfm_fill_small_holes_batched(*args, _stream_ptr()), "fill_small_holes")
+
+        def scatter_holes(*args):
+            _lib.check(L.vlfm_depth_scatter_holes_batched(*args, _stream_ptr()), "depth_scatter_holes")
+
+        return self._ingest(depth, tf, min_depth, max_depth, fx, fy, env, want_colmax, update_obstacles, prepare, fill_holes,
+                            scatter_holes)
+
+    def _ingest(self, depth, tf, min_depth, max_depth, fx, fy, env, want_colmax: bool, update_obstacles: bool, prepare,
+                fill_holes, scatter_holes):
+        """The ingest record of n observations (optics: scalars or length-n arrays) and the launches, for ``ingest`` and
+        ``ingest_cameras``.  Every argument is checked before any state changes.  Then ``prepare(tf [n,4,4], reach [n], cap)``
+        does the caller's bookkeeping and returns the (rows, journal capacity) of the hole buffers; ``reach``: of a texel in
+        the map plane, in cells (None without an obstacle update), ``cap``: the journal capacity this call needs (0 without
+        hole filling).  ``fill_holes(*args)`` / ``scatter_holes(*args)`` launch the caller's entry point of the hole chain
+        with the arguments both forms share.  Returns the key buffer (every row) or None."""
         import torch
+
+        from .value_map import per_observation
 
         n, H, W = depth.shape
         tf = np.asarray(tf, np.float64).reshape(n, 4, 4)
         assert np.array_equal(tf[:, 3, :], np.tile([0.0, 0, 0, 1], (n, 1))), "camera transforms must be affine"
+        lo, hi = per_observation(min_depth, n), per_observation(max_depth, n)
+        fxs, fys = per_observation(fx, n), per_observation(fy, n)
+        env = np.asarray(env).reshape(-1)
+        assert env.shape == (n,), "one slot id per observation"
+        assert int(env.max()) < self.n_envs and int(env.min()) >= 0, "environment slot out of range"
+        fill = update_obstacles and self._hole_area_thresh != -1
         prm = np.zeros(n, INGEST_DTYPE)
         prm["tf"] = tf[:, :3, :].reshape(n, 12)
-        prm["depth_scale"], prm["depth_offset"], prm["depth_max"] = max_depth - min_depth, min_depth, max_depth
-        prm["fx"], prm["fy"] = fx, fy
+        prm["depth_scale"], prm["depth_offset"], prm["depth_max"] = hi - lo, lo, hi
+        prm["fx"], prm["fy"] = fxs, fys
         prm["min_height"], prm["max_height"] = self._min_height, self._max_height
-        prm["env"] = np.arange(n) if env_ids is None else np.asarray(env_ids)
-        assert int(prm["env"].max()) < self.n_envs and int(prm["env"].min()) >= 0, "environment slot out of range"
-        prm["scatter"] = (1 if update_obstacles else 0) | (2 if self._hole_area_thresh == -1 else 0)
-        if update_obstacles:
-            reach_px = max_depth * float(np.sqrt(1.0 + (W / 2 / fx) ** 2 + (H / 2 / fy) ** 2)) * self.pixels_per_meter
-            self._note_ingest(np.asarray(prm["env"], np.int64), tf, reach_px)
+        prm["env"] = env
+        # bit 2: zero texels wait for fill_small_holes; bit 1: every zero texel -> 1.0 (obstacle_map.py:87-89)
+        prm["scatter"] = (1 if update_obstacles else 0) | (4 if fill else 2 if self._hole_area_thresh == -1 else 0)
+        # reach of a texel in the map plane: |(z, x, y)| <= max_depth * sqrt(1 + (W/2fx)^2 + (H/2fy)^2)
+        reach = hi * np.sqrt(1.0 + (W / 2 / fxs) ** 2 + (H / 2 / fys) ** 2) * self.pixels_per_meter if update_obstacles else None
+        cap = int(min(self.size * self.size, (2 * int(np.ceil(reach.max())) + 3) ** 2)) if fill else 0
+        rows, cap = prepare(tf, reach, cap)
         keys = None
         if want_colmax:
             if self.colmax_keys is None or self.colmax_keys.shape != (max(n, self.n_envs), W):
                 self.colmax_keys = torch.zeros((max(n, self.n_envs), W), dtype=torch.int32, device=self.device)
             keys = self.colmax_keys
-        L = _lib.lib()
-        fill = update_obstacles and self._hole_area_thresh != -1
-        if fill:
-            prm["scatter"] |= 4  # zero texels wait for fill_small_holes
-            # the speculative pass journals the bits it sets per observation; two observations of one slot in the same
-            # launch would hide each other's first-time bits (the reference's multi-camera loop is sequential anyway)
-            assert len(np.unique(prm["env"])) == n, "one observation per environment slot and call"
         with torch.cuda.device(self.device):
             d_prm = self._ring_ingest.upload(prm)
-            if not fill:
-                # hole_area_thresh == -1 (every zero texel -> 1.0, obstacle_map.py:87-89) or no obstacle update:
-                # one pass over the depth images
-                _lib.check(L.vlfm_depth_ingest_batched(depth.data_ptr(), n, H, W, d_prm.data_ptr(),
-                                                       keys.data_ptr() if keys is not None else None,
-                                                       self.obstacle_bits.data_ptr() if update_obstacles else None,
-                                                       self.size, self.pixels_per_meter, self.status.data_ptr(),
-                                                       None, None, None, _stream_ptr()), "depth_ingest")
-            else:
+            holes = jref = None
+            if fill:
                 # fill_small_holes (img_utils.py:361-390) sits between reading the depth and scattering it, but it only
                 # decides the fate of texels inside zero regions: the single streaming pass SPECULATIVELY places every
                 # non-zero texel (journalling the obstacle bits it is the first to set), reduces the column maxima and
@@ -246,33 +270,26 @@ class ObstacleMapBatch:
                 # from the two bit planes.  Only an "island" frame -- valid texels enclosed by a small hole, which the
                 # reference's filled contour rewrites to 1.0 (img_utils.py:385-388) -- has its journalled bits taken
                 # back and its valid texels outside the filled area placed again; every other image is read exactly once.
-                # reach of a texel in the map plane: |(z, x, y)| <= max_depth * sqrt(1 + (W/2fx)^2 + (H/2fy)^2)
-                reach = max_depth * float(np.sqrt(1.0 + (W / 2 / fx) ** 2 + (H / 2 / fy) ** 2)) * self.pixels_per_meter
-                cap = int(min(self.size * self.size, (2 * int(np.ceil(reach)) + 3) ** 2))
-                holes, filled, scratch, counts, journal = self._hole_buffers(n, H, W, cap)
+                holes, filled, scratch, counts, journal = self._hole_buffers(rows, H, W, cap)
                 jref = ctypes.byref(journal)
                 if self._journal_dirty:
                     # an earlier step launched the speculative pass but never reached fill_small_holes (which consumes the
                     # journal and resets its counters): entries of that step must not be undone by a later island frame
                     self._journal_count.zero_()
                 self._journal_dirty = True
-                _lib.check(L.vlfm_depth_ingest_batched(depth.data_ptr(), n, H, W, d_prm.data_ptr(),
-                                                       keys.data_ptr() if keys is not None else None,
-                                                       self.obstacle_bits.data_ptr(), self.size,
-                                                       self.pixels_per_meter, self.status.data_ptr(),
-                                                       holes.data_ptr(), None, jref, _stream_ptr()), "depth_ingest")
-                _lib.check(L.vlfm_fill_small_holes_batched(holes.data_ptr(), self.status.data_ptr(), n, H, W,
-                                                           float(self._hole_area_thresh), scratch.data_ptr(),
-                                                           scratch.numel(), self.HOLE_CAP_PTS, self.HOLE_CAP_CONTOURS,
-                                                           filled.data_ptr(), counts.data_ptr(), d_prm.data_ptr(),
-                                                           self.obstacle_bits.data_ptr(), self.size, jref,
-                                                           _stream_ptr()), "fill_small_holes")
+            # the one pass over the depth images (no fill: atomicOr only, duplicates of a slot are safe)
+            _lib.check(_lib.lib().vlfm_depth_ingest_batched(
+                depth.data_ptr(), n, H, W, d_prm.data_ptr(), keys.data_ptr() if keys is not None else None,
+                self.obstacle_bits.data_ptr() if update_obstacles else None, self.size, self.pixels_per_meter,
+                self.status.data_ptr(), holes.data_ptr() if fill else None, None, jref, _stream_ptr()), "depth_ingest")
+            if fill:
+                fill_holes(holes.data_ptr(), self.status.data_ptr(), n, H, W, float(self._hole_area_thresh),
+                           scratch.data_ptr(), scratch.numel(), self.HOLE_CAP_PTS, self.HOLE_CAP_CONTOURS, filled.data_ptr(),
+                           counts.data_ptr(), d_prm.data_ptr(), self.obstacle_bits.data_ptr(), self.size, jref)
                 self._journal_dirty = False   # consumed: fill_small_holes_kernel leaves every counter at zero
-                _lib.check(L.vlfm_depth_scatter_holes_batched(d_prm.data_ptr(), n, H, W, holes.data_ptr(),
-                                                              filled.data_ptr(), counts.data_ptr(),
-                                                              self.obstacle_bits.data_ptr(), self.size,
-                                                              self.pixels_per_meter, self.status.data_ptr(),
-                                                              depth.data_ptr(), _stream_ptr()), "depth_scatter_holes")
+                scatter_holes(d_prm.data_ptr(), n, H, W, holes.data_ptr(), filled.data_ptr(), counts.data_ptr(),
+                              self.obstacle_bits.data_ptr(), self.size, self.pixels_per_meter, self.status.data_ptr(),
+                              depth.data_ptr())
         return keys
 
     # ------------------------------------------------------------------------------------------ step, part 1: camera rig
@@ -319,84 +336,45 @@ class ObstacleMapBatch:
         ``check_status`` (IndexError), after which the obstacle planes hold the points placed so far, as after ``ingest``."""
         import torch
 
-        from .value_map import per_observation, stack_rig_frames
+        from .value_map import stack_rig_frames
 
         depth = stack_rig_frames(depth)
         if not torch.is_tensor(depth):
             depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32)).to(self.device)
         depth = depth.contiguous()
-        n, H, W = depth.shape
-        tf = np.asarray(tf, np.float64).reshape(n, 4, 4)
-        assert np.array_equal(tf[:, 3, :], np.tile([0.0, 0, 0, 1], (n, 1))), "camera transforms must be affine"
-        lo, hi = per_observation(min_depth, n), per_observation(max_depth, n)
-        fxs, fys = per_observation(fx, n), per_observation(fy, n)
+        n = depth.shape[0]
         env = np.asarray(env_ids, np.int64).reshape(-1)
-        assert env.shape == (n,), "one slot id per observation"
-        assert int(env.max()) < self.n_envs and int(env.min()) >= 0, "environment slot out of range"
-        prm = np.zeros(n, INGEST_DTYPE)
-        prm["tf"] = tf[:, :3, :].reshape(n, 12)
-        prm["depth_scale"], prm["depth_offset"], prm["depth_max"] = hi - lo, lo, hi
-        prm["fx"], prm["fy"] = fxs, fys
-        prm["min_height"], prm["max_height"] = self._min_height, self._max_height
-        prm["env"] = env
-        fill = self._hole_area_thresh != -1
-        prm["scatter"] = 1 | (4 if fill else 2)
-        reach = hi * np.sqrt(1.0 + (W / 2 / fxs) ** 2 + (H / 2 / fys) ** 2) * self.pixels_per_meter
-        slots, win = self.rig_windows(env, tf, reach, self.size, self.pixels_per_meter)
-        self._union(self._dirty_obst, slots, win)
-        rows = max(n, self.n_envs)
-        if self.status.shape[0] < rows:     # status words are per OBSERVATION: a rig has more of them than slots
-            grown = torch.zeros((rows, 2), dtype=torch.int32, device=self.device)
-            grown[:self.status.shape[0]] = self.status
-            self.status = grown
-            self._h_status = torch.zeros((rows, 2), dtype=torch.int32).pin_memory()
-        if self._ring_ingest.nbytes < n * INGEST_DTYPE.itemsize:
-            self._ring_ingest = UploadRing(self.device, n * INGEST_DTYPE.itemsize, slots=8)
-        keys = None
-        if want_colmax:
-            if self.colmax_keys is None or self.colmax_keys.shape != (rows, W):
-                self.colmax_keys = torch.zeros((rows, W), dtype=torch.int32, device=self.device)
-            keys = self.colmax_keys
         L = _lib.lib()
-        with torch.cuda.device(self.device):
-            d_prm = self._ring_ingest.upload(prm)
-            if not fill:   # every zero texel -> 1.0 (obstacle_map.py:87-89): atomicOr only, duplicates of a slot are safe
-                _lib.check(L.vlfm_depth_ingest_batched(depth.data_ptr(), n, H, W, d_prm.data_ptr(),
-                                                       keys.data_ptr() if keys is not None else None,
-                                                       self.obstacle_bits.data_ptr(), self.size, self.pixels_per_meter,
-                                                       self.status.data_ptr(), None, None, None, _stream_ptr()),
-                           "depth_ingest")
-                return keys[:n] if keys is not None else None
-            cap = int(min(self.size * self.size, (2 * int(np.ceil(reach.max())) + 3) ** 2))
-            # sized for the high-water mark: the number of observations changes when a slot drops out of a step, and a
-            # reallocation would re-zero every hole / scratch / journal buffer
+
+        def prepare(tf, reach, cap):
+            slots, win = self.rig_windows(env, tf, reach, self.size, self.pixels_per_meter)
+            self._union(self._dirty_obst, slots, win)
+            rows = max(n, self.n_envs)
+            if self.status.shape[0] < rows:     # status words are per OBSERVATION: a rig has more of them than slots
+                grown = torch.zeros((rows, 2), dtype=torch.int32, device=self.device)
+                grown[:self.status.shape[0]] = self.status
+                self.status = grown
+                self._h_status = torch.zeros((rows, 2), dtype=torch.int32).pin_memory()
+            if self._ring_ingest.nbytes < n * INGEST_DTYPE.itemsize:
+                self._ring_ingest = UploadRing(self.device, n * INGEST_DTYPE.itemsize, slots=8)
+            if not cap:
+                return n, 0
+            # hole filling: buffers sized for the high-water mark -- the number of observations changes when a slot drops
+            # out of a step, and a reallocation would re-zero every hole / scratch / journal buffer
             self._rig_high = (max(n, self._rig_high[0]), max(cap, self._rig_high[1]))
-            holes, filled, scratch, counts, journal = self._hole_buffers(self._rig_high[0], H, W, self._rig_high[1])
             if self._slot_undone is None:
                 self._slot_undone = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
-            jref = ctypes.byref(journal)
-            if self._journal_dirty:
-                self._journal_count.zero_()
-            self._journal_dirty = True
-            _lib.check(L.vlfm_depth_ingest_batched(depth.data_ptr(), n, H, W, d_prm.data_ptr(),
-                                                   keys.data_ptr() if keys is not None else None,
-                                                   self.obstacle_bits.data_ptr(), self.size, self.pixels_per_meter,
-                                                   self.status.data_ptr(), holes.data_ptr(), None, jref, _stream_ptr()),
-                       "depth_ingest")
-            _lib.check(L.vlfm_fill_small_holes_rig_batched(holes.data_ptr(), self.status.data_ptr(), n, H, W,
-                                                           float(self._hole_area_thresh), scratch.data_ptr(),
-                                                           scratch.numel(), self.HOLE_CAP_PTS, self.HOLE_CAP_CONTOURS,
-                                                           filled.data_ptr(), counts.data_ptr(), d_prm.data_ptr(),
-                                                           self.obstacle_bits.data_ptr(), self.size, jref,
-                                                           self._slot_undone.data_ptr(), self.n_envs, _stream_ptr()),
+            return self._rig_high
+
+        def fill_holes(*args):
+            _lib.check(L.vlfm_fill_small_holes_rig_batched(*args, self._slot_undone.data_ptr(), self.n_envs, _stream_ptr()),
                        "fill_small_holes_rig")
-            self._journal_dirty = False
-            _lib.check(L.vlfm_depth_scatter_holes_rig_batched(d_prm.data_ptr(), n, H, W, holes.data_ptr(),
-                                                              filled.data_ptr(), counts.data_ptr(),
-                                                              self.obstacle_bits.data_ptr(), self.size,
-                                                              self.pixels_per_meter, self.status.data_ptr(),
-                                                              depth.data_ptr(), self._slot_undone.data_ptr(),
-                                                              _stream_ptr()), "depth_scatter_holes_rig")
+
+        def scatter_holes(*args):
+            _lib.check(L.vlfm_depth_scatter_holes_rig_batched(*args, self._slot_undone.data_ptr(), _stream_ptr()),
+                       "depth_scatter_holes_rig")
+
+        keys = self._ingest(depth, tf, min_depth, max_depth, fx, fy, env, want_colmax, True, prepare, fill_holes, scatter_holes)
         return keys[:n] if keys is not None else None
 
     def _hole_buffers(self, n: int, H: int, W: int, journal_cap: int):

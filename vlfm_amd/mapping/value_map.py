@@ -366,6 +366,55 @@ class ValueMapBatch:
         return colmax[:n]
 
     # ------------------------------------------------------------------------------------------ update
+    def _device_values(self, values):
+        """values -> device f64 [n, C] (device-resident scores straight from the ITC head make no host round trip)."""
+        import torch
+
+        if torch.is_tensor(values):
+            return values.to(device=self.device, dtype=torch.float64).reshape(-1, self.channels).contiguous()
+        return torch.from_numpy(
+            np.ascontiguousarray(np.asarray(values, np.float64).reshape(-1, self.channels))).to(self.device)
+
+    def _keys_from_depth(self, depth, n: int):
+        """The column-max keys of [n,H,W] depth frames (device tensor, or host array that is uploaded), when no shared depth
+        ingest handed them in."""
+        import torch
+
+        if not torch.is_tensor(depth):
+            depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32)).to(self.device)
+        depth = depth.reshape(n, depth.shape[-2], depth.shape[-1]).contiguous()
+        assert depth.dtype == torch.float32
+        return self.column_max(depth)
+
+    def _explored_and_written(self):
+        """(explored, written) plane pointers of an update, (None, None) without an obstacle map attached."""
+        import torch
+
+        if self.explored_bits is None:
+            self._written_stale = True   # cells fused from here on are not recorded in the plane
+            return None, None
+        ex = self.explored_bits
+        assert ex.dtype == torch.int32 and ex.is_contiguous() and ex.shape[-2] == self.size
+        if self._written is None or self._written_stale:
+            # conf may already hold values (an obstacle map attached mid-episode, or detached for a while and
+            # attached again): (re)start from conf != 0
+            if self._written is None:
+                self._written = torch.zeros((self.n_envs, self.size, (self.size + 31) // 32),
+                                            dtype=torch.int32, device=self.device)
+            _lib.check(_lib.lib().vlfm_bits_pack((self.conf != 0).to(torch.uint8).contiguous().data_ptr(),
+                                                 self._written.data_ptr(), self.n_envs, self.size, self.size,
+                                                 _stream_ptr()), "bits_pack")
+            self._written_stale = False
+        return ex.data_ptr(), self._written.data_ptr()
+
+    def _counters_ptr(self, n: int):
+        """Per-observation completion counters of the key hand-back: zero between launches."""
+        import torch
+
+        if self._counters is None or self._counters.numel() < n:
+            self._counters = torch.zeros(max(n, self.n_envs), dtype=torch.int32, device=self.device)
+        return self._counters.data_ptr()
+
     def update(self, values, depth, tf_camera_to_episodic, min_depth: float, max_depth: float, fov: float,
                env_ids: Optional[Sequence[int]] = None, colmax=None) -> None:
         """ValueMap.update_map for n observations at once (value_map.py:100-128).
@@ -375,11 +424,7 @@ class ValueMapBatch:
         """
         import torch
 
-        if torch.is_tensor(values):  # device-resident scores straight from the ITC head: no host round trip
-            d_vals = values.to(device=self.device, dtype=torch.float64).reshape(-1, self.channels).contiguous()
-        else:
-            d_vals = torch.from_numpy(
-                np.ascontiguousarray(np.asarray(values, np.float64).reshape(-1, self.channels))).to(self.device)
+        d_vals = self._device_values(values)
         n = d_vals.shape[0]
         # Host prologue FIRST: a camera outside the map (AssertionError, img_utils.py:43) or a bad slot list must fail before
         # any column maximum is reduced into the key buffer -- keys are only re-zeroed by a completed update, and stale keys
@@ -401,42 +446,15 @@ class ValueMapBatch:
                 colmax.zero_()
             raise
         if colmax is None:
-            if not torch.is_tensor(depth):
-                depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32)).to(self.device)
-            depth = depth.reshape(n, depth.shape[-2], depth.shape[-1]).contiguous()
-            assert depth.dtype == torch.float32
-            colmax = self.column_max(depth)
-        L = _lib.lib()
+            colmax = self._keys_from_depth(depth, n)
         with torch.cuda.device(self.device):
-            ring = self._rings(n)
-            d_pose = ring.upload(pose)
-            explored_ptr = None
-            if self.explored_bits is not None:
-                ex = self.explored_bits
-                assert ex.dtype == torch.int32 and ex.is_contiguous() and ex.shape[-2] == self.size
-                explored_ptr = ex.data_ptr()
-            written_ptr = None
-            if explored_ptr is None:
-                self._written_stale = True   # cells fused from here on are not recorded in the plane
-            else:
-                if self._written is None or self._written_stale:
-                    # conf may already hold values (an obstacle map attached mid-episode, or detached for a while and
-                    # attached again): (re)start from conf != 0
-                    if self._written is None:
-                        self._written = torch.zeros((self.n_envs, self.size, (self.size + 31) // 32),
-                                                    dtype=torch.int32, device=self.device)
-                    _lib.check(L.vlfm_bits_pack((self.conf != 0).to(torch.uint8).contiguous().data_ptr(),
-                                                self._written.data_ptr(), self.n_envs, self.size, self.size,
-                                                _stream_ptr()), "bits_pack")
-                    self._written_stale = False
-                written_ptr = self._written.data_ptr()
-            if self._counters is None or self._counters.numel() < n:
-                self._counters = torch.zeros(max(n, self.n_envs), dtype=torch.int32, device=self.device)
-            _lib.check(L.vlfm_value_map_update_fused_batched(
+            d_pose = self._rings(n).upload(pose)
+            explored_ptr, written_ptr = self._explored_and_written()
+            _lib.check(_lib.lib().vlfm_value_map_update_fused_batched(
                 colmax.data_ptr(), W, d_tan.data_ptr(), d_tmpl.data_ptr(), d_bits.data_ptr(), T, d_pose.data_ptr(),
                 d_vals.data_ptr(), n, self.conf.data_ptr(), self.value.data_ptr(), self.size, self.channels,
                 self.pixels_per_meter, float(min_depth), float(max_depth), int(self.use_max_confidence),
-                _lib.FUSION_TYPES[self.fusion_type], explored_ptr, written_ptr, self._counters.data_ptr(),
+                _lib.FUSION_TYPES[self.fusion_type], explored_ptr, written_ptr, self._counters_ptr(n),
                 _TEMPLATES.quadrant(self.device, fov, max_depth, self.pixels_per_meter,
                                     self._min_confidence).data_ptr(), _stream_ptr()), "value_map_update_fused")
 
@@ -455,11 +473,7 @@ class ValueMapBatch:
         anything is launched (``colmax`` keys handed in are zeroed); the maps are then unchanged, ``n_updates`` too."""
         import torch
 
-        if torch.is_tensor(values):
-            d_vals = values.to(device=self.device, dtype=torch.float64).reshape(-1, self.channels).contiguous()
-        else:
-            d_vals = torch.from_numpy(
-                np.ascontiguousarray(np.asarray(values, np.float64).reshape(-1, self.channels))).to(self.device)
+        d_vals = self._device_values(values)
         n = d_vals.shape[0]
         try:
             if colmax is None:
@@ -480,38 +494,16 @@ class ValueMapBatch:
             raise
         self.n_updates += plan["counts"]
         if colmax is None:
-            if not torch.is_tensor(depth):
-                depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32)).to(self.device)
-            depth = depth.reshape(n, depth.shape[-2], depth.shape[-1]).contiguous()
-            assert depth.dtype == torch.float32
-            colmax = self.column_max(depth)
-        L = _lib.lib()
+            colmax = self._keys_from_depth(depth, n)
         with torch.cuda.device(self.device):
             d_pose = self._rings(n).upload(pose)
-            explored_ptr = written_ptr = None
-            if self.explored_bits is None:
-                self._written_stale = True   # cells fused from here on are not recorded in the plane
-            else:
-                ex = self.explored_bits
-                assert ex.dtype == torch.int32 and ex.is_contiguous() and ex.shape[-2] == self.size
-                explored_ptr = ex.data_ptr()
-                if self._written is None or self._written_stale:   # (re)start from conf != 0, as update() does
-                    if self._written is None:
-                        self._written = torch.zeros((self.n_envs, self.size, (self.size + 31) // 32),
-                                                    dtype=torch.int32, device=self.device)
-                    _lib.check(L.vlfm_bits_pack((self.conf != 0).to(torch.uint8).contiguous().data_ptr(),
-                                                self._written.data_ptr(), self.n_envs, self.size, self.size,
-                                                _stream_ptr()), "bits_pack")
-                    self._written_stale = False
-                written_ptr = self._written.data_ptr()
-            if self._counters is None or self._counters.numel() < n:
-                self._counters = torch.zeros(max(n, self.n_envs), dtype=torch.int32, device=self.device)
+            explored_ptr, written_ptr = self._explored_and_written()
             static = plan["d_static"].data_ptr()
-            _lib.check(L.vlfm_value_map_update_rig_batched(
+            _lib.check(_lib.lib().vlfm_value_map_update_rig_batched(
                 colmax.data_ptr(), W, d_pose.data_ptr(), static, static + n * VM_OPTICS_DTYPE.itemsize, plan["n_slots"], n,
                 plan["T_max"], d_vals.data_ptr(), self.conf.data_ptr(), self.value.data_ptr(),
                 self.size, self.channels, self.pixels_per_meter, int(self.use_max_confidence),
-                _lib.FUSION_TYPES[self.fusion_type], explored_ptr, written_ptr, self._counters.data_ptr(),
+                _lib.FUSION_TYPES[self.fusion_type], explored_ptr, written_ptr, self._counters_ptr(n),
                 _stream_ptr()), "value_map_update_rig")
 
     def _rig_plan(self, env_ids, min_depth, max_depth, fov, n: int, W: int) -> Dict[str, Any]:

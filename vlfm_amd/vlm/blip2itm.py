@@ -716,6 +716,7 @@ class BLIP2ITM:
         self._text_cache: Dict[str, torch.Tensor] = {}
         self._prompt_cache: Dict[tuple, tuple] = {}
         self._proj_t = None
+        self._graphs, self._prompt_graphs = {}, {}   # captured forwards of cosine_batch_graphed / cosine_prompts_batch_graphed
         self.two_stream_min = None    # e.g. 64: run batches of at least that many images as two halves on two streams
         self._side_stream = None
 
@@ -797,22 +798,31 @@ class BLIP2ITM:
         """``cosine_batch`` replayed from a captured HIP graph (one per (shape, prompts) key): the ~650 kernel launches
         of a ViT-g + Q-Former forward collapse into one graph launch, which is what bounds small batches (launch-bound
         below ~16 images).  The input is copied into the graph's static buffer; the result is the graph's static output."""
-        key = (tuple(images_u8.shape), tuple(txts))
-        if not hasattr(self, "_graphs"):
-            self._graphs = {}
-        if key not in self._graphs:
+        return self._replay(self._graphs, (tuple(images_u8.shape), tuple(txts)), lambda x: self.cosine_batch(x, txts), images_u8)
+
+    def _replay(self, graphs: dict, key, forward, images_u8: torch.Tensor, keep_alive=()) -> torch.Tensor:
+        """``forward(images)`` replayed from the HIP graph ``graphs[key]``, captured at the first call; ``keep_alive``: tensors
+        whose addresses the graph holds besides its input and output (they live as long as it does)."""
+        if key not in graphs:
             static_in = images_u8.clone()
             for _ in range(2):  # warm-up outside capture: coefficient tables, text features, hipBLASLt workspaces
-                self.cosine_batch(static_in, txts)
+                forward(static_in)
             torch.cuda.synchronize(self.device)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                static_out = self.cosine_batch(static_in, txts)
-            self._graphs[key] = (g, static_in, static_out)
-        g, static_in, static_out = self._graphs[key]
+                static_out = forward(static_in)
+            graphs[key] = (g, static_in, static_out, keep_alive)
+        g, static_in, static_out, _ = graphs[key]
         static_in.copy_(images_u8)
         g.replay()
         return static_out
+
+    def _projection(self):
+        """(weight^T, bias) of the vision projection in f32, as the ITC head kernels take them."""
+        if self._proj_t is None:
+            self._proj_t = (self.model.vision_projection.weight.float().t().contiguous(),
+                            self.model.vision_projection.bias.float().contiguous())
+        return self._proj_t
 
     def _query_feats(self, images_u8: torch.Tensor) -> torch.Tensor:
         """[B,H,W,3] u8 -> the Q-Former's query outputs [B,NQ,H] f32: preprocessing, ViT-g and Q-Former, the part of the forward
@@ -855,10 +865,7 @@ class BLIP2ITM:
         else:
             assert len(txts) == B
             text = torch.stack([self.text_feature(t) for t in txts]).contiguous()
-        if self._proj_t is None:
-            self._proj_t = (self.model.vision_projection.weight.float().t().contiguous(),
-                            self.model.vision_projection.bias.float().contiguous())
-        return ops.itc_head(q, self._proj_t[0], self._proj_t[1], text)
+        return ops.itc_head(q, *self._projection(), text)
 
     def _prompt_tensors(self, prompts, B: int):
         """(text table [U,P], index [B,T] int32) of a prompt structure, built and uploaded once per structure (the index is
@@ -884,32 +891,14 @@ class BLIP2ITM:
         B = images_u8.shape[0]
         q = self._query_feats(images_u8)
         table, index, _ = self._prompt_tensors(prompts, B)
-        if self._proj_t is None:
-            self._proj_t = (self.model.vision_projection.weight.float().t().contiguous(),
-                            self.model.vision_projection.bias.float().contiguous())
-        return ops.itc_head_multi(q, self._proj_t[0], self._proj_t[1], table, index)
+        return ops.itc_head_multi(q, *self._projection(), table, index)
 
     def cosine_prompts_batch_graphed(self, images_u8: torch.Tensor, prompts) -> torch.Tensor:
         """``cosine_prompts_batch`` replayed from a captured HIP graph, one per (shape, prompt structure) key, as
         ``cosine_batch_graphed``: the table and the index are the cached tensors of that structure, static under replay."""
         table, index, structure = self._prompt_tensors(prompts, images_u8.shape[0])
-        key = (tuple(images_u8.shape), structure)
-        if not hasattr(self, "_prompt_graphs"):
-            self._prompt_graphs = {}
-        if key not in self._prompt_graphs:
-            static_in = images_u8.clone()
-            for _ in range(2):  # warm-up outside capture: coefficient tables, text features, hipBLASLt workspaces
-                self.cosine_prompts_batch(static_in, prompts)
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                static_out = self.cosine_prompts_batch(static_in, prompts)
-            # (the graph holds the addresses of the table and the index: they live as long as it does)
-            self._prompt_graphs[key] = (g, static_in, static_out, table, index)
-        g, static_in, static_out = self._prompt_graphs[key][:3]
-        static_in.copy_(images_u8)
-        g.replay()
-        return static_out
+        return self._replay(self._prompt_graphs, (tuple(images_u8.shape), structure),
+                            lambda x: self.cosine_prompts_batch(x, prompts), images_u8, keep_alive=(table, index))
 
     def check_numerics(self) -> None:
         """Raise if a split-precision f32 GEMM of the Q-Former met an operand outside f16's range since the last check (its result is
