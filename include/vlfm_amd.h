@@ -368,6 +368,22 @@ int vlfm_vit_attention_f16(const void* d_qkv, void* d_out, int batch, int tokens
 int vlfm_gemm_f16_nt(const void* d_x, const void* d_w, const void* d_bias, void* d_c, int m, int n, int k, int epilogue,
                      void* stream);
 
+/* (ABI 13) The two-piece split-precision projection in ONE pass of the same kernel: out = X[M][K] . (W1 + 2^-11 W2)[N_out][K]^T + bias,
+ * f16 operands, f32 bias, f32 result, every output element fl(acc1 + fl(bias + 2^-11 acc2)) -- the arithmetic of the two f32-output
+ * library GEMMs it replaces, smallest term first -- written once.  d_w_pair is [2 N_out][K] f16: for every block of 64 output
+ * channels its 64 rows of W1, then its 64 rows of W2.  The result is BLOCK-MAJOR: d_out[block][m][64] f32 (block = channel / 64), so
+ * the 64 channels of one head over consecutive rows are contiguous.  K % 64 == 0, N_out % 64 == 0; d_bias_f32 may be NULL. */
+int vlfm_gemm_f16_pair_f32_nt(const void* d_x, const void* d_w_pair, const void* d_bias_f32, void* d_out, int m, int n_out, int k,
+                              void* stream);
+
+/* (ABI 13) The Q-Former's cross-attention in f32 (csrc/qformer_attention.hip): d_out[b][q][h * 64 ..] = softmax_t(scale * <q, K_t>) V_t
+ * for d_q / d_out [batch][queries][heads * 64] f32 and K / V read from the block-major tensor of vlfm_gemm_f16_pair_f32_nt
+ * ([blocks][m_total][64] f32): image b is rows [b * tokens, (b + 1) * tokens), head h of K is block k_block0 + h, of V block
+ * v_block0 + h.  Head width 64; 1 <= queries <= 32, 1 <= tokens <= 257, batch * tokens <= m_total; anything else returns
+ * VLFM_ERR_INVALID and the caller uses the library attention.  Rows of d_out beyond `batch` are not written. */
+int vlfm_qformer_cross_attention_f32(const void* d_q, const void* d_kv_blocks, void* d_out, int batch, int tokens, int queries,
+                                     int heads, int k_block0, int v_block0, int m_total, float scale, void* stream);
+
 /* Diagnostic, host only (no GPU needed): the order in which vlfm_gemm_f16_nt's 8-phase kernels walk the 256 x 256 tiles of an
  * m x n result -- list position i -> (m-tile, n-tile) in out[2 i], out[2 i + 1]; position i runs on XCD i % 8, the persistent kernel's
  * workgroup w takes positions w, w + grid, ...  Returns the number of tiles (negative: error).  group_m <= 0: the default. */

@@ -13,7 +13,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlfm_amd.so")
-SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "detect_ops.hip", "object_cloud.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "host.cpp"]
+SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "qformer_attention.hip", "detect_ops.hip", "object_cloud.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "host.cpp"]
 
 VLFM_OK = 0
 VLFM_ERR_INVALID = -1
@@ -130,6 +130,8 @@ def lib() -> ctypes.CDLL:
         L.vlfm_layernorm_bias_f16.argtypes = [vp, vp, vp, vp, vp, ci, ci, ctypes.c_float, vp]
         L.vlfm_vit_attention_f16.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_float, vp]
         L.vlfm_gemm_f16_nt.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
+        L.vlfm_gemm_f16_pair_f32_nt.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
+        L.vlfm_qformer_cross_attention_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp]
         L.vlfm_gemm_f32_nt.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]
         L.vlfm_split_f32_to_f16_pair.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp]
         L.vlfm_layernorm_rows_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ctypes.c_float, vp]

@@ -49,7 +49,8 @@ constexpr int BUF = 2 * OPER;      // W tile + X tile
 constexpr int EPI_ROW = 272;       // epilogue staging row stride (128 n x 2 B + 16)
 constexpr int EPI_WAVE = 64 * EPI_ROW;
 constexpr int GEMM_LDS = 8 * EPI_WAVE > 2 * BUF ? 8 * EPI_WAVE : 2 * BUF;
-enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_ACCUM = 2 };   // 2: C += X . W^T (+ bias): the residual-stream GEMMs (projection, fc2)
+enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_ACCUM = 2,     // 2: C += X . W^T (+ bias): the residual-stream GEMMs (projection, fc2)
+       EPI_PAIR_F32 = 3 };   // 3: W holds the two f16 pieces of an f32 weight, interleaved by 64-channel blocks; f32 block-major result
 
 struct GemmArgs {
     const _Float16* x;     // [M][K]
@@ -352,6 +353,37 @@ __device__ __forceinline__ void epi2_pass(const floatx4 (&acc)[8][4], const half
 #pragma unroll
     for (int it = 0; it < 8; it++) v[it] = *reinterpret_cast<const half8*>(stg + (it * 8 + rsub) * EPI2_ROW + chunk * 16);
 }
+// EPI_PAIR_F32: W is [2 N_out][K], for every block of 64 output channels its 64 rows of W1 (the f16 head of an f32 weight), then its
+// 64 rows of W2 (the f16 remainder, scaled by 2^11).  A wavefront's 128 n-columns are then [64 of W1 | 64 of W2] of ONE block, i.e.
+// its P_H0 and P_H1 halves: acc[ii] and acc[4 + ii] of a lane are the two partial products of the same output elements, and
+//     out = fl(acc_H0 + fl(bias + 2^-11 acc_H1))        (bias f32; 2^-11 acc_H1 is exact)
+// is the arithmetic of addmm(bias, x, W2^T, alpha = 2^-11) followed by addmm(o, x, W1^T): smallest term first, every step in f32,
+// with the f32 result written ONCE.  The 64 channels go through the wavefront's staging rows in two passes of 32 f32 -- the same
+// 144-byte rows as the f16 passes -- and leave as 128-byte half rows of the block-major result out[block][m][64].
+template <int P>
+__device__ __forceinline__ void epi_pair_pass(const floatx4 (&acc)[8][4], const floatx4 (&bias4)[4], unsigned char* stg, int g4, int c16,
+                                              int rsub, int chunk, floatx4 (&v)[8]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i2 = 0; i2 < 2; i2++) {
+        constexpr int I0 = 2 * P;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            floatx4 r;
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const float low = acc[4 + I0 + i2][j][e] * 0x1p-11f;
+                const float mid = bias4[I0 + i2][e] + low;
+                r[e] = acc[I0 + i2][j][e] + mid;
+            }
+            *reinterpret_cast<floatx4*>(stg + (j * 16 + c16) * EPI2_ROW + (i2 * 16 + g4) * 4) = r;
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);   // wavefront-private rows: no workgroup barrier
+#pragma unroll
+    for (int it = 0; it < 8; it++) v[it] = *reinterpret_cast<const floatx4*>(stg + (it * 8 + rsub) * EPI2_ROW + chunk * 16);
+}
+// (EPI_PAIR_F32: a.bias points to N / 2 f32 values -- the same 512 bytes per tile at the same byte offset as 256 halves)
 __device__ __forceinline__ void stage_bias(const GemmArgs& a, lds_ptr lds, int wave, int lane, int n_first) {
     if (a.bias != nullptr && wave == 0 && lane < 32) {
         const _Float16* src = a.bias + min(n_first + lane * 8, a.N - 8);
@@ -421,11 +453,20 @@ __global__ __launch_bounds__(512) void gemm_f16_8pp_kernel(GemmArgs a) {
         // ---- the tile's 256 bias values come from LDS (stage_bias(): requested with the tile's first loads).  Nothing in the
         // epilogue's arithmetic depends on a VMEM load -- a bias quad loaded here made hipcc drain vmcnt(0), prefetch included,
         // before the first addition
-        half4 bias4[8];
+        half4 bias4[EPI == EPI_PAIR_F32 ? 1 : 8];
+        floatx4 biasf[EPI == EPI_PAIR_F32 ? 4 : 1];     // EPI_PAIR_F32: the wavefront's 64 channels, f32
+        if constexpr (EPI == EPI_PAIR_F32) {
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const half4 ld = *reinterpret_cast<const half4*>(smem + PBIAS_OFF + (wn * 128 + i * 16 + g4) * 2);
-            bias4[i] = has_bias ? ld : half4{(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+            for (int i = 0; i < 4; i++) {
+                const floatx4 ld = *reinterpret_cast<const floatx4*>(smem + PBIAS_OFF + (wn * 64 + i * 16 + g4) * 4);
+                biasf[i] = has_bias ? ld : floatx4{0.f, 0.f, 0.f, 0.f};
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const half4 ld = *reinterpret_cast<const half4*>(smem + PBIAS_OFF + (wn * 128 + i * 16 + g4) * 2);
+                bias4[i] = has_bias ? ld : half4{(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- K-tile 0 of the next tile -> buffer 0.  Unconditional (a branch here makes hipcc drain vmcnt at the join): the last
@@ -454,6 +495,31 @@ __global__ __launch_bounds__(512) void gemm_f16_8pp_kernel(GemmArgs a) {
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- bias (+ GELU), f16, transpose through the wavefront's staging rows: two passes of 64 n
+        if constexpr (EPI == EPI_PAIR_F32) {
+            // ---- pair sum + f32 bias, transpose through the staging rows: two passes of 32 f32 channels, block-major stores
+            (void)bias4; (void)old;
+            floatx4 p0[8], p1[8];
+            epi_pair_pass<0>(g.acc, biasf, stg, g4, c16, rsub, chunk, p0);
+            epi_pair_pass<1>(g.acc, biasf, stg, g4, c16, rsub, chunk, p1);
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_waitcnt(0x0F70);   // this wavefront's share of the next K-tile 0 is in LDS (no store is in flight yet)
+            __builtin_amdgcn_sched_barrier(0);
+            const int nblk = n0 + wn * 128;       // first of the block's 128 interleaved W rows; the block is nblk / 128
+            if (store && nblk + 128 <= a.N) {
+                float* ob = reinterpret_cast<float*>(a.c) + (size_t)(nblk >> 7) * (size_t)a.M * 64 + chunk * 4;
+#pragma unroll
+                for (int it = 0; it < 8; it++) {
+                    const int m = m0 + wm * 64 + it * 8 + rsub;
+                    if (m < a.M) *reinterpret_cast<floatx4*>(ob + (size_t)m * 64) = p0[it];
+                }
+#pragma unroll
+                for (int it = 0; it < 8; it++) {
+                    const int m = m0 + wm * 64 + it * 8 + rsub;
+                    if (m < a.M) *reinterpret_cast<floatx4*>(ob + (size_t)m * 64 + 32) = p1[it];
+                }
+            }
+        } else {
+        (void)biasf;
         half8 v0[8], v1[8];
         epi2_pass<EPI, 0>(g.acc, bias4, stg, g4, c16, rsub, chunk, v0);
         epi2_pass<EPI, 1>(g.acc, bias4, stg, g4, c16, rsub, chunk, v1);
@@ -484,6 +550,7 @@ __global__ __launch_bounds__(512) void gemm_f16_8pp_kernel(GemmArgs a) {
                 }
             }
         }
+        }
         if (!more) break;
         bid = nbid; m0 = m1; n0 = n1;
 #pragma unroll
@@ -513,7 +580,9 @@ static int launch_gemm(const GemmArgs& a, hipStream_t stream) {
     const int nwg = a.tiles_m * a.tiles_n;
     const dim3 grid(nwg < n_cu ? nwg : n_cu), block(512);
     // (profile name by epilogue: in the ViT block 0 = qkv, 1 = fc1 + GELU, 2 = projection and fc2, one launch each)
-    VLFM_TIMED(EPI == EPI_BIAS ? "gemm_f16_8pp_kernel<0>" : EPI == EPI_BIAS_GELU ? "gemm_f16_8pp_kernel<1>" : "gemm_f16_8pp_kernel<2>", stream);
+    // (3 = the Q-Former's cross-attention K / V projection, once per forward)
+    VLFM_TIMED(EPI == EPI_BIAS ? "gemm_f16_8pp_kernel<0>" : EPI == EPI_BIAS_GELU ? "gemm_f16_8pp_kernel<1>" :
+               EPI == EPI_ACCUM ? "gemm_f16_8pp_kernel<2>" : "gemm_f16_8pp_kernel<3>", stream);
     VLFM_KLAUNCH((gemm_f16_8pp_kernel<EPI>), grid, block, GEMM_LDS_P, stream, a);
     return check_launch("gemm_f16_8pp_kernel");
 }
@@ -536,6 +605,27 @@ extern "C" int vlfm_gemm_f16_nt(const void* d_x, const void* d_w, const void* d_
     if (epilogue == 0) return launch_gemm<EPI_BIAS>(a, (hipStream_t)stream);
     if (epilogue == 1) return launch_gemm<EPI_BIAS_GELU>(a, (hipStream_t)stream);
     return launch_gemm<EPI_ACCUM>(a, (hipStream_t)stream);
+}
+
+// out[block][m][64] (f32) = X[M][K] . (W1 + 2^-11 W2)[N_out][K]^T + bias[N_out] (f32), block = 64 output channels: the two-piece
+// split-precision projection in ONE pass (EPI_PAIR_F32).  d_w_pair is [2 N_out][K] f16: per block its 64 rows of W1, then its 64
+// rows of W2.  K % 64 == 0, N_out % 64 == 0; M tails and an odd number of blocks (a half-filled last tile) are handled.
+extern "C" int vlfm_gemm_f16_pair_f32_nt(const void* d_x, const void* d_w_pair, const void* d_bias_f32, void* d_out, int m, int n_out,
+                                         int k, void* stream) {
+    if (m == 0 || n_out == 0) return VLFM_OK;
+    if (!d_x || !d_w_pair || !d_out || m < 0 || n_out < 0 || k <= 0 || (k % GK) != 0 || (n_out % 64) != 0)
+        return fail(VLFM_ERR_INVALID, "gemm_f16_pair_f32_nt: K and N_out must be multiples of 64");
+    if ((size_t)m * (size_t)k * 2 >= (1ull << 32) || (size_t)n_out * (size_t)k * 4 >= (1ull << 32))
+        return fail(VLFM_ERR_INVALID, "gemm_f16_pair_f32_nt: an operand of 4 GB or more (32-bit byte offsets inside an operand)");
+    GemmArgs a;
+    a.x = (const _Float16*)d_x; a.w = (const _Float16*)d_w_pair;
+    a.bias = (const _Float16*)d_bias_f32;       // f32 values: see stage_bias()
+    a.c = (_Float16*)d_out;                     // f32, block-major: the epilogue casts it back
+    a.M = m; a.N = 2 * n_out; a.K = k;
+    a.tiles_m = (m + GB - 1) / GB; a.tiles_n = (a.N + GB - 1) / GB;
+    a.group_m = 4;
+    a.split_ragged = 1;
+    return launch_gemm<EPI_PAIR_F32>(a, (hipStream_t)stream);
 }
 
 // The tile order of the 8-phase kernels, evaluated on the HOST (tests/test_gemm_tile_order_cpu.py: a bijection for every shape, the

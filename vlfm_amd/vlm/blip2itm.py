@@ -285,10 +285,19 @@ class _BertAttention(nn.Module):
         return o[..., :hid], o[..., hid:]
 
     def forward(self, x: torch.Tensor, kv: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
-                kv_proj: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
-        """``kv_proj`` = (key(kv), value(kv)) computed by the caller (all cross-attention layers in one GEMM set)."""
+                kv_proj: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, kv_blocks=None) -> torch.Tensor:
+        """``kv_proj`` = (key(kv), value(kv)) computed by the caller (all cross-attention layers in one GEMM set).
+        ``kv_blocks`` = (blocks, tokens, k_block0, v_block0): the same projections block-major (ops.linear_pair_f32), attended by
+        csrc/qformer_attention.hip (heads of 64, f32)."""
         b, n, d = x.shape
         h = self.heads
+        if kv_blocks is not None:
+            from . import ops
+
+            blocks, tokens, k_block0, v_block0 = kv_blocks
+            q = _qlinear(x, self.query.weight, self.query.bias).contiguous()
+            a = ops.qformer_cross_attention(q, blocks, tokens, h, k_block0, v_block0, (d // h) ** -0.5)
+            return self.LayerNorm(_qlinear(a, self.dense.weight, self.dense.bias, residual=x))
         if kv_proj is not None:
             q = _qlinear(x, self.query.weight, self.query.bias).view(b, n, h, d // h).transpose(1, 2)
             k = kv_proj[0].reshape(b, -1, h, d // h).transpose(1, 2)
@@ -364,6 +373,10 @@ class Blip2ITCModel(nn.Module):
         self.split_kv = True  # Q-Former cross-attention K/V projections of f16 tokens via exact 3-way weight split
         self.split_kv_min_rows = 32 * 257
         self._kv_all = None
+        # the two-piece projection in ONE GEMM pass with a block-major f32 result, and the cross-attention kernel that streams it
+        # (ops.linear_pair_f32 / ops.qformer_cross_attention); needs split_kv, KV_SPLIT_PIECES == 2 and heads of 64
+        self.fused_cross_kv = True
+        self._kv_pair = None
 
     # ---- weights ---------------------------------------------------------------------------------------------
     def init_random(self, seed: int = 0) -> "Blip2ITCModel":
@@ -386,6 +399,7 @@ class Blip2ITCModel(nn.Module):
         parameters in place."""
         self._deferred_c = None
         self._kv_all = None
+        self._kv_pair = None
         for layer in self.q_layers:
             layer.attention._qkv_fused = None
             if layer.crossattention is not None:
@@ -585,12 +599,18 @@ class Blip2ITCModel(nn.Module):
                     and image_tokens.shape[0] * image_tokens.shape[1] >= self.split_kv_min_rows)
         enc = image_tokens if split_ok else image_tokens.to(self.q_layernorm.weight.dtype)
         h = self.q_layernorm(self.query_tokens).expand(enc.shape[0], -1, -1)
-        proj = self._project_all_kv(enc) if split_ok else None
+        fused = split_ok and self._fused_cross_ok(enc)
+        blocks = self._project_all_kv_blocks(enc) if fused else None
+        proj = self._project_all_kv(enc) if split_ok and not fused else None
         hid, at = self.cfg.q_hidden, 0
         for layer in self.q_layers:
             h = layer.attention(h)
             if layer.crossattention is not None:
-                if proj is not None:
+                if blocks is not None:
+                    # weight order [K_l | V_l] per layer, heads of 64 = one block each: K heads, then V heads
+                    h = layer.crossattention(h, kv_blocks=(blocks, enc.shape[1], at // 64, (at + hid) // 64))
+                    at += 2 * hid
+                elif proj is not None:
                     h = layer.crossattention(h, kv_proj=(proj[..., at:at + hid], proj[..., at + hid:at + 2 * hid]))
                     at += 2 * hid
                 else:
@@ -598,18 +618,49 @@ class Blip2ITCModel(nn.Module):
             h = layer.ffn_query(h)
         return h
 
-    def _project_all_kv(self, tokens16: torch.Tensor) -> torch.Tensor:
-        """key / value projections of EVERY cross-attention layer in one exact-split GEMM set ([B,257,1408] f16 ->
-        [B,257, layers * 2 * hidden] f32, layer-major [K_0 | V_0 | K_1 | V_1 ...]): the image tokens are the same for all
-        layers, and one wide GEMM runs closer to the MFMA peak than six narrow ones (_BertAttention._project_kv_f16 is
-        the per-layer form)."""
-        if self._kv_all is None or self._kv_all[0].device != tokens16.device:
+    def _fused_cross_ok(self, tokens16: torch.Tensor) -> bool:
+        """The geometry csrc/qformer_attention.hip and the pair epilogue of csrc/gemm_f16.hip take; everything else runs the
+        two-launch projection and the library attention."""
+        from . import ops
+
+        c = self.cfg
+        return (self.fused_cross_kv and KV_SPLIT_PIECES == 2 and not torch.is_grad_enabled()
+                and self.q_layernorm.weight.dtype == torch.float32
+                and c.q_hidden % c.q_heads == 0 and c.q_hidden // c.q_heads == ops.QFORMER_ATTENTION_HEAD
+                and c.num_query_tokens <= ops.QFORMER_ATTENTION_MAX_QUERIES
+                and 1 <= tokens16.shape[1] <= ops.QFORMER_ATTENTION_MAX_TOKENS and c.v_hidden % 64 == 0
+                and tokens16.shape[0] * tokens16.shape[1] * c.v_hidden * 2 < (1 << 32))
+
+    def _kv_all_pieces(self, device):
+        """(w1t, w2t, w3t, bias) of every cross-attention layer's [K_l | V_l] weights (transposed views [K, N]), built once per
+        device; the interleaved two-piece operand of the one-pass projection lives beside it."""
+        if self._kv_all is None or self._kv_all[0].device != device:
             cross = [l.crossattention for l in self.q_layers if l.crossattention is not None]
             w = torch.cat([torch.cat([c.key.weight, c.value.weight]) for c in cross])
             bias = torch.cat([torch.cat([c.key.bias, c.value.bias]) for c in cross]).detach().float()
             w1, w2, w3 = _exact_split3(w)
             self._kv_all = (w1.t(), w2.t(), w3.t(), bias)
-        o = _split_gemm(tokens16.reshape(-1, tokens16.shape[-1]), self._kv_all[:3], self._kv_all[3])
+            self._kv_pair = None
+        return self._kv_all
+
+    def _project_all_kv_blocks(self, tokens16: torch.Tensor) -> torch.Tensor:
+        """``_project_all_kv`` in ONE GEMM pass (two pieces): [B,T,1408] f16 -> [layers * 2 * hidden / 64, B * T, 64] f32, block-major
+        -- block 24 l + h is head h of K_l, block 24 l + 12 + h head h of V_l at the real sizes; one (image, head) is T x 256 B
+        contiguous, which is what csrc/qformer_attention.hip streams."""
+        from . import ops
+
+        w1t, w2t, _, bias = self._kv_all_pieces(tokens16.device)
+        if self._kv_pair is None:
+            self._kv_pair = (ops.interleave_pair_weights(w1t.t(), w2t.t()), bias.contiguous())
+        return ops.linear_pair_f32(tokens16.reshape(-1, tokens16.shape[-1]), *self._kv_pair)
+
+    def _project_all_kv(self, tokens16: torch.Tensor) -> torch.Tensor:
+        """key / value projections of EVERY cross-attention layer in one exact-split GEMM set ([B,257,1408] f16 ->
+        [B,257, layers * 2 * hidden] f32, layer-major [K_0 | V_0 | K_1 | V_1 ...]): the image tokens are the same for all
+        layers, and one wide GEMM runs closer to the MFMA peak than six narrow ones (_BertAttention._project_kv_f16 is
+        the per-layer form)."""
+        pieces = self._kv_all_pieces(tokens16.device)
+        o = _split_gemm(tokens16.reshape(-1, tokens16.shape[-1]), pieces[:3], pieces[3])
         return o.view(*tokens16.shape[:-1], -1)
 
     def text_feature(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:

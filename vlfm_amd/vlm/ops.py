@@ -325,6 +325,56 @@ def linear_gelu(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> to
     return linear_f16(x, weight, bias, "bias_gelu")
 
 
+def interleave_pair_weights(w1: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
+    """The weight operand of ``linear_pair_f32``: [2 N, K] f16 holding, for every block of 64 output channels, its 64 rows of ``w1``
+    and then its 64 rows of ``w2`` (both [N, K] f16, N % 64 == 0)."""
+    assert w1.shape == w2.shape and w1.dtype == w2.dtype == torch.float16 and w1.dim() == 2 and w1.shape[0] % 64 == 0
+    n, k = w1.shape
+    return torch.stack([w1.reshape(n // 64, 64, k), w2.reshape(n // 64, 64, k)], dim=1).reshape(2 * n, k).contiguous()
+
+
+def linear_pair_f32(x: torch.Tensor, w_pair: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x @ (W1 + 2^-11 W2).T + bias in f32 from f16 operands, ONE pass of csrc/gemm_f16.hip (epilogue EPI_PAIR_F32): the two-piece
+    split-precision projection with the f32 result written once, ``fl(acc1 + fl(bias + 2^-11 acc2))`` as the two addmm calls it
+    replaces compute it.  x [M, K] f16, ``w_pair`` from ``interleave_pair_weights``, bias [N] f32.  Returns the result BLOCK-MAJOR:
+    [N / 64, M, 64] f32, block = 64 consecutive output channels (``out[c // 64, m, c % 64]`` is element (m, c))."""
+    assert x.is_cuda and x.dtype == torch.float16 and x.is_contiguous() and x.dim() == 2
+    assert w_pair.dtype == torch.float16 and w_pair.is_contiguous() and w_pair.shape[1] == x.shape[1] and w_pair.shape[0] % 128 == 0
+    M, K = x.shape
+    N = w_pair.shape[0] // 2
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N)
+    if out is None:
+        out = torch.empty((N // 64, M, 64), dtype=torch.float32, device=x.device)
+    else:
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (N // 64, M, 64) and out.device == x.device
+    _lib.check(_lib.lib().vlfm_gemm_f16_pair_f32_nt(x.data_ptr(), w_pair.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                                    out.data_ptr(), M, N, K, _stream()), "gemm_f16_pair_f32_nt")
+    return out
+
+
+QFORMER_ATTENTION_MAX_TOKENS, QFORMER_ATTENTION_MAX_QUERIES, QFORMER_ATTENTION_HEAD = 257, 32, 64
+
+
+def qformer_cross_attention(q: torch.Tensor, kv_blocks: torch.Tensor, tokens: int, heads: int, k_block0: int, v_block0: int,
+                            scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax(q k^T * scale) v in f32 for the Q-Former's cross-attention (csrc/qformer_attention.hip): ``q`` [B, Q, heads * 64] f32,
+    K / V read from ``kv_blocks`` [blocks, M_total, 64] (``linear_pair_f32``'s result; image b is rows [b tokens, (b + 1) tokens),
+    head h of K is block ``k_block0 + h``, of V ``v_block0 + h``).  Returns [B, Q, heads * 64] f32."""
+    assert q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.dim() == 3 and q.shape[2] == heads * 64
+    assert kv_blocks.dtype == torch.float32 and kv_blocks.is_contiguous() and kv_blocks.dim() == 3 and kv_blocks.shape[2] == 64
+    assert kv_blocks.device == q.device and max(k_block0, v_block0) + heads <= kv_blocks.shape[0] and min(k_block0, v_block0) >= 0
+    B, Q, _ = q.shape
+    if out is None:
+        out = torch.empty_like(q)
+    else:
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[1:] == q.shape[1:] and out.shape[0] >= B
+    _lib.check(_lib.lib().vlfm_qformer_cross_attention_f32(q.data_ptr(), kv_blocks.data_ptr(), out.data_ptr(), B, tokens, Q, heads,
+                                                           k_block0, v_block0, kv_blocks.shape[1], float(scale), _stream()),
+               "qformer_cross_attention_f32")
+    return out
+
+
 VIT_ATTENTION_TOKENS, VIT_ATTENTION_HEADS = 257, (88,)
 
 
