@@ -722,6 +722,69 @@ int vlfm_jpeg_encode_batched(const uint8_t* d_in, int n, int H, int W, int rgb_o
                              uint8_t* d_out, size_t capacity, uint32_t* d_lengths, void* d_scratch, size_t scratch_bytes,
                              void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * JPEG decoder (ABI 14): n baseline 4:2:0 files of one H x W to uint8 [n][H][W][3] device frames, bit-equal to libjpeg-turbo
+ * as Pillow drives it (Image.open(...).convert("RGB")) for files an encoder made from 8-bit pixels (csrc/jpeg_decode.hip;
+ * tests/jpeg_dec_ref.py is the NumPy form).  Accepted: SOF0, 8-bit samples, three components sampled 2x2, 1x1, 1x1 with any
+ * ids and table selectors, one interleaved scan, 8-bit quantisation tables, the file's own Huffman tables (Annex K's or
+ * optimised), any restart interval; APPn (but Adobe APP14) and COM segments and 0xFF fill bytes are skipped.
+ *
+ * vlfm_jpeg_parse_host: walks the markers of one file up to the scan.  Fills *frame (table_set = 0) and *set: per component
+ *   (Y, Cb, Cr) the quantisation table in natural order and the DC and AC Huffman tables in canonical-compare form: a
+ *   left-aligned 16-bit window x has code length 1 + #{l : x >= limit[l]} (17: no such code), and its symbol is
+ *   vals[(x >> (16 - len)) - delta[len - 1]].  Returns VLFM_OK, VLFM_ERR_INVALID for a null argument, or a positive reason
+ *   code for a file the decoder does not take; vlfm_jpeg_parse_reason gives its text.  A prefix of a file that ends behind
+ *   SOS parses like the file (this is how the header of the device form below is read).
+ * vlfm_jpeg_decode_chunk_bytes: the bytes of a file one workgroup of the marker scan takes; chunk c is file bytes
+ *   [c * chunk, (c + 1) * chunk).
+ * vlfm_jpeg_decode_scratch_bytes: the scratch the call below needs; 0 for invalid sizes.  Its first
+ *   n * ceil(H/16) * ceil(W/16) * 768 bytes are, after the call, the coefficients of the scan in the encoder's layout: 64 int16
+ *   per block in zigzag order, blocks in scan order (MCUs row-major; Y00 Y01 Y10 Y11 Cb Cr), absolute DC values.
+ * vlfm_jpeg_decode_batched: file i is the d_lengths[i] bytes (device int32) at d_files + d_offsets[i] (device int64), or,
+ *   with d_offsets null, at d_files + i * stride; no byte outside [d_files, d_files + files_bytes) or, without offsets, outside
+ *   the file's stride is read whatever the lengths say, and at most max_file_bytes of a file.  d_frames [n] and d_sets
+ *   [n_sets] are device copies of what vlfm_jpeg_parse_host filled, table_set indexing d_sets.  d_header, if not null, is a
+ *   device copy of the header_bytes every file must start with (compared on the device).  max_segments >= the largest
+ *   ceil(MCUs / restart_interval) of the batch (1 for files without restart markers).  rgb_order 0 writes R to slot 2 of a
+ *   pixel (cv2.imdecode's BGR, the convention of vlfm_jpeg_roundtrip_batched), 1 to slot 0.  d_status int32 [n]: 0 for a
+ *   good frame, else the largest of the VLFM_JPEG_BAD_* codes the stream ran into; such a frame's pixels are unspecified, every other
+ *   frame is complete, and nothing outside d_out, d_status and d_scratch is written: every index formed from stream bits is
+ *   range-checked or clamped before use.  Surplus bits behind a segment's last MCU are accepted.  Six kernel launches and
+ *   one memset on `stream`, no synchronisation; every grid is sized from n, the MCU count, max_segments and max_file_bytes.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct vlfm_jpeg_huff {
+    uint32_t limit[16];
+    int32_t delta[16];
+    uint8_t vals[256];
+} vlfm_jpeg_huff;                                   /* 384 bytes */
+typedef struct vlfm_jpeg_table_set {
+    uint16_t quant[3][64];
+    vlfm_jpeg_huff dc[3];
+    vlfm_jpeg_huff ac[3];
+} vlfm_jpeg_table_set;                              /* 2688 bytes */
+typedef struct vlfm_jpeg_frame {
+    int32_t height, width, restart_interval, scan_offset, table_set, reserved[3];
+} vlfm_jpeg_frame;                                  /* 32 bytes */
+enum {
+    VLFM_JPEG_BAD_HEADER = 1,      /* device form: the file does not start with the given header */
+    VLFM_JPEG_BAD_LENGTH = 2,      /* the file ends at or before the first byte of its scan */
+    VLFM_JPEG_BAD_EOI = 3,         /* no EOI behind the scan (or another marker first) */
+    VLFM_JPEG_BAD_RESTART = 4,     /* RSTn out of order, or not ceil(MCUs / Ri) - 1 of them */
+    VLFM_JPEG_BAD_CODE = 5,        /* a bit pattern that is no code of the table in force */
+    VLFM_JPEG_BAD_SIZE = 6,        /* a DC size above 11 or an AC size above 10 */
+    VLFM_JPEG_BAD_INDEX = 7,       /* a run that passes zigzag index 63 */
+    VLFM_JPEG_BAD_BITS = 8         /* a segment out of bits before its MCUs are complete */
+};
+int vlfm_jpeg_parse_host(const uint8_t* h_file, size_t len, vlfm_jpeg_frame* frame, vlfm_jpeg_table_set* set);
+const char* vlfm_jpeg_parse_reason(int code);
+size_t vlfm_jpeg_decode_chunk_bytes(void);
+size_t vlfm_jpeg_decode_scratch_bytes(int n, int H, int W, size_t max_file_bytes);
+int vlfm_jpeg_decode_batched(const uint8_t* d_files, size_t files_bytes, const int64_t* d_offsets, size_t stride,
+                             const int32_t* d_lengths, int n, int H, int W, const vlfm_jpeg_frame* d_frames,
+                             const vlfm_jpeg_table_set* d_sets, int n_sets, const uint8_t* d_header, int header_bytes,
+                             int max_segments, size_t max_file_bytes, int rgb_order, uint8_t* d_out, int32_t* d_status,
+                             void* d_scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

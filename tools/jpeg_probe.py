@@ -7,7 +7,11 @@ per configuration.  Usage: python tools/jpeg_probe.py [--reps 30] [--step [--no-
 
 --encode times the encoder instead (transport.jpeg_encode_batch, csrc/jpeg_entropy.hip): natural 640x480 and 1280x720 frames
 and rendered 1000x1000 map frames of a stepped harness, each alternated call by call with the path it replaces -- download
-the raw frames, encode them with Pillow on 16 threads."""
+the raw frames, encode them with Pillow on 16 threads.
+
+--decode times the decoder (transport.jpeg_decode_batch, csrc/jpeg_decode.hip) in its device form on files Pillow wrote
+without restart markers and with one restart interval per MCU row, and on this package's files of rendered 1000x1000 maps,
+each alternated call by call with the path it replaces: Pillow decode on 16 threads plus the upload of the raw frames."""
 import argparse
 import json
 import os
@@ -145,6 +149,104 @@ def encode_all(device, reps):
                                         reps, pool)), flush=True)
 
 
+def decode(device, what, files, reps, pool):
+    """Median device time of jpeg_decode_batch (device form: the files lie in a [n, capacity] device tensor and share their
+    header) alternated with the host path: Pillow decode on the thread pool + H2D of the raw frames (wall time).  Also the
+    wall time of the host form (parse, one upload, decode)."""
+    import io
+
+    import numpy as np
+    import torch
+    from PIL import Image
+
+    from vlfm_amd.vlm.transport import jpeg_decode_batch, jpeg_decode_scratch, jpeg_parse
+
+    n = len(files)
+    info = jpeg_parse(files[0])
+    h, w, header = info["height"], info["width"], files[0][:info["scan_offset"]]
+    assert all(f[:len(header)] == header for f in files)
+    cap = (max(map(len, files)) + 15) & ~15
+    host = np.zeros((n, cap), np.uint8)
+    for i, f in enumerate(files):
+        host[i, :len(f)] = np.frombuffer(f, np.uint8)
+    d_files = torch.from_numpy(host).to(device)
+    d_len = torch.tensor([len(f) for f in files], dtype=torch.int32, device=device)
+    out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=device)
+    status = torch.empty(n, dtype=torch.int32, device=device)
+    scratch = jpeg_decode_scratch(n, h, w, cap, device)
+
+    def host_one(f):
+        return np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))
+
+    def host_path():
+        t0 = time.perf_counter()
+        frames = torch.from_numpy(np.stack(list(pool.map(host_one, files)))).to(device)
+        torch.cuda.synchronize()
+        return 1000 * (time.perf_counter() - t0), frames
+
+    def host_form():
+        t0 = time.perf_counter()
+        jpeg_decode_batch(files, channel_order="rgb", out=out, status=status, scratch=scratch, device=device)
+        torch.cuda.synchronize()
+        return 1000 * (time.perf_counter() - t0)
+
+    for _ in range(3):
+        jpeg_decode_batch(d_files, d_len, header=header, channel_order="rgb", out=out, status=status, scratch=scratch)
+    host_path()
+    host_form()
+    torch.cuda.synchronize()
+    ms, host_ms, form_ms = [], [], []
+    for r in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        jpeg_decode_batch(d_files, d_len, header=header, channel_order="rgb", out=out, status=status, scratch=scratch)
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+        if r < max(3, reps // 5):   # (the host paths are slow: a few alternations give their medians)
+            host_ms.append(host_path()[0])
+            form_ms.append(host_form())
+    jpeg_decode_batch(d_files, d_len, header=header, channel_order="rgb", out=out, status=status, scratch=scratch)
+    same = bool(torch.equal(out, host_path()[1])) and not bool(status.any())
+    med, host_med = float(np.median(ms)), float(np.median(host_ms))
+    return {"what": what, "n": n, "H": h, "W": w, "restart_interval": info["restart_interval"], "median_ms": round(med, 4),
+            "min_ms": round(min(ms), 4), "us_per_frame": round(1000 * med / n, 2), "file_bytes": int(sum(map(len, files))),
+            "host_pillow16_upload_ms": round(host_med, 2), "speedup": round(host_med / med, 2),
+            "host_form_wall_ms": round(float(np.median(form_ms)), 2), "pixels_equal_pillow": same}
+
+
+def decode_all(device, reps):
+    import io
+    from concurrent.futures import ThreadPoolExecutor
+
+    import torch
+    from PIL import Image
+
+    from vlfm_amd.harness import BatchedEpisodes
+
+    def pillow_files(x, **kw):
+        out = []
+        for f in x:
+            buf = io.BytesIO()
+            Image.fromarray(f).save(buf, format="JPEG", quality=90, subsampling="4:2:0", **kw)
+            out.append(buf.getvalue())
+        return out
+
+    with ThreadPoolExecutor(16) as pool:
+        for n, h, w in [(1, 480, 640), (8, 480, 640), (64, 480, 640), (256, 480, 640), (16, 720, 1280)]:
+            x = _natural_frames(n, h, w, n * h)
+            print(json.dumps(decode(device, "jpeg_decode_batch q90 natural", pillow_files(x), reps, pool)), flush=True)
+            if h == 480:
+                print(json.dumps(decode(device, "jpeg_decode_batch q90 natural, Ri = one MCU row",
+                                        pillow_files(x, restart_marker_rows=1), reps, pool)), flush=True)
+        sim = BatchedEpisodes(64, device=device, use_blip2=False, world="rooms", render_trajectories=True)
+        for _ in range(40):
+            sim.step()
+        torch.cuda.synchronize(device)
+        for name, files in sim.render_jpeg().items():
+            print(json.dumps(decode(device, f"jpeg_decode_batch q90 rendered {name}", files, reps, pool)), flush=True)
+
+
 def step_rate(device, envs, steps, rounds, preroll, use_blip2):
     import torch
 
@@ -194,6 +296,7 @@ def main():
     ap.add_argument("--step", action="store_true", help="also time the BatchedEpisodes step, switch off and on")
     ap.add_argument("--no-blip2", action="store_true", help="--step with stub cosines instead of the BLIP-2 forward")
     ap.add_argument("--encode", action="store_true", help="time the encoder (and the host path it replaces) instead")
+    ap.add_argument("--decode", action="store_true", help="time the decoder (and the host path it replaces) instead")
     args = ap.parse_args()
     import torch
 
@@ -205,6 +308,9 @@ def main():
     torch.set_num_threads(1)
     if args.encode:
         encode_all(device, args.reps)
+        return
+    if args.decode:
+        decode_all(device, args.reps)
         return
     for n, h, w in [(1, 480, 640), (8, 480, 640), (64, 480, 640), (256, 480, 640), (16, 720, 1280), (128, 720, 1280)]:
         print(json.dumps(roundtrip(device, n, h, w, args.reps)), flush=True)

@@ -316,6 +316,64 @@ __global__ void __launch_bounds__(THREADS) jpeg_code_kernel(const uint8_t* __res
     }
 }
 
+// The decoder's second half (jpeg_decode.hip calls it): the coefficient buffer of a decoded scan -- the layout
+// jpeg_code_kernel<true, *> writes -- times the frame's own quantisation tables (jddctmgr.c: coef * quantval), through the
+// same IDCT columns and rows, to the decoded planes.  Same grid and thread roles as jpeg_code_kernel.
+__global__ void __launch_bounds__(THREADS) jpeg_idct_kernel(const int16_t* __restrict__ coef,
+                                                            const vlfm_jpeg_frame* __restrict__ frames,
+                                                            const vlfm_jpeg_table_set* __restrict__ sets, int n_sets,
+                                                            Geometry g, uint8_t* __restrict__ planes) {
+    __shared__ int cblk[BLOCKS * CBLOCK];
+    const int t = threadIdx.x;
+    const int per_frame = g.mh * g.tiles_x;
+    const int f = blockIdx.x / per_frame;
+    const int rem = blockIdx.x - f * per_frame;
+    const int m = rem / g.tiles_x;
+    const int x0 = (rem - m * g.tiles_x) * TILE_W;
+    const int b = t >> 3, r = t & 7;
+    const int u = b < 16 ? (b & 7) >> 1 : (b - 16) & 3;            // MCU of the tile
+    const int mx = x0 / 16 + u;
+    const int k = b < 16 ? (b >> 3) * 2 + (b & 1) : 4 + ((b - 16) >> 2);
+    const int set = min(max(frames[f].table_set, 0), n_sets - 1);
+    const uint16_t* q = sets[set].quant[b < 16 ? 0 : k - 3];
+    int* cb = cblk + b * CBLOCK;
+    // zigzag positions 8r .. 8r+7 of block b: one 16-byte load, dequantised into their natural places
+    uint4 w = make_uint4(0, 0, 0, 0);
+    if (mx < g.mw)
+        w = *reinterpret_cast<const uint4*>(coef + ((((size_t)f * g.mh + m) * g.mw + mx) * 6 + k) * 64 + 8 * r);
+    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int nat = kNaturalOrder[8 * r + j];
+        const int c = (int)(int16_t)(ww[j >> 1] >> (16 * (j & 1)));
+        cb[(nat >> 3) * CSTRIDE + (nat & 7)] = c * (int)q[nat];
+    }
+    __syncthreads();
+    int v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = cb[i * CSTRIDE + r];
+    idct8<CONST_BITS - PASS1_BITS>(v);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) cb[i * CSTRIDE + r] = v[i];
+    __syncthreads();
+    // row r of block b, as in jpeg_code_kernel: IDCT pass 2, range limit, 8 samples to the decoded planes
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = cb[r * CSTRIDE + i];
+    idct8<CONST_BITS + PASS1_BITS + 3>(v);
+    uint2 o;
+    o.x = range_limit(v[0]) | range_limit(v[1]) << 8 | range_limit(v[2]) << 16 | range_limit(v[3]) << 24;
+    o.y = range_limit(v[4]) | range_limit(v[5]) << 8 | range_limit(v[6]) << 16 | range_limit(v[7]) << 24;
+    uint8_t* fs = planes + (size_t)f * g.frame_scratch();
+    if (b < 16) {
+        const int col = x0 + (b & 7) * 8, ys = 16 * g.mw;
+        if (col < ys) *reinterpret_cast<uint2*>(fs + (size_t)(16 * m + (b >> 3) * 8 + r) * ys + col) = o;
+    } else {
+        const int col = x0 / 2 + u * 8, cs = 8 * g.mw;
+        uint8_t* plane = fs + (size_t)256 * g.mh * g.mw + (size_t)(k - 4) * 64 * g.mh * g.mw;
+        if (col < cs) *reinterpret_cast<uint2*>(plane + (size_t)(8 * m + r) * cs + col) = o;
+    }
+}
+
 // Ten chroma samples, columns j0-1 .. j0+8 clamped to the real width [0, cw) (the clamp is how h2v2_fancy_upsample's
 // first and last outputs treat the edge: the missing neighbour is the sample itself).
 __device__ __forceinline__ void load10(const uint8_t* row, int j0, int cw, int* v) {
@@ -342,6 +400,8 @@ __device__ __forceinline__ int upsample_px(const int* s, const int* raw, int p, 
     return (p & 1) ? (3 * s[t] + s[t + 1] + 7) >> 4 : (3 * s[t] + s[t - 1] + 8) >> 4;
 }
 
+// kRgb = false: slot 0 = B, 2 = R (the round trip's order, what cv2.imdecode returns); true: slot 0 = R.
+template <bool kRgb>
 __global__ void __launch_bounds__(256) jpeg_upsample_kernel(const uint8_t* __restrict__ scratch, Geometry g,
                                                             uint8_t* __restrict__ out) {
     const int runs = (g.W + 15) >> 4;
@@ -381,10 +441,10 @@ __global__ void __launch_bounds__(256) jpeg_upsample_kernel(const uint8_t* __res
         const int R = min(max(Y + ((fix16(1.402) * xcr + ONE_HALF) >> 16), 0), 255);
         const int B = min(max(Y + ((fix16(1.772) * xcb + ONE_HALF) >> 16), 0), 255);
         const int G = min(max(Y + ((-fix16(0.34414) * xcb + ONE_HALF - fix16(0.71414) * xcr) >> 16), 0), 255);
-        const int e = 3 * p;   // slot 0 = B, 1 = G, 2 = R
-        ow[e >> 2] |= (uint32_t)B << (8 * (e & 3));
+        const int e = 3 * p;   // slot 0 = B, 1 = G, 2 = R (kRgb: 0 = R, 2 = B)
+        ow[e >> 2] |= (uint32_t)(kRgb ? R : B) << (8 * (e & 3));
         ow[(e + 1) >> 2] |= (uint32_t)G << (8 * ((e + 1) & 3));
-        ow[(e + 2) >> 2] |= (uint32_t)R << (8 * ((e + 2) & 3));
+        ow[(e + 2) >> 2] |= (uint32_t)(kRgb ? B : R) << (8 * ((e + 2) & 3));
     }
     uint8_t* dst = out + ((size_t)f * g.H + y) * 3 * g.W + 3 * x0;
     if (g.vec_out && x0 + 16 <= g.W) {
@@ -421,6 +481,34 @@ int launch_coefficients(const uint8_t* d_in, int n, int H, int W, int rgb_order,
                      reinterpret_cast<uint8_t*>(d_coef));
     }
     return check_launch("jpeg_coef_kernel");
+}
+
+// The decoder's pixel half (jpeg_decode.hip calls it): coefficients -> decoded planes -> frames.
+int launch_pixels(const int16_t* d_coef, const vlfm_jpeg_frame* d_frames, const vlfm_jpeg_table_set* d_sets, int n_sets, int n,
+                  int H, int W, int rgb_order, uint8_t* d_planes, uint8_t* d_out, hipStream_t st) {
+    Geometry g;
+    g.n = n; g.H = H; g.W = W;
+    g.mh = (H + 15) / 16; g.mw = (W + 15) / 16;
+    g.tiles_x = (g.mw + TILE_MCUS - 1) / TILE_MCUS;
+    g.ch = (H + 1) / 2; g.cw = (W + 1) / 2;
+    g.vec_in = 0;
+    g.vec_out = (3 * (size_t)W) % 16 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0;
+    const size_t code_blocks = (size_t)n * g.mh * g.tiles_x;
+    const size_t up_blocks = ((size_t)n * H * ((W + 15) / 16) + 255) / 256;
+    if (code_blocks > 0x7fffffff || up_blocks > 0x7fffffff)
+        return fail(VLFM_ERR_INVALID, "jpeg_decode_batched: batch too large for one launch");
+    {
+        VLFM_TIMED("jpeg_idct_kernel", st);
+        VLFM_KLAUNCH(jpeg_idct_kernel, dim3((unsigned)code_blocks), dim3(THREADS), 0, st, d_coef, d_frames, d_sets, n_sets, g,
+                     d_planes);
+    }
+    if (int rc = check_launch("jpeg_idct_kernel")) return rc;
+    {
+        VLFM_TIMED("jpeg_upsample_kernel", st);
+        auto kernel = rgb_order ? jpeg_upsample_kernel<true> : jpeg_upsample_kernel<false>;
+        VLFM_KLAUNCH(kernel, dim3((unsigned)up_blocks), dim3(256), 0, st, d_planes, g, d_out);
+    }
+    return check_launch("jpeg_upsample_kernel");
 }
 
 }  // namespace jpeg
@@ -503,7 +591,8 @@ extern "C" int vlfm_jpeg_roundtrip_batched(const uint8_t* d_in, uint8_t* d_out, 
     if (int rc = check_launch("jpeg_code_kernel")) return rc;
     {
         VLFM_TIMED("jpeg_upsample_kernel", st);
-        VLFM_KLAUNCH(jpeg_upsample_kernel, dim3((unsigned)up_blocks), dim3(256), 0, st, scratch, g, d_out);
+        auto kernel = jpeg_upsample_kernel<false>;
+        VLFM_KLAUNCH(kernel, dim3((unsigned)up_blocks), dim3(256), 0, st, scratch, g, d_out);
     }
     return check_launch("jpeg_upsample_kernel");
 }

@@ -51,3 +51,17 @@ def split_mjpeg(data: bytes) -> List[bytes]:
         out.append(data[pos:end + 2])
         pos = end + 2
     return out
+
+
+def read_mjpeg(path, device=None, batch: int = 64, channel_order: str = "rgb"):
+    """The frames of a raw Motion-JPEG file, decoded on the GPU: a generator of ``[k,H,W,3]`` uint8 device tensors, k <=
+    ``batch`` (``transport.jpeg_decode_batch_checked`` over ``split_mjpeg``).  Raises ValueError if the frames of one batch
+    differ in size or a stream is damaged."""
+    from ..vlm.transport import jpeg_decode_batch_checked
+
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    with open(os.fspath(path), "rb") as f:
+        files = split_mjpeg(f.read())
+    for i in range(0, len(files), batch):
+        yield jpeg_decode_batch_checked(files[i:i + batch], channel_order=channel_order, device=device)

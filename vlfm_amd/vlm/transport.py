@@ -243,3 +243,217 @@ def image_to_str_batch(images_u8, quality: int = 90):
     import base64
 
     return [base64.b64encode(b).decode() for b in jpeg_encode_batch_bytes(images_u8, quality, "bgr")]
+
+
+# ---------------------------------------------------------------------------------------------------------------- decoder
+JPEG_FRAME_DTYPE = np.dtype([("height", "<i4"), ("width", "<i4"), ("restart_interval", "<i4"), ("scan_offset", "<i4"),
+                             ("table_set", "<i4"), ("reserved", "<i4", (3,))])
+JPEG_HUFF_DTYPE = np.dtype([("limit", "<u4", (16,)), ("delta", "<i4", (16,)), ("vals", "u1", (256,))])
+JPEG_TABLE_SET_DTYPE = np.dtype([("quant", "<u2", (3, 64)), ("dc", JPEG_HUFF_DTYPE, (3,)), ("ac", JPEG_HUFF_DTYPE, (3,))])
+assert JPEG_FRAME_DTYPE.itemsize == 32 and JPEG_TABLE_SET_DTYPE.itemsize == 2688
+JPEG_STATUS = {1: "the file does not start with the given header", 2: "the file ends before its scan starts",
+               3: "no EOI behind the scan", 4: "restart markers out of order or miscounted", 5: "invalid Huffman code",
+               6: "coefficient size out of range", 7: "zigzag index past 63", 8: "a segment ran out of bits"}
+
+
+def _jpeg_parse_raw(data, what: str):
+    import ctypes
+
+    from .. import _lib
+
+    buf = np.frombuffer(data, np.uint8)
+    frame, tset = np.zeros(1, JPEG_FRAME_DTYPE), np.zeros(1, JPEG_TABLE_SET_DTYPE)
+    keep = np.ascontiguousarray(buf) if buf.size else np.zeros(1, np.uint8)
+    rc = _lib.lib().vlfm_jpeg_parse_host(keep.ctypes.data, ctypes.c_size_t(buf.size), frame.ctypes.data, tset.ctypes.data)
+    if rc > 0:
+        raise ValueError(f"{what}: {_lib.lib().vlfm_jpeg_parse_reason(rc).decode()}")
+    _lib.check(rc, "jpeg_parse_host")
+    return frame, tset
+
+
+def jpeg_parse(file) -> dict:
+    """What stands in front of the scan of a baseline 4:2:0 JPEG file (bytes-like): ``height``, ``width``,
+    ``restart_interval`` (0: none), ``scan_offset`` (the scan's first byte), ``quant`` ([3,64] uint16, natural order, per
+    component) and ``dc`` / ``ac`` (per component the Huffman table in the form the kernel reads: ``limit``, ``delta``,
+    ``vals``).  Raises ValueError with the reason for a file ``jpeg_decode_batch`` does not take."""
+    frame, tset = _jpeg_parse_raw(file, "jpeg_parse")
+    out = {k: int(frame[k][0]) for k in ("height", "width", "restart_interval", "scan_offset")}
+    out["quant"] = tset["quant"][0].copy()
+    for kind in ("dc", "ac"):
+        out[kind] = [{k: tset[kind][0][c][k].copy() for k in ("limit", "delta", "vals")} for c in range(3)]
+    return out
+
+
+def jpeg_decode_scratch(n: int, height: int, width: int, max_file_bytes: int, device) -> "torch.Tensor":
+    """A device buffer that ``jpeg_decode_batch(..., scratch=)`` accepts for n files of height x width, none longer than
+    ``max_file_bytes`` (device form: the capacity of a slot).  After a call its first n * MCUs * 768 bytes hold the scan's
+    coefficients in the encoder's layout (int16 [n, 6 * MCUs, 64], zigzag order, absolute DC values)."""
+    import torch
+
+    from .. import _lib
+
+    return torch.empty(int(_lib.lib().vlfm_jpeg_decode_scratch_bytes(n, height, width, max_file_bytes)), dtype=torch.uint8,
+                       device=device)
+
+
+def jpeg_decode_batch(files, lengths=None, header=None, channel_order: str = "bgr", out=None, status=None, scratch=None,
+                      device=None):
+    """Baseline 4:2:0 JPEG files of one size to ``(out [n,H,W,3] uint8, status [n] int32)``, both on the device; every frame
+    whose status is 0 is bit-equal to ``PIL.Image.open(file).convert("RGB")`` (csrc/jpeg_decode.hip), in slot order B, G, R for
+    ``channel_order="bgr"`` (what ``cv2.imdecode`` returns, the convention of ``jpeg_roundtrip_batch``) or R, G, B for ``"rgb"``.
+
+    Host form: ``files`` is a sequence of bytes-like objects; they are parsed on the host (ValueError naming the frame and the
+    reason for a file the decoder does not take, or whose size differs from the first one's) and uploaded in one copy to
+    ``device`` (default: the current one).  Every file may have its own tables and restart interval.
+
+    Device form: ``files`` is the ``[n, capacity] uint8`` device tensor and ``lengths`` the ``int32 [n]`` device tensor that
+    ``jpeg_encode_batch`` returns, and ``header`` the bytes every file starts with (``jpeg_header(q, H, W)`` for this
+    package's files).  The device compares them; no byte of the files crosses to the host.
+
+    A non-zero status (``JPEG_STATUS``) marks a frame whose stream is damaged: its pixels are unspecified, the other frames
+    are complete.  Runs on the current stream, with no synchronisation.  ``out``, ``status`` and ``scratch``
+    (``jpeg_decode_scratch``) may be passed in.  Raises ValueError for a wrong dtype, shape, device or contiguity, buffers that
+    overlap, an unknown channel order or an empty batch."""
+    import torch
+
+    from .. import _lib
+    from .ops import _stream
+
+    if channel_order not in ("bgr", "rgb"):
+        raise ValueError(f"channel_order must be 'bgr' or 'rgb', got {channel_order!r}")
+    device_form = isinstance(files, torch.Tensor)
+    if device_form:
+        x = files
+        if x.dtype != torch.uint8 or x.dim() != 2 or x.device.type != "cuda" or not x.is_contiguous():
+            raise ValueError("the device form expects a contiguous [n, capacity] uint8 tensor on a GPU")
+        n, cap = x.shape
+        if n == 0 or cap == 0:
+            raise ValueError("jpeg_decode_batch expects a non-empty batch")
+        if (not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,)
+                or lengths.device != x.device or not lengths.is_contiguous()):
+            raise ValueError(f"lengths must be a contiguous int32 tensor of shape ({n},) on the files' device")
+        if not isinstance(header, (bytes, bytearray, memoryview)) or len(header) == 0:
+            raise ValueError("the device form needs header= (bytes): what every file starts with")
+        if len(header) > cap:
+            raise ValueError("the header is longer than a file slot")
+        frame, tset = _jpeg_parse_raw(header, "header")
+        if int(frame["scan_offset"][0]) != len(header):
+            raise ValueError("header must end with the SOS segment")
+        frames, sets, dev, max_file = np.repeat(frame, n), tset, x.device, cap
+        blob_parts = [frames.tobytes(), sets.tobytes(), bytes(header)]
+    else:
+        if lengths is not None or header is not None:
+            raise ValueError("lengths= and header= belong to the device form")
+        try:
+            views = [np.frombuffer(f, np.uint8) for f in files]
+        except TypeError as exc:
+            raise ValueError(f"files must be bytes-like objects: {exc}") from None
+        n = len(views)
+        if n == 0:
+            raise ValueError("jpeg_decode_batch expects a non-empty batch")
+        frames, set_index, set_list = np.zeros(n, JPEG_FRAME_DTYPE), {}, []
+        for i, v in enumerate(views):
+            fr, ts = _jpeg_parse_raw(v, f"frame {i}")
+            key = ts.tobytes()
+            if key not in set_index:
+                set_index[key] = len(set_list)
+                set_list.append(key)
+            frames[i] = fr[0]
+            frames[i]["table_set"] = set_index[key]
+            if (fr["height"][0], fr["width"][0]) != (frames[0]["height"], frames[0]["width"]):
+                raise ValueError(f"frame {i} is {fr['height'][0]} x {fr['width'][0]}, the batch is "
+                                 f"{frames[0]['height']} x {frames[0]['width']}")
+        sets = np.frombuffer(b"".join(set_list), JPEG_TABLE_SET_DTYPE)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if dev.type != "cuda":
+            raise ValueError("jpeg_decode_batch decodes on a GPU")
+        max_file = max(v.size for v in views)
+        offs = np.zeros(n, np.int64)
+        pos = 0
+        for i, v in enumerate(views):
+            offs[i] = pos
+            pos += (v.size + 15) & ~15
+        lens = np.array([v.size for v in views], np.int32)
+        packed = np.zeros(pos, np.uint8)
+        for o, v in zip(offs, views):
+            packed[o:o + v.size] = v
+        blob_parts = [frames.tobytes(), sets.tobytes(), offs.tobytes(), lens.tobytes(), packed.tobytes()]
+    h, w = int(frames[0]["height"]), int(frames[0]["width"])
+    mcus = -(-h // 16) * -(-w // 16)
+    ri = frames["restart_interval"].astype(np.int64)
+    max_seg = int(np.max(np.where(ri > 0, -(-mcus // np.maximum(ri, 1)), 1)))
+
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3) or out.device != dev
+          or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {h}, {w}, 3) on the decoding device")
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+    elif (not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or tuple(status.shape) != (n,)
+          or status.device != dev or not status.is_contiguous()):
+        raise ValueError(f"status must be a contiguous int32 tensor of shape ({n},) on the decoding device")
+    need = int(_lib.lib().vlfm_jpeg_decode_scratch_bytes(n, h, w, max_file))
+    if need == 0:
+        raise ValueError(f"{n} files of {h} x {w} and up to {max_file} bytes are not a batch the decoder takes")
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)          # (the caching allocator: no device allocation)
+    elif (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint8 or scratch.device != dev
+          or not scratch.is_contiguous() or scratch.numel() < need or scratch.data_ptr() % 16):
+        raise ValueError(f"scratch must be a contiguous, 16-byte aligned uint8 device tensor of at least {need} bytes")
+
+    def span(t):
+        return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+
+    bufs = [("out", out), ("status", status), ("scratch", scratch)]
+    if device_form:
+        bufs = [("the files", files), ("lengths", lengths)] + bufs
+    for i, (na, a) in enumerate(bufs):
+        for nb_, b in bufs[i + 1:]:
+            (a0, a1), (b0, b1) = span(a), span(b)
+            if a0 < b1 and b0 < a1:
+                raise ValueError(f"{nb_} must not overlap {na}")
+
+    # one upload: frame records, table sets and (host form) offsets, lengths and the files, each part 16-byte aligned
+    starts, total = [], 0
+    for part in blob_parts:
+        starts.append(total)
+        total += (len(part) + 15) & ~15
+    host = np.zeros(total, np.uint8)
+    for s, part in zip(starts, blob_parts):
+        host[s:s + len(part)] = np.frombuffer(part, np.uint8)
+    blob = torch.from_numpy(host).to(dev)
+    base = blob.data_ptr()
+    assert base % 16 == 0
+    with torch.cuda.device(dev):
+        if device_form:
+            args = (files.data_ptr(), files.numel(), None, cap, lengths.data_ptr(), n, h, w, base, base + starts[1],
+                    1, base + starts[2], len(header))
+        else:
+            args = (base + starts[4], total - starts[4], base + starts[2], 0, base + starts[3], n, h, w, base,
+                    base + starts[1], len(sets), None, 0)
+        _lib.check(_lib.lib().vlfm_jpeg_decode_batched(*args, max_seg, max_file, int(channel_order == "rgb"), out.data_ptr(),
+                                                       status.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()),
+                   "jpeg_decode_batched")
+    return out, status
+
+
+def jpeg_decode_batch_checked(files, lengths=None, header=None, channel_order: str = "bgr", out=None, status=None,
+                              scratch=None, device=None):
+    """``jpeg_decode_batch`` with one synchronisation: returns ``out`` alone and raises ValueError naming the frames whose
+    stream is damaged, and how."""
+    out, status = jpeg_decode_batch(files, lengths, header, channel_order, out, status, scratch, device)
+    st = status.cpu().numpy()                               # (waits for the decoder)
+    bad = np.nonzero(st)[0]
+    if bad.size:
+        raise ValueError("damaged JPEG streams: " + ", ".join(
+            f"frame {int(i)} ({JPEG_STATUS.get(int(st[i]), int(st[i]))})" for i in bad))
+    return out
+
+
+def str_to_image_batch(strings, device=None):
+    """``str_to_image`` of server_wrapper.py:64-68 for a batch: base64 texts of JPEG files of one size to a ``[n,H,W,3]`` uint8
+    device tensor, in the slot order ``cv2.imdecode`` gives (B, G, R).  One synchronisation (``jpeg_decode_batch_checked``)."""
+    import base64
+
+    return jpeg_decode_batch_checked([base64.b64decode(s) for s in strings], channel_order="bgr", device=device)
