@@ -55,6 +55,106 @@ def test_nms_matches_oracle(gpu_device, n):
     assert det_ops.nms(torch.zeros((0, 4), device=gpu_device), torch.zeros(0, device=gpu_device), 0.5).numel() == 0
 
 
+def _nms_boxes(n, span, seed):
+    """The recipe of test_nms_matches_oracle plus exact duplicates ACROSS the word slots of nms_scan_kernel (a lane keeps the
+    "removed" bits of ranks 4096 k ... 4096 k + 4095 in word slot k): boxes of up to 64 ranks below 4096 are copied onto boxes ranked
+    4096 and later (half of them onto ranks >= 8192 where there are any), so that a box of slot 0 has to suppress one of slot 1 / 2."""
+    rng = np.random.default_rng(seed)
+    xy = rng.uniform(0, span, (n, 2)).astype(np.float32)
+    wh = rng.uniform(5, 200, (n, 2)).astype(np.float32)
+    boxes = np.concatenate([xy, xy + wh], 1)
+    scores = rng.permutation(n).astype(np.float32) / n              # distinct scores: the order is unambiguous
+    order = np.argsort(-scores, kind="stable")
+    tail = n - 4096
+    dup = min(64, (tail + 1) // 2)                                   # leave about half of a short tail to the recipe
+    if dup > 0:
+        src = rng.choice(4096, dup, replace=False)
+        dst = 4096 + rng.choice(tail, dup, replace=False)
+        far = min(dup // 2, (n - 8192) // 2)                         # ... and of a short tail beyond 8192
+        if far > 0:
+            dst[dup - far:] = 8192 + rng.choice(n - 8192, far, replace=False)
+        boxes[order[dst]] = boxes[order[src]]
+    return boxes, scores, order
+
+
+@pytest.mark.parametrize("n,span,thresholds", [(4096, 2000, (0.45, 0.9)), (4097, 2000, (0.45, 0.9)), (4160, 2000, (0.45, 0.9)),
+                                               (4300, 2000, (0.45, 0.9)), (8200, 3000, (0.45, 0.9)), (32768, 3000, (0.45,))])
+def test_nms_word_slots(gpu_device, n, span, thresholds):
+    """NMS beyond 4096 boxes, up to the kernel's limit of 32768: the scan keeps 8 words of "removed" bits per lane and selects word
+    slot k = rank / 4096; slots >= 1, the column-word reads `lane + 64 k` and the limit itself run only here.  Exact equality with the
+    oracle.  Sizes 4096 (64 column words exactly), 4097 and 4160 (one rank / one column word into slot 1) are the edges; from 4300 on
+    the case must prove something: at least 50 boxes ranked >= 4096 suppressed and at least 50 kept (4097 and 4160 have 1 and 64 such
+    ranks and cannot reach 50 + 50)."""
+    from oracle.ref_detect import nms as ref_nms
+    from vlfm_amd.vlm import det_ops
+
+    boxes, scores, order = _nms_boxes(n, span, seed=n)
+    bg, sg = torch.from_numpy(boxes).to(gpu_device), torch.from_numpy(scores).to(gpu_device)
+    want = None
+    for thr in thresholds:
+        want = ref_nms(boxes, scores, thr)
+        rank = np.empty(n, np.int64)
+        rank[order] = np.arange(n)
+        kept_tail = int((rank[want] >= 4096).sum())
+        dead_tail = (n - 4096) - kept_tail
+        if thr == 0.45:
+            if n > 4096:
+                assert dead_tail >= min(50, (n - 4096 + 1) // 2), (n, dead_tail, kept_tail)   # the forced duplicates at the least
+            if n >= 4300:
+                assert dead_tail >= 50 and kept_tail >= 50, (n, dead_tail, kept_tail)
+            if n > 8192:                                             # word slot 2: the forced duplicates at the least
+                assert (n - 8192) - int((rank[want] >= 8192).sum()) >= min(32, (n - 8192) // 2)
+        got = det_ops.nms(bg, sg, thr).cpu().numpy()
+        assert np.array_equal(got, want), (n, thr, len(got), len(want))
+    capped = det_ops.nms(bg, sg, thresholds[-1], 300).cpu().numpy()            # yolov7's max_det
+    assert np.array_equal(capped, want[:300])
+
+
+def test_nms_degenerate_boxes(gpu_device):
+    """Zero-area boxes (IoU = 0 / 0 with each other), boxes with x2 < x1 (negative area) and a pair whose IoU EQUALS the threshold
+    (unit squares overlapping by half: 1/3; `>` keeps both) come out as the oracle decides: both use f32 and a strict `>`."""
+    from oracle.ref_detect import nms as ref_nms
+    from vlfm_amd.vlm import det_ops
+
+    n = 130
+    rng = np.random.default_rng(130)
+    xy = rng.uniform(0, 300, (n, 2)).astype(np.float32)
+    wh = rng.uniform(5, 200, (n, 2)).astype(np.float32)
+    boxes = np.concatenate([xy, xy + wh], 1)
+    boxes[10:20, 2:] = boxes[10:20, :2]                              # points: zero area, some inside other boxes
+    boxes[20] = boxes[21] = boxes[10]                                # identical zero-area boxes: 0 / 0
+    boxes[22:26, 2] = boxes[22:26, 0]                                # zero width, positive height
+    boxes[30:40, [0, 2]] = boxes[30:40, [2, 0]]                      # x2 < x1
+    boxes[40] = boxes[30]                                            # a duplicate of an inverted box
+    boxes[100] = (5000.0, 5000.0, 5001.0, 5001.0)                    # unit squares overlapping by half, away from the rest
+    boxes[101] = (5000.5, 5000.0, 5001.5, 5001.0)
+    scores = rng.permutation(n).astype(np.float32) / n
+    third = np.float32(1 / 3)
+    a, b = boxes[100], boxes[101]
+    inter = (min(a[2], b[2]) - max(a[0], b[0])) * (min(a[3], b[3]) - max(a[1], b[1]))
+    assert np.float32(inter) / np.float32(np.float32(1 + 1) - np.float32(inter)) == third
+    bg, sg = torch.from_numpy(boxes).to(gpu_device), torch.from_numpy(scores).to(gpu_device)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for thr in (third, 0.45, 0.0):
+            want = ref_nms(boxes, scores, thr)
+            got = det_ops.nms(bg, sg, float(thr)).cpu().numpy()
+            assert np.array_equal(got, want), (thr, len(got), len(want))
+            if thr == third:
+                assert 100 in got and 101 in got                     # IoU == threshold: not suppressed
+        below = np.nextafter(third, np.float32(0))
+        got = det_ops.nms(bg, sg, float(below)).cpu().numpy()
+        assert np.array_equal(got, ref_nms(boxes, scores, below)) and (100 in got) != (101 in got)
+
+
+def test_nms_refuses_more_than_32768_boxes(gpu_device):
+    from vlfm_amd.vlm import det_ops
+
+    n = 32769
+    boxes = torch.zeros(n, 4, device=gpu_device)
+    with pytest.raises(RuntimeError, match="nms"):
+        det_ops.nms(boxes, torch.arange(n, device=gpu_device, dtype=torch.float32), 0.5)
+
+
 def test_preprocess_sam_matches_pil(gpu_device):
     from PIL import Image
 

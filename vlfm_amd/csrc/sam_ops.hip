@@ -70,26 +70,31 @@ __global__ __launch_bounds__(256) void layernorm_rows_f32_kernel(const float* __
         v[k] = i < C4 ? irow[i] : make_float4(0.f, 0.f, 0.f, 0.f);
         s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
     }
+    // The f32 mean carries its own rounding (half an ulp of |mean| at the least, plus the summation's): on rows with a large common
+    // offset (mean 50, deviation 1 or less) that alone is 2e-6 .. 4e-5 of the normalised output.  The differences v - mean are (nearly)
+    // exact, so their average `rest` IS that error: subtract it as well (sum (d - rest)^2 = sum d^2 - C rest^2).
     const float mean = wave_sum(s) / (float)C;
-    float q = 0.f;
+    float q = 0.f, e = 0.f;
 #pragma unroll
     for (int k = 0; k < MAXV; k++) {
         if (lane + 64 * k < C4) {
             const float a = v[k].x - mean, b2 = v[k].y - mean, c = v[k].z - mean, d = v[k].w - mean;
             q += (a * a + b2 * b2) + (c * c + d * d);
+            e += (a + b2) + (c + d);
         }
     }
-    const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+    const float rest = wave_sum(e) / (float)C;
+    const float rstd = rsqrtf(fmaxf(wave_sum(q) / (float)C - rest * rest, 0.f) + eps);
 #pragma unroll
     for (int k = 0; k < MAXV; k++) {
         const int i = lane + 64 * k;
         if (i < C4) {
             const float4 g = reinterpret_cast<const float4*>(gamma)[i], bb = reinterpret_cast<const float4*>(beta)[i];
             float4 o;
-            o.x = (v[k].x - mean) * rstd * g.x + bb.x;
-            o.y = (v[k].y - mean) * rstd * g.y + bb.y;
-            o.z = (v[k].z - mean) * rstd * g.z + bb.z;
-            o.w = (v[k].w - mean) * rstd * g.w + bb.w;
+            o.x = ((v[k].x - mean) - rest) * rstd * g.x + bb.x;
+            o.y = ((v[k].y - mean) - rest) * rstd * g.y + bb.y;
+            o.z = ((v[k].z - mean) - rest) * rstd * g.z + bb.z;
+            o.w = ((v[k].w - mean) - rest) * rstd * g.w + bb.w;
             orow[i] = o;
         }
     }
