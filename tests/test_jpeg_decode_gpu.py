@@ -134,6 +134,24 @@ def _guards_intact(big, nbytes):
     return bool((big[:GUARD] == 0xA5).all()) and bool((big[GUARD + nbytes:] == 0xA5).all())
 
 
+def test_unaligned_out(gpu_device):
+    """Host form into an `out` that starts one byte into a sentinel-filled buffer: the pixel half decides on 16-byte stores
+    from the pointer as well as from 3W % 16 (at 48x64 the pointer alone decides).  Pixels equal Pillow, sentinels intact.  (This pins the results, not the flag: the
+    hardware takes a 16-byte store at any address, so a wrongly set flag would cost speed and show here only as a fault.)"""
+    for (n, h, w), order in (((2, 48, 64), "bgr"), ((2, 33, 47), "rgb")):
+        files = [pillow_file(jpeg_ref.frame("noise", h, w, i), 90) for i in range(n)]
+        nbytes = n * h * w * 3
+        big = torch.full((nbytes + 64,), 0xA5, dtype=torch.uint8, device=gpu_device)
+        out = big[1:1 + nbytes].view(n, h, w, 3)
+        assert out.data_ptr() % 16 == 1
+        got, status = T().jpeg_decode_batch(files, channel_order=order, out=out, device=gpu_device)
+        assert got.data_ptr() == out.data_ptr() and not status.cpu().numpy().any()
+        px = out.cpu().numpy()
+        for i, f in enumerate(files):
+            assert np.array_equal(px[i], dec.pillow_pixels(f, order == "rgb")), (h, w, i)
+        assert bool((big[:1] == 0xA5).all()) and bool((big[1 + nbytes:] == 0xA5).all()), (h, w)
+
+
 def test_damaged_streams(gpu_device):
     """Each damaged 48 x 80 file sits between two good ones.  The CPU model (test_jpeg_decode_cpu.py) has run the same bytes with
     every index asserted in range.  Status non-zero where the model's is, neighbours equal Pillow, guard bytes intact."""

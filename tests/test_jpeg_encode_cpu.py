@@ -112,6 +112,35 @@ def test_bound_and_scratch_are_zero_for_invalid_sizes():
     assert L.vlfm_jpeg_encode_bound(1, 1) > 0 and L.vlfm_jpeg_encode_bound(8000, 8000) > 0
 
 
+# (n, H, W): roundtrip scratch, encode scratch, encode bound, decode scratch at max_file_bytes 1000 and 65536.  Recorded from
+# the library of the commit before the three JPEG translation units were folded onto csrc/jpeg_common.h (795fde3), built and
+# queried on the CPU before the first edit: the fold must not move a size.
+SIZES_BEFORE_THE_FOLD = {
+    (1, 1, 1): (384, 2112, 3115, 2240, 67008),
+    (1, 16, 16): (384, 2112, 3115, 2240, 67008),
+    (1, 17, 9): (768, 4128, 5605, 3392, 68160),
+    (1, 33, 47): (3456, 18400, 23035, 11488, 76256),
+    (1, 480, 640): (460800, 2445920, 2988625, 1388288, 1453056),
+    (1, 479, 641): (472320, 2507056, 3063325, 1422960, 1487728),
+    (1, 1000, 1000): (1524096, 8089744, 9883435, 4589248, 4654016),
+    (3, 1, 1): (1152, 6256, 3115, 6704, 201008),
+    (3, 16, 16): (1152, 6256, 3115, 6704, 201008),
+    (3, 17, 9): (2304, 12320, 5605, 10176, 204480),
+    (3, 33, 47): (10368, 55152, 23035, 34448, 228752),
+    (3, 480, 640): (1382400, 7337696, 2988625, 4164832, 4359136),
+    (3, 479, 641): (1416960, 7521120, 3063325, 4268880, 4463184),
+    (3, 1000, 1000): (4572288, 24269184, 9883435, 13767728, 13962032),
+}
+
+
+def test_scratch_sizes_and_bound_do_not_move():
+    L = _lib().lib()
+    for (n, h, w), want in SIZES_BEFORE_THE_FOLD.items():
+        got = (L.vlfm_jpeg_scratch_bytes(n, h, w), L.vlfm_jpeg_encode_scratch_bytes(n, h, w), L.vlfm_jpeg_encode_bound(h, w),
+               L.vlfm_jpeg_decode_scratch_bytes(n, h, w, 1000), L.vlfm_jpeg_decode_scratch_bytes(n, h, w, 65536))
+        assert got == want, (n, h, w)
+
+
 def test_mjpeg_writer_output_splits_back_into_its_files(tmp_path):
     from vlfm_amd.utils.mjpeg import MjpegWriter, split_mjpeg
 

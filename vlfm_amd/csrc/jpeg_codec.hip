@@ -35,9 +35,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vlfm_amd.h"
+#include "jpeg_common.h"
 #include "profile.h"
-#include "status.h"
 
 namespace vlfm {
 namespace jpeg {
@@ -47,11 +46,6 @@ constexpr double kFdctFormL1 = 2.69e6, kIdctFormNorm = 3.36e5;
 static_assert(kFdctFormL1 * 128.0 + (1 << 21) < 2147483647.0, "islow FDCT intermediates must fit in int32");
 static_assert(kIdctFormNorm * 2045.0 + (1 << 21) < 2147483647.0, "islow IDCT intermediates must fit in int32");
 
-constexpr int TILE_MCUS = 4;                 // MCUs per workgroup, side by side
-constexpr int TILE_W = 16 * TILE_MCUS;       // 64 pixels
-constexpr int TILE_ROW_BYTES = 3 * TILE_W;   // 192 bytes of interleaved samples per tile row
-constexpr int BLOCKS = 6 * TILE_MCUS;        // 16 Y + 4 Cb + 4 Cr
-constexpr int THREADS = 8 * BLOCKS;          // one thread per block row (then per block column): 192
 constexpr int CSTRIDE = 9;                   // LDS coefficient row stride (ints): rows of a block on different banks
 constexpr int CBLOCK = 8 * CSTRIDE;
 static_assert(THREADS == 16 * TILE_ROW_BYTES / 16, "one 16-byte load per thread fills the tile");
@@ -134,27 +128,7 @@ __device__ __forceinline__ uint32_t range_limit(int x) {
     return (uint32_t)(j < 128 ? j + 128 : j < 512 ? 255 : j < 896 ? 0 : j - 896);
 }
 
-struct QuantTables {
-    uint16_t q[2][64];   // luma, chroma quantval in natural order (jcparam.c jpeg_add_quant_table), 1..255
-};
-
-struct Geometry {
-    int n, H, W;
-    int mh, mw;          // MCU rows / columns: ceil(H/16), ceil(W/16)
-    int tiles_x;         // ceil(mw / TILE_MCUS)
-    int ch, cw;          // real chroma size: ceil(H/2), ceil(W/2)
-    int vec_in, vec_out; // 16-byte global access allowed for the frame rows (3W % 16 == 0 and the pointer is aligned)
-    // scratch plane geometry per frame: Y [16 mh][16 mw], Cb and Cr [8 mh][8 mw]
-    __host__ __device__ size_t frame_scratch() const { return (size_t)384 * mh * mw; }
-};
-
 __device__ __forceinline__ uint32_t byte_of(const uint32_t* w, int i) { return (w[i >> 2] >> (8 * (i & 3))) & 0xffu; }
-
-// jutils.c jpeg_natural_order: the natural (row-major) index of the k-th coefficient in zigzag order
-__device__ const uint8_t kNaturalOrder[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                                              12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                                              35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                                              58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // kEncode = false: the round trip (decoded planes to `scratch`).  kEncode = true: the encoder's coefficient pass, which
 // stops after quantisation and stores every block of the scan as 64 int16 in zigzag order, blocks in scan order (MCUs
@@ -461,23 +435,15 @@ __global__ void __launch_bounds__(256) jpeg_upsample_kernel(const uint8_t* __res
 }
 
 // The encoder's coefficient pass (jpeg_entropy.hip calls it): 768 bytes per MCU to d_coef.
-int launch_coefficients(const uint8_t* d_in, int n, int H, int W, int rgb_order, const uint16_t* h_tables, int16_t* d_coef,
+int launch_coefficients(const uint8_t* d_in, int n, int H, int W, int rgb_order, const QuantTables& qt, int16_t* d_coef,
                         hipStream_t st) {
     Geometry g;
-    g.n = n; g.H = H; g.W = W;
-    g.mh = (H + 15) / 16; g.mw = (W + 15) / 16;
-    g.tiles_x = (g.mw + TILE_MCUS - 1) / TILE_MCUS;
-    g.ch = (H + 1) / 2; g.cw = (W + 1) / 2;
-    g.vec_in = (3 * (size_t)W) % 16 == 0 && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0;
-    g.vec_out = 0;
-    QuantTables qt;
-    for (int i = 0; i < 128; ++i) qt.q[i >> 6][i & 63] = h_tables[i];
-    const size_t code_blocks = (size_t)n * g.mh * g.tiles_x;
-    if (code_blocks > 0x7fffffff) return fail(VLFM_ERR_INVALID, "jpeg_encode_batched: batch too large for one launch");
+    if (!geometry(n, H, W, &g, d_in) || g.code_grid() > 0x7fffffff)   // (the entry point has validated the size)
+        return fail(VLFM_ERR_INVALID, "jpeg_encode_batched: batch too large for one launch");
     auto kernel = rgb_order ? jpeg_code_kernel<true, true> : jpeg_code_kernel<true, false>;
     {
         VLFM_TIMED("jpeg_coef_kernel", st);
-        VLFM_KLAUNCH(kernel, dim3((unsigned)code_blocks), dim3(THREADS), 0, st, d_in, qt, g,
+        VLFM_KLAUNCH(kernel, dim3((unsigned)g.code_grid()), dim3(THREADS), 0, st, d_in, qt, g,
                      reinterpret_cast<uint8_t*>(d_coef));
     }
     return check_launch("jpeg_coef_kernel");
@@ -487,26 +453,19 @@ int launch_coefficients(const uint8_t* d_in, int n, int H, int W, int rgb_order,
 int launch_pixels(const int16_t* d_coef, const vlfm_jpeg_frame* d_frames, const vlfm_jpeg_table_set* d_sets, int n_sets, int n,
                   int H, int W, int rgb_order, uint8_t* d_planes, uint8_t* d_out, hipStream_t st) {
     Geometry g;
-    g.n = n; g.H = H; g.W = W;
-    g.mh = (H + 15) / 16; g.mw = (W + 15) / 16;
-    g.tiles_x = (g.mw + TILE_MCUS - 1) / TILE_MCUS;
-    g.ch = (H + 1) / 2; g.cw = (W + 1) / 2;
-    g.vec_in = 0;
-    g.vec_out = (3 * (size_t)W) % 16 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0;
-    const size_t code_blocks = (size_t)n * g.mh * g.tiles_x;
-    const size_t up_blocks = ((size_t)n * H * ((W + 15) / 16) + 255) / 256;
-    if (code_blocks > 0x7fffffff || up_blocks > 0x7fffffff)
+    // (the entry point has validated the size)
+    if (!geometry(n, H, W, &g, nullptr, d_out) || g.code_grid() > 0x7fffffff || g.upsample_grid() > 0x7fffffff)
         return fail(VLFM_ERR_INVALID, "jpeg_decode_batched: batch too large for one launch");
     {
         VLFM_TIMED("jpeg_idct_kernel", st);
-        VLFM_KLAUNCH(jpeg_idct_kernel, dim3((unsigned)code_blocks), dim3(THREADS), 0, st, d_coef, d_frames, d_sets, n_sets, g,
-                     d_planes);
+        VLFM_KLAUNCH(jpeg_idct_kernel, dim3((unsigned)g.code_grid()), dim3(THREADS), 0, st, d_coef, d_frames, d_sets, n_sets,
+                     g, d_planes);
     }
     if (int rc = check_launch("jpeg_idct_kernel")) return rc;
     {
         VLFM_TIMED("jpeg_upsample_kernel", st);
         auto kernel = rgb_order ? jpeg_upsample_kernel<true> : jpeg_upsample_kernel<false>;
-        VLFM_KLAUNCH(kernel, dim3((unsigned)up_blocks), dim3(256), 0, st, d_planes, g, d_out);
+        VLFM_KLAUNCH(kernel, dim3((unsigned)g.upsample_grid()), dim3(256), 0, st, d_planes, g, d_out);
     }
     return check_launch("jpeg_upsample_kernel");
 }
@@ -519,8 +478,6 @@ using namespace vlfm;
 using namespace vlfm::jpeg;
 
 namespace {
-// libjpeg's JPEG_MAX_DIMENSION: the largest frame side a JPEG can carry.
-constexpr int kMaxDim = 65500;
 const uint16_t kStdLuma[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55,
                                14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
                                18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
@@ -529,16 +486,6 @@ const uint16_t kStdChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66,
                                  24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
                                  99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
                                  99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-
-bool geometry(int n, int H, int W, Geometry* g) {
-    if (n <= 0 || H <= 0 || W <= 0 || H > kMaxDim || W > kMaxDim) return false;
-    g->n = n; g->H = H; g->W = W;
-    g->mh = (H + 15) / 16; g->mw = (W + 15) / 16;
-    g->tiles_x = (g->mw + TILE_MCUS - 1) / TILE_MCUS;
-    g->ch = (H + 1) / 2; g->cw = (W + 1) / 2;
-    g->vec_in = g->vec_out = 0;
-    return true;
-}
 }  // namespace
 
 extern "C" int vlfm_jpeg_quant_tables_host(int quality, uint16_t* h_tables) {

@@ -28,15 +28,11 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "../../include/vlfm_amd.h"
+#include "jpeg_common.h"
 #include "profile.h"
-#include "status.h"
 
 namespace vlfm {
 namespace jpeg {
-
-int launch_pixels(const int16_t* d_coef, const vlfm_jpeg_frame* d_frames, const vlfm_jpeg_table_set* d_sets, int n_sets, int n,
-                  int H, int W, int rgb_order, uint8_t* d_planes, uint8_t* d_out, hipStream_t st);
 
 constexpr int DCHUNK = 4096;          // file bytes per scan workgroup: 256 threads x 16 B
 constexpr int STAGE_BYTES = 1024;     // unstuffed stream bytes a wavefront stages in LDS: 64 lanes x 16 B
@@ -104,20 +100,11 @@ __device__ __forceinline__ int classify(const uint8_t* p, uint32_t scan0, uint32
     return (i > scan0 && p[i - 1] == 0xffu) ? DROP : KEEP;
 }
 
-__device__ __forceinline__ uint32_t wave_inclusive_sum_u32(uint32_t x, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-
 // Exclusive sums of a and b over the 256 threads of the workgroup; the sums to *ta, *tb.  `part` holds 8 words.
 __device__ __forceinline__ void block_exclusive_sum2(uint32_t a, uint32_t b, uint32_t* part, uint32_t* ea, uint32_t* eb,
                                                      uint32_t* ta, uint32_t* tb) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t ia = wave_inclusive_sum_u32(a, lane), ib = wave_inclusive_sum_u32(b, lane);
+    const uint32_t ia = wave_inclusive_sum(a, lane), ib = wave_inclusive_sum(b, lane);
     __syncthreads();
     if (lane == 63) {
         part[wave] = ia;
@@ -443,12 +430,6 @@ using namespace vlfm;
 using namespace vlfm::jpeg;
 
 namespace {
-constexpr int kMaxDim = 65500;
-// jutils.c jpeg_natural_order
-const uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
 enum {
     R_NOT_JPEG = 1, R_MALFORMED, R_PROCESS, R_PRECISION, R_COMPONENTS, R_SAMPLING, R_SCAN, R_QUANT16, R_NO_TABLE, R_ADOBE,
     R_DIMENSION, R_NO_SCAN, R_COUNT
@@ -486,12 +467,10 @@ bool derive(const uint8_t* bits, const uint8_t* vals, int count, vlfm_jpeg_huff*
     return true;
 }
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 bool layout(int n, int H, int W, size_t max_file_bytes, DecLayout* l) {
-    if (n <= 0 || H <= 0 || W <= 0 || H > kMaxDim || W > kMaxDim || max_file_bytes == 0 || max_file_bytes > 0x7fffffffu)
-        return false;
-    const size_t mcus = (size_t)((H + 15) / 16) * ((W + 15) / 16);
+    Geometry g;
+    if (!geometry(n, H, W, &g) || max_file_bytes == 0 || max_file_bytes > 0x7fffffffu) return false;
+    const size_t mcus = g.mcus();
     l->n = n;
     l->mcus = (int)mcus;
     l->chunks = (int)((max_file_bytes + DCHUNK - 1) / DCHUNK);
@@ -563,7 +542,7 @@ extern "C" int vlfm_jpeg_parse_host(const uint8_t* p, size_t len, vlfm_jpeg_fram
                 if (pq > 1 || tq > 3) return R_MALFORMED;
                 if (pq == 1) return R_QUANT16;
                 if (j + 65 > n) return R_MALFORMED;
-                for (int z = 0; z < 64; ++z) quant[tq][kNatural[z]] = s[j + 1 + z];
+                for (int z = 0; z < 64; ++z) quant[tq][kNaturalOrder[z]] = s[j + 1 + z];
                 have_q[tq] = true;
                 j += 65;
             }

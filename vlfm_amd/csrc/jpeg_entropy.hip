@@ -27,15 +27,11 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "../../include/vlfm_amd.h"
+#include "jpeg_common.h"
 #include "profile.h"
-#include "status.h"
 
 namespace vlfm {
 namespace jpeg {
-
-int launch_coefficients(const uint8_t* d_in, int n, int H, int W, int rgb_order, const uint16_t* h_tables, int16_t* d_coef,
-                        hipStream_t st);
 
 constexpr int kHeaderBytes = 623;
 // The most bits one block can take: a DC code of at most 11 bits + 11 amplitude bits, and 63 AC coefficients each with a
@@ -44,7 +40,6 @@ constexpr int kMaxBlockBits = 11 + 11 + 63 * (16 + 10);   // 1660
 constexpr int GROUP = 16;                                 // blocks per pack workgroup
 constexpr int WINDOW_WORDS = GROUP * kMaxBlockBits / 32 + 2 + 6;
 constexpr int CHUNK = 4096;                               // stream bytes per stuffing workgroup: 256 threads x 16 B
-constexpr int kMaxDim = 65500;
 
 struct HuffTables {
     uint32_t ac[2][256];   // code << 5 | length, by run/size symbol; luma, chroma
@@ -99,15 +94,6 @@ __device__ __forceinline__ Token block_token(const int16_t* __restrict__ cf, int
         t.len = (int)(e & 31);
     }
     return t;
-}
-
-__device__ __forceinline__ int wave_inclusive_sum(int x, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    return x;
 }
 
 // Exclusive sum of v over the kThreads threads of the workgroup; *total gets the sum.  `part` holds kThreads / 64 words.
@@ -311,10 +297,6 @@ using namespace vlfm;
 using namespace vlfm::jpeg;
 
 namespace {
-// jutils.c jpeg_natural_order
-const uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 // jcparam.c std_huff_tables (JPEG Annex K.3 - K.6): BITS[1..16], then HUFFVAL
 const uint8_t kDcLumaBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
 const uint8_t kDcChromaBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
@@ -368,12 +350,11 @@ const HuffTables& huff_tables() {
 // blocks per frame, or 0 where the encoder does not go: invalid sizes, and frames whose stream could pass 2^32 bits (bit
 // offsets and lengths are 32-bit: about 10 000 x 10 000 pixels).
 size_t frame_blocks(int H, int W) {
-    if (H <= 0 || W <= 0 || H > kMaxDim || W > kMaxDim) return 0;
-    const size_t nb = (size_t)6 * ((H + 15) / 16) * ((W + 15) / 16);
+    Geometry g;
+    if (!geometry(1, H, W, &g)) return 0;   // (one frame: only H and W are in question here)
+    const size_t nb = 6 * g.mcus();
     return nb * kMaxBlockBits + 64 > 0xffffffffull ? 0 : nb;
 }
-
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 bool layout(int n, int H, int W, Layout* l) {
     const size_t nb = frame_blocks(H, W);
@@ -411,7 +392,7 @@ void make_header(const uint16_t* tables, int H, int W, uint8_t* out) {
     for (int t = 0; t < 2; ++t) {
         uint8_t dqt[65];
         dqt[0] = (uint8_t)t;
-        for (int i = 0; i < 64; ++i) dqt[1 + i] = (uint8_t)tables[64 * t + kNatural[i]];
+        for (int i = 0; i < 64; ++i) dqt[1 + i] = (uint8_t)tables[64 * t + kNaturalOrder[i]];
         put_segment(p, 0xdb, dqt, 65);
     }
     const uint8_t sof[15] = {8, (uint8_t)(H >> 8), (uint8_t)H, (uint8_t)(W >> 8), (uint8_t)W, 3, 1, 0x22, 0, 2, 0x11, 1,
@@ -430,17 +411,12 @@ void make_header(const uint16_t* tables, int H, int W, uint8_t* out) {
     const uint8_t sos[10] = {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
     put_segment(p, 0xda, sos, 10);
 }
-
-bool tables_valid(const uint16_t* t) {
-    for (int i = 0; i < 128; ++i)
-        if (t[i] < 1 || t[i] > 255) return false;
-    return true;
-}
 }  // namespace
 
 extern "C" int vlfm_jpeg_header_host(int quality, int H, int W, uint8_t* h_out, size_t cap, size_t* len) {
     uint16_t tables[128];
-    if (!h_out || !len || H <= 0 || W <= 0 || H > kMaxDim || W > kMaxDim)
+    Geometry g;
+    if (!h_out || !len || !geometry(1, H, W, &g))   // (one frame: g only checks H and W)
         return fail(VLFM_ERR_INVALID, "jpeg_header_host: bad argument");
     if (int rc = vlfm_jpeg_quant_tables_host(quality, tables)) return rc;
     *len = kHeaderBytes;
@@ -463,11 +439,12 @@ extern "C" int vlfm_jpeg_encode_batched(const uint8_t* d_in, int n, int H, int W
                                         uint8_t* d_out, size_t capacity, uint32_t* d_lengths, void* d_scratch,
                                         size_t scratch_bytes, void* stream) {
     Layout l;
+    QuantTables qt;
     if (!d_in || !d_out || !d_lengths || !h_tables || capacity == 0 || (rgb_order != 0 && rgb_order != 1))
         return fail(VLFM_ERR_INVALID, "jpeg_encode_batched: bad argument");
     if (!layout(n, H, W, &l))
         return fail(VLFM_ERR_INVALID, "jpeg_encode_batched: bad frame size (or a frame too large for 32-bit bit offsets)");
-    if (!tables_valid(h_tables))
+    if (!load_quant_tables(h_tables, &qt))
         return fail(VLFM_ERR_INVALID, "jpeg_encode_batched: quantisation table entries must be 1..255");
     if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15))
         return fail(VLFM_ERR_INVALID, "jpeg_encode_batched: scratch must be a 16-byte aligned device buffer");
@@ -489,7 +466,7 @@ extern "C" int vlfm_jpeg_encode_batched(const uint8_t* d_in, int n, int H, int W
     memset(&hdr, 0, sizeof hdr);
     make_header(h_tables, H, W, reinterpret_cast<uint8_t*>(hdr.w));   // (little-endian host: byte i of the word array)
 
-    if (int rc = launch_coefficients(d_in, n, H, W, rgb_order, h_tables, coef, st)) return rc;
+    if (int rc = launch_coefficients(d_in, n, H, W, rgb_order, qt, coef, st)) return rc;
     {
         VLFM_TIMED("jpeg_length_kernel", st);
         VLFM_KLAUNCH(jpeg_length_kernel, dim3((unsigned)length_grid), dim3(256), 0, st, coef, ht, l.nb, blocks, bits);

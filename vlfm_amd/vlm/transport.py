@@ -43,6 +43,46 @@ def jpeg_quant_tables(quality: int) -> np.ndarray:
     return _tables_cache[q]
 
 
+JPEG_MAX_DIMENSION = 65500   # libjpeg's limit on a frame side (csrc/jpeg_common.h: kMaxDim)
+
+
+def _buffer(name: str, t, dtype, shape, device, where: str):
+    """``t`` if it is a contiguous tensor of ``dtype`` and ``shape`` on ``device``; a new one for None."""
+    import torch
+
+    shape = tuple(int(d) for d in shape)
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or t.device != device
+            or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[-1]} tensor of shape {shape} on {where}")
+    return t
+
+
+def _scratch(scratch, need: int, device):
+    import torch
+
+    if scratch is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)   # (the caching allocator: no device allocation)
+    if (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint8 or scratch.device != device
+            or not scratch.is_contiguous() or scratch.numel() < need or scratch.data_ptr() % 16):
+        raise ValueError(f"scratch must be a contiguous, 16-byte aligned uint8 device tensor of at least {need} bytes")
+    return scratch
+
+
+def _overlap(a, b) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def _no_overlap(bufs) -> None:
+    """``bufs``: (name, tensor) pairs, no two of which may share a byte."""
+    for i, (na, a) in enumerate(bufs):
+        for nb, b in bufs[i + 1:]:
+            if _overlap(a, b):
+                raise ValueError(f"{nb} must not overlap {na}")
+
+
 def jpeg_roundtrip_scratch(n: int, height: int, width: int, device) -> "torch.Tensor":
     """A device buffer that ``jpeg_roundtrip_batch(..., scratch=)`` accepts for n frames of height x width."""
     import torch
@@ -172,8 +212,8 @@ def jpeg_encode_batch(images_u8, quality: int = 90, channel_order: str = "bgr", 
     n, h, w, _ = x.shape
     if n == 0 or h == 0 or w == 0:
         raise ValueError(f"jpeg_encode_batch expects a non-empty batch, got shape {tuple(x.shape)}")
-    if h > 65500 or w > 65500:
-        raise ValueError("JPEG frames are at most 65500 pixels on a side")
+    if h > JPEG_MAX_DIMENSION or w > JPEG_MAX_DIMENSION:
+        raise ValueError(f"JPEG frames are at most {JPEG_MAX_DIMENSION} pixels on a side")
     bound = jpeg_encode_bound(h, w)
     if bound == 0:
         raise ValueError(f"a {h} x {w} frame is too large for the encoder's 32-bit bit offsets")
@@ -182,32 +222,10 @@ def jpeg_encode_batch(images_u8, quality: int = 90, channel_order: str = "bgr", 
     if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or int(capacity) < 1:
         raise ValueError(f"capacity must be a positive integer, got {capacity!r}")
     capacity = int(capacity)
-    if out is None:
-        out = torch.empty((n, capacity), dtype=torch.uint8, device=x.device)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, capacity)
-          or out.device != x.device or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {capacity}) on the input's device")
-    if lengths is None:
-        lengths = torch.empty(n, dtype=torch.int32, device=x.device)
-    elif (not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,)
-          or lengths.device != x.device or not lengths.is_contiguous()):
-        raise ValueError(f"lengths must be a contiguous int32 tensor of shape ({n},) on the input's device")
-    need = int(_lib.lib().vlfm_jpeg_encode_scratch_bytes(n, h, w))
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=x.device)   # (the caching allocator: no device allocation)
-    elif (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint8 or scratch.device != x.device
-          or not scratch.is_contiguous() or scratch.numel() < need or scratch.data_ptr() % 16):
-        raise ValueError(f"scratch must be a contiguous, 16-byte aligned uint8 device tensor of at least {need} bytes")
-
-    def span(t):
-        return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
-
-    bufs = [("the input", x), ("out", out), ("lengths", lengths), ("scratch", scratch)]
-    for i, (na, a) in enumerate(bufs):
-        for nb_, b in bufs[i + 1:]:
-            (a0, a1), (b0, b1) = span(a), span(b)
-            if a0 < b1 and b0 < a1:
-                raise ValueError(f"{nb_} must not overlap {na}")
+    out = _buffer("out", out, torch.uint8, (n, capacity), x.device, "the input's device")
+    lengths = _buffer("lengths", lengths, torch.int32, (n,), x.device, "the input's device")
+    scratch = _scratch(scratch, int(_lib.lib().vlfm_jpeg_encode_scratch_bytes(n, h, w)), x.device)
+    _no_overlap([("the input", x), ("out", out), ("lengths", lengths), ("scratch", scratch)])
     tables = jpeg_quant_tables(int(quality))
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().vlfm_jpeg_encode_batched(x.data_ptr(), n, h, w, int(channel_order == "rgb"),
@@ -383,36 +401,14 @@ def jpeg_decode_batch(files, lengths=None, header=None, channel_order: str = "bg
     ri = frames["restart_interval"].astype(np.int64)
     max_seg = int(np.max(np.where(ri > 0, -(-mcus // np.maximum(ri, 1)), 1)))
 
-    if out is None:
-        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3) or out.device != dev
-          or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {h}, {w}, 3) on the decoding device")
-    if status is None:
-        status = torch.empty(n, dtype=torch.int32, device=dev)
-    elif (not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or tuple(status.shape) != (n,)
-          or status.device != dev or not status.is_contiguous()):
-        raise ValueError(f"status must be a contiguous int32 tensor of shape ({n},) on the decoding device")
+    out = _buffer("out", out, torch.uint8, (n, h, w, 3), dev, "the decoding device")
+    status = _buffer("status", status, torch.int32, (n,), dev, "the decoding device")
     need = int(_lib.lib().vlfm_jpeg_decode_scratch_bytes(n, h, w, max_file))
     if need == 0:
         raise ValueError(f"{n} files of {h} x {w} and up to {max_file} bytes are not a batch the decoder takes")
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)          # (the caching allocator: no device allocation)
-    elif (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint8 or scratch.device != dev
-          or not scratch.is_contiguous() or scratch.numel() < need or scratch.data_ptr() % 16):
-        raise ValueError(f"scratch must be a contiguous, 16-byte aligned uint8 device tensor of at least {need} bytes")
-
-    def span(t):
-        return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
-
-    bufs = [("out", out), ("status", status), ("scratch", scratch)]
-    if device_form:
-        bufs = [("the files", files), ("lengths", lengths)] + bufs
-    for i, (na, a) in enumerate(bufs):
-        for nb_, b in bufs[i + 1:]:
-            (a0, a1), (b0, b1) = span(a), span(b)
-            if a0 < b1 and b0 < a1:
-                raise ValueError(f"{nb_} must not overlap {na}")
+    scratch = _scratch(scratch, need, dev)
+    _no_overlap(([("the files", files), ("lengths", lengths)] if device_form else [])
+                + [("out", out), ("status", status), ("scratch", scratch)])
 
     # one upload: frame records, table sets and (host form) offsets, lengths and the files, each part 16-byte aligned
     starts, total = [], 0
