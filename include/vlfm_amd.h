@@ -785,6 +785,20 @@ int vlfm_jpeg_decode_batched(const uint8_t* d_files, size_t files_bytes, const i
                              int max_segments, size_t max_file_bytes, int rgb_order, uint8_t* d_out, int32_t* d_status,
                              void* d_scratch, size_t scratch_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Rooms world renderer (ABI 15): the depth frames n cameras see in a world of axis-aligned boxes, ray-cast per image column
+ * in ONE launch (csrc/world_render.hip), bit for bit what vlfm_amd.harness.RoomsRenderer.render_cameras computes with torch
+ * f64 operations and, for the tabulated headings, what synthetic.depth_from_profile(synthetic.wall_profile(...)) computes
+ * in NumPy.  Test-world infrastructure of the batched harness (the reference observes through Habitat): it lets a closed-loop
+ * episode render from wherever the robot's own actions took it.
+ *   d_cameras  n records of 8 doubles (64 bytes): x, y, cos(yaw), sin(yaw), camera height, fx (pixels), min_depth, max_depth
+ *              (max_depth > min_depth: the frame is normalised to that range and clamped to [1e-3, 1])
+ *   d_boxes    [n_boxes][4] doubles: x0, y0, x1, y1
+ *   d_out      [n][H][W] float
+ * The boxes, one image row and one band of rows must fit 64 KB of LDS (VLFM_ERR_INVALID otherwise). */
+int vlfm_rooms_raycast(const double* d_cameras, int n, const double* d_boxes, int n_boxes, int H, int W, float* d_out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

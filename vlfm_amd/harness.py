@@ -32,8 +32,9 @@ import torch
 from . import _lib
 from .mapping.base_map import require_gpu
 from .mapping.value_map import ValueMapBatch
-from .synthetic import BOXES, CAMERA_HEIGHT, HEADINGS, MAX_DEPTH, MIN_DEPTH, YAWS, Trajectory, camera_intrinsics, \
-    depth_frame, integrate, plan_actions, pose_to_tf, rgb_frame, tf_of
+from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TURN_RIGHT, BOXES, CAMERA_HEIGHT, HEADINGS, \
+    MAX_DEPTH, MIN_DEPTH, YAWS, BangBangController, ReplayController, Trajectory, camera_intrinsics, depth_frame, integrate, \
+    plan_actions, pose_to_tf, rgb_frame, step_poses, tf_of
 
 PROMPT = "Seems like there is a target_object ahead."  # vlfm/policy/base_objectnav_policy.py:377
 TARGETS = ["chair", "bed", "potted plant", "toilet", "tv", "couch"]  # HM3D ObjectNav categories
@@ -191,6 +192,7 @@ class RoomsRenderer:
         at = [[poses[o + t] for o in offs] for t in range(episode_len)]
         self.pose_table = np.array([[(x, y, YAWS[k]) for (x, y, k) in row] for row in at])       # [L,E,3]
         self.tf_table = np.stack([np.stack([tf_of(x, y, k) for (x, y, k) in row]) for row in at])  # [L,E,4,4]
+        self.k_table = np.array([[k for (_, _, k) in row] for row in at], np.int64)               # [L,E] heading indices
         f64 = dict(dtype=torch.float64, device=device)
         self.xy = torch.tensor([[(x, y) for (x, y, _) in row] for row in at], **f64)             # [L,E,2]
         self.cs = torch.tensor([[HEADINGS[k] for (_, _, k) in row] for row in at], **f64)        # [L,E,2] exact (cos, sin)
@@ -254,6 +256,36 @@ class RoomsRenderer:
         hi = MAX_DEPTH if hi is None else hi
         return ((d - lo) / (hi - lo)).clamp(1e-3, 1.0).float()
 
+    @torch.no_grad()
+    def cast_cameras(self, tf: np.ndarray, hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``render_cameras`` -- same arguments, the same frames bit for bit -- in ONE kernel launch on the current stream
+        (csrc/world_render.hip) instead of a chain of torch f64 operations over [n,W,B] and [n,H,W] temporaries: what a
+        closed-loop step, which cannot pre-render, pays per step.  The camera records (x, y, cos, sin, height, fx, lo, hi) are
+        built on the host and cross in one small copy.  ``out``: a contiguous f32 [n,H,W] device tensor to render into."""
+        tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
+        n = len(tf)
+        rec = np.empty((n, 8), np.float64)
+        rec[:, 0:2], rec[:, 2:4], rec[:, 4] = tf[:, :2, 3], tf[:, :2, 0], tf[:, 2, 3]
+        rec[:, 5] = camera_intrinsics(self.W)[0] if hfov is None else self.W / (2 * np.tan(np.asarray(hfov, np.float64) / 2))
+        rec[:, 6] = MIN_DEPTH if min_depth is None else np.asarray(min_depth, np.float64)
+        rec[:, 7] = MAX_DEPTH if max_depth is None else np.asarray(max_depth, np.float64)
+        if not np.all(rec[:, 7] > rec[:, 6]):
+            raise ValueError("cast_cameras: every camera needs max_depth > min_depth")
+        if out is None:
+            out = torch.empty((n, self.H, self.W), dtype=torch.float32, device=self.device)
+        elif out.shape != (n, self.H, self.W) or out.dtype != torch.float32 or not out.is_contiguous() \
+                or out.device != self.boxes.device:
+            raise ValueError(f"cast_cameras: out must be a contiguous f32 [{n},{self.H},{self.W}] tensor on {self.boxes.device}")
+        if n == 0:
+            return out
+        with torch.cuda.device(self.boxes.device):
+            d_rec = torch.from_numpy(rec).to(self.boxes.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().vlfm_rooms_raycast(d_rec.data_ptr(), n, self.boxes.data_ptr(), len(self.boxes), self.H, self.W,
+                                                     out.data_ptr(), stream), "rooms_raycast")
+        return out
+
     def prepare(self, t0: int, n: int) -> None:
         self.window = torch.stack([self.render((t0 + i) % self.L) for i in range(n)])
         self.window_t0 = t0
@@ -285,7 +317,8 @@ class BatchedEpisodes:
                  coco_threshold: float = 0.8, non_coco_threshold: float = 0.4, pointnav_stop_radius: float = 0.9,
                  object_map_erosion_size: float = 5, concurrent_vlm_max_envs: int = 0,
                  render_trajectories: bool = False, emulate_jpeg: bool = False, rig: Optional[CameraRig] = None,
-                 text_prompt: str = PROMPT, exploration_thresh: Optional[float] = None) -> None:
+                 text_prompt: str = PROMPT, exploration_thresh: Optional[float] = None, closed_loop: bool = False,
+                 controller=None) -> None:
         # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
         # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -293,6 +326,23 @@ class BatchedEpisodes:
         self.prompt_lists = episode_prompts(text_prompt, exploration_thresh, self.targets)
         self.C = len(self.prompt_lists[0]) if self.prompt_lists else len(text_prompt.split("|"))
         self.exploration_thresh = exploration_thresh
+        # closed_loop: the actions MOVE the robots (synthetic.step_poses) and every step observes from where they now are
+        # (RoomsRenderer.cast_cameras) instead of from the next pose of the planned tour; the actions are the PointNav
+        # controller's when it has the discrete head, else ``controller``'s: any object with
+        # act(modes, rho_theta [E,2], stops [E], collided [E]) -> int64 [E] action ids (default: BangBangController)
+        self.closed_loop = bool(closed_loop)
+        if self.closed_loop:
+            if world != "rooms" or host_inputs:
+                raise ValueError("closed_loop needs the rooms world rendered on the device (world='rooms', host_inputs=False)")
+            if not obstacle or not select_frontiers:
+                raise ValueError("closed_loop needs the obstacle map and the frontier selection (obstacle=True, "
+                                 "select_frontiers=True): without a goal there is nothing to act on")
+            if pointnav is not None and not getattr(pointnav, "discrete", False):
+                raise ValueError("closed_loop needs discrete action ids: a PointNav policy with the continuous head cannot "
+                                 "drive the 30 degree / 0.25 m world")
+        elif controller is not None:
+            raise ValueError("a controller acts only in a closed_loop harness")
+        self.controller = (controller if controller is not None else BangBangController()) if self.closed_loop else None
         self.device = require_gpu(device)
         # rig: K cameras per environment (CameraRig) fused into the environment's maps by ONE ingest_cameras / update_cameras per
         # step (step() -> _step_rig()); None = one camera at the robot pose, the step as it always was
@@ -352,6 +402,17 @@ class BatchedEpisodes:
             self.depth_pool, self.rgb_pool = depth_pool.to(self.device), rgb_pool.to(self.device)
         if self.rooms is not None:
             self.pose_table, self.tf_table = self.rooms.pose_table, self.rooms.tf_table
+            if self.closed_loop:
+                # live state: where each robot is; an episode starts at the environment's open-loop start pose (diverse, in
+                # free space) and returns there when episode_len wraps
+                self._start_xy, self._start_k = self.pose_table[0][:, :2].copy(), self.rooms.k_table[0].copy()
+                self.world_xy, self.world_k = self._start_xy.copy(), self._start_k.copy()
+                self._collided = np.zeros(n_envs, bool)
+                self._live_frames = None
+                z = lambda dt: np.zeros(n_envs, dt)   # noqa: E731
+                self.closed_loop_stats = {"path_length": z(np.float64), "collisions": z(np.int64), "forward_steps": z(np.int64),
+                                          "turn_steps": z(np.int64), "stops": z(np.int64)}
+                self.last_poses = self.last_world_actions = None
         else:
             trajs = [Trajectory(i) for i in self.env_ids]
             self.pose_table = np.array([[tr.step() for tr in trajs] for _ in range(episode_len)])  # [L,E,3]
@@ -457,6 +518,11 @@ class BatchedEpisodes:
         self.prev_goals = np.zeros((self.E, 2))
         if self.pointnav is not None:
             self.pointnav.reset()
+        if self.closed_loop:
+            self.world_xy, self.world_k = self._start_xy.copy(), self._start_k.copy()
+            self._collided[:] = False
+            if hasattr(self.controller, "reset"):
+                self.controller.reset()
 
     # ------------------------------------------------------------------------------------------ scripted detector head
     def _sightings_at(self, t_ep: int) -> List:
@@ -732,11 +798,15 @@ class BatchedEpisodes:
     def prepare(self, n_steps: int) -> None:
         """Render the depth frames of the next ``n_steps`` steps now (rooms world), so that a timed region that follows
         finds its inputs resident in HBM, as the benchmark contract asks."""
+        if self.closed_loop:
+            return      # nothing to pre-render: the poses of the coming steps depend on the actions still to be taken
         if self.rooms is not None:
             self.rooms.prepare(self.t % self.episode_len, n_steps)
 
     def current_depth(self, n: int) -> torch.Tensor:
         """The depth frames of the first ``n`` environments at the current step (diagnostics: bench.count_stored_cells)."""
+        if self.closed_loop:
+            return self._live_depth(self.t % self.episode_len, self._poses_tf(0)[1], fresh=True)[:n]
         if self.rooms is not None:
             return self.rooms.frame(self.t % self.episode_len)[:n]
         return self.depth_pool[self.t % self.depth_pool.shape[0]][:n].to(self.device)
@@ -747,6 +817,10 @@ class BatchedEpisodes:
         before a measurement, instead of timing the empty world of an episode's first steps."""
         saved = (self.blip2, self.detector, self.sam, self.selectors, self.pointnav, self.object_maps)
         self.blip2 = self.detector = self.sam = self.selectors = self.pointnav = self.object_maps = None
+        if self.closed_loop:
+            # the decision is host logic and stays (only the models are stubbed): without it the robots would stand still.  The
+            # actions come from ``controller`` for these steps
+            self.selectors = saved[3]
         try:
             for _ in range(n_steps):
                 self.step()
@@ -819,6 +893,9 @@ class BatchedEpisodes:
                     mine = v[env_of == e]
                     if len(mine):
                         best[e] = float(max(explore_reduce_values(mine.tolist(), self.exploration_thresh)))
+        # closed loop: where the robot ended up, not where the plan would have had it (getattr: tests/test_multi_prompt_cpu.py
+        # calls this method on a stand-in object; the constructor always sets the attribute)
+        final = self._poses_tf(0)[0] if getattr(self, "closed_loop", False) else self.pose_table[(self.t - 1) % self.episode_len]
         for e, env_id in enumerate(self.env_ids):
             episode_id = self.episodes_done * len(self.env_ids) + e
             scene = f"synthetic{env_id:04d}"
@@ -826,7 +903,7 @@ class BatchedEpisodes:
                 continue
             log_episode(episode_id, scene, {
                 "target_object": self.targets[e], "num_steps": int(self.episode_len),
-                "final_pose": [float(v) for v in self.pose_table[(self.t - 1) % self.episode_len][e]],
+                "final_pose": [float(v) for v in final[e]],
                 "num_frontiers": int(len(n_fr[e])) if n_fr is not None else 0,
                 "best_frontier_value_last_step": best[e]})
 
@@ -860,15 +937,52 @@ class BatchedEpisodes:
         """The rig's observations of episode step ``t_ep``: (frames [E*K,H,W] device f32, camera transforms [E*K,4,4], slot of
         each frame [E*K], camera index of each frame [E*K]) -- environment-major, cameras in rig order."""
         K = len(self.rig)
-        tf = self.rig.camera_tfs(self.tf_table[t_ep]).reshape(self.E * K, 4, 4)
+        tf = self.rig.camera_tfs(self._poses_tf(t_ep)[1]).reshape(self.E * K, 4, 4)
         cam = np.tile(np.arange(K), self.E)
         hf = np.array([self.fov if c.hfov is None else c.hfov for c in self.rig.cameras])[cam]
         lo, hi = (np.array([getattr(c, a) for c in self.rig.cameras], np.float64)[cam] for a in ("min_depth", "max_depth"))
-        frames = self.rooms.render_cameras(tf, hf, lo, hi)
+        frames = self.rooms.cast_cameras(tf, hf, lo, hi) if self.closed_loop else self.rooms.render_cameras(tf, hf, lo, hi)
         if self.rooms.painter is not None:     # scripted objects: in front of the DESIGNATED camera (the detector stage's frame)
             d_idx = torch.from_numpy(np.arange(self.E) * K + self.rig.designated).to(self.device)
             frames[d_idx] = self.rooms.painter(t_ep, frames[d_idx])
         return frames, tf, np.repeat(np.arange(self.E), K), cam
+
+    # ---- closed loop: the live poses, the frames seen from them, the world's answer to the step's actions
+    def _poses_tf(self, t_ep: int):
+        """(poses [E,3] = x, y, yaw; robot -> episodic transforms [E,4,4]) of this step: the planned tour's at episode step
+        ``t_ep``, or, closed-loop, where the robots are."""
+        if not self.closed_loop:
+            return self.pose_table[t_ep], self.tf_table[t_ep]
+        yaw = np.array(YAWS)[self.world_k]
+        return (np.concatenate([self.world_xy, yaw[:, None]], axis=1),
+                np.stack([tf_of(x, y, k) for (x, y), k in zip(self.world_xy, self.world_k)]))
+
+    def _live_depth(self, t_ep: int, tf: np.ndarray, fresh: bool = False) -> torch.Tensor:
+        """The robots' own depth frames at the transforms ``tf`` (one kernel launch), scripted objects painted in.  The step
+        renders into one buffer it keeps (every reader of the previous step's frames was joined back into the main stream)."""
+        if self._live_frames is None and not fresh:
+            self._live_frames = torch.empty((self.E, self.H, self.W), dtype=torch.float32, device=self.device)
+        d = self.rooms.cast_cameras(tf, out=None if fresh else self._live_frames)
+        return self.rooms.painter(t_ep, d) if self.rooms.painter is not None else d
+
+    def _advance_world(self, poses: np.ndarray) -> None:
+        """Closed loop, after the policy acted: the step's actions -- the PointNav controller's discrete ids with the policy's
+        TURN_LEFT / STOP overrides, else ``controller``'s -- move the robots (synthetic.step_poses); ``poses`` are the poses
+        the step observed from."""
+        if self.pointnav is not None and self.last_actions is not None:
+            acts = self.last_actions.detach().reshape(self.E).cpu().numpy().astype(np.int64)
+        else:
+            acts = np.asarray(self.controller.act(self.last_modes, self.last_rho_theta, self.last_stops, self._collided),
+                              np.int64).reshape(self.E)
+        self.world_xy, self.world_k, self._collided = step_poses(self.world_xy, self.world_k, acts)
+        st = self.closed_loop_stats
+        fwd = acts == ACTION_FORWARD
+        st["forward_steps"] += fwd
+        st["collisions"] += self._collided
+        st["turn_steps"] += (acts == ACTION_TURN_LEFT) | (acts == ACTION_TURN_RIGHT)
+        st["stops"] += acts == ACTION_STOP
+        st["path_length"] += 0.25 * (fwd & ~self._collided)
+        self.last_poses, self.last_world_actions = np.array(poses, np.float64), acts
 
     # ---- the pieces step() and _step_rig() share; each enqueues on the stream that is current when it is called
     def _transported(self, rgb: torch.Tensor) -> torch.Tensor:
@@ -935,7 +1049,7 @@ class BatchedEpisodes:
         t_ep = self.t % self.episode_len
         rig, E = self.rig, self.E
         cams = rig.cameras
-        poses, tf_robot = self.pose_table[t_ep], self.tf_table[t_ep]
+        poses, tf_robot = self._poses_tf(t_ep)
         depth, tf, slot, cam = self.rig_observations(t_ep)
         per = lambda f: np.array([f(c) for c in cams])[cam]   # noqa: E731
         lo, hi = per(lambda c: c.min_depth), per(lambda c: c.max_depth)
@@ -995,6 +1109,8 @@ class BatchedEpisodes:
         self.values.update_cameras(cos.reshape(n_v, self.C), None, tf[v_idx], lo[v_idx], hi[v_idx], hfov[v_idx], slot[v_idx],
                                    colmax=self._rig_keys)
         self._score_and_act(wps, env_of, poses, t_ep, lambda: depth[torch.from_numpy(d_rows).to(self.device)])
+        if self.closed_loop:
+            self._advance_world(poses)
 
     def step(self) -> None:
         if self.t and self.t % self.episode_len == 0:
@@ -1009,13 +1125,17 @@ class BatchedEpisodes:
         if self.host_inputs:
             depth = self.depth_dev.copy_(self.depth_pool[k], non_blocking=True)
             rgb = self.rgb_dev.copy_(self.rgb_pool[kr], non_blocking=True)
+        elif self.closed_loop:
+            depth, rgb = None, self.rgb_pool[kr]       # rendered below, from the live poses
         elif self.rooms is not None:
             depth, rgb = self.rooms.frame(self.t % self.episode_len), self.rgb_pool[kr]
         else:
             depth, rgb = self.depth_pool[k], self.rgb_pool[kr]
         rgb = self._transported(rgb)
         t_ep = self.t % self.episode_len
-        poses, tf = self.pose_table[t_ep], self.tf_table[t_ep]
+        poses, tf = self._poses_tf(t_ep)
+        if self.closed_loop:
+            depth = self._live_depth(t_ep, tf)
         # ---- mapping, part 1 (side stream): one depth pass feeds both maps, then the obstacle/frontier pipeline
         main, side = self._open_step(poses)
         with torch.cuda.stream(side):
@@ -1071,3 +1191,5 @@ class BatchedEpisodes:
             cos.record_stream(main)
         self.values.update(cos.reshape(self.E, self.C), None, tf, MIN_DEPTH, MAX_DEPTH, self.fov, colmax=colmax)
         self._score_and_act(wps, env_of, poses, t_ep, lambda: depth)
+        if self.closed_loop:
+            self._advance_world(poses)
