@@ -799,6 +799,24 @@ int vlfm_jpeg_decode_batched(const uint8_t* d_files, size_t files_bytes, const i
 int vlfm_rooms_raycast(const double* d_cameras, int n, const double* d_boxes, int n_boxes, int H, int W, float* d_out,
                        void* stream);
 
+/* Rooms world with objects (ABI 16): vlfm_rooms_raycast's frames with up to 8 objects per environment -- axis-aligned boxes
+ * with a vertical extent -- standing in front of the walls, rendered with occlusion in ONE launch (plus a fill of d_stats),
+ * bit for bit what vlfm_amd.synthetic.render_objects_numpy / object_stats_numpy compute.
+ *   d_objects  [n_envs][8][8] doubles: x0, y0, x1, y1, z0, z1, valid (0 = no object in this slot), pad
+ *   d_env_of   [n] the environment (row of d_objects) each camera looks at, in [0, n_envs) (checked by the caller: the
+ *              kernel treats anything else as "no objects")
+ *   d_depth    [n][H][W] float; d_ids [n][H][W] uint8: 0 = wall / floor, k + 1 = object slot k
+ *   d_stats    [n][8][5] int32 per object slot: visible pixels, first / last column, first / last row;
+ *              (0, W, -1, H, -1) for an object without a pixel
+ * Per column u an object is hit by the walls' slab test at t = f64(f32(tmin)) and covers the rows r with
+ * ceil((height - z1) fx / t) <= r - H/2 <= floor((height - z0) fx / t); a pixel takes the f32 minimum of wall, floor and
+ * the covering objects, and the id of the nearest covering object (lowest slot among equals) where that is STRICTLY nearer
+ * than wall and floor.  The boxes, 69 bytes per image column and one band of rows must fit 64 KB of LDS, and H <= 32768
+ * (VLFM_ERR_INVALID otherwise, nothing written). */
+int vlfm_rooms_raycast_objects(const double* d_cameras, int n, const double* d_boxes, int n_boxes, const double* d_objects,
+                               const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids,
+                               int32_t* d_stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

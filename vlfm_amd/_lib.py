@@ -212,6 +212,7 @@ def lib() -> ctypes.CDLL:
         L.vlfm_jpeg_decode_batched.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ci, ci, ci, vp, vp, ci, vp, ci, ci,
                                                ctypes.c_size_t, ci, vp, vp, vp, ctypes.c_size_t, vp]
         L.vlfm_rooms_raycast.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp]
+        L.vlfm_rooms_raycast_objects.argtypes = [vp, ci, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp]
         _lib = L
     return _lib
 

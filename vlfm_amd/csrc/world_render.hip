@@ -142,3 +142,269 @@ extern "C" int vlfm_rooms_raycast(const double* d_cameras, int n, const double* 
                  reinterpret_cast<const CameraRec*>(d_cameras), d_boxes, n_boxes, H, W, band, vec4, d_out);
     return check_launch("rooms_raycast_kernel");
 }
+
+// ------------------------------------------------------------------------------------------------------------ world objects
+// vlfm_rooms_raycast_objects: the same frames with up to 8 objects per environment standing in front of the walls -- axis-aligned
+// boxes with a vertical extent (x0 y0 x1 y1 z0 z1) -- rendered with occlusion, plus an instance-id plane and per (camera, object)
+// the visible pixel count and bounding box.  Arithmetic (synthetic.render_objects_numpy is the host statement of it):
+//
+//   column u, object k:  the walls' slab test against the footprint; t = f64(f32(tmin)), or no hit
+//                        rlo = ceil(((height - z1) * fx) / t),  rhi = floor(((height - z0) * fx) / t)     (one rounding per step)
+//                        nobj = normalise(t);  the object covers the rows r with rlo <= r - H/2 <= rhi
+//   pixel:               depth = min(wall(u), floor(r), nobj of the covering objects)
+//                        id    = k + 1 of the covering object with the smallest nobj (lowest k among equals) if that is
+//                                STRICTLY smaller than min(wall(u), floor(r)), else 0
+//
+// Layout: the grid and the bands of the kernel above.  Per column a workgroup keeps one 8-byte entry (nobj, rlo, rhi as int16)
+// per object slot and a byte whose bit k says "object k can show in this column of this band": an object that misses the column,
+// lies wholly outside the band's rows or is not nearer than the column's wall never sets its bit, so a group of four columns
+// whose four mask bytes are zero costs one more LDS dword read than in the kernel above and stores a zero id dword.
+// Stats: every lane keeps the running (count, bounding box) of the object it saw last in registers and flushes it into the
+// workgroup's LDS table with integer atomics when the object changes and at the end; then ONE global integer atomic per
+// (workgroup, object, field) that saw a pixel.  Integer add / min / max commute: the result does not depend on the order.
+namespace vlfm {
+namespace world {
+
+constexpr int MAX_OBJECTS = 8;                // vlfm_amd.h: objects per environment
+constexpr int OBJ_REC = 8;                    // doubles per object record: x0 y0 x1 y1 z0 z1 valid pad
+
+struct ObjCol {                               // one object in one column
+    float nobj;
+    short rlo, rhi;                           // rows relative to H/2, clamped to the int16 range (H <= 32768: |r - H/2| fits)
+};
+
+struct LaneStats {                            // the run of pixels of one object a lane is accumulating
+    int id, count, cmin, cmax, rmin, rmax;
+};
+
+__device__ __forceinline__ void stats_flush(const LaneStats& a, int* sstat) {
+    if (a.id == 0) return;
+    int* s = sstat + 5 * (a.id - 1);
+    atomicAdd(s + 0, a.count);
+    atomicMin(s + 1, a.cmin);
+    atomicMax(s + 2, a.cmax);
+    atomicMin(s + 3, a.rmin);
+    atomicMax(s + 4, a.rmax);
+}
+
+__device__ __forceinline__ void stats_note(LaneStats& a, int id, int c, int r, int* sstat) {
+    if (id != a.id) {
+        stats_flush(a, sstat);
+        a = LaneStats{id, 0, c, c, r, r};
+    }
+    ++a.count;
+    a.cmin = min(a.cmin, c);
+    a.cmax = max(a.cmax, c);
+    a.rmin = min(a.rmin, r);
+    a.rmax = max(a.rmax, r);
+}
+
+// one pixel: `bg` = min(wall, floor); the objects named by `mask` in column `u`; rr = r - H/2
+__device__ __forceinline__ float shade(float bg, unsigned mask, const ObjCol* __restrict__ ent, int wp, int u, int rr, int& id) {
+    float best = __builtin_inff();
+    id = 0;
+    while (mask) {
+        const int k = __ffs(mask) - 1;
+        mask &= mask - 1;
+        const ObjCol e = ent[k * wp + u];
+        if ((int)e.rlo <= rr && rr <= (int)e.rhi && e.nobj < best) {      // ascending k, strict <: the lowest k among equals
+            best = e.nobj;
+            id = k + 1;
+        }
+    }
+    if (!(best < bg)) id = 0;
+    return fminf(bg, best);
+}
+
+__global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
+    const CameraRec* __restrict__ cameras, const double* __restrict__ boxes, int n_boxes, const double* __restrict__ objects,
+    const int32_t* __restrict__ env_of, int n_envs, int H, int W, int band, int vec4, float* __restrict__ out,
+    uint8_t* __restrict__ ids, int32_t* __restrict__ stats) {
+    extern __shared__ double smem[];
+    const int r0 = blockIdx.x * band;
+    if (r0 >= H) return;                                   // (uniform for the workgroup: before any barrier)
+    const int rows = min(band, H - r0);
+    const int tid = threadIdx.x;
+    const int wp = (W + 3) & ~3;
+    double* sbox = smem;                                   // [n_boxes][4]
+    double* sobj = sbox + 4 * n_boxes;                     // [8][8]
+    ObjCol* ent = reinterpret_cast<ObjCol*>(sobj + MAX_OBJECTS * OBJ_REC);      // [8][wp]
+    float* ncol = reinterpret_cast<float*>(ent + MAX_OBJECTS * wp);            // [wp]: 16-byte aligned (32 * n_boxes + 512 + 64 * wp in)
+    float* nrow = ncol + wp;                               // [band]
+    int* sstat = reinterpret_cast<int*>(nrow + band);      // [8][5]
+    uint8_t* cmask = reinterpret_cast<uint8_t*>(sstat + 5 * MAX_OBJECTS);       // [wp]: 4-byte aligned
+    const CameraRec cam = cameras[blockIdx.y];
+    const int env = env_of[blockIdx.y];
+    const bool has_env = env >= 0 && env < n_envs;         // (the host wrapper refuses anything else; never read out of bounds)
+    for (int i = tid; i < 4 * n_boxes; i += THREADS) sbox[i] = boxes[i];
+    for (int i = tid; i < MAX_OBJECTS * OBJ_REC; i += THREADS) sobj[i] = has_env ? objects[(size_t)env * MAX_OBJECTS * OBJ_REC + i] : 0.0;
+    for (int i = tid; i < 5 * MAX_OBJECTS; i += THREADS) {
+        const int f = i % 5;
+        sstat[i] = f == 0 ? 0 : (f == 1 ? W : (f == 3 ? H : -1));
+    }
+    const double span = cam.hi - cam.lo;
+    const double inf = __builtin_inf();
+    for (int i = tid; i < rows; i += THREADS) {
+        const int rr = r0 + i - H / 2;
+        const double floor_d = rr > 0 ? __dmul_rn(cam.height, cam.fx) / (double)rr : inf;
+        nrow[i] = normalise(floor_d, cam.lo, span);
+    }
+    __syncthreads();
+    const int rr_first = r0 - H / 2, rr_last = r0 + rows - 1 - H / 2;
+    for (int u = tid; u < wp; u += THREADS) {
+        if (u >= W) {                                      // padding columns of the last group of four: never shaded
+            cmask[u] = 0;
+            continue;
+        }
+        const double m = -(double)(u - W / 2) / cam.fx;
+        double dx = __dsub_rn(cam.c, __dmul_rn(cam.s, m));
+        double dy = __dadd_rn(cam.s, __dmul_rn(cam.c, m));
+        if (fabs(dx) < 1e-12) dx = 1e-12;
+        if (fabs(dy) < 1e-12) dy = 1e-12;
+        double best = inf;
+        for (int b = 0; b < n_boxes; ++b) {
+            const double tx0 = (sbox[4 * b + 0] - cam.x) / dx, tx1 = (sbox[4 * b + 2] - cam.x) / dx;
+            const double ty0 = (sbox[4 * b + 1] - cam.y) / dy, ty1 = (sbox[4 * b + 3] - cam.y) / dy;
+            const double tmin = fmax(fmin(tx0, tx1), fmin(ty0, ty1));
+            const double tmax = fmin(fmax(tx0, tx1), fmax(ty0, ty1));
+            if (tmax >= fmax(tmin, 0.0) && tmin > 0.0) best = fmin(best, tmin);
+        }
+        const float wall = (float)best;                    // the host path keeps the profile in f32
+        const float nwall = normalise((double)wall, cam.lo, span);
+        ncol[u] = nwall;
+        unsigned mask = 0;
+        for (int k = 0; k < MAX_OBJECTS; ++k) {
+            const double* o = sobj + OBJ_REC * k;
+            if (o[6] == 0.0) continue;
+            const double tx0 = (o[0] - cam.x) / dx, tx1 = (o[2] - cam.x) / dx;
+            const double ty0 = (o[1] - cam.y) / dy, ty1 = (o[3] - cam.y) / dy;
+            const double tmin = fmax(fmin(tx0, tx1), fmin(ty0, ty1));
+            const double tmax = fmin(fmax(tx0, tx1), fmax(ty0, ty1));
+            if (!(tmax >= fmax(tmin, 0.0) && tmin > 0.0)) continue;
+            const double t = (double)(float)tmin;
+            const double lo_r = ceil(__dmul_rn(__dsub_rn(cam.height, o[5]), cam.fx) / t);
+            const double hi_r = floor(__dmul_rn(__dsub_rn(cam.height, o[4]), cam.fx) / t);
+            // (a NaN bound -- 0 / 0 when f32(tmin) underflowed -- covers nothing; the comparisons below are false for it)
+            if (!(lo_r <= hi_r) || !(lo_r <= (double)rr_last) || !(hi_r >= (double)rr_first)) continue;
+            const float nobj = normalise(t, cam.lo, span);
+            if (!(nobj < nwall)) continue;                 // not strictly nearer than the column's wall: neither depth nor id changes
+            ObjCol e;
+            e.nobj = nobj;
+            e.rlo = (short)fmax(lo_r, -32768.0);           // (lo_r <= rr_last < 32768 and hi_r >= rr_first >= -32768 here)
+            e.rhi = (short)fmin(hi_r, 32767.0);
+            ent[k * wp + u] = e;
+            mask |= 1u << k;
+        }
+        cmask[u] = (uint8_t)mask;
+    }
+    __syncthreads();
+    const size_t base = ((size_t)blockIdx.y * H + r0) * (size_t)W;     // the band's rows are contiguous
+    float* dst = out + base;
+    uint8_t* idst = ids + base;
+    LaneStats acc{0, 0, 0, 0, 0, 0};
+    if (vec4) {
+        const int ng = W >> 2, total = rows * ng;
+        const int dr = THREADS / ng, dg = THREADS % ng;
+        int r = tid / ng, g = tid % ng;
+        float4* dst4 = reinterpret_cast<float4*>(dst);
+        uint32_t* idst4 = reinterpret_cast<uint32_t*>(idst);
+        const float4* ncol4 = reinterpret_cast<const float4*>(ncol);
+        const uint32_t* cmask4 = reinterpret_cast<const uint32_t*>(cmask);
+        for (int idx = tid; idx < total; idx += THREADS) {
+            const float4 cv = ncol4[g];
+            const float rv = nrow[r];
+            const uint32_t m4 = cmask4[g];
+            float4 d = make_float4(fminf(cv.x, rv), fminf(cv.y, rv), fminf(cv.z, rv), fminf(cv.w, rv));
+            uint32_t id4 = 0;
+            if (m4) {
+                const int rr = r0 + r - H / 2, u = 4 * g;
+                int id;
+                if (m4 & 0xffu) { d.x = shade(d.x, m4 & 0xffu, ent, wp, u, rr, id); if (id) { id4 |= (uint32_t)id; stats_note(acc, id, u, r0 + r, sstat); } }
+                if ((m4 >> 8) & 0xffu) { d.y = shade(d.y, (m4 >> 8) & 0xffu, ent, wp, u + 1, rr, id); if (id) { id4 |= (uint32_t)id << 8; stats_note(acc, id, u + 1, r0 + r, sstat); } }
+                if ((m4 >> 16) & 0xffu) { d.z = shade(d.z, (m4 >> 16) & 0xffu, ent, wp, u + 2, rr, id); if (id) { id4 |= (uint32_t)id << 16; stats_note(acc, id, u + 2, r0 + r, sstat); } }
+                if (m4 >> 24) { d.w = shade(d.w, m4 >> 24, ent, wp, u + 3, rr, id); if (id) { id4 |= (uint32_t)id << 24; stats_note(acc, id, u + 3, r0 + r, sstat); } }
+            }
+            dst4[idx] = d;
+            idst4[idx] = id4;
+            r += dr;
+            g += dg;
+            if (g >= ng) {
+                g -= ng;
+                ++r;
+            }
+        }
+    } else {
+        const int total = rows * W;
+        const int dr = THREADS / W, dc = THREADS % W;
+        int r = tid / W, c = tid % W;
+        for (int idx = tid; idx < total; idx += THREADS) {
+            float d = fminf(ncol[c], nrow[r]);
+            int id = 0;
+            const unsigned m1 = cmask[c];
+            if (m1) {
+                d = shade(d, m1, ent, wp, c, r0 + r - H / 2, id);
+                if (id) stats_note(acc, id, c, r0 + r, sstat);
+            }
+            dst[idx] = d;
+            idst[idx] = (uint8_t)id;
+            r += dr;
+            c += dc;
+            if (c >= W) {
+                c -= W;
+                ++r;
+            }
+        }
+    }
+    stats_flush(acc, sstat);
+    __syncthreads();
+    if (tid < 5 * MAX_OBJECTS && sstat[5 * (tid / 5)] > 0) {          // one atomic per (workgroup, object that showed, field)
+        int32_t* gdst = stats + (size_t)blockIdx.y * 5 * MAX_OBJECTS + tid;
+        const int f = tid % 5, v = sstat[tid];
+        if (f == 0) atomicAdd(gdst, v);
+        else if (f == 1 || f == 3) atomicMin(gdst, v);
+        else atomicMax(gdst, v);
+    }
+}
+
+// d_stats rows to (0, W, -1, H, -1): the identity of the add / min / max / min / max the render kernel applies
+__global__ void rooms_stats_init_kernel(int32_t* __restrict__ stats, int total, int H, int W) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int f = i % 5;
+    stats[i] = f == 0 ? 0 : (f == 1 ? W : (f == 3 ? H : -1));
+}
+
+}  // namespace world
+}  // namespace vlfm
+
+extern "C" int vlfm_rooms_raycast_objects(const double* d_cameras, int n, const double* d_boxes, int n_boxes,
+                                          const double* d_objects, const int32_t* d_env_of, int n_envs, int H, int W,
+                                          float* d_depth, uint8_t* d_ids, int32_t* d_stats, void* stream) {
+    static_assert(sizeof(ObjCol) == 8, "object column entry layout");
+    if (n < 0 || n > 65535 || n_boxes < 0 || n_envs <= 0 || H <= 0 || W <= 0 || H > 32768 ||
+        (n > 0 && (!d_cameras || !d_objects || !d_env_of || !d_depth || !d_ids || !d_stats)) || (n_boxes > 0 && !d_boxes))
+        return fail(VLFM_ERR_INVALID, "rooms_raycast_objects: bad argument");
+    if (n == 0) return VLFM_OK;
+    const long long want = 4LL * device_cu_count();         // row bands: as in vlfm_rooms_raycast
+    long long bands = (want + n - 1) / n;
+    const long long most = (H + MIN_BAND_ROWS - 1) / MIN_BAND_ROWS;
+    bands = bands < 1 ? 1 : (bands > most ? most : bands);
+    const int band = (int)((H + bands - 1) / bands);
+    const int grid_x = (H + band - 1) / band;
+    const size_t wp = (size_t)((W + 3) & ~3);
+    const size_t lds = (size_t)n_boxes * 32 + MAX_OBJECTS * OBJ_REC * 8 + wp * MAX_OBJECTS * sizeof(ObjCol) + wp * 4 +
+                       (size_t)band * 4 + 5 * MAX_OBJECTS * 4 + wp;
+    if (lds > 64 * 1024)
+        return fail(VLFM_ERR_INVALID, "rooms_raycast_objects: boxes + 69 bytes per image column + one row band exceed 64 KB of LDS");
+    const int vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_depth) % 16 == 0) && (reinterpret_cast<uintptr_t>(d_ids) % 4 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    const int total = n * 5 * MAX_OBJECTS;
+    VLFM_KLAUNCH(rooms_stats_init_kernel, dim3((total + THREADS - 1) / THREADS), dim3(THREADS), 0, st, d_stats, total, H, W);
+    int rc = check_launch("rooms_stats_init_kernel");
+    if (rc != VLFM_OK) return rc;
+    VLFM_TIMED("rooms_raycast_objects_kernel", st);
+    VLFM_KLAUNCH(rooms_raycast_objects_kernel, dim3(grid_x, n), dim3(THREADS), lds, st,
+                 reinterpret_cast<const CameraRec*>(d_cameras), d_boxes, n_boxes, d_objects, d_env_of, n_envs, H, W, band, vec4,
+                 d_depth, d_ids, d_stats);
+    return check_launch("rooms_raycast_objects_kernel");
+}

@@ -24,7 +24,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -34,7 +34,7 @@ from .mapping.base_map import require_gpu
 from .mapping.value_map import ValueMapBatch
 from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TURN_RIGHT, BOXES, CAMERA_HEIGHT, HEADINGS, \
     MAX_DEPTH, MIN_DEPTH, YAWS, BangBangController, ReplayController, Trajectory, camera_intrinsics, depth_frame, integrate, \
-    plan_actions, pose_to_tf, rgb_frame, step_poses, tf_of
+    WORLD_MAX_OBJECTS, object_layout, plan_actions, pose_to_tf, rect_distance, rgb_frame, step_poses, tf_of
 
 PROMPT = "Seems like there is a target_object ahead."  # vlfm/policy/base_objectnav_policy.py:377
 TARGETS = ["chair", "bed", "potted plant", "toilet", "tv", "couch"]  # HM3D ObjectNav categories
@@ -105,6 +105,53 @@ class ScriptedSightings:
             return [(target, 0.9, (cx, cy, ax, ay), depth)]
         wrong = "tv" if target != "tv" else "chair"
         return [(wrong, 0.93, (cx, cy, ax, ay), depth)] if (g & 1) else [(target, 0.35, (cx, cy, ax, ay), depth)]
+
+
+@dataclass(frozen=True)
+class WorldObjects:
+    """``BatchedEpisodes(world_objects=WorldObjects(...))``: target and distractor objects stand IN the rooms world
+    (synthetic.object_layout), the ray caster renders them with occlusion and reports what is in view, and the environments
+    run ObjectNav episodes that end on the policy's STOP (success within ``success_distance`` metres of the target's
+    footprint), on "no frontier" or after ``max_episode_steps`` steps.  An object with at least ``min_pixels`` visible pixels
+    is a sighting of its class at ``confidence``; from a quarter of that on, at ``faint_confidence`` (which the confidence filter
+    has to drop).  ``layout``: any callable (env_id, episode, robot_xy) -> [(class, box6)], at most 8 objects."""
+    min_pixels: int = 200
+    confidence: float = 0.9
+    faint_confidence: float = 0.35
+    success_distance: float = 1.0
+    max_episode_steps: int = 500
+    layout: Callable = object_layout
+
+
+def sightings_from_stats(stats, classes, min_pixels: int, confidence: float, faint_confidence: float):
+    """The scripted detector head of a world with objects: ``stats`` [E,8,5] (visible pixels, first / last column, first / last
+    row per object slot, as the ray caster returns them) and ``classes`` (per environment the class names of its slots) ->
+    [(env slot, class, confidence, (cx, cy, ax, ay), object slot)] in the format of ``_sightings_at``: the VISIBLE bounding box
+    as centre and half-extents.  ``count >= min_pixels``: confident; ``min_pixels / 4 <= count < min_pixels``: faint; less:
+    not seen.  Pure host function."""
+    out = []
+    for e, names in enumerate(classes):
+        for k, name in enumerate(names):
+            count, cmin, cmax, rmin, rmax = (int(v) for v in stats[e][k])
+            if 4 * count < min_pixels:
+                continue
+            box = ((cmin + cmax + 1) / 2, (rmin + rmax + 1) / 2, (cmax - cmin + 1) / 2, (rmax - rmin + 1) / 2)
+            out.append((e, name, confidence if count >= min_pixels else faint_confidence, box, k))
+    return out
+
+
+def objectnav_outcome(stopped: bool, navigating: bool, no_frontier: bool, steps_done: int, max_steps: int, robot_xy, target_box,
+                      success_distance: float) -> Optional[str]:
+    """How an ObjectNav episode ends with this step, or None if it goes on: a STOP issued while navigating to an object goal is
+    a "success" when the robot is within ``success_distance`` of the target's footprint rectangle (``target_box``; None = the
+    layout has no target) and a "wrong_stop" otherwise; a stop for want of frontiers is "no_frontier"; ``steps_done`` steps
+    (this one included) reaching ``max_steps`` is a "timeout".  Pure host function."""
+    if stopped and navigating:
+        near = target_box is not None and rect_distance(robot_xy, target_box) <= success_distance
+        return "success" if near else "wrong_stop"
+    if no_frontier:
+        return "no_frontier"
+    return "timeout" if steps_done >= max_steps else None
 
 
 SAM_BATCH_BUCKETS = (1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 20, 24, 28, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256)
@@ -286,6 +333,54 @@ class RoomsRenderer:
                                                      out.data_ptr(), stream), "rooms_raycast")
         return out
 
+    @torch.no_grad()
+    def cast_cameras_objects(self, tf: np.ndarray, objects: np.ndarray, env_of, hfov: Optional[np.ndarray] = None,
+                             min_depth=None, max_depth=None, out: Optional[torch.Tensor] = None):
+        """``cast_cameras`` with the objects of the cameras' environments standing in the world (vlfm_rooms_raycast_objects, one
+        launch on the current stream): ``objects`` [n_envs,8,8] f64 on the host -- x0, y0, x1, y1, z0, z1, valid, pad per slot;
+        it crosses in one small copy -- and ``env_of`` [n], the row of ``objects`` each camera looks at.  Returns (depth f32
+        [n,H,W], ids u8 [n,H,W]: 0 = wall / floor, k + 1 = object slot k, stats int32 [n,8,5]: visible pixels, first / last
+        column, first / last row of each slot; (0, W, -1, H, -1) for none), all on the device, bit for bit
+        synthetic.render_objects_numpy / object_stats_numpy.  ``out``: the depth buffer, as in ``cast_cameras``."""
+        from .synthetic import WORLD_MAX_OBJECTS
+
+        tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
+        n = len(tf)
+        objects = np.ascontiguousarray(objects, np.float64)
+        if objects.ndim != 3 or objects.shape[0] < 1 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
+            raise ValueError(f"cast_cameras_objects: objects must be [n_envs >= 1, {WORLD_MAX_OBJECTS}, 8]")
+        env_of = np.ascontiguousarray(np.asarray(env_of).reshape(-1), np.int32)
+        if len(env_of) != n or np.any((env_of < 0) | (env_of >= len(objects))):
+            raise ValueError("cast_cameras_objects: env_of must name one row of objects per camera")
+        rec = np.empty((n, 8), np.float64)
+        rec[:, 0:2], rec[:, 2:4], rec[:, 4] = tf[:, :2, 3], tf[:, :2, 0], tf[:, 2, 3]
+        rec[:, 5] = camera_intrinsics(self.W)[0] if hfov is None else self.W / (2 * np.tan(np.asarray(hfov, np.float64) / 2))
+        rec[:, 6] = MIN_DEPTH if min_depth is None else np.asarray(min_depth, np.float64)
+        rec[:, 7] = MAX_DEPTH if max_depth is None else np.asarray(max_depth, np.float64)
+        if not np.all(rec[:, 7] > rec[:, 6]):
+            raise ValueError("cast_cameras_objects: every camera needs max_depth > min_depth")
+        dev = self.boxes.device
+        if out is None:
+            out = torch.empty((n, self.H, self.W), dtype=torch.float32, device=dev)
+        elif out.shape != (n, self.H, self.W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"cast_cameras_objects: out must be a contiguous f32 [{n},{self.H},{self.W}] tensor on {dev}")
+        ids = torch.empty((n, self.H, self.W), dtype=torch.uint8, device=dev)
+        stats = torch.empty((n, WORLD_MAX_OBJECTS, 5), dtype=torch.int32, device=dev)
+        if n == 0:
+            return out, ids, stats
+        with torch.cuda.device(dev):
+            # camera records, object records and env_of in ONE host buffer and one copy (all 8-byte aligned pieces)
+            blob = np.concatenate([rec.reshape(-1), objects.reshape(-1), np.zeros((n + 1) // 2, np.float64)])
+            blob[rec.size + objects.size:].view(np.int32)[:n] = env_of
+            d_blob = torch.from_numpy(blob).to(dev)
+            p = d_blob.data_ptr()
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().vlfm_rooms_raycast_objects(p, n, self.boxes.data_ptr(), len(self.boxes), p + 8 * rec.size,
+                                                             p + 8 * (rec.size + objects.size), len(objects), self.H, self.W,
+                                                             out.data_ptr(), ids.data_ptr(), stats.data_ptr(), stream),
+                       "rooms_raycast_objects")
+        return out, ids, stats
+
     def prepare(self, t0: int, n: int) -> None:
         self.window = torch.stack([self.render((t0 + i) % self.L) for i in range(n)])
         self.window_t0 = t0
@@ -318,7 +413,7 @@ class BatchedEpisodes:
                  object_map_erosion_size: float = 5, concurrent_vlm_max_envs: int = 0,
                  render_trajectories: bool = False, emulate_jpeg: bool = False, rig: Optional[CameraRig] = None,
                  text_prompt: str = PROMPT, exploration_thresh: Optional[float] = None, closed_loop: bool = False,
-                 controller=None) -> None:
+                 controller=None, world_objects: Optional[WorldObjects] = None) -> None:
         # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
         # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -343,6 +438,16 @@ class BatchedEpisodes:
         elif controller is not None:
             raise ValueError("a controller acts only in a closed_loop harness")
         self.controller = (controller if controller is not None else BangBangController()) if self.closed_loop else None
+        # world_objects: objects stand in the rooms world, the detector head reports what the ray caster saw of them, and the
+        # environments run scored ObjectNav episodes (WorldObjects); None = every step is the step it always was
+        self.world_objects = world_objects
+        if world_objects is not None:
+            if not self.closed_loop:
+                raise ValueError("world_objects needs closed_loop=True: the objects are seen from where the robot is")
+            if sightings is not None:
+                raise ValueError("world_objects replaces the scripted sightings: give one of the two")
+            if rig is not None:
+                raise ValueError("world_objects renders the robot's own camera: it cannot be combined with a camera rig")
         self.device = require_gpu(device)
         # rig: K cameras per environment (CameraRig) fused into the environment's maps by ONE ingest_cameras / update_cameras per
         # step (step() -> _step_rig()); None = one camera at the robot pose, the step as it always was
@@ -413,6 +518,16 @@ class BatchedEpisodes:
                 self.closed_loop_stats = {"path_length": z(np.float64), "collisions": z(np.int64), "forward_steps": z(np.int64),
                                           "turn_steps": z(np.int64), "stops": z(np.int64)}
                 self.last_poses = self.last_world_actions = None
+                if world_objects is not None:
+                    self._ep_index, self._ep_clock = z(np.int64), z(np.int64)
+                    self._ep_path, self._ep_first = z(np.float64), np.full(n_envs, -1, np.int64)
+                    self._live_ids = self._live_stats = None
+                    self._live_sightings: List = []
+                    self.objectnav_stats = {"episodes": z(np.int64), "successes": z(np.int64), "wrong_stops": z(np.int64),
+                                            "no_frontier_stops": z(np.int64), "timeouts": z(np.int64), "episode_env": [],
+                                            "episode_outcome": [], "episode_steps": [], "episode_path_length": [],
+                                            "episode_first_sighting": []}
+                    self._draw_layouts(range(n_envs))
         else:
             trajs = [Trajectory(i) for i in self.env_ids]
             self.pose_table = np.array([[tr.step() for tr in trajs] for _ in range(episode_len)])  # [L,E,3]
@@ -523,11 +638,19 @@ class BatchedEpisodes:
             self._collided[:] = False
             if hasattr(self.controller, "reset"):
                 self.controller.reset()
+            if self.world_objects is not None:      # running episodes end as timeouts; everybody draws a layout from the start pose
+                running = np.flatnonzero(self._ep_clock > 0)
+                for e in running:
+                    self._score_episode(int(e), "timeout")
+                self._ep_index[running] += 1
+                self._draw_layouts(range(self.E))
 
     # ------------------------------------------------------------------------------------------ scripted detector head
     def _sightings_at(self, t_ep: int) -> List:
         """[(env slot, phrase, confidence, (cx, cy, ax, ay), depth)] of episode step ``t_ep`` (memoised: the painter asks when
         the frame is rendered, the step asks again when it runs)."""
+        if self.world_objects is not None:
+            return self._live_sightings          # what the ray caster saw of the objects in this step's frames
         if t_ep not in self._sight_cache:
             if len(self._sight_cache) > 4096:
                 self._sight_cache.clear()
@@ -631,7 +754,10 @@ class BatchedEpisodes:
                 pe = envs + [envs[-1]] * (n_pad - len(envs))
                 pb = np.concatenate([boxes, np.repeat(boxes[-1:], n_pad - len(envs), axis=0)], axis=0)
                 masks = self.sam.segment_bboxes(rgb[pe], torch.from_numpy(pb).to(torch.float32)[:, None, :])[:len(envs), 0]
-            if masks is None or self.scripted_masks:
+            if (masks is None or self.scripted_masks) and self.world_objects is not None:
+                # the instance's own pixels: the id plane of the frame the box was reported from
+                masks = torch.stack([self._live_ids[e] == self._instance_of(e, boxes[j]) + 1 for j, e in enumerate(envs)])
+            elif masks is None or self.scripted_masks:
                 # without pretrained weights the segmenter's logits mean nothing: the mask handed on is the box's inscribed ellipse
                 # (the MobileSAM forward above still ran and is timed); also the stand-in when no segmenter is attached
                 masks = ellipse_masks(np.stack([(boxes[:, 0] + boxes[:, 2]) / 2, (boxes[:, 1] + boxes[:, 3]) / 2,
@@ -652,6 +778,8 @@ class BatchedEpisodes:
     def _episode_steps(self, t_ep: int) -> np.ndarray:
         """Steps since each environment's last episode start (the policy's ``_num_steps``): the harness step for everybody
         without a script, the script's per-environment episode clock with one."""
+        if getattr(self, "world_objects", None) is not None:
+            return self._ep_clock                   # per environment: an episode ends when ITS robot stops or gives up
         if self.sightings is None:
             return np.full(self.E, t_ep, np.int64)
         return self._schedule(t_ep)[0]
@@ -672,9 +800,12 @@ class BatchedEpisodes:
         """Environments whose scripted episode ends with this step (the robot "arrived": the reference's episode ends on STOP):
         their maps, object map, selector and controller state are reset for the next episode, which starts in place."""
         self.last_episode_end = np.zeros(self.E, bool)
-        if self.sightings is None:
+        if self.world_objects is not None:
+            done = self._objectnav_ends()
+        elif self.sightings is None:
             return
-        done = np.flatnonzero(self._schedule(t_ep)[1]).tolist()
+        else:
+            done = np.flatnonzero(self._schedule(t_ep)[1]).tolist()
         if not done:
             return
         from .policy_step import FrontierSelector
@@ -692,6 +823,68 @@ class BatchedEpisodes:
         if self.pointnav is not None:
             self.pointnav.reset(done)
         self.object_stats["episodes_ended"] = self.object_stats.get("episodes_ended", 0) + len(done)
+        if self.world_objects is not None:       # the next episode: a new layout around the robot, which stays where it is
+            if hasattr(self.controller, "reset"):
+                self.controller.reset(done)
+            self._ep_index[done] += 1
+            self._draw_layouts(done)
+
+    # ---- world objects: layouts, what the ray caster saw, how episodes end
+    def _draw_layouts(self, envs) -> None:
+        """The objects of the episodes that ``envs`` start now, from where their robots stand: ``self._objects`` [E,8,8] (the ray
+        caster's records), ``self._object_classes`` and the slot of each environment's target (-1: none)."""
+        if not hasattr(self, "_objects"):
+            self._objects = np.zeros((self.E, WORLD_MAX_OBJECTS, 8))
+            self._object_classes: List[List[str]] = [[] for _ in range(self.E)]
+            self._target_slot = np.full(self.E, -1, np.int64)
+        for e in envs:
+            lay = list(self.world_objects.layout(self.env_ids[e], int(self._ep_index[e]), self.world_xy[e].copy()))
+            if len(lay) > WORLD_MAX_OBJECTS:
+                raise ValueError(f"a layout may hold at most {WORLD_MAX_OBJECTS} objects")
+            self._objects[e] = 0.0
+            for k, (_, box) in enumerate(lay):
+                self._objects[e, k, :6], self._objects[e, k, 6] = np.asarray(box, np.float64), 1.0
+            self._object_classes[e] = [cls for cls, _ in lay]
+            self._target_slot[e] = next((k for k, (cls, _) in enumerate(lay) if cls == self.targets[e]), -1)
+            self._ep_clock[e], self._ep_path[e], self._ep_first[e] = 0, 0.0, -1
+
+    def _instance_of(self, e: int, box_px: np.ndarray) -> int:
+        """The object slot behind a detection of environment ``e``'s target class with the pixel box ``box_px`` (xyxy): the
+        sighting of that class whose visible bounding box is nearest."""
+        best, slot = None, -1
+        for (se, phrase, _, (cx, cy, ax, ay), k) in self._live_sightings:
+            if se == e and phrase == self.targets[e]:
+                d = float(np.abs(np.array([cx - ax, cy - ay, cx + ax, cy + ay]) - box_px).sum())
+                if best is None or d < best:
+                    best, slot = d, k
+        return slot
+
+    def _score_episode(self, e: int, outcome: str) -> None:
+        st = self.objectnav_stats
+        st["episodes"][e] += 1
+        st[{"success": "successes", "wrong_stop": "wrong_stops", "no_frontier": "no_frontier_stops",
+            "timeout": "timeouts"}[outcome]][e] += 1
+        st["episode_env"].append(e)
+        st["episode_outcome"].append(outcome)
+        st["episode_steps"].append(int(self._ep_clock[e]))
+        st["episode_path_length"].append(float(self._ep_path[e]))
+        st["episode_first_sighting"].append(int(self._ep_first[e]))
+
+    def _objectnav_ends(self) -> List[int]:
+        """Decided after ``_navigate``: the environments whose ObjectNav episode ends with this step (objectnav_outcome), scored."""
+        wo, done = self.world_objects, []
+        self._ep_clock += 1                          # this step is taken
+        for e in range(self.E):
+            navigating = bool(self.last_modes) and self.last_modes[e] == "navigate"
+            exploring = bool(self.last_modes) and self.last_modes[e] == "explore"
+            k = int(self._target_slot[e])
+            out = objectnav_outcome(bool(self.last_stops[e]), navigating, bool(self.last_stops[e]) and exploring,
+                                    int(self._ep_clock[e]), wo.max_episode_steps, self.world_xy[e],
+                                    self._objects[e, k, :4] if k >= 0 else None, wo.success_distance)
+            if out is not None:
+                self._score_episode(e, out)
+                done.append(e)
+        return done
 
     def _decide(self, wps: np.ndarray, env_of: np.ndarray, vals, poses: np.ndarray, t_ep: int):
         """BaseObjectNavPolicy.act's three modes for every environment (base_objectnav_policy.py:126-135): 12 initialisation
@@ -911,7 +1104,8 @@ class BatchedEpisodes:
         """The detector on the frames ``rgb`` [E,H,W,3] of episode step ``t_ep`` (one frame per environment) -> per-environment
         ObjectDetections, or None without a detector and without a scripted head."""
         # YOLOv7 takes the frames alone; GroundingDINO is prompted (MP3D-style caption, habitat_policies.py:139-141)
-        scripted = self.sightings is not None and (self.detector is not None or self.object_maps is not None)
+        scripted = (self.sightings is not None or getattr(self, "world_objects", None) is not None) and \
+            (self.detector is not None or self.object_maps is not None)
         if self.detector is None:
             d = None
         elif self.detector_is_prompted:
@@ -962,6 +1156,18 @@ class BatchedEpisodes:
         renders into one buffer it keeps (every reader of the previous step's frames was joined back into the main stream)."""
         if self._live_frames is None and not fresh:
             self._live_frames = torch.empty((self.E, self.H, self.W), dtype=torch.float32, device=self.device)
+        if self.world_objects is not None:
+            d, ids, stats = self.rooms.cast_cameras_objects(tf, self._objects, np.arange(self.E),
+                                                            out=None if fresh else self._live_frames)
+            if not fresh:
+                wo = self.world_objects
+                self._live_ids, self._live_stats = ids, stats.cpu().numpy()     # the one extra D2H copy of this mode
+                self._live_sightings = sightings_from_stats(self._live_stats, self._object_classes, wo.min_pixels, wo.confidence,
+                                                            wo.faint_confidence)
+                for (e, _, conf, _, k) in self._live_sightings:
+                    if k == self._target_slot[e] and conf == wo.confidence and self._ep_first[e] < 0:
+                        self._ep_first[e] = self._ep_clock[e]
+            return d
         d = self.rooms.cast_cameras(tf, out=None if fresh else self._live_frames)
         return self.rooms.painter(t_ep, d) if self.rooms.painter is not None else d
 
@@ -974,7 +1180,11 @@ class BatchedEpisodes:
         else:
             acts = np.asarray(self.controller.act(self.last_modes, self.last_rho_theta, self.last_stops, self._collided),
                               np.int64).reshape(self.E)
-        self.world_xy, self.world_k, self._collided = step_poses(self.world_xy, self.world_k, acts)
+        extra = None
+        if self.world_objects is not None:
+            acts = np.where(self.last_episode_end, ACTION_STOP, acts)     # an episode that ended: the robot stays where it is
+            extra = np.where(self._objects[:, :, 6:7] != 0.0, self._objects[:, :, :4], np.nan)
+        self.world_xy, self.world_k, self._collided = step_poses(self.world_xy, self.world_k, acts, extra)
         st = self.closed_loop_stats
         fwd = acts == ACTION_FORWARD
         st["forward_steps"] += fwd
@@ -982,6 +1192,8 @@ class BatchedEpisodes:
         st["turn_steps"] += (acts == ACTION_TURN_LEFT) | (acts == ACTION_TURN_RIGHT)
         st["stops"] += acts == ACTION_STOP
         st["path_length"] += 0.25 * (fwd & ~self._collided)
+        if self.world_objects is not None:
+            self._ep_path += 0.25 * (fwd & ~self._collided)
         self.last_poses, self.last_world_actions = np.array(poses, np.float64), acts
 
     # ---- the pieces step() and _step_rig() share; each enqueues on the stream that is current when it is called

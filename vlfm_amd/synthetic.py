@@ -229,11 +229,13 @@ ACTION_STOP, ACTION_FORWARD, ACTION_TURN_LEFT, ACTION_TURN_RIGHT = 0, 1, 2, 3
 STEP_MARGIN = 0.2          # the clearance plan_actions asserts for every pose of the tour
 
 
-def step_poses(xy, k, actions):
+def step_poses(xy, k, actions, extra_boxes=None):
     """Apply one action per robot: ``xy`` [E,2] f64 positions, ``k`` [E] heading indices (multiples of 30 degrees),
     ``actions`` [E] action ids -> (xy, k, collided [E] bool), new arrays.  A turn changes k by +-1 mod 12; FORWARD adds
     0.25 * HEADINGS[k] (the expression of `integrate`) unless the new position lies within STEP_MARGIN of a box, in which case
-    the move is refused (pose unchanged, ``collided`` set: no sliding along walls); STOP changes nothing."""
+    the move is refused (pose unchanged, ``collided`` set: no sliding along walls); STOP changes nothing.  ``extra_boxes``
+    [E,K,4] f64: per robot up to K more boxes (x0, y0, x1, y1; a NaN row is "none") that refuse its moves like the walls do:
+    the objects of its own environment (world objects section below)."""
     xy = np.array(xy, np.float64).reshape(-1, 2)
     k = np.array(k, np.int64).reshape(-1)
     a = np.asarray(actions).reshape(-1).astype(np.int64)
@@ -247,6 +249,13 @@ def step_poses(xy, k, actions):
     m = STEP_MARGIN
     blocked = np.any((BOXES[None, :, 0] - m <= new[:, None, 0]) & (new[:, None, 0] <= BOXES[None, :, 2] + m) &
                      (BOXES[None, :, 1] - m <= new[:, None, 1]) & (new[:, None, 1] <= BOXES[None, :, 3] + m), axis=1)
+    if extra_boxes is not None:
+        x = np.asarray(extra_boxes, np.float64)
+        if x.ndim != 3 or x.shape[0] != len(xy) or x.shape[2] != 4:
+            raise ValueError("step_poses: extra_boxes must be [E,K,4]")
+        # (every comparison with a NaN row is False: such a row blocks nothing)
+        blocked = blocked | np.any((x[:, :, 0] - m <= new[:, None, 0]) & (new[:, None, 0] <= x[:, :, 2] + m) &
+                                   (x[:, :, 1] - m <= new[:, None, 1]) & (new[:, None, 1] <= x[:, :, 3] + m), axis=1)
     forward = a == ACTION_FORWARD
     collided = forward & blocked
     xy[forward & ~blocked] = new[forward & ~blocked]
@@ -329,3 +338,114 @@ class ReplayController:
         row = self.actions[self.i % len(self.actions)]
         self.i += 1
         return row.copy()
+
+
+# ---------------------------------------------------------------------------------------------- world objects
+# Target and distractor objects standing IN the rooms world: an object is an axis-aligned box with a vertical extent,
+# (x0, y0, x1, y1, z0, z1) in metres, plus a class name.  The ray caster renders them with occlusion (csrc/world_render.hip:
+# vlfm_rooms_raycast_objects; `render_objects_numpy` below is the host statement of the same arithmetic), `step_poses` refuses
+# moves into them, and the batched harness reports as detections what is actually in view (BatchedEpisodes(world_objects=...)).
+WORLD_MAX_OBJECTS = 8
+# free-standing centres, hand-placed over the hall and the ring rooms: `object_layout` asserts that each keeps 0.65 m to every
+# wall (the largest footprint half-extent, 0.5 m, plus most of a robot's STEP_MARGIN)
+OBJECT_SPOTS = [(0.0, 2.6), (3.2, 0.4), (-0.4, -1.8), (-3.2, 0.2), (3.2, -3.2), (-3.3, 3.2),            # hall
+                (5.6, 3.0), (8.6, 0.6), (8.8, 8.6), (2.2, 5.6), (1.8, 8.8), (-5.2, 6.6), (-8.6, 8.6), (-8.6, 2.0),   # ring
+                (-5.8, -1.2), (-8.6, -3.0), (-3.0, -6.0), (0.0, -8.6), (4.0, -5.4), (8.6, -8.0), (5.2, -8.6), (-8.0, -5.6)]
+# class (the harness's TARGETS, in its order) -> (half-extent x, half-extent y, z0, z1).  All stand on the floor with a top
+# between 0.7 and 1.5 m: they cut the obstacle map's 0.61-0.88 m band, so what refuses a move is also an obstacle on the map.
+OBJECT_SIZES = {"chair": (0.25, 0.25, 0.0, 0.9), "bed": (0.5, 0.45, 0.0, 0.7), "potted plant": (0.2, 0.2, 0.0, 1.3),
+                "toilet": (0.2, 0.3, 0.0, 0.8), "tv": (0.45, 0.1, 0.0, 1.2), "couch": (0.5, 0.35, 0.0, 0.85)}
+OBJECT_START_CLEARANCE = 1.5   # no object on a spot nearer than this to the robot: no episode starts solved
+
+
+def _mix32(a: int, b: int, salt: int) -> int:
+    """The 32-bit mixer of harness.ScriptedSightings._mix (a murmur3-style finaliser): a pure function, no global RNG."""
+    h = (a * 2654435761 + b * 40503 + salt * 97 + 0x9E3779B9) & 0xFFFFFFFF
+    h ^= h >> 16
+    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
+    h ^= h >> 13
+    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
+    return h ^ (h >> 16)
+
+
+def object_box(cls: str, cx: float, cy: float):
+    """The box6 of an object of class ``cls`` centred on (cx, cy)."""
+    hx, hy, z0, z1 = OBJECT_SIZES[cls]
+    return (cx - hx, cy - hy, cx + hx, cy + hy, z0, z1)
+
+
+def object_layout(env_id: int, episode: int, robot_xy):
+    """[(class, box6)] of environment ``env_id``'s episode number ``episode`` for a robot that starts it at ``robot_xy``: the
+    environment's target class (the harness's rule: class ``env_id mod 6``) on one spot, one distractor of another class on
+    another; both spots picked by the hash of (env_id, episode) among the spots farther than OBJECT_START_CLEARANCE from the
+    robot.  Deterministic."""
+    assert len(OBJECT_SPOTS) >= 12
+    for (sx, sy) in OBJECT_SPOTS:                       # hand-placed, like the legs of the tour
+        assert not _blocked(sx, sy, 0.65), (sx, sy)
+    classes = list(OBJECT_SIZES)
+    target = classes[env_id % len(classes)]
+    rx, ry = float(robot_xy[0]), float(robot_xy[1])
+    free = [p for p in OBJECT_SPOTS if np.hypot(p[0] - rx, p[1] - ry) > OBJECT_START_CLEARANCE]
+    a = _mix32(env_id, episode, 21) % len(free)
+    b = (a + 1 + _mix32(env_id, episode, 22) % (len(free) - 1)) % len(free)
+    other = [c for c in classes if c != target]
+    distractor = other[_mix32(env_id, episode, 23) % len(other)]
+    return [(target, object_box(target, *free[a])), (distractor, object_box(distractor, *free[b]))]
+
+
+def rect_distance(xy, box) -> float:
+    """Distance from the point ``xy`` to the rectangle box[:4] = (x0, y0, x1, y1); 0 inside."""
+    dx = max(box[0] - xy[0], 0.0, xy[0] - box[2])
+    dy = max(box[1] - xy[1], 0.0, xy[1] - box[3])
+    return float(np.hypot(dx, dy))
+
+
+def _normalise(d, lo, hi):
+    return np.clip((d - lo) / (hi - lo), 1e-3, 1.0).astype(np.float32)
+
+
+def render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6):
+    """(depth f32 [H,W], ids u8 [H,W]) seen by ONE camera at (x, y), heading (c, s) = (cos, sin), ``height`` above the floor,
+    focal length ``fx`` pixels, range [lo, hi]: the walls and the floor of `wall_profile` / `depth_from_profile`, and the
+    objects ``boxes6`` [K,6] in front of them.  Per column u an object is hit at t = f64(f32(tmin)) of the walls' slab test
+    and covers the rows rr = r - H//2 with ceil((height - z1) fx / t) <= rr <= floor((height - z0) fx / t); the pixel's depth
+    is the f32 minimum of the normalised wall, floor and covering objects, its id is k + 1 of the nearest covering object
+    (lowest k among equals) where that is STRICTLY nearer than wall and floor, else 0.  Whole-array f64 NumPy."""
+    boxes6 = np.asarray(boxes6, np.float64).reshape(-1, 6)
+    m = -(np.arange(W, dtype=np.float64) - W // 2) / fx
+    dx, dy = c - s * m, s + c * m
+    dx = np.where(np.abs(dx) < 1e-12, 1e-12, dx)[:, None]
+    dy = np.where(np.abs(dy) < 1e-12, 1e-12, dy)[:, None]
+
+    def slab(b):       # [W,B] distance along the optical axis to each box, inf where the column misses it
+        tx0, tx1 = (b[None, :, 0] - x) / dx, (b[None, :, 2] - x) / dx
+        ty0, ty1 = (b[None, :, 1] - y) / dy, (b[None, :, 3] - y) / dy
+        tmin = np.maximum(np.minimum(tx0, tx1), np.minimum(ty0, ty1))
+        tmax = np.minimum(np.maximum(tx0, tx1), np.maximum(ty0, ty1))
+        return np.where((tmax >= np.maximum(tmin, 0.0)) & (tmin > 0.0), tmin, np.inf)
+
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        wall = slab(BOXES).min(axis=1).astype(np.float32).astype(np.float64)
+        rr = (np.arange(H) - H // 2)[:, None]
+        floor = np.where(rr > 0, (height * fx) / np.maximum(rr, 1), np.inf)
+        bg = np.minimum(_normalise(wall, lo, hi)[None, :], _normalise(floor, lo, hi))              # [H,W] f32
+        if not len(boxes6):
+            return bg, np.zeros((H, W), np.uint8)
+        t = slab(boxes6).astype(np.float32).astype(np.float64)                                      # [W,K]
+        rlo = np.ceil(((height - boxes6[None, :, 5]) * fx) / t)
+        rhi = np.floor(((height - boxes6[None, :, 4]) * fx) / t)
+        cover = np.isfinite(t)[None] & (rlo[None] <= rr[:, :, None]) & (rr[:, :, None] <= rhi[None])   # [H,W,K]
+        layers = np.where(cover, _normalise(t, lo, hi)[None], np.float32(np.inf))
+    best, arg = layers.min(axis=2), layers.argmin(axis=2)           # (argmin: the first, i.e. lowest, k among equals)
+    return np.minimum(bg, best), np.where(best < bg, arg + 1, 0).astype(np.uint8)
+
+
+def object_stats_numpy(ids, K: int = WORLD_MAX_OBJECTS) -> np.ndarray:
+    """int32 [K,5] = (pixel count, first column, last column, first row, last row) of each object k in the id plane ``ids``
+    (object k has id k + 1); (0, W, -1, H, -1) for an object with no pixel."""
+    H, W = ids.shape
+    out = np.empty((K, 5), np.int32)
+    for k in range(K):
+        r, c = np.nonzero(ids == k + 1)
+        out[k] = (len(r), c.min(), c.max(), r.min(), r.max()) if len(r) else (0, W, -1, H, -1)
+    return out
