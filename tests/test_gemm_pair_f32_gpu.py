@@ -80,8 +80,10 @@ def test_pair_gemm_rejects_unsupported_shapes(gpu_device):
 
 
 def test_pair_gemm_is_deterministic_under_repetition(gpu_device):
-    """Race screen (the convention of tests/test_gemm_f16_gpu.py): the epilogue keeps the next tile's K-tile 0 in flight and its stores
-    drain under the next tile, so a wrong wait count is a RARE wrong tile -- 30 launches, bitwise equal to the first."""
+    """Race screen (the convention of tests/test_gemm_f16_gpu.py) at ONE tile per workgroup: (1028, 1536, 1408) is 5 x 12 = 60 tiles on
+    a grid of 60, so it covers the counted waits of one tile's K loop and the epilogue's re-request of its own K-tile 0 -- 30 launches,
+    bitwise equal to the first.  No workgroup has a next tile here: the prefetch that is read and the stores that drain under the next
+    tile's first phases are screened on a 780-tile schedule in tests/test_qformer_batch_scale_gpu.py."""
     from vlfm_amd.vlm import ops
 
     shape = (1028, 1536, 1408)
