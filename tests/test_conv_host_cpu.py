@@ -1,11 +1,13 @@
 """Host side of csrc/conv_nhwc.hip (no GPU): the filter-row packing the kernel reads (det_ops.pack_conv_weight), the layer shapes
 it takes, the in-place concatenation plan of the yolov7-e6e graph, and the tile-shape estimate (vlfm_conv_nhwc_tile).  The
-convolution itself is checked on the GPU in tests/test_conv_nhwc_gpu.py; the reference side is vlfm/vlm/yolov7.py:35-48,89."""
+convolution itself is checked on the GPU in tests/test_conv_nhwc_gpu.py and tests/test_conv_nhwc_exact_gpu.py; the reference side is
+vlfm/vlm/yolov7.py:35-48,89."""
 import ctypes
 
 import pytest
 import torch
 
+import conv_ref
 from vlfm_amd import _lib
 from vlfm_amd.vlm import det_ops
 from vlfm_amd.vlm.yolov7_e6e import Concat, Conv, YoloV7E6E
@@ -83,8 +85,28 @@ def tile(pixels, cin, cout, k):
     return bm.value, bn.value
 
 
+# the five shapes conv_nhwc.hip compiles (256 x 256 and 256 x 128 could never be picked -- the proof is a comment at pick_cfg --
+# and were removed); conv_ref.TILE_WITNESS has a layer for each, which tests/test_conv_nhwc_exact_gpu.py runs
+TILE_SHAPES = [(256, 64), (128, 128), (128, 64), (64, 128), (64, 64)]
+TILE_WITNESS = {shape: (B * Ho * Wo, cout) for shape, (B, Ho, Wo, cout) in conv_ref.TILE_WITNESS.items()}
+assert TILE_WITNESS == {(64, 64): (70, 72), (128, 64): (8211, 72), (128, 128): (10881, 136), (256, 64): (16390, 136),
+                        (64, 128): (5379, 328)}
+
+
+def test_every_tile_shape_has_a_witness_and_nothing_else_is_picked():
+    assert set(TILE_WITNESS) == set(TILE_SHAPES)
+    for shape, (pixels, cout) in TILE_WITNESS.items():
+        for cin in (64, 72, 512):                     # every shape's cost has the same K factor: the pick is (pixels, cout)'s alone
+            for k in (1, 3):
+                assert tile(pixels, cin, cout, k) == shape, (shape, pixels, cin, cout, k)
+    for pixels in (1, 70, 560, 2240, 8960, 35840, 1146880):
+        for cout in range(8, 1281, 8):
+            t = tile(pixels, 64, cout, 3)
+            assert t in TILE_SHAPES and t == tile(pixels, 72, cout, 1), (pixels, cout, t)
+
+
 def test_tile_shape_estimate():
-    shapes = {(256, 256), (256, 128), (256, 64), (128, 128), (128, 64), (64, 128), (64, 64)}
+    shapes = set(TILE_SHAPES)
     for pixels in (1, 70, 4480, 35840, 1146880, 9175040):
         for cin, cout, k in ((64, 64, 3), (128, 128, 3), (512, 512, 3), (1280, 640, 1), (320, 255, 1), (80, 80, 1), (16, 80, 3)):
             assert tile(pixels, cin, cout, k) in shapes

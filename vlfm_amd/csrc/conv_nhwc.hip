@@ -14,7 +14,7 @@
 // tap falls into the zero padding (or beyond M) fetch from a 16-byte zero page instead -- no im2col buffer, no padded copy.
 // LDS layout, the XOR slot permutation that makes the MFMA fragment reads conflict-free, the operand roles (A-operand = filter rows,
 // so a lane ends up with 4 consecutive output channels of one pixel) and the transposing epilogue are those of gemm_f16.hip.
-// Tile: BM pixels x BN channels from seven shapes between 256 x 256 and 64 x 64, chosen per layer by a cost estimate (pick_cfg);
+// Tile: BM pixels x BN channels from five shapes between 256 x 64 / 128 x 128 and 64 x 64, chosen per layer by a cost estimate (pick_cfg);
 // 8 wavefronts; two LDS buffers; the lock-step schedule.  Pixel strides of input and output are arguments: a layer can read a channel slice of a concatenation buffer
 // and write into one.
 #include <hip/hip_runtime.h>
@@ -267,26 +267,32 @@ static int launch(ConvArgs a, int act, hipStream_t stream) {
 // fill the chip when a layer has few pixels (7x10 and 14x20 feature maps) and waste less on narrow layers.
 struct TileCfg { int bm, bn; double rate; };      // rate: relative throughput of a CU running this shape (a tile sweep:
                                                   // with these the pick is within 1.3 % of the best shape summed over the probe layers)
-static const TileCfg kCfg[] = {{256, 256, 0.85}, {256, 128, 1.00}, {256, 64, 0.95}, {128, 128, 1.05},
-                               {128, 64, 0.85},  {64, 128, 0.82},  {64, 64, 0.62}};
-constexpr int kNumCfg = 7;   // (a 512 x 64 shape -- a third less LDS traffic per MFMA, but one workgroup per CU -- measured 24 % slower
+static const TileCfg kCfg[] = {{256, 64, 0.95}, {128, 128, 1.05}, {128, 64, 0.85}, {64, 128, 0.82}, {64, 64, 0.62}};
+constexpr int kNumCfg = 5;   // (a 512 x 64 shape -- a third less LDS traffic per MFMA, but one workgroup per CU -- measured 24 % slower
                              //  than 256 x 64 on the 64-channel layers and removed)
 
 template <bool GEN>
 static int launch_cfg(const ConvArgs& a, int cfg, int act, hipStream_t stream) {
     switch (cfg) {
-        case 0: return launch<256, 256, 64, 128, GEN>(a, act, stream);
-        case 1: return launch<256, 128, 64, 64, GEN>(a, act, stream);
-        case 2: return launch<256, 64, 32, 64, GEN>(a, act, stream);
-        case 3: return launch<128, 128, 32, 64, GEN>(a, act, stream);
-        case 4: return launch<128, 64, 32, 32, GEN>(a, act, stream);
-        case 5: return launch<64, 128, 16, 64, GEN>(a, act, stream);
+        case 0: return launch<256, 64, 32, 64, GEN>(a, act, stream);
+        case 1: return launch<128, 128, 32, 64, GEN>(a, act, stream);
+        case 2: return launch<128, 64, 32, 32, GEN>(a, act, stream);
+        case 3: return launch<64, 128, 16, 64, GEN>(a, act, stream);
         default: return launch<64, 64, 16, 32, GEN>(a, act, stream);
     }
 }
 
 // Estimated time of a layer under a tile shape, in units of (256 x 256 x 64) MFMA tiles at the big shape's rate: the busiest CU works
 // through ceil(tiles / 256) tiles (workgroups are dealt round-robin), each costing its padded volume over the shape's rate.
+// Every shape's cost carries the same factor (ktiles + 1.5), so the pick depends on M and cout alone.
+//
+// The table once held 256 x 256 (rate 0.85) and 256 x 128 (rate 1.00) as well.  Neither could ever be picked, because 128 x 128
+// (rate 1.05) is strictly cheaper for every layer: ceil(M / 128) <= 2 ceil(M / 256) and the same for cout, so 128 x 128 has at most 4 x the tiles of
+// 256 x 256 and at most 2 x those of 256 x 128 (same 128 channels), and ceil(4 n / 256) <= 4 ceil(n / 256) carries that to the
+// per-CU counts per0, per1.  With t = per_cu * (bm * bn / 65536) / rate (the common factor left out):
+//     t(128 x 128) <= 4 per0 * 0.25 / 1.05 = 0.952 per0  <  per0 / 0.85       = 1.176 per0 = t(256 x 256)
+//     t(128 x 128) <= 2 per1 * 0.25 / 1.05 = 0.476 per1  <  per1 * 0.5 / 1.00 = 0.5 per1   = t(256 x 128)
+// so their eight kernels were dead code and went; the pick of every layer is what it was (tests/test_conv_host_cpu.py).
 static int pick_cfg(int M, int cout, int ktiles) {
     int best = 0;
     double best_t = 1e300;
