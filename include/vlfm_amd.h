@@ -529,6 +529,37 @@ size_t vlfm_dbscan_scratch_bytes(int n);
 int vlfm_dbscan_largest_cluster(const double* d_points, int n, double eps, int min_points, void* d_scratch,
                                 size_t scratch_bytes, int32_t* d_labels, int32_t* d_keep, int32_t* d_num_keep, void* stream);
 
+/* The same three stages for ALL detections of a step (ABI 17).  The number of kernel launches does not depend on the number of
+ * jobs.  Results are bit-identical to the per-detection functions above.
+ *
+ * Stage 1, vlfm_object_cloud_batch_stats: d_masks [jobs][H][W] u8, d_erosion [jobs] i32 on the device (erosion iterations per job;
+ * max_erosion = their maximum, known to the host).  d_stats [jobs][4] i32 = (points of the eroded mask, first and last occupied
+ * column of the UN-eroded mask, or -1 -1 for an empty one, 0).  The eroded planes and their row offsets stay in d_scratch
+ * (vlfm_object_cloud_batch_scratch_bytes(jobs, H, W)) for stage 2.
+ *
+ * Stage 2, vlfm_object_cloud_batch_expand: d_depth [frames][H][W] f32; d_jobs [n_jobs][6] i32 on the device = (stage-1 job,
+ * depth frame, points to write, first output point, first entry of d_ranks or -1, 0).  Output point s of a job is the masked
+ * pixel of np.where rank d_ranks[first + s] (or rank s without a rank list) as f64 (z, -x, -y) in d_points [capacity][3];
+ * max_points = the largest "points to write".  scratch_jobs = the `jobs` of the stage-1 call that filled d_scratch.
+ *
+ * Stage 3, vlfm_dbscan_largest_cluster_batch: d_jobs [n_jobs][3] i64 on the device = (n, first point in d_points, byte offset of
+ * the job's scratch: a multiple of 256, vlfm_dbscan_batch_scratch_bytes(n) bytes); max_n = the largest n (<= 8192).  The points
+ * of job j's largest cluster are written in order to d_kept at the job's own first point, their number to d_num_keep[j]
+ * (0 = only noise, or n == 0).
+ *
+ * vlfm_object_cloud_launch_count: kernels launched so far by every function of this section (diagnostics, tests). */
+size_t vlfm_object_cloud_batch_scratch_bytes(int jobs, int height, int width);
+int vlfm_object_cloud_batch_stats(const uint8_t* d_masks, const int32_t* d_erosion, int jobs, int max_erosion, int height, int width,
+                                  void* d_scratch, int32_t* d_stats, void* stream);
+int vlfm_object_cloud_batch_expand(const float* d_depth, int frames, int height, int width, double min_depth, double max_depth,
+                                   double fx, double fy, const void* d_scratch, int scratch_jobs, const int32_t* d_jobs, int n_jobs,
+                                   int max_points, const int32_t* d_ranks, int n_ranks, double* d_points, int capacity, void* stream);
+size_t vlfm_dbscan_batch_scratch_bytes(int n);
+int vlfm_dbscan_largest_cluster_batch(const double* d_points, int capacity, const int64_t* d_jobs, int n_jobs, int max_n, double eps,
+                                      int min_points, void* d_scratch, size_t scratch_bytes, double* d_kept, int32_t* d_num_keep,
+                                      void* stream);
+long long vlfm_object_cloud_launch_count(void);
+
 /* ---------------------------------------------------------------------------------------------
  * ObstacleMap planes are bit-packed: 1 bit per cell, row stride ceil(cols/32) u32 words, bit x&31 of word x>>5.
  * ------------------------------------------------------------------------------------------- */

@@ -5,10 +5,16 @@
       objects of synthetic.object_layout and with a full set of 8 (the 8 spots nearest to the robot), and
       rooms_raycast_kernel (walls only) on the same cameras in the same session.
   (b) env-steps/s of a closed-loop harness with and without world_objects at 8 and 256 environments: stub cosines, no
-      detector, object_maps=True, alternating windows.
+      detector, object_maps=True, alternating windows; --batch-object-maps on | off | both runs the world_objects harness with
+      the batched object-map update, with one update_map per detection, or both side by side, and reports the object-cloud
+      kernel launches and host read-backs per step of each.
+  (c) --batch-trace: kernel time of the batched object-map update for 1 / 16 / 64 detections (objects in view of the tour poses) at 640x480
+      next to the per-detection kernels for the same detections, from one `rocprofv3 --kernel-trace --stats` run of its own.
 
     python tools/world_objects_probe.py [--steps 20] [--skip-steps] [--skip-trace] [--out profiles/world_objects_probe.txt]
-    python tools/world_objects_probe.py --trace-child        # the process (a) points rocprofv3 at"""
+    python tools/world_objects_probe.py --skip-trace --batch-object-maps both --batch-trace --out profiles/object_maps_batch_probe.txt
+    python tools/world_objects_probe.py --trace-child        # the process (a) points rocprofv3 at
+    python tools/world_objects_probe.py --batch-trace-child  # the process (c) points rocprofv3 at"""
 import argparse
 import glob
 import os
@@ -113,38 +119,151 @@ def probe_trace(lines, workdir: str) -> None:
     print(lines[-1], flush=True)
 
 
-def probe_steps(steps: int, lines) -> None:
+BATCH_TRACE_JOBS, BATCH_TRACE_REPS, BATCH_TRACE_WARMUP = (1, 16, 64), 10, 2
+BATCH_KERNELS = ("mask_pack_batch_kernel", "mask_erode_batch_kernel", "mask_stats_batch_kernel", "cloud_expand_batch_kernel",
+                 "dbscan_adjacency_batch_kernel", "dbscan_cluster_batch_kernel")
+SINGLE_KERNELS = ("mask_pack_kernel", "mask_erode_kernel", "cloud_extract_kernel", "dbscan_adjacency_kernel",
+                  "dbscan_cluster_kernel")
+
+
+def batch_trace_child() -> None:
+    """64 objects as the cameras of `scene` see them; per D in BATCH_TRACE_JOBS: warm-up + BATCH_TRACE_REPS
+    batched updates of the first D detections, then as many rounds of D per-detection updates."""
+    import numpy as np
+    import torch
+
+    from vlfm_amd.mapping import object_point_cloud_map as opm
+    from vlfm_amd.synthetic import MAX_DEPTH, MIN_DEPTH, camera_intrinsics
+
+    dev = torch.device("cuda:0")
+    # at the tour poses of `scene` the two objects of the default layout are in view of 16 cameras out of 256: the detections
+    # come from the full set of 8 objects per environment instead -- (camera, object) pairs with at least 600 visible pixels that keep 100 points after the erosion, repeated if there are fewer than 64
+    rr, tf, objects = scene(256, 8, dev)
+    depth = torch.empty((256, H, W), dtype=torch.float32, device=dev)
+    _, ids, seen = rr.cast_cameras_objects(tf, objects, np.arange(256), out=depth)
+    visible = seen[:, :, 0].cpu().numpy()
+    pairs = [(e, k) for e in range(256) for k in range(visible.shape[1]) if visible[e, k] >= 600][:4 * max(BATCH_TRACE_JOBS)]
+    masks_all = torch.stack([ids[e] == k + 1 for e, k in pairs])
+    _, st = opm.mask_stats_batch(masks_all.contiguous().view(torch.uint8), [5] * len(pairs), dev)
+    good = [i for i in range(len(pairs)) if st[i, 0] >= 100]
+    assert good, "no object in view"
+    good = (good * max(BATCH_TRACE_JOBS))[:max(BATCH_TRACE_JOBS)]
+    frames = [pairs[i][0] for i in good]
+    masks_all = masks_all[torch.tensor(good, device=dev)]
+    print("points " + " ".join(str(int(st[i, 0])) for i in good), flush=True)
+    fx, fy, _ = camera_intrinsics(W)
+    for D in BATCH_TRACE_JOBS:
+        maps = [opm.ObjectPointCloudMap(5, device=dev, rng=np.random.RandomState(j)) for j in range(D)]
+        masks = masks_all[:D]
+        for _ in range(BATCH_TRACE_WARMUP + BATCH_TRACE_REPS):
+            list(opm.extract_object_clouds_batch(maps, depth, frames[:D], masks, MIN_DEPTH, MAX_DEPTH, fx, fy))
+        torch.cuda.synchronize()
+        for _ in range(BATCH_TRACE_WARMUP + BATCH_TRACE_REPS):
+            for j in range(D):
+                maps[j]._extract_object_cloud(depth[frames[j]], masks[j], MIN_DEPTH, MAX_DEPTH, fx, fy)
+        torch.cuda.synchronize()
+
+
+def probe_batch_trace(lines, workdir: str) -> None:
+    import numpy as np
+
+    if shutil.which("rocprofv3") is None:
+        raise RuntimeError("rocprofv3 not found: the kernel-time leg needs it")
+    shutil.rmtree(workdir, ignore_errors=True)
+    os.makedirs(workdir)
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", workdir, "-o", "object_maps_batch", "--", sys.executable,
+           os.path.abspath(__file__), "--batch-trace-child"]
+    with open(os.path.join(workdir, "child.log"), "w") as log:
+        subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, timeout=420)
+    dbs = glob.glob(os.path.join(workdir, "**", "*_results.db"), recursive=True)
+    if not dbs:
+        raise RuntimeError(f"no rocprofv3 database under {workdir}")
+    rows = sqlite3.connect(dbs[0]).execute("select name, start, end from kernels order by start").fetchall()
+
+    def short(name):
+        base = name.split("(")[0].split("::")[-1]
+        return base[:-3] if base.endswith(".kd") else base
+
+    rows = [(short(n), (e - s) * 1e-3) for n, s, e in rows]
+    # calls end with their clustering kernel (every traced detection keeps >= 100 points, one wave, one chunk)
+    calls = {"batch": [], "single": []}
+    for kind, names, last in (("batch", BATCH_KERNELS, "dbscan_cluster_batch_kernel"), ("single", SINGLE_KERNELS, "dbscan_cluster_kernel")):
+        cur = {}
+        for n, us in rows:
+            if n not in names:
+                continue
+            cur[n] = cur.get(n, 0.0) + us
+            if n == last:
+                calls[kind].append(cur)
+                cur = {}
+    per = BATCH_TRACE_WARMUP + BATCH_TRACE_REPS
+    want = (per * len(BATCH_TRACE_JOBS), per * sum(BATCH_TRACE_JOBS))
+    if (len(calls["batch"]), len(calls["single"])) != want:
+        raise RuntimeError(f"expected {want} batched calls / detections in the trace, found {len(calls['batch'])} and {len(calls['single'])}")
+    b0 = s0 = 0
+    for D in BATCH_TRACE_JOBS:
+        batch = calls["batch"][b0 + BATCH_TRACE_WARMUP:b0 + per]
+        single = [calls["single"][s0 + r * D:s0 + (r + 1) * D] for r in range(BATCH_TRACE_WARMUP, per)]
+        b0, s0 = b0 + per, s0 + per * D
+        stage = lambda c: (c.get("mask_pack_batch_kernel", 0) + c.get("mask_erode_batch_kernel", 0) + c["mask_stats_batch_kernel"],
+                           c["cloud_expand_batch_kernel"], c["dbscan_adjacency_batch_kernel"], c["dbscan_cluster_batch_kernel"])
+        med = [float(np.median([stage(c)[i] for c in batch])) for i in range(4)]
+        tot = [sum(stage(c)) for c in batch]
+        one = [sum(sum(c.values()) for c in rnd) for rnd in single]
+        lines.append("batch-kernels D=%2d 640x480  stage 1 %8.1f us  expansion %7.1f us  adjacency %8.1f us  clusters %8.1f us  "
+                     "sum %9.1f us (%.1f-%.1f)   per-detection kernels for the same %d detections %9.1f us (%.1f-%.1f)   %d rounds each"
+                     % (D, *med, *stats(tot), D, *stats(one), len(batch)))
+        print(lines[-1], flush=True)
+
+
+def probe_steps(steps: int, lines, batch: str = "on") -> None:
     import time
 
     import torch
 
+    from vlfm_amd import _lib
     from vlfm_amd.harness import BatchedEpisodes, WorldObjects
+    from vlfm_amd.mapping import object_point_cloud_map as opm
 
     dev = torch.device("cuda:0")
+    L = _lib.lib()
     for E in (8, 256):
         kw = dict(device=dev, use_blip2=False, select_frontiers=True, episode_len=500, closed_loop=True, object_maps=True)
-        sims = {"with world_objects": BatchedEpisodes(E, world_objects=WorldObjects(), **kw), "without": BatchedEpisodes(E, **kw)}
+        sims = {}
+        if batch in ("on", "both"):
+            sims["with world_objects" if batch == "on" else "world_objects batched"] = BatchedEpisodes(
+                E, world_objects=WorldObjects(), batch_object_maps=True, **kw)
+        if batch in ("off", "both"):
+            sims["with world_objects" if batch == "off" else "world_objects one by one"] = BatchedEpisodes(
+                E, world_objects=WorldObjects(), batch_object_maps=False, **kw)
+        sims["without"] = BatchedEpisodes(E, **kw)
         rate = {k: [] for k in sims}
+        work = {k: [0, 0] for k in sims}       # object-cloud kernel launches, host read-backs inside the windows
         for s in sims.values():
             for _ in range(15):            # the initialisation turns and the first decisions
                 s.step()
         for _ in range(3):                 # alternating windows
             for name, s in sims.items():
                 torch.cuda.synchronize()
+                before = (L.vlfm_object_cloud_launch_count(), opm.SYNCS[0])
                 t0 = time.perf_counter()
                 for _ in range(steps):
                     s.step()
                 torch.cuda.synchronize()
                 rate[name].append(E * steps / (time.perf_counter() - t0))
+                work[name][0] += L.vlfm_object_cloud_launch_count() - before[0]
+                work[name][1] += opm.SYNCS[0] - before[1]
         for name, s in sims.items():
             s.check()
             extra = ""
             if s.world_objects is not None:
                 st = s.objectnav_stats
-                extra = "   %d detections, %d cloud updates; episodes ended: %d (%d successes, %d wrong stops, %d no frontier)" % (
+                extra = ("   %d detections, %d cloud updates; episodes ended: %d (%d successes, %d wrong stops, %d no frontier); "
+                         "object-map stage per step: %.1f kernel launches, %.1f host read-backs") % (
                     s.object_stats["detections"], s.object_stats["cloud_updates"], int(st["episodes"].sum()),
-                    int(st["successes"].sum()), int(st["wrong_stops"].sum()), int(st["no_frontier_stops"].sum()))
-            lines.append("steps  E=%3d  %-19s %8.1f env-steps/s (%.1f-%.1f over 3 windows of %d steps)%s"
+                    int(st["successes"].sum()), int(st["wrong_stops"].sum()), int(st["no_frontier_stops"].sum()),
+                    work[name][0] / (3 * steps), work[name][1] / (3 * steps))
+            lines.append("steps  E=%3d  %-24s %8.1f env-steps/s (%.1f-%.1f over 3 windows of %d steps)%s"
                          % (E, name, *stats(rate[name]), steps, extra))
             print(lines[-1], flush=True)
         del sims
@@ -157,22 +276,30 @@ def main() -> None:
     ap.add_argument("--skip-steps", action="store_true")
     ap.add_argument("--skip-trace", action="store_true")
     ap.add_argument("--trace-child", action="store_true")
+    ap.add_argument("--batch-object-maps", choices=("on", "off", "both"), default="on",
+                    help="leg (b): the world_objects harness with the batched object-map update, without it, or both")
+    ap.add_argument("--batch-trace", action="store_true", help="leg (c): kernel time of the batched update, a trace of its own")
+    ap.add_argument("--batch-trace-child", action="store_true")
     ap.add_argument("--workdir", default=os.path.join(ROOT, "scratch", "world_objects_trace"),
                     help="where the kernel trace of leg (a) is written (removed and rewritten by every run)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.trace_child:
         return trace_child()
+    if a.batch_trace_child:
+        return batch_trace_child()
     lines = []
     if not a.skip_trace:
         probe_trace(lines, a.workdir)      # first: this process has not touched the device yet
+    if a.batch_trace:
+        probe_batch_trace(lines, a.workdir + "_batch")
     import torch
 
     assert torch.cuda.is_available(), "world_objects_probe measures on the GPU; there is no CPU path"
     lines.insert(0, "world_objects_probe: device %s; (a) rocprofv3 kernel trace, median (min-max); (b) stub cosines, no detector, "
                     "object_maps=True" % torch.cuda.get_device_name(0))
     if not a.skip_steps:
-        probe_steps(a.steps, lines)
+        probe_steps(a.steps, lines, a.batch_object_maps)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

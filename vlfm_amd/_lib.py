@@ -170,6 +170,15 @@ def lib() -> ctypes.CDLL:
         L.vlfm_dbscan_scratch_bytes.argtypes = [ci]
         L.vlfm_dbscan_scratch_bytes.restype = ctypes.c_size_t
         L.vlfm_dbscan_largest_cluster.argtypes = [vp, ci, cd, ci, vp, ctypes.c_size_t, vp, vp, vp, vp]
+        L.vlfm_object_cloud_batch_scratch_bytes.argtypes = [ci, ci, ci]
+        L.vlfm_object_cloud_batch_scratch_bytes.restype = ctypes.c_size_t
+        L.vlfm_object_cloud_batch_stats.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
+        L.vlfm_object_cloud_batch_expand.argtypes = [vp, ci, ci, ci, cd, cd, cd, cd, vp, ci, vp, ci, ci, vp, ci, vp, ci, vp]
+        L.vlfm_dbscan_batch_scratch_bytes.argtypes = [ci]
+        L.vlfm_dbscan_batch_scratch_bytes.restype = ctypes.c_size_t
+        L.vlfm_dbscan_largest_cluster_batch.argtypes = [vp, ci, vp, ci, ci, cd, ci, vp, ctypes.c_size_t, vp, vp, vp]
+        L.vlfm_object_cloud_launch_count.argtypes = []
+        L.vlfm_object_cloud_launch_count.restype = ctypes.c_longlong
         L.vlfm_bits_pack.argtypes = [vp, vp, ci, ci, ci, vp]
         L.vlfm_bits_unpack.argtypes = [vp, vp, ci, ci, ci, vp]
         L.vlfm_bits_dilate.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]

@@ -413,7 +413,7 @@ class BatchedEpisodes:
                  object_map_erosion_size: float = 5, concurrent_vlm_max_envs: int = 0,
                  render_trajectories: bool = False, emulate_jpeg: bool = False, rig: Optional[CameraRig] = None,
                  text_prompt: str = PROMPT, exploration_thresh: Optional[float] = None, closed_loop: bool = False,
-                 controller=None, world_objects: Optional[WorldObjects] = None) -> None:
+                 controller=None, world_objects: Optional[WorldObjects] = None, batch_object_maps: bool = True) -> None:
         # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
         # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -426,6 +426,9 @@ class BatchedEpisodes:
         # controller's when it has the discrete head, else ``controller``'s: any object with
         # act(modes, rho_theta [E,2], stops [E], collided [E]) -> int64 [E] action ids (default: BangBangController)
         self.closed_loop = bool(closed_loop)
+        # batch_object_maps: all detections of a step go through the object-cloud kernels together (update_maps_batch); False =
+        # one ObjectPointCloudMap.update_map after the other -- same clouds, same random draws, kept for comparison
+        self.batch_object_maps = bool(batch_object_maps)
         if self.closed_loop:
             if world != "rooms" or host_inputs:
                 raise ValueError("closed_loop needs the rooms world rendered on the device (world='rooms', host_inputs=False)")
@@ -732,8 +735,8 @@ class BatchedEpisodes:
     def _update_object_maps(self, dets, rgb: torch.Tensor, depth: torch.Tensor, tf: np.ndarray) -> None:
         """BaseObjectNavPolicy._update_object_map for every environment (base_objectnav_policy.py:285-352): class + confidence
         filters, ONE MobileSAM call for all surviving boxes of the batch (the reference re-encodes the frame per box too),
-        ObjectPointCloudMap.update_map per mask (csrc/object_cloud.hip: erosion, back-projection, DBSCAN), update_explored
-        per environment and step."""
+        ObjectPointCloudMap.update_map per mask (csrc/object_cloud.hip: erosion, back-projection, DBSCAN) -- all masks of the step
+        in one update_maps_batch unless batch_object_maps=False -- update_explored per environment and step."""
         jobs = []
         for e, det in enumerate(dets):
             det.filter_by_class(self.targets[e].split("|"))
@@ -765,11 +768,19 @@ class BatchedEpisodes:
                                       self.H, self.W, self.device)
             self.last_masks = (envs, masks)
             self.object_stats["masks"] += len(jobs)
-            for j, e in enumerate(envs):
-                om = self.object_maps[e]
-                before = len(om.clouds.get(self.targets[e], ()))
-                om.update_map(self.targets[e], depth[e], masks[j], tf[e], MIN_DEPTH, MAX_DEPTH, self.fx, self.fy)
-                self.object_stats["cloud_updates"] += int(len(om.clouds.get(self.targets[e], ())) != before)
+            if self.batch_object_maps:
+                from .mapping.object_point_cloud_map import update_maps_batch
+
+                # depth frame of job j = environment envs[j]; counted per job like the loop below
+                self.object_stats["cloud_updates"] += sum(update_maps_batch(
+                    [self.object_maps[e] for e in envs], [self.targets[e] for e in envs], depth, envs, masks, tf[envs],
+                    MIN_DEPTH, MAX_DEPTH, self.fx, self.fy))
+            else:
+                for j, e in enumerate(envs):
+                    om = self.object_maps[e]
+                    before = len(om.clouds.get(self.targets[e], ()))
+                    om.update_map(self.targets[e], depth[e], masks[j], tf[e], MIN_DEPTH, MAX_DEPTH, self.fx, self.fy)
+                    self.object_stats["cloud_updates"] += int(len(om.clouds.get(self.targets[e], ())) != before)
         for e, om in enumerate(self.object_maps):
             if om.clouds:
                 om.update_explored(tf[e], MAX_DEPTH, self.fov)     # cone_fov = get_fov(fx, width) (:349)
