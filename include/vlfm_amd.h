@@ -362,9 +362,10 @@ int vlfm_vit_attention_f16(const void* d_qkv, void* d_out, int batch, int tokens
 /* C[M][N] = epilogue(X[M][K] . W[N][K]^T + bias[N]): f16 operands and result, f32 accumulation on the matrix cores
  * (hand-written MFMA kernels, csrc/gemm_f16.hip: 256 x 256 x 64 tiles, LDS-DMA staging, 8-phase schedule).  epilogue 0 = bias
  * only, 1 = bias + EXACT (erf) GELU on the f32 accumulator -- the fc1 + GELU of the ViT-g MLP inside the forward of
- * blip2itm.py:52 in one pass (hipBLASLt's fused GELU is the tanh approximation) --, 2 (ABI 6) = accumulate: C += X . W^T + bias,
- * summed in f32, the residual-stream GEMMs (projection, fc2).  K % 64 == 0, N % 8 == 0, each operand below 4 GB; d_bias may be
- * NULL. */
+ * blip2itm.py:52 in one pass (hipBLASLt's fused GELU is the tanh approximation) --, 2 (ABI 6) = accumulate, the residual-stream
+ * GEMMs (projection, fc2): C = f16(f16(X . W^T + bias) + C) -- product and bias are rounded to f16, then added to the stream in
+ * f32 and rounded once more, as `c + linear(x, w, bias)` in f16 does.  K % 64 == 0, N % 8 == 0, each operand below 4 GB; d_bias
+ * may be NULL.  d_x, d_w, d_c and a non-NULL d_bias must be 16-byte aligned (VLFM_ERR_INVALID otherwise). */
 int vlfm_gemm_f16_nt(const void* d_x, const void* d_w, const void* d_bias, void* d_c, int m, int n, int k, int epilogue,
                      void* stream);
 
@@ -372,7 +373,8 @@ int vlfm_gemm_f16_nt(const void* d_x, const void* d_w, const void* d_bias, void*
  * f16 operands, f32 bias, f32 result, every output element fl(acc1 + fl(bias + 2^-11 acc2)) -- the arithmetic of the two f32-output
  * library GEMMs it replaces, smallest term first -- written once.  d_w_pair is [2 N_out][K] f16: for every block of 64 output
  * channels its 64 rows of W1, then its 64 rows of W2.  The result is BLOCK-MAJOR: d_out[block][m][64] f32 (block = channel / 64), so
- * the 64 channels of one head over consecutive rows are contiguous.  K % 64 == 0, N_out % 64 == 0; d_bias_f32 may be NULL. */
+ * the 64 channels of one head over consecutive rows are contiguous.  K % 64 == 0, N_out % 64 == 0; d_bias_f32 may be NULL.  Every
+ * pointer must be 16-byte aligned (VLFM_ERR_INVALID otherwise). */
 int vlfm_gemm_f16_pair_f32_nt(const void* d_x, const void* d_w_pair, const void* d_bias_f32, void* d_out, int m, int n_out, int k,
                               void* stream);
 

@@ -98,6 +98,11 @@ def test_preprocess_at_batch_equals_two_launch_and_pil(gpu_device, n, dtype, ban
 
 
 # ------------------------------------------------------------------------------------------------ LayerNorm(x + c)
+def _ln_rows_per_wave(rows):
+    """vlfm_layernorm_bias_f16's launcher (csrc/vlm_ops.hip: rpw = rows / 8192 clamped to [1, LN_ROWS = 8]), restated"""
+    return min(max(rows // 8192, 1), 8)
+
+
 @pytest.mark.parametrize("rows,dim,rpw", [(16448, 1408, 2), (32896, 1408, 4), (65792, 1408, 8), (24581, 1408, 3), (73729, 1408, 8),
                                           (65792, 2048, 8)])
 def test_layernorm_bias_at_batch_vs_f64(gpu_device, rows, dim, rpw):
@@ -106,7 +111,7 @@ def test_layernorm_bias_at_batch_vs_f64(gpu_device, rows, dim, rpw):
     from vlfm_amd import _lib
     from vlfm_amd.vlm import ops
 
-    assert min(max(rows // 8192, 1), 8) == rpw                  # the launcher's rows per wavefront
+    assert _ln_rows_per_wave(rows) == rpw
     g = torch.Generator(device=gpu_device).manual_seed(rows + dim)
     x = (torch.randn(rows, dim, generator=g, device=gpu_device) * 3).half()
     c = torch.randn(dim, generator=g, device=gpu_device)
@@ -330,3 +335,113 @@ def test_blip2_cosine_at_the_benchmark_batch_vs_fp32(gpu_device):
     assert bool(torch.isfinite(got).all())
     err = (got - want).abs()
     assert float(err.max()) <= 5e-4, (float(err.max()), int(err.argmax()))
+
+
+# ------------------------------------------------------------------------------------------------ value edges: LayerNorm, attention
+def _layernorm_into(x, cb, w, b, y, rows, dim):
+    from vlfm_amd import _lib
+    from vlfm_amd.vlm import ops
+
+    _lib.check(_lib.lib().vlfm_layernorm_bias_f16(x.data_ptr(), cb.data_ptr() if cb is not None else None, w.data_ptr(), b.data_ptr(),
+                                                 y.data_ptr(), rows, dim, 1e-6, ops._stream()), "layernorm_bias_f16")
+
+
+@pytest.mark.parametrize("pattern", ["massive_channels", "offset_1000", "near_60000"])
+@pytest.mark.parametrize("dim", [1408, 136, 2048])
+def test_layernorm_bias_value_edges_vs_f64(gpu_device, dim, pattern):
+    """vlfm_layernorm_bias_f16 where EVA ViT-g's residual stream goes: two channels at +-400 in a row of 0.5-sigma noise (the massive
+    activations), every channel offset by 1000 (the mean dwarfs the spread: a one-pass variance would cancel), values near +-60000 (the
+    sum of squares near 5e12).  41 rows = one per wavefront; D = 1408, 136 (17 vectors: a partly filled wavefront) and 2048.
+    Bound, measured against the library and not fixed: max|kernel - f64| <= 2 max|lib - f64| + 2^-11 max|f64|, lib = F.layer_norm in
+    f32 on the same x.float() + c, rounded to f16 -- as good as the library's f32 path to within the order of the sums, plus one final
+    rounding falling the other way at the largest output."""
+    rows = 41
+    assert _ln_rows_per_wave(rows) == 1 and (dim == 136) == ((dim // 8) % 64 == 17)
+    g = torch.Generator(device=gpu_device).manual_seed(dim * 3 + len(pattern))
+    x = torch.randn(rows, dim, generator=g, device=gpu_device) * 0.5
+    if pattern == "massive_channels":
+        x[:, 3], x[:, 700 if dim > 700 else 100] = 400.0, -400.0
+    elif pattern == "offset_1000":
+        x += 1000.0
+    else:
+        x = torch.where(torch.rand(rows, dim, generator=g, device=gpu_device) < 0.5, -1.0, 1.0) * (60000.0 + 200.0 * x)
+    x = x.half()
+    assert bool(torch.isfinite(x).all())
+    c = torch.randn(dim, generator=g, device=gpu_device)
+    w = (1 + 0.2 * torch.randn(dim, generator=g, device=gpu_device)).half()
+    b = (0.3 * torch.randn(dim, generator=g, device=gpu_device)).half()
+    for cb in (c, None):
+        y = _nan_f16(rows + 1, dim, device=gpu_device)
+        _layernorm_into(x, cb, w, b, y, rows, dim)
+        assert _is_nan_bits(y[rows]), "the guard row behind the last row was written"
+        got = y[:rows]
+        assert bool(torch.isfinite(got).all())
+        xs = x.float() + cb if cb is not None else x.float()
+        ref = torch.nn.functional.layer_norm(x.double() + (cb.double() if cb is not None else 0.0), (dim,), w.double(), b.double(), 1e-6)
+        lib = torch.nn.functional.layer_norm(xs, (dim,), w.float(), b.float(), 1e-6).half()
+        err_k, err_l, top = float((got.double() - ref).abs().max()), float((lib.double() - ref).abs().max()), float(ref.abs().max())
+        print(f"layernorm D={dim} {pattern} c={'yes' if cb is not None else 'no'}: kernel {err_k:.3e} library f32 {err_l:.3e} "
+              f"max|ref| {top:.3f} bound {2 * err_l + 2.0 ** -11 * top:.3e}")
+        assert err_k <= 2 * err_l + 2.0 ** -11 * top, (err_k, err_l, top)
+
+
+@pytest.mark.parametrize("dim", [2048, 128])
+def test_layernorm_bias_of_constant_rows_is_beta_bit_for_bit(gpu_device, dim):
+    """1 / D is a power of two at D = 2048 and 128: a row of one dyadic value v has the exact sum D v, the exact mean v, deviations of
+    exactly zero, and LayerNorm returns beta bit for bit whatever 1 / sqrt(eps) and gamma are -- row 20 is all zeros.  c = None."""
+    rows = 41
+    g = torch.Generator(device=gpu_device).manual_seed(dim)
+    x = ((torch.arange(rows, device=gpu_device, dtype=torch.float32) - 20) / 8).half()[:, None].expand(rows, dim).contiguous()
+    assert not bool(x[20].any()) and float(x.abs().max()) * dim < 2 ** 24 / 8
+    w = (1 + 0.2 * torch.randn(dim, generator=g, device=gpu_device)).half()
+    b = (0.3 * torch.randn(dim, generator=g, device=gpu_device)).half()
+    assert bool((b != 0).all())
+    y = _nan_f16(rows + 1, dim, device=gpu_device)
+    _layernorm_into(x, None, w, b, y, rows, dim)
+    assert _is_nan_bits(y[rows])
+    diff = y[:rows].view(torch.int16) != b.view(torch.int16)[None, :]
+    assert not bool(diff.any()), (int(diff.sum()), diff.nonzero()[0].tolist())
+
+
+def test_vit_attention_value_edges(gpu_device):
+    """vlfm_vit_attention_f16 on three images: 0 -- queries scaled until the scores reach about +-60 (the max-subtracted softmax must
+    neither overflow nor go NaN); 1 -- a head whose CLS query (the VALU path) is won by the LAST key, 256 (the one-token tail tile);
+    2 -- q = 0: every p_i is exactly 1, the softmax is uniform and the output is the key-mean of v, within one f16 ulp of its f16
+    rounding (the only inexact steps are the f32 sum of 257 f16 values and the final scaling).  Bound for the first two: 6e-3 against
+    f64, test_vit_attention_kernel_vs_fp32_reference's for the same distribution of v.  Finite, and identical bits over 3 runs."""
+    import conv_ref as R
+
+    B = 3
+    g = torch.Generator(device=gpu_device).manual_seed(60)
+    qkv = torch.randn(B, S, 3, HEADS, DH, generator=g, device=gpu_device) * 1.5
+    raw = (qkv[0, :, 0].permute(1, 0, 2) @ qkv[0, :, 1].permute(1, 2, 0)) * DH ** -0.5       # [H, S, S]
+    qkv[0, :, 0] *= 60.0 / float(raw.abs().max())
+    qkv[1, 0, 0, 2] = 3.0 * qkv[1, 256, 1, 2]
+    qkv[2, :, 0] = 0.0
+    x = qkv.half().reshape(B * S, 3 * HEADS * DH).contiguous()
+    xb = x.view(B, S, 3, HEADS, DH).double()
+    q, k, v = [xb[:, :, i].permute(0, 2, 1, 3) for i in range(3)]            # [b, H, S, D]
+    scores = q @ k.transpose(-1, -2) * DH ** -0.5
+    prob = torch.softmax(scores, dim=-1)
+    assert 58.0 <= float(scores[0].abs().max()) <= 62.0 and float(scores[0].max()) >= 45.0 and float(scores[0].min()) <= -45.0
+    assert int(prob[1, 2, 0].argmax()) == 256 and float(prob[1, 2, 0, 256]) > 0.9
+    assert not bool(scores[2].any())
+    ref = (prob @ v).permute(0, 2, 1, 3).reshape(B * S, HEADS * DH)
+    outs = []
+    for _ in range(3):
+        out = _nan_f16((B + 1) * S, HEADS * DH, device=gpu_device)
+        _attention_into(x, out, B)
+        assert _is_nan_bits(out[B * S:]), "the guard image behind the last one was written"
+        outs.append(out[:B * S])
+    got = outs[0]
+    assert bool(torch.isfinite(got).all())
+    assert all(torch.equal(got.view(torch.int16), o.view(torch.int16)) for o in outs[1:])
+    err = (got.double() - ref).abs()
+    per_image = [float(err[i * S:(i + 1) * S].max()) for i in range(B)]
+    print(f"attention value edges: max |err| per image {per_image}, max|score| {float(scores.abs().max()):.1f}")
+    assert max(per_image) <= 6e-3, (per_image, int(err.argmax()))
+    mean = v[2].mean(dim=1)                                                   # [H, D]: what every query of image 2 returns
+    want = R.f16_bits(mean.reshape(1, HEADS * DH).expand(S, HEADS * DH).cpu().numpy())
+    ulps = R.ulp_distance(got[2 * S:].contiguous().view(torch.int16).cpu().numpy(), want)
+    print(f"attention, uniform softmax: max {int(ulps.max())} f16 ulp from the key-mean, {int((ulps > 0).sum())} of {ulps.size} off")
+    assert int(ulps.max()) <= 1

@@ -569,8 +569,11 @@ __global__ __launch_bounds__(512) void gemm_f16_8pp_kernel(GemmArgs a) {
 using namespace vlfm;
 
 // C = epilogue(X . W^T + bias), f16 in / f16 out / f32 accumulate.  epilogue: 0 = bias only, 1 = bias + exact (erf) GELU,
-// 2 = accumulate into C (C += X . W^T + bias: the residual-stream GEMMs).  K must be a multiple of 64, N a multiple of 8; M and N
-// tails are handled.  d_bias may be NULL.  One kernel: the persistent 8-phase schedule, one workgroup per CU (a multiple of 8 of them).
+// 2 = accumulate into C (the residual-stream GEMMs): C = f16(f16(X . W^T + bias) + C) -- product and bias are rounded to f16, then
+// added to the stream in f32 and rounded once more, which is the framework's `c + F.linear(x, w, bias)` in f16
+// (tests/test_gemm_f16_exact_gpu.py pins it).  K must be a multiple of 64, N a multiple of 8; M and N tails are handled.  d_bias
+// may be NULL.  X, W, C and the bias are read and written in 16-byte pieces (LDS-DMA, half8): they must be 16-byte aligned.
+// One kernel: the persistent 8-phase schedule, one workgroup per CU (a multiple of 8 of them).
 template <int EPI>
 static int launch_gemm(const GemmArgs& a, hipStream_t stream) {
     const void* fn = reinterpret_cast<const void*>(gemm_f16_8pp_kernel<EPI>);
@@ -592,6 +595,8 @@ extern "C" int vlfm_gemm_f16_nt(const void* d_x, const void* d_w, const void* d_
     if (m == 0 || n == 0) return VLFM_OK;
     if (!d_x || !d_w || !d_c || m < 0 || n < 0 || k <= 0 || (k % GK) != 0 || (n % 8) != 0 || epilogue < 0 || epilogue > 2)
         return fail(VLFM_ERR_INVALID, "gemm_f16_nt: K must be a multiple of 64, N of 8, epilogue 0, 1 or 2");
+    if (((uintptr_t)d_x | (uintptr_t)d_w | (uintptr_t)d_c | (uintptr_t)d_bias) & 15)
+        return fail(VLFM_ERR_INVALID, "gemm_f16_nt: X, W, C and the bias must be 16-byte aligned");
     if ((size_t)m * (size_t)k * 2 >= (1ull << 32) || (size_t)n * (size_t)k * 2 >= (1ull << 32))
         return fail(VLFM_ERR_INVALID, "gemm_f16_nt: an operand of 4 GB or more (32-bit byte offsets inside an operand)");
     GemmArgs a;
@@ -609,12 +614,15 @@ extern "C" int vlfm_gemm_f16_nt(const void* d_x, const void* d_w, const void* d_
 
 // out[block][m][64] (f32) = X[M][K] . (W1 + 2^-11 W2)[N_out][K]^T + bias[N_out] (f32), block = 64 output channels: the two-piece
 // split-precision projection in ONE pass (EPI_PAIR_F32).  d_w_pair is [2 N_out][K] f16: per block its 64 rows of W1, then its 64
-// rows of W2.  K % 64 == 0, N_out % 64 == 0; M tails and an odd number of blocks (a half-filled last tile) are handled.
+// rows of W2.  K % 64 == 0, N_out % 64 == 0; M tails and an odd number of blocks (a half-filled last tile) are handled.  Every
+// pointer must be 16-byte aligned.
 extern "C" int vlfm_gemm_f16_pair_f32_nt(const void* d_x, const void* d_w_pair, const void* d_bias_f32, void* d_out, int m, int n_out,
                                          int k, void* stream) {
     if (m == 0 || n_out == 0) return VLFM_OK;
     if (!d_x || !d_w_pair || !d_out || m < 0 || n_out < 0 || k <= 0 || (k % GK) != 0 || (n_out % 64) != 0)
         return fail(VLFM_ERR_INVALID, "gemm_f16_pair_f32_nt: K and N_out must be multiples of 64");
+    if (((uintptr_t)d_x | (uintptr_t)d_w_pair | (uintptr_t)d_out | (uintptr_t)d_bias_f32) & 15)
+        return fail(VLFM_ERR_INVALID, "gemm_f16_pair_f32_nt: X, the weight pair, the result and the bias must be 16-byte aligned");
     if ((size_t)m * (size_t)k * 2 >= (1ull << 32) || (size_t)n_out * (size_t)k * 4 >= (1ull << 32))
         return fail(VLFM_ERR_INVALID, "gemm_f16_pair_f32_nt: an operand of 4 GB or more (32-bit byte offsets inside an operand)");
     GemmArgs a;

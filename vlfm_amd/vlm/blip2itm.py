@@ -171,7 +171,7 @@ class _VitBlock(nn.Module):
                 self.hip_attention = False
         if a is not None:
             if "proj" in hip and x2.is_contiguous():
-                ops.linear_f16(a, self.projection.weight, None, "accumulate", out=x2)     # x += a Wp^T, summed in f32
+                ops.linear_f16(a, self.projection.weight, None, "accumulate", out=x2)     # x = f16(f16(a Wp^T) + x)
             else:
                 x2.addmm_(a, self.projection.weight.t())
         elif self._packed is not None:

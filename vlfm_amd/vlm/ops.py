@@ -303,13 +303,16 @@ def linear_f16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     """epilogue(x @ weight.T + bias), f16 in / f16 out, f32 accumulation on the matrix cores: the hand-written 256 x 256 x 64
     8-phase GEMM of csrc/gemm_f16.hip.  x [M, K], weight [N, K], bias [N] or None.  epilogue "bias": the plain Linear;
     "bias_gelu": exact (erf) GELU on the f32 accumulators (hipBLASLt only fuses the tanh approximation, so the library path is a GEMM
-    plus a separate pass over the 4x-wide activation); "accumulate": ``out += x @ weight.T (+ bias)`` in place, summed in f32 -- the
-    residual-stream GEMMs (``out`` is required)."""
+    plus a separate pass over the 4x-wide activation); "accumulate": the residual-stream GEMMs, in place (``out`` is required):
+    ``out = f16(f16(x @ weight.T + bias) + out)`` -- product and bias are rounded to f16, then added to the stream in f32 and rounded
+    once more, which is ``out + F.linear(x, weight, bias)`` in f16.  x, weight, bias and out must be 16-byte aligned (the kernel
+    moves 16-byte pieces): a view with an odd storage offset is refused, copy it first."""
     assert x.is_cuda and x.dtype == torch.float16 and x.is_contiguous() and x.dim() == 2
     assert weight.dtype == torch.float16 and weight.is_contiguous() and weight.shape[1] == x.shape[1]
     assert bias is None or (bias.dtype == torch.float16 and bias.is_contiguous())
     M, K = x.shape
     N = weight.shape[0]
+    assert all(t is None or t.data_ptr() % 16 == 0 for t in (x, weight, bias, out)), "linear_f16: 16-byte aligned tensors only"
     if out is None:
         assert epilogue != "accumulate", "accumulate needs the tensor to accumulate into"
         out = torch.empty((M, N), dtype=torch.float16, device=x.device)
@@ -338,12 +341,14 @@ def linear_pair_f32(x: torch.Tensor, w_pair: torch.Tensor, bias: Optional[torch.
     """x @ (W1 + 2^-11 W2).T + bias in f32 from f16 operands, ONE pass of csrc/gemm_f16.hip (epilogue EPI_PAIR_F32): the two-piece
     split-precision projection with the f32 result written once, ``fl(acc1 + fl(bias + 2^-11 acc2))`` as the two addmm calls it
     replaces compute it.  x [M, K] f16, ``w_pair`` from ``interleave_pair_weights``, bias [N] f32.  Returns the result BLOCK-MAJOR:
-    [N / 64, M, 64] f32, block = 64 consecutive output channels (``out[c // 64, m, c % 64]`` is element (m, c))."""
+    [N / 64, M, 64] f32, block = 64 consecutive output channels (``out[c // 64, m, c % 64]`` is element (m, c)).  Every tensor must be
+    16-byte aligned."""
     assert x.is_cuda and x.dtype == torch.float16 and x.is_contiguous() and x.dim() == 2
     assert w_pair.dtype == torch.float16 and w_pair.is_contiguous() and w_pair.shape[1] == x.shape[1] and w_pair.shape[0] % 128 == 0
     M, K = x.shape
     N = w_pair.shape[0] // 2
     assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N)
+    assert all(t is None or t.data_ptr() % 16 == 0 for t in (x, w_pair, bias, out)), "linear_pair_f32: 16-byte aligned tensors only"
     if out is None:
         out = torch.empty((N // 64, M, 64), dtype=torch.float32, device=x.device)
     else:
