@@ -400,7 +400,8 @@ int vlfm_gemm_f16_work_items(int m, int n, int grid, int* out, int capacity_pair
  * groundingdino's build_model [ext]), and of MobileSAM's TinyViT (vlfm/vlm/sam.py:40-57).
  *   activation  0 none, 1 ReLU, 2 exact (erf) GELU; d_bias / d_residual may be NULL (d_residual may alias d_c)
  *   precision   0 = v_mfma_f32_32x32x2_f32: bit for bit a k-ordered f32 fma chain (157 TFLOP/s peak)
- *               1 = every operand as hi + 2^-11 lo' in two f16 (representation error <= 2^-24 |a|, f32's own unit roundoff), three
+ *               1 = every operand as hi + 2^-11 lo' in two f16 (representation error <= 2^-23 |a|, one f32 ulp, for |a| >= 2^-12;
+ *                   2^-36 absolute below, which is at most 2^-22 |a| on [2^-14, 2^-12)), three
  *                   f16 MFMAs per product block, f32 accumulation: f32-grade results at 5.3x the matrix rate.  Needs d_w_hi / d_w_lo
  *                   = vlfm_split_f32_to_f16_pair(d_w) (once per layer) and d_overflow, a device int that the kernel ORs with 1 when
  *                   an |operand| >= 65504 (f16's range) was met: the result of that call is then invalid and the caller must

@@ -12,7 +12,8 @@ pytestmark = pytest.mark.gpu
 # (M, N, K): Swin stage 1 qkv / mlp, stage 3 mlp, encoder FFN, fusion projection, decoder, ragged tails
 SHAPES = [(4096, 96, 96), (4096, 384, 96), (2500, 96, 384), (1200, 1536, 384), (3000, 2048, 256), (3000, 256, 2048),
           (6380, 1024, 256), (900, 256, 256), (777, 132, 64), (130, 36, 32),
-          # the split form's 256-wide tile (N % 256 == 0 or N >= 640): full tiles, an n tail inside a wide tile, an m tail
+          # wide N (chosen for a 256-wide split tile that was measured and is not dispatched: both forms run 128 x 128 tiles here):
+          # 5 to 18 full n-tiles, an m tail
           (1000, 768, 192), (515, 2304, 96), (2049, 640, 64), (300, 1152, 384),
           # the BLIP-2 Q-Former's Linears at 256 images (8192 query rows): attention / output, intermediate, output of the MLP
           (8192, 768, 768), (8192, 3072, 768), (8192, 768, 3072)]

@@ -8,13 +8,15 @@
 //                saturated by one wavefront per SIMD, LDS and HBM are nearly idle -- what matters is never to stall the pipe.
 //   precision 1  SPLIT: every f32 operand a is written as hi + 2^-11 lo' with hi = f16(a), lo' = f16((a - hi) 2^11): the
 //                remainder a - hi is exact in f32 and has at most 13 significant bits, of which lo' keeps 11, so
-//                |a - (hi + 2^-11 lo')| <= 2^-24 |a| -- f32's own unit roundoff -- for |a| >= 2^-14; below, hi and lo' are
-//                f16-subnormal and the bound is 2^-36 absolute instead (2e-6 relative at 3e-6).  Then a b = hi_a hi_b + 2^-11 (hi_a lo'_b + lo'_a hi_b)
-//                + O(2^-24 |a b|): THREE v_mfma_f32_32x32x16_f16 (exact 22-bit products, f32 accumulation) in place of eight
+//                |a - (hi + 2^-11 lo')| <= 2^-23 |a| -- one f32 ulp, attained at 1 + 2^-12 + 2^-23 -- for |a| >= 2^-12; below, lo'
+//                (and from 2^-14 down hi too) is f16-subnormal and the bound is 2^-36 absolute instead: at most 2^-22 |a| on
+//                [2^-14, 2^-12), 2e-6 relative at 3e-6 (tests/test_gemm_f32_ref_cpu.py).  Then a b = hi_a hi_b + 2^-11 (hi_a lo'_b + lo'_a hi_b)
+//                + O(2^-22 |a b|): THREE v_mfma_f32_32x32x16_f16 (exact 22-bit products, f32 accumulation) in place of eight
 //                32x32x2_f32, i.e. 16 / 3 = 5.3 x the matrix rate of the exact form (833 TFLOP/s-equivalent peak).  The two cross terms
 //                share one accumulator that is scaled by 2^-11 in the epilogue.  |a| >= 65504 cannot be represented: the kernel
 //                raises a sticky device flag instead of producing infinities silently and the caller re-runs the exact form
-//                (vlfm_gemm_f32_overflow_flag).  tests/test_gemm_f32_gpu.py measures both forms against an f64 reference.
+//                (vlfm_gemm_f32_overflow_flag).  tests/test_gemm_f32_gpu.py measures both forms against an f64 reference;
+//                tests/test_gemm_f32_exact_gpu.py holds each to its definition, bit for bit.
 //
 // Tile: 128 (m) x 128 (n) per workgroup of 4 wavefronts (2 x 2, each 64 x 64 = 2 x 2 MFMA tiles of 32 x 32), K-tile 32 floats =
 // 128-byte rows -- the row geometry of gemm_f16.hip, so staging (global_load_lds, 16 B per lane, slot ^ ((row >> 1) & 7)) and the
