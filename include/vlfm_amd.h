@@ -564,6 +564,41 @@ int vlfm_dbscan_largest_cluster_batch(const double* d_points, int capacity, cons
 long long vlfm_object_cloud_launch_count(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * Queries over device mirrors of the accumulated object clouds (ABI 18, csrc/cloud_query.hip): what
+ * ObjectPointCloudMap.update_explored and get_best_object ask of a cloud (object_point_cloud_map.py:77-144,172-183,
+ * geometry_utils.py:91-116), for many clouds in one launch.  The number of launches does not depend on the number of queries.
+ * ------------------------------------------------------------------------------------------- */
+
+/* One query = one cloud.  d_rows [n][4] f64 (x, y, z, tag), 32-byte aligned; d_slots [n] i32: -1 for a point whose tag is 1.0,
+ * else the index (< n_slots) of its tag in the caller's table of the cloud's other tag values.  p = the cone's origin (cone) or
+ * the position (closest: its first k entries, k = 2 or 3).  heading, half_fov (= cone_fov / 2), range: the cone; flag_offset:
+ * where the cloud's 2 * n_slots flags start in d_flags. */
+typedef struct {
+    const double* d_rows;
+    const int32_t* d_slots;
+    double p[3];
+    double heading, half_fov, range;
+    int32_t n, k, flag_offset, n_slots;
+} vlfm_cloud_query;
+
+/* d_flags (zeroed by the caller) [flag_offset + s] = 1 when slot s has a point with dist <= range and |angle diff| <= half_fov,
+ * [flag_offset + n_slots + s] = 1 when it has a point with dist <= range whose |angle diff| lies within 1e-9 rad of half_fov:
+ * such a point is UNCERTAIN (the device's atan2 is not NumPy's) and is counted on neither side; the caller decides it.  Points of
+ * slot -1 are skipped.  max_points = the largest n.  One launch. */
+int vlfm_cloud_cone_flags(const vlfm_cloud_query* d_queries, int n_queries, int max_points, int32_t* d_flags, void* stream);
+
+/* d_result [n_queries][4] i32 = (points with tag 1.0, np.argmin of norm(rows[:, :k] - p) over those points as an index into the
+ * WHOLE cloud or -1 when there is none, the same over all points or -1 for an empty cloud, 0).  The minimum is taken over the
+ * rounded roots; ties go to the lowest index.  Two launches: per-chunk partials into d_scratch
+ * (vlfm_cloud_closest_scratch_bytes(n_queries, max_points)), then one wavefront per query. */
+size_t vlfm_cloud_closest_scratch_bytes(int n_queries, int max_points);
+int vlfm_cloud_closest(const vlfm_cloud_query* d_queries, int n_queries, int max_points, void* d_scratch, size_t scratch_bytes,
+                       int32_t* d_result, void* stream);
+/* points per workgroup chunk; kernels launched so far by the functions of this section */
+int vlfm_cloud_query_chunk(void);
+long long vlfm_cloud_query_launch_count(void);
+
+/* ---------------------------------------------------------------------------------------------
  * ObstacleMap planes are bit-packed: 1 bit per cell, row stride ceil(cols/32) u32 words, bit x&31 of word x>>5.
  * ------------------------------------------------------------------------------------------- */
 int vlfm_bits_pack(const uint8_t* d_src, uint32_t* d_dst, int planes, int rows, int cols, void* stream);

@@ -7,14 +7,21 @@
   (b) env-steps/s of a closed-loop harness with and without world_objects at 8 and 256 environments: stub cosines, no
       detector, object_maps=True, alternating windows; --batch-object-maps on | off | both runs the world_objects harness with
       the batched object-map update, with one update_map per detection, or both side by side, and reports the object-cloud
-      kernel launches and host read-backs per step of each.
+      kernel launches and host read-backs per step of each; --device-object-clouds on | off | both does the same for the device
+      mirrors of the clouds (update_explored_batch / get_best_objects_batch against one NumPy pass per environment) and adds the
+      cloud-query launches, the bytes uploaded to the mirrors and the points re-evaluated on the host per step.
   (c) --batch-trace: kernel time of the batched object-map update for 1 / 16 / 64 detections (objects in view of the tour poses) at 640x480
       next to the per-detection kernels for the same detections, from one `rocprofv3 --kernel-trace --stats` run of its own.
 
+  (d) --cloud-trace: kernel time of the two cloud queries (csrc/cloud_query.hip) over 256 mirrored clouds of 20 000 and of
+      100 000 points, from one `rocprofv3 --kernel-trace --stats` run of its own, against the bytes of the mirrors.
+
     python tools/world_objects_probe.py [--steps 20] [--skip-steps] [--skip-trace] [--out profiles/world_objects_probe.txt]
     python tools/world_objects_probe.py --skip-trace --batch-object-maps both --batch-trace --out profiles/object_maps_batch_probe.txt
+    python tools/world_objects_probe.py --skip-trace --device-object-clouds both --out profiles/object_clouds_device_probe.txt
     python tools/world_objects_probe.py --trace-child        # the process (a) points rocprofv3 at
-    python tools/world_objects_probe.py --batch-trace-child  # the process (c) points rocprofv3 at"""
+    python tools/world_objects_probe.py --batch-trace-child  # the process (c) points rocprofv3 at
+    python tools/world_objects_probe.py --cloud-trace-child  # the process (d) points rocprofv3 at"""
 import argparse
 import glob
 import os
@@ -216,7 +223,74 @@ def probe_batch_trace(lines, workdir: str) -> None:
         print(lines[-1], flush=True)
 
 
-def probe_steps(steps: int, lines, batch: str = "on") -> None:
+CLOUD_TRACE_POINTS, CLOUD_TRACE_CLOUDS, CLOUD_TRACE_REPS, CLOUD_TRACE_WARMUP = (20000, 100000), 256, 10, 2
+CLOUD_KERNELS = ("cloud_cone_kernel", "cloud_closest_partial_kernel", "cloud_closest_final_kernel")
+HBM_PEAK = 8.0e12        # bytes/s, MI355X specification
+
+
+def cloud_trace_child() -> None:
+    """256 maps with one cloud each: points uniform in a 2 m box, half of them trusted, the others under 8 far tags.  The cone looks
+    AWAY from the box from 1.5 m with every point in range: every far point goes through the whole test and none is dropped, so
+    all rounds see the same clouds."""
+    import numpy as np
+    import torch
+
+    from vlfm_amd.mapping import object_point_cloud_map as opm
+
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(0)
+    tf = np.eye(4)
+    tf[0, 3] = 1.5
+    for n in CLOUD_TRACE_POINTS:
+        maps = []
+        for _ in range(CLOUD_TRACE_CLOUDS):
+            m = opm.ObjectPointCloudMap(5, device=dev)
+            tags = np.where(rng.random(n) < 0.5, 1.0, (1 + rng.integers(0, 8, n)) / 16.0)
+            m.clouds = {"chair": np.concatenate([rng.uniform(-1.0, 1.0, (n, 3)), tags[:, None]], axis=1)}
+            maps.append(m)
+        for _ in range(CLOUD_TRACE_WARMUP + CLOUD_TRACE_REPS):
+            assert not any(opm.update_explored_batch(maps, [tf] * len(maps), 8.0, 1.38))
+            goals = opm.get_best_objects_batch(maps, ["chair"] * len(maps), [np.array([1.5, 0.0])] * len(maps))
+            assert all(g is not None for g in goals)
+        torch.cuda.synchronize()
+        del maps
+        torch.cuda.empty_cache()
+
+
+def probe_cloud_trace(lines, workdir: str) -> None:
+    import numpy as np
+
+    if shutil.which("rocprofv3") is None:
+        raise RuntimeError("rocprofv3 not found: the kernel-time leg needs it")
+    shutil.rmtree(workdir, ignore_errors=True)
+    os.makedirs(workdir)
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", workdir, "-o", "cloud_queries", "--", sys.executable,
+           os.path.abspath(__file__), "--cloud-trace-child"]
+    with open(os.path.join(workdir, "child.log"), "w") as log:
+        subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, timeout=420)
+    dbs = glob.glob(os.path.join(workdir, "**", "*_results.db"), recursive=True)
+    if not dbs:
+        raise RuntimeError(f"no rocprofv3 database under {workdir}")
+    rows = sqlite3.connect(dbs[0]).execute("select name, start, end from kernels order by start").fetchall()
+    per = CLOUD_TRACE_WARMUP + CLOUD_TRACE_REPS
+    us = {k: [(e - s) * 1e-3 for n, s, e in rows if k in n] for k in CLOUD_KERNELS}
+    if any(len(v) != per * len(CLOUD_TRACE_POINTS) for v in us.values()):
+        raise RuntimeError(f"expected {per * len(CLOUD_TRACE_POINTS)} dispatches of each cloud-query kernel, found "
+                           f"{[len(v) for v in us.values()]}")
+    for i, n in enumerate(CLOUD_TRACE_POINTS):
+        cone, part, fin = (np.array(us[k][i * per + CLOUD_TRACE_WARMUP:(i + 1) * per]) for k in CLOUD_KERNELS)
+        closest = part + fin
+        rows_b, slots_b = 32.0 * n * CLOUD_TRACE_CLOUDS, 4.0 * n * CLOUD_TRACE_CLOUDS
+        lines.append("cloud-kernels %d clouds x %6d points (%.1f MB of rows, %.1f MB of slots)  cone %7.1f us (%.1f-%.1f) = %4.1f %% of "
+                     "the HBM peak for rows + slots   closest: partials %7.1f us + final %5.1f us = %7.1f us (%.1f-%.1f) = %4.1f %% of "
+                     "the HBM peak for the rows   %d rounds"
+                     % (CLOUD_TRACE_CLOUDS, n, rows_b / 1e6, slots_b / 1e6, *stats(cone),
+                        100 * (rows_b + slots_b) / (stats(cone)[0] * 1e-6) / HBM_PEAK, float(np.median(part)), float(np.median(fin)),
+                        *stats(closest), 100 * rows_b / (stats(closest)[0] * 1e-6) / HBM_PEAK, len(cone)))
+        print(lines[-1], flush=True)
+
+
+def probe_steps(steps: int, lines, batch: str = "on", clouds: str = "on") -> None:
     import time
 
     import torch
@@ -230,22 +304,26 @@ def probe_steps(steps: int, lines, batch: str = "on") -> None:
     for E in (8, 256):
         kw = dict(device=dev, use_blip2=False, select_frontiers=True, episode_len=500, closed_loop=True, object_maps=True)
         sims = {}
-        if batch in ("on", "both"):
-            sims["with world_objects" if batch == "on" else "world_objects batched"] = BatchedEpisodes(
-                E, world_objects=WorldObjects(), batch_object_maps=True, **kw)
-        if batch in ("off", "both"):
-            sims["with world_objects" if batch == "off" else "world_objects one by one"] = BatchedEpisodes(
-                E, world_objects=WorldObjects(), batch_object_maps=False, **kw)
+        for device_clouds in ([True] if clouds == "on" else [False] if clouds == "off" else [True, False]):
+            where = "" if clouds != "both" else (", device clouds" if device_clouds else ", host clouds")
+            if batch in ("on", "both"):
+                sims[("with world_objects" if batch == "on" else "world_objects batched") + where] = BatchedEpisodes(
+                    E, world_objects=WorldObjects(), batch_object_maps=True, device_object_clouds=device_clouds, **kw)
+            if batch in ("off", "both"):
+                sims[("with world_objects" if batch == "off" else "world_objects one by one") + where] = BatchedEpisodes(
+                    E, world_objects=WorldObjects(), batch_object_maps=False, device_object_clouds=device_clouds, **kw)
         sims["without"] = BatchedEpisodes(E, **kw)
         rate = {k: [] for k in sims}
-        work = {k: [0, 0] for k in sims}       # object-cloud kernel launches, host read-backs inside the windows
+        # object-cloud kernel launches, host read-backs, cloud-query launches, uploaded bytes, band points inside the windows
+        work = {k: [0, 0, 0, 0, 0] for k in sims}
         for s in sims.values():
             for _ in range(15):            # the initialisation turns and the first decisions
                 s.step()
         for _ in range(3):                 # alternating windows
             for name, s in sims.items():
                 torch.cuda.synchronize()
-                before = (L.vlfm_object_cloud_launch_count(), opm.SYNCS[0])
+                before = (L.vlfm_object_cloud_launch_count(), opm.SYNCS[0], L.vlfm_cloud_query_launch_count(),
+                          opm.UPLOADED_BYTES[0], opm.BAND_POINTS[0])
                 t0 = time.perf_counter()
                 for _ in range(steps):
                     s.step()
@@ -253,17 +331,22 @@ def probe_steps(steps: int, lines, batch: str = "on") -> None:
                 rate[name].append(E * steps / (time.perf_counter() - t0))
                 work[name][0] += L.vlfm_object_cloud_launch_count() - before[0]
                 work[name][1] += opm.SYNCS[0] - before[1]
+                work[name][2] += L.vlfm_cloud_query_launch_count() - before[2]
+                work[name][3] += opm.UPLOADED_BYTES[0] - before[3]
+                work[name][4] += opm.BAND_POINTS[0] - before[4]
         for name, s in sims.items():
             s.check()
             extra = ""
             if s.world_objects is not None:
                 st = s.objectnav_stats
                 extra = ("   %d detections, %d cloud updates; episodes ended: %d (%d successes, %d wrong stops, %d no frontier); "
-                         "object-map stage per step: %.1f kernel launches, %.1f host read-backs") % (
+                         "object-map stage per step: %.1f kernel launches, %.1f host read-backs; cloud queries per step: %.1f "
+                         "launches, %.0f bytes uploaded, %.2f band points") % (
                     s.object_stats["detections"], s.object_stats["cloud_updates"], int(st["episodes"].sum()),
                     int(st["successes"].sum()), int(st["wrong_stops"].sum()), int(st["no_frontier_stops"].sum()),
-                    work[name][0] / (3 * steps), work[name][1] / (3 * steps))
-            lines.append("steps  E=%3d  %-24s %8.1f env-steps/s (%.1f-%.1f over 3 windows of %d steps)%s"
+                    work[name][0] / (3 * steps), work[name][1] / (3 * steps), work[name][2] / (3 * steps),
+                    work[name][3] / (3 * steps), work[name][4] / (3 * steps))
+            lines.append("steps  E=%3d  %-40s %8.1f env-steps/s (%.1f-%.1f over 3 windows of %d steps)%s"
                          % (E, name, *stats(rate[name]), steps, extra))
             print(lines[-1], flush=True)
         del sims
@@ -278,8 +361,12 @@ def main() -> None:
     ap.add_argument("--trace-child", action="store_true")
     ap.add_argument("--batch-object-maps", choices=("on", "off", "both"), default="on",
                     help="leg (b): the world_objects harness with the batched object-map update, without it, or both")
+    ap.add_argument("--device-object-clouds", choices=("on", "off", "both"), default="on",
+                    help="leg (b): update_explored and the object goals asked of device mirrors of the clouds, of NumPy, or both")
     ap.add_argument("--batch-trace", action="store_true", help="leg (c): kernel time of the batched update, a trace of its own")
     ap.add_argument("--batch-trace-child", action="store_true")
+    ap.add_argument("--cloud-trace", action="store_true", help="leg (d): kernel time of the cloud queries, a trace of its own")
+    ap.add_argument("--cloud-trace-child", action="store_true")
     ap.add_argument("--workdir", default=os.path.join(ROOT, "scratch", "world_objects_trace"),
                     help="where the kernel trace of leg (a) is written (removed and rewritten by every run)")
     ap.add_argument("--out", default=None)
@@ -288,18 +375,22 @@ def main() -> None:
         return trace_child()
     if a.batch_trace_child:
         return batch_trace_child()
+    if a.cloud_trace_child:
+        return cloud_trace_child()
     lines = []
     if not a.skip_trace:
         probe_trace(lines, a.workdir)      # first: this process has not touched the device yet
     if a.batch_trace:
         probe_batch_trace(lines, a.workdir + "_batch")
+    if a.cloud_trace:
+        probe_cloud_trace(lines, a.workdir + "_clouds")
     import torch
 
     assert torch.cuda.is_available(), "world_objects_probe measures on the GPU; there is no CPU path"
     lines.insert(0, "world_objects_probe: device %s; (a) rocprofv3 kernel trace, median (min-max); (b) stub cosines, no detector, "
                     "object_maps=True" % torch.cuda.get_device_name(0))
     if not a.skip_steps:
-        probe_steps(a.steps, lines, a.batch_object_maps)
+        probe_steps(a.steps, lines, a.batch_object_maps, a.device_object_clouds)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

@@ -13,7 +13,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlfm_amd.so")
-SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "qformer_attention.hip", "detect_ops.hip", "object_cloud.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "world_render.hip", "host.cpp"]
+SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "qformer_attention.hip", "detect_ops.hip", "object_cloud.hip", "cloud_query.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "world_render.hip", "host.cpp"]
 
 VLFM_OK = 0
 VLFM_ERR_INVALID = -1
@@ -57,6 +57,13 @@ class VmOptics(ctypes.Structure):
                 ("template_size", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class CloudQuery(ctypes.Structure):
+    _fields_ = [("d_rows", ctypes.c_void_p), ("d_slots", ctypes.c_void_p), ("p", ctypes.c_double * 3),
+                ("heading", ctypes.c_double), ("half_fov", ctypes.c_double), ("range", ctypes.c_double),
+                ("n", ctypes.c_int32), ("k", ctypes.c_int32), ("flag_offset", ctypes.c_int32), ("n_slots", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(CloudQuery) == 80
 assert ctypes.sizeof(ScatterJournal) == 24 and ctypes.sizeof(VmOptics) == 48
 assert ctypes.sizeof(VmPose) == 64 and ctypes.sizeof(IngestParams) == 152 and ctypes.sizeof(FogParams) == 48 + 16 * FOG_MAX_POLY
 
@@ -179,6 +186,13 @@ def lib() -> ctypes.CDLL:
         L.vlfm_dbscan_largest_cluster_batch.argtypes = [vp, ci, vp, ci, ci, cd, ci, vp, ctypes.c_size_t, vp, vp, vp]
         L.vlfm_object_cloud_launch_count.argtypes = []
         L.vlfm_object_cloud_launch_count.restype = ctypes.c_longlong
+        L.vlfm_cloud_cone_flags.argtypes = [vp, ci, ci, vp, vp]
+        L.vlfm_cloud_closest_scratch_bytes.argtypes = [ci, ci]
+        L.vlfm_cloud_closest_scratch_bytes.restype = ctypes.c_size_t
+        L.vlfm_cloud_closest.argtypes = [vp, ci, ci, vp, ctypes.c_size_t, vp, vp]
+        L.vlfm_cloud_query_chunk.argtypes = []
+        L.vlfm_cloud_query_launch_count.argtypes = []
+        L.vlfm_cloud_query_launch_count.restype = ctypes.c_longlong
         L.vlfm_bits_pack.argtypes = [vp, vp, ci, ci, ci, vp]
         L.vlfm_bits_unpack.argtypes = [vp, vp, ci, ci, ci, vp]
         L.vlfm_bits_dilate.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]

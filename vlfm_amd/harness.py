@@ -413,7 +413,8 @@ class BatchedEpisodes:
                  object_map_erosion_size: float = 5, concurrent_vlm_max_envs: int = 0,
                  render_trajectories: bool = False, emulate_jpeg: bool = False, rig: Optional[CameraRig] = None,
                  text_prompt: str = PROMPT, exploration_thresh: Optional[float] = None, closed_loop: bool = False,
-                 controller=None, world_objects: Optional[WorldObjects] = None, batch_object_maps: bool = True) -> None:
+                 controller=None, world_objects: Optional[WorldObjects] = None, batch_object_maps: bool = True,
+                 device_object_clouds: bool = True) -> None:
         # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
         # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -429,6 +430,11 @@ class BatchedEpisodes:
         # batch_object_maps: all detections of a step go through the object-cloud kernels together (update_maps_batch); False =
         # one ObjectPointCloudMap.update_map after the other -- same clouds, same random draws, kept for comparison
         self.batch_object_maps = bool(batch_object_maps)
+        # device_object_clouds: update_explored and the object goals of all environments are asked of device mirrors of the clouds,
+        # one launch and one read-back each per step (update_explored_batch, get_best_objects_batch); False = one NumPy pass per
+        # environment over its accumulated clouds -- same clouds, same goals, kept for comparison
+        self.device_object_clouds = bool(device_object_clouds)
+        self.last_explored_drops = None         # device_object_clouds: per environment with clouds, did this step drop a far tag
         if self.closed_loop:
             if world != "rooms" or host_inputs:
                 raise ValueError("closed_loop needs the rooms world rendered on the device (world='rooms', host_inputs=False)")
@@ -736,7 +742,8 @@ class BatchedEpisodes:
         """BaseObjectNavPolicy._update_object_map for every environment (base_objectnav_policy.py:285-352): class + confidence
         filters, ONE MobileSAM call for all surviving boxes of the batch (the reference re-encodes the frame per box too),
         ObjectPointCloudMap.update_map per mask (csrc/object_cloud.hip: erosion, back-projection, DBSCAN) -- all masks of the step
-        in one update_maps_batch unless batch_object_maps=False -- update_explored per environment and step."""
+        in one update_maps_batch unless batch_object_maps=False -- update_explored per environment and step (one
+        update_explored_batch over the environments that have clouds unless device_object_clouds=False)."""
         jobs = []
         for e, det in enumerate(dets):
             det.filter_by_class(self.targets[e].split("|"))
@@ -781,9 +788,15 @@ class BatchedEpisodes:
                     before = len(om.clouds.get(self.targets[e], ()))
                     om.update_map(self.targets[e], depth[e], masks[j], tf[e], MIN_DEPTH, MAX_DEPTH, self.fx, self.fy)
                     self.object_stats["cloud_updates"] += int(len(om.clouds.get(self.targets[e], ())) != before)
-        for e, om in enumerate(self.object_maps):
-            if om.clouds:
-                om.update_explored(tf[e], MAX_DEPTH, self.fov)     # cone_fov = get_fov(fx, width) (:349)
+        have = [e for e, om in enumerate(self.object_maps) if om.clouds]
+        if self.device_object_clouds:
+            from .mapping.object_point_cloud_map import update_explored_batch
+
+            self.last_explored_drops = dict(zip(have, update_explored_batch(
+                [self.object_maps[e] for e in have], [tf[e] for e in have], MAX_DEPTH, self.fov)))
+        else:
+            for e in have:
+                self.object_maps[e].update_explored(tf[e], MAX_DEPTH, self.fov)     # cone_fov = get_fov(fx, width) (:349)
 
     # ------------------------------------------------------------------------------------------ act
     def _episode_steps(self, t_ep: int) -> np.ndarray:
@@ -914,10 +927,17 @@ class BatchedEpisodes:
             vals = np.asarray(vals, np.float64).reshape(-1, self.C) if vals is not None else np.zeros((0, self.C))
         bounds = np.searchsorted(env_of, np.arange(self.E + 1))
         ep_steps = self._episode_steps(t_ep)
+        object_goals = None              # (getattr: the stand-in objects of tests/test_host_logic.py again)
+        if self.object_maps is not None and getattr(self, "device_object_clouds", False):
+            from .mapping.object_point_cloud_map import get_best_objects_batch
+
+            object_goals = get_best_objects_batch(self.object_maps, self.targets, [poses[e, :2] for e in range(self.E)])
         for e in range(self.E):
             target, robot_xy = self.targets[e], poses[e, :2]
             obj = None
-            if self.object_maps is not None and self.object_maps[e].has_object(target):
+            if object_goals is not None:
+                obj = object_goals[e]
+            elif self.object_maps is not None and self.object_maps[e].has_object(target):
                 obj = self.object_maps[e].get_best_object(target, robot_xy)        # every step, like the reference (:123)
             if ep_steps[e] < 12:     # _done_initializing flips after the 12th call (habitat_policies.py:150-153)
                 modes.append("initialize")

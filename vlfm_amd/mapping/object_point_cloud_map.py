@@ -5,10 +5,15 @@ The per-detection heavy lifting -- mask erosion, masked back-projection, DBSCAN 
 (``_extract_object_cloud``, :150-170) -- runs in HIP kernels (csrc/object_cloud.hip); the bookkeeping around it (range ids,
 closest point, ``get_best_object`` hysteresis, ``update_explored``) is O(points kept) NumPy on the host exactly as in the
 reference, INCLUDING its draws from NumPy's global RNG (``np.random.choice`` for the 5000-point subsample,
-``np.random.rand`` for the out-of-range ids), so that a seeded run reproduces the reference's clouds."""
+``np.random.rand`` for the out-of-range ids), so that a seeded run reproduces the reference's clouds.
+
+The two questions asked of the ACCUMULATED clouds in every step -- which far tags are now in view (``update_explored``) and where
+the closest point is (``get_best_object``) -- can also be asked of many maps at once: every map keeps a device mirror of its
+clouds (``CloudMirror``), and ``update_explored_batch`` / ``get_best_objects_batch`` (csrc/cloud_query.hip) answer them with one
+launch and one read-back per call.  The host arrays stay the source of truth, and what changes them stays host code."""
 from __future__ import annotations
 
-from typing import Dict, Iterator, List, Sequence, Tuple, Union
+from typing import Dict, Iterator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -67,6 +72,79 @@ SUBSAMPLE = 5000                   # get_random_subarray's size (:165)
 DBSCAN_EPS, DBSCAN_MIN_POINTS = 0.2, 100
 DEFAULT_SCRATCH_BUDGET = 256 << 20
 SYNCS = [0]                        # host read-backs made by this module so far (tools/world_objects_probe.py)
+UPLOADED_BYTES = [0]               # bytes of cloud rows and slots copied to device mirrors so far
+BAND_POINTS = [0]                  # points update_explored_batch re-evaluated on the host (slots the device left uncertain)
+CONE_BAND = 1e-9                   # rad: csrc/cloud_query.hip's CQ_BAND
+MIRROR_MIN_ROWS = 1024
+
+
+class CloudMirror:
+    """What one map knows about the cloud stored under one class name beyond the host array itself: one i32 SLOT per point (-1 for
+    tag 1.0, else the index of the tag in ``table``, the distinct other tags in order of first appearance) and a device copy of
+    the first ``on_device`` rows and slots.  Valid only for the very array ``key`` = (id, rows) names; ``array`` holds that array
+    so that its id cannot be handed to another one meanwhile."""
+
+    __slots__ = ("key", "array", "slots", "table", "index", "rows_d", "slots_d", "on_device")
+
+    def __init__(self, array: np.ndarray, slots: np.ndarray, table: List[float]) -> None:
+        self.key, self.array = (id(array), len(array)), array
+        self.slots, self.table = slots, list(table)
+        self.index = {t: i for i, t in enumerate(self.table)}
+        self.rows_d = self.slots_d = None
+        self.on_device = 0
+
+    def rebind(self, array: np.ndarray, slots: np.ndarray) -> None:
+        self.key, self.array, self.slots = (id(array), len(array)), array, slots
+
+    def slot_of(self, tag: float) -> int:
+        if tag not in self.index:
+            self.index[tag] = len(self.table)
+            self.table.append(tag)
+        return self.index[tag]
+
+
+def block_slots(tags: np.ndarray, slot_of) -> np.ndarray:
+    """Slots of one committed block, whose tags are 1.0 and / or ONE other value: ``slot_of(value)`` names that value's slot."""
+    far = tags != 1
+    slots = np.full(len(tags), -1, np.int32)
+    if far.any():
+        slots[far] = slot_of(float(tags[np.argmax(far)]))
+    return slots
+
+
+def slots_of_array(tags: np.ndarray) -> Tuple[np.ndarray, List[float]]:
+    """(slots, table) of an array nothing is known about: -1 for tag 1.0, the other values numbered by first appearance."""
+    slots = np.full(len(tags), -1, np.int32)
+    far = np.flatnonzero(tags != 1)
+    if len(far) == 0:
+        return slots, []
+    values, first, inverse = np.unique(tags[far], return_index=True, return_inverse=True)
+    rank = np.empty(len(values), np.int32)
+    order = np.argsort(first, kind="stable")
+    rank[order] = np.arange(len(values), dtype=np.int32)
+    slots[far] = rank[inverse.reshape(-1)]
+    return slots, [float(v) for v in values[order]]
+
+
+def merge_cone_flags(inside: np.ndarray, uncertain: np.ndarray, decide) -> List[int]:
+    """The slots to drop: those the device saw inside the cone, and of those it left uncertain (and did not also see inside) the
+    ones for which ``decide(slot)`` -- the host's own evaluation of the slot's points -- says so.  Ascending."""
+    inside, uncertain = np.asarray(inside) != 0, np.asarray(uncertain) != 0
+    if inside.shape != uncertain.shape:
+        raise ValueError("merge_cone_flags: one flag of each kind per slot")
+    seen = set(np.flatnonzero(inside).tolist())
+    seen.update(int(s) for s in np.flatnonzero(uncertain & ~inside) if decide(int(s)))
+    return sorted(seen)
+
+
+def apply_hysteresis(previous: Union[np.ndarray, None], candidate: np.ndarray, curr_position: np.ndarray) -> Tuple[np.ndarray, bool]:
+    """get_best_object's rule (:82-100): (goal, whether the goal is the NEW candidate).  The previous goal is kept when the closest
+    point moved < 0.1 m, or < 0.5 m while the robot is still more than 2 m away."""
+    if previous is not None:
+        moved = np.linalg.norm(candidate - previous)
+        if moved < 0.1 or (moved < 0.5 and np.linalg.norm(curr_position - candidate) > 2.0):
+            return previous, False
+    return candidate, True
 
 
 def get_random_subarray(points, size: int, rng=np.random):
@@ -96,10 +174,12 @@ class ObjectPointCloudMap:
         self.clouds = {}
         self._bufs = None
         self._near_only: Dict[str, tuple] = {}     # name -> (id(cloud array), rows): every tag of that array is 1.0
+        self._mirrors: Dict[str, CloudMirror] = {}  # name -> slots and device copy of the array stored under that name
 
     def reset(self) -> None:
         self.clouds, self.last_target_coord = {}, None
         self._near_only = {}
+        self._mirrors = {}
 
     def _all_near(self, name: str) -> bool:
         """True when the cloud stored under ``name`` is known to hold only trusted (tag 1.0) points -- bookkeeping of update_map /
@@ -137,6 +217,7 @@ class ObjectPointCloudMap:
         known = self.clouds.get(object_name)
         near_only = (known is None or self._all_near(object_name)) and bool(np.all(tags == 1))
         self.clouds[object_name] = tagged if known is None else np.concatenate((known, tagged), axis=0)
+        self._mirror_commit(object_name, known, tagged)
         if near_only:
             self._near_only[object_name] = (id(self.clouds[object_name]), len(self.clouds[object_name]))
         else:
@@ -148,14 +229,13 @@ class ObjectPointCloudMap:
         # (a cloud of trusted points only IS its target cloud: no copy, no mask -- the harness asks this for every environment
         # and step, on clouds of 10^5 points)
         cloud = self.clouds[target_class] if self._all_near(target_class) else self.get_target_cloud(target_class)
-        candidate = self._get_closest_point(cloud, curr_position)[:2]
-        previous = self.last_target_coord
-        if previous is not None:
-            moved = np.linalg.norm(candidate - previous)
-            if moved < 0.1 or (moved < 0.5 and np.linalg.norm(curr_position - candidate) > 2.0):
-                return previous
-        self.last_target_coord = candidate
-        return candidate
+        return self._goal_with_hysteresis(self._get_closest_point(cloud, curr_position)[:2], curr_position)
+
+    def _goal_with_hysteresis(self, candidate: np.ndarray, curr_position: np.ndarray) -> np.ndarray:
+        goal, is_new = apply_hysteresis(self.last_target_coord, candidate, curr_position)
+        if is_new:
+            self.last_target_coord = candidate
+        return goal
 
     def update_explored(self, tf_camera_to_episodic: np.ndarray, max_depth: float, cone_fov: float) -> None:
         """Forget far-tagged observations the robot is now looking at from within half the depth range (:103-135): every
@@ -164,10 +244,88 @@ class ObjectPointCloudMap:
         for name, cloud in list(self.clouds.items()):
             if self._all_near(name):
                 continue       # only tags other than 1 can be dropped (`- {1}` below): nothing to do, same result
-            seen_tags = set(within_fov_cone(origin, heading, cone_fov, max_depth * 0.5, cloud)[..., -1].tolist()) - {1}
-            for t in seen_tags:
-                cloud = cloud[cloud[..., -1] != t]
-            self.clouds[name] = cloud
+            self._explore_cloud(name, cloud, origin, heading, max_depth, cone_fov)
+
+    def _explore_cloud(self, name: str, cloud: np.ndarray, origin: np.ndarray, heading: float, max_depth: float,
+                       cone_fov: float) -> bool:
+        """``update_explored`` for one cloud on the host; whether a tag was dropped."""
+        seen_tags = set(within_fov_cone(origin, heading, cone_fov, max_depth * 0.5, cloud)[..., -1].tolist()) - {1}
+        self._drop_tags(name, cloud, seen_tags)
+        return bool(seen_tags)
+
+    def _drop_tags(self, name: str, cloud: np.ndarray, seen_tags) -> None:
+        """Remove every point of ``cloud`` (the array stored under ``name``) that carries one of ``seen_tags`` (:127-132), and keep
+        the mirror's slots in step with the same masks; the device copy is stale afterwards and is uploaded again in full."""
+        mirror = self._mirror_for(name, cloud)
+        slots = mirror.slots if mirror is not None else None
+        for t in seen_tags:
+            keep = cloud[..., -1] != t
+            cloud = cloud[keep]
+            if slots is not None:
+                slots = slots[keep]
+        self.clouds[name] = cloud
+        if mirror is not None and seen_tags:
+            mirror.rebind(cloud, slots)
+            mirror.on_device = 0
+        elif mirror is None:
+            self._mirrors.pop(name, None)
+
+    # ------------------------------------------------------------------------------------------ device mirror
+    def _mirror_for(self, name: str, cloud: np.ndarray) -> Optional[CloudMirror]:
+        """The mirror of ``name`` if it describes exactly ``cloud``, else None."""
+        mirror = self._mirrors.get(name)
+        return mirror if mirror is not None and mirror.key == (id(cloud), len(cloud)) else None
+
+    def _mirror_commit(self, name: str, known: Union[np.ndarray, None], tagged: np.ndarray) -> None:
+        """``clouds[name]`` has just become ``known`` + ``tagged``: record that, and the block's slots.  No device work here -- the
+        next batched query uploads the appended rows."""
+        cloud, tags = self.clouds[name], tagged[:, -1]
+        if known is None:
+            mirror = CloudMirror(cloud, np.zeros(0, np.int32), [])
+            mirror.rebind(cloud, block_slots(tags, mirror.slot_of))
+            self._mirrors[name] = mirror
+            return
+        mirror = self._mirror_for(name, known)
+        if mirror is None:
+            self._mirrors.pop(name, None)      # an array this map did not build: looked at as a whole by the next query
+            return
+        mirror.rebind(cloud, np.concatenate((mirror.slots, block_slots(tags, mirror.slot_of))))
+
+    def _mirror_sync(self, name: str) -> Optional[CloudMirror]:
+        """Bring the device copy of ``clouds[name]`` up to date on the current stream and return its mirror -- None when the array
+        cannot be mirrored (not an (N, 4) C-contiguous f64 array, or one holding a non-finite value): its queries take the host path."""
+        import torch
+
+        cloud = self.clouds[name]
+        mirror = self._mirror_for(name, cloud)
+        if mirror is None:
+            self._mirrors.pop(name, None)
+            if not (isinstance(cloud, np.ndarray) and cloud.dtype == np.float64 and cloud.ndim == 2 and cloud.shape[1] == 4
+                    and cloud.flags.c_contiguous and bool(np.isfinite(cloud).all())):
+                return None
+            mirror = self._mirrors[name] = CloudMirror(cloud, *slots_of_array(cloud[:, -1]))
+        n = len(cloud)
+        if mirror.on_device == n and mirror.rows_d is not None:
+            return mirror
+        if mirror.rows_d is None or mirror.rows_d.shape[0] < n:
+            rows = max(MIRROR_MIN_ROWS, 2 * mirror.rows_d.shape[0] if mirror.rows_d is not None else 0)
+            while rows < n:
+                rows *= 2
+            old_rows, old_slots = mirror.rows_d, mirror.slots_d
+            mirror.rows_d = torch.empty((rows, 4), dtype=torch.float64, device=self.device)
+            mirror.slots_d = torch.empty(rows, dtype=torch.int32, device=self.device)
+            if old_rows is not None and mirror.on_device:
+                mirror.rows_d[:mirror.on_device].copy_(old_rows[:mirror.on_device])
+                mirror.slots_d[:mirror.on_device].copy_(old_slots[:mirror.on_device])
+                # the old blocks go back to the allocator with this stream's copies still queued
+                old_rows.record_stream(torch.cuda.current_stream(self.device))
+                old_slots.record_stream(torch.cuda.current_stream(self.device))
+        lo = mirror.on_device
+        mirror.rows_d[lo:n].copy_(torch.from_numpy(cloud[lo:n]))
+        mirror.slots_d[lo:n].copy_(torch.from_numpy(mirror.slots[lo:n]))
+        UPLOADED_BYTES[0] += (n - lo) * (32 + 4)
+        mirror.on_device = n
+        return mirror
 
     def get_target_cloud(self, target_class: str) -> np.ndarray:
         """The trusted (tag 1) points when there are any, else everything (:137-144)."""
@@ -419,3 +577,133 @@ def update_maps_batch(maps: Sequence[ObjectPointCloudMap], object_names: Sequenc
         maps[j]._commit(object_names[j], cloud, lambda off=off: off, tfs[j], max_depth)
         changed.append(len(maps[j].clouds.get(object_names[j], ())) != before)
     return changed
+
+
+# ---------------------------------------------------------------------------------------------- queries over device mirrors
+QUERY_DTYPE = np.dtype([("d_rows", "<u8"), ("d_slots", "<u8"), ("p", "<f8", (3,)), ("heading", "<f8"), ("half_fov", "<f8"),
+                        ("range", "<f8"), ("n", "<i4"), ("k", "<i4"), ("flag_offset", "<i4"), ("n_slots", "<i4")])
+assert QUERY_DTYPE.itemsize == 80      # vlfm_cloud_query
+
+
+def _check_queries(what: str, maps, *per_map) -> int:
+    """Refusals that need no device: the number of maps."""
+    E = len(maps)
+    if any(len(x) != E for x in per_map):
+        raise ValueError(f"{what}: one entry per map in every argument")
+    if E and any(m.device != maps[0].device for m in maps):
+        raise ValueError(f"{what}: all maps must live on one device")
+    return E
+
+
+def _query_row(q, mirror: CloudMirror, n: int, p, k: int) -> None:
+    q["d_rows"], q["d_slots"], q["n"], q["k"] = mirror.rows_d.data_ptr(), mirror.slots_d.data_ptr(), n, k
+    q["p"][:k] = p
+
+
+def update_explored_batch(maps: Sequence[ObjectPointCloudMap], tfs: Sequence[np.ndarray], max_depth: float,
+                          cone_fov: float) -> List[bool]:
+    """``maps[i].update_explored(tfs[i], max_depth, cone_fov)`` for every i, over every class of every map, with ONE launch over
+    the device mirrors of the clouds and ONE read-back, whatever the number of maps; returns, per map, whether anything was
+    dropped.  The device says, per far-tag slot of a cloud, whether a point of it lies inside the cone; the removal is the host's
+    own ``cloud[cloud[..., -1] != t]``, so the clouds are those of the per-map method bit for bit.  A point whose angle lies
+    within ``CONE_BAND`` of the cone's edge is decided by ``within_fov_cone`` on the host (``BAND_POINTS``); clouds that cannot be
+    mirrored, and every cloud when the band would reach the wrap at +-pi, take the per-map path."""
+    import torch
+
+    E = _check_queries("update_explored_batch", maps, tfs)
+    dropped = [False] * E
+    if E == 0:
+        return dropped
+    half, cone_range = cone_fov / 2, max_depth * 0.5
+    device_ok = bool(np.isfinite(half) and np.isfinite(cone_range) and half + CONE_BAND < np.pi)
+    dev = maps[0].device
+    asked = []                                 # (map, name, mirror, origin, heading, first flag, slots)
+    total = 0
+    with torch.cuda.device(dev):
+        for i, m in enumerate(maps):
+            origin, heading = np.asarray(tfs[i])[:3, 3], extract_yaw(tfs[i])
+            on_device = device_ok and bool(np.isfinite(origin).all() and np.isfinite(heading))
+            for name, cloud in list(m.clouds.items()):
+                if m._all_near(name):
+                    continue
+                mirror = m._mirror_sync(name) if on_device and len(cloud) else None
+                if mirror is None:
+                    dropped[i] |= m._explore_cloud(name, m.clouds[name], origin, heading, max_depth, cone_fov)
+                elif mirror.table:             # (no far tag: nothing can be dropped)
+                    asked.append((i, name, mirror, origin, heading, total, len(mirror.table)))
+                    total += 2 * len(mirror.table)
+        if not asked:
+            return dropped
+        q = np.zeros(len(asked), QUERY_DTYPE)
+        for row, (i, name, mirror, origin, heading, first, n_slots) in zip(q, asked):
+            _query_row(row, mirror, mirror.on_device, origin, 3)
+            row["heading"], row["half_fov"], row["range"], row["flag_offset"], row["n_slots"] = heading, half, cone_range, first, n_slots
+        q_d = torch.from_numpy(q.view(np.uint8)).to(dev)
+        flags = torch.zeros(total, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().vlfm_cloud_cone_flags(q_d.data_ptr(), len(asked), int(q["n"].max()), flags.data_ptr(), _stream_ptr()),
+                   "cloud_cone_flags")
+        SYNCS[0] += 1
+        host = flags.cpu().numpy()
+    for i, name, mirror, origin, heading, first, n_slots in asked:
+        m = maps[i]
+
+        def decide(slot: int) -> bool:
+            points = m.clouds[name][mirror.slots == slot]
+            BAND_POINTS[0] += len(points)
+            return len(within_fov_cone(origin, heading, cone_fov, cone_range, points)) > 0
+
+        slots = merge_cone_flags(host[first:first + n_slots], host[first + n_slots:first + 2 * n_slots], decide)
+        if slots:
+            m._drop_tags(name, m.clouds[name], [mirror.table[s] for s in slots])
+            dropped[i] = True
+    return dropped
+
+
+def get_best_objects_batch(maps: Sequence[ObjectPointCloudMap], target_classes: Sequence[str],
+                           positions: Sequence[np.ndarray]) -> List[Optional[np.ndarray]]:
+    """``maps[i].get_best_object(target_classes[i], positions[i]) if maps[i].has_object(target_classes[i]) else None`` for every
+    i, in order (a map may repeat: its hysteresis sees the calls one after the other), with one launch sequence over the device
+    mirrors and one read-back.  The device returns, per cloud, the number of trusted points and np.argmin's index of the closest
+    trusted point and of the closest point; the host reads the candidate from its own array and applies the hysteresis.  Maps
+    with ``use_dbscan=False`` and clouds that cannot be mirrored take the per-map path."""
+    import torch
+
+    E = _check_queries("get_best_objects_batch", maps, target_classes, positions)
+    if E == 0:
+        return []
+    dev = maps[0].device
+    asked: Dict[int, int] = {}                 # map index -> query
+    rows = []
+    with torch.cuda.device(dev):
+        for i, m in enumerate(maps):
+            name, p = target_classes[i], np.asarray(positions[i])
+            if not m.has_object(name) or not m.use_dbscan or p.shape not in ((2,), (3,)) or not np.isfinite(p).all():
+                continue
+            mirror = m._mirror_sync(name)
+            if mirror is not None:
+                asked[i] = len(rows)
+                rows.append((mirror, mirror.on_device, p.astype(np.float64)))
+        if rows:
+            L = _lib.lib()
+            q = np.zeros(len(rows), QUERY_DTYPE)
+            for row, (mirror, n, p) in zip(q, rows):
+                _query_row(row, mirror, n, p, len(p))
+            longest = int(q["n"].max())
+            q_d = torch.from_numpy(q.view(np.uint8)).to(dev)
+            need = L.vlfm_cloud_closest_scratch_bytes(len(rows), longest)
+            scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+            result = torch.empty((len(rows), 4), dtype=torch.int32, device=dev)
+            _lib.check(L.vlfm_cloud_closest(q_d.data_ptr(), len(rows), longest, scratch.data_ptr(), need, result.data_ptr(),
+                                            _stream_ptr()), "cloud_closest")
+            SYNCS[0] += 1
+            found = result.cpu().numpy()
+    out: List[Optional[np.ndarray]] = [None] * E
+    for i, m in enumerate(maps):
+        name = target_classes[i]
+        if i in asked:
+            trusted, first_trusted, first = (int(v) for v in found[asked[i]][:3])
+            pick = first_trusted if trusted else first
+            out[i] = m._goal_with_hysteresis(rows[asked[i]][0].array[pick][:2].copy(), positions[i])
+        elif m.has_object(name):
+            out[i] = m.get_best_object(name, positions[i])
+    return out
