@@ -886,6 +886,49 @@ int vlfm_rooms_raycast_objects(const double* d_cameras, int n, const double* d_b
                                const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids,
                                int32_t* d_stats, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Geodesic distances in the rooms world (ABI 19, csrc/geodesic.hip): the length of the shortest collision-free path from a
+ * point to an ObjectNav goal, which SPL, SoftSPL and distance_to_goal are made of (the reference reads them off Habitat's
+ * navmesh).  Bit for bit vlfm_amd.synthetic.geodesic_field_numpy / geodesic_query_numpy: f64, one rounding per operation,
+ * no fused multiply-add, the expressions as written here.
+ *   rectangles  the n_boxes shared wall boxes (x0, y0, x1, y1), then the environment's object slots with valid != 0 in slot
+ *               order, each inflated to (x0 - margin, y0 - margin, x1 + margin, y1 + margin).  OPEN sets.
+ *   blocked     the segment p -> q is blocked by a rectangle iff some t in (0, 1) puts p + t (q - p) strictly inside it:
+ *               per axis, with d = q - p:  d == 0: the interval is (-inf, inf) if lo < p < hi, else empty;  otherwise
+ *               t0 = (lo - p) / d, t1 = (hi - p) / d, interval (min(t0, t1), max(t0, t1));
+ *               blocked iff max(enter_x, enter_y, 0) < min(exit_x, exit_y, 1).  A segment along an edge or through a corner
+ *               is free.  Evaluated from p to q: source -> corner, corner of lower index -> corner of higher index (one
+ *               verdict per pair), query point -> source or corner.
+ *   nodes       the corners (x0,y0) (x1,y0) (x1,y1) (x0,y1) of every rectangle, in rectangle order, without those that lie
+ *               strictly inside some rectangle.  Edge weight w(a, b) = sqrt(dx*dx + dy*dy).
+ *   field       the least dist with  dist[c] = min(min over the sources s that see c of w(s, c),
+ *                                                  min over the corners u that see c of fl(dist[u] + w(u, c))),
+ *               inf where nothing reaches (what Dijkstra from the sources returns with the same additions).
+ *   query       d(p) = min(min over the sources p sees of w(p, s), min over the corners p sees of fl(w(p, c) + dist[c])),
+ *               inf when nothing is reachable (every segment out of a point strictly inside a rectangle is blocked).
+ * Two rectangles that exactly abut leave a slit of zero width that a path may use: d can only come out shorter for it.
+ *
+ * vlfm_geodesic_fields: the fields of n environments, ONE launch (one workgroup per environment) on `stream`.
+ *   d_boxes         [n_boxes][4] doubles, shared;  margin: the inflation
+ *   d_objects       [n][8][8] doubles: vlfm_rooms_raycast_objects' records (x0 y0 x1 y1 z0 z1 valid pad)
+ *   d_sources       [n][max_sources][2] doubles, d_source_counts [n] int32 (clamped to [0, max_sources]; 0: every dist is inf)
+ *   d_rects         [n][R][4] doubles out, R = n_boxes + 8;  d_nodes [n][4R][2] doubles out;  d_dist [n][4R] doubles out;
+ *                   d_counts [n][2] int32 out: rectangles, nodes.  Table tails are zeros at infinite distance.
+ * The tables of 4R candidate nodes and their 4R x 4R visibility bitmap must fit 64 KB of LDS (VLFM_ERR_INVALID otherwise,
+ * nothing launched): R <= 141.
+ *
+ * vlfm_geodesic_query: d of m points, ONE launch (one workgroup per point) on `stream`.
+ *   d_points        [m][2] doubles;  d_field_of [m] int32: the field of each point; outside [0, n_fields): the answer is NaN
+ *   d_rects, d_nodes, d_dist, d_counts, d_sources, d_source_counts, max_sources, n_boxes: the n_fields fields as built above
+ *   d_out           [m] doubles
+ * n == 0 and m == 0 return VLFM_OK without a launch. */
+int vlfm_geodesic_fields(const double* d_boxes, int n_boxes, double margin, const double* d_objects, const double* d_sources,
+                         const int32_t* d_source_counts, int n, int max_sources, double* d_rects, double* d_nodes,
+                         double* d_dist, int32_t* d_counts, void* stream);
+int vlfm_geodesic_query(const double* d_points, const int32_t* d_field_of, int m, int n_fields, int n_boxes,
+                        const double* d_rects, const double* d_nodes, const double* d_dist, const int32_t* d_counts,
+                        const double* d_sources, const int32_t* d_source_counts, int max_sources, double* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

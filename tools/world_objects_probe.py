@@ -16,9 +16,15 @@
   (d) --cloud-trace: kernel time of the two cloud queries (csrc/cloud_query.hip) over 256 mirrored clouds of 20 000 and of
       100 000 points, from one `rocprofv3 --kernel-trace --stats` run of its own, against the bytes of the mirrors.
 
+  (e) --objectnav-metrics: the geodesic kernels behind SPL / SoftSPL / distance_to_goal (csrc/geodesic.hip) at 256 environments
+      of the rooms world with the two objects of synthetic.object_layout -- kernel time from the library's own dispatch events
+      (vlfm_profile_enable), the host call around it, and the host statement (NumPy) for the same work; leg (b) then also runs a
+      world_objects harness with objectnav_metrics=True beside the others and prints its objectnav_summary().
+
     python tools/world_objects_probe.py [--steps 20] [--skip-steps] [--skip-trace] [--out profiles/world_objects_probe.txt]
     python tools/world_objects_probe.py --skip-trace --batch-object-maps both --batch-trace --out profiles/object_maps_batch_probe.txt
     python tools/world_objects_probe.py --skip-trace --device-object-clouds both --out profiles/object_clouds_device_probe.txt
+    python tools/world_objects_probe.py --skip-trace --objectnav-metrics --out profiles/objectnav_metrics_probe.txt
     python tools/world_objects_probe.py --trace-child        # the process (a) points rocprofv3 at
     python tools/world_objects_probe.py --batch-trace-child  # the process (c) points rocprofv3 at
     python tools/world_objects_probe.py --cloud-trace-child  # the process (d) points rocprofv3 at"""
@@ -290,7 +296,79 @@ def probe_cloud_trace(lines, workdir: str) -> None:
         print(lines[-1], flush=True)
 
 
-def probe_steps(steps: int, lines, batch: str = "on", clouds: str = "on") -> None:
+GEODESIC_ENVS, GEODESIC_GROUPS, GEODESIC_LAUNCHES, GEODESIC_HOST_ENVS = 256, 5, 10, 8
+
+
+def probe_geodesic(lines) -> None:
+    """Leg (e): 256 fields and 256 queries, warm, GEODESIC_GROUPS groups of GEODESIC_LAUNCHES launches each; per group the mean
+    kernel time of the dispatch events and the mean host time of the whole call (uploads, launch, synchronise)."""
+    import time
+
+    import numpy as np
+    import torch
+
+    from vlfm_amd import _lib
+    from vlfm_amd import synthetic as S
+
+    dev = torch.device("cuda:0")
+    n = GEODESIC_ENVS
+    rr, _, objects = scene(n, 2, dev)
+    xy = rr.pose_table[150][:, :2]
+    targets = objects[:, 0, :4]
+    field_of = np.arange(n)
+    L = _lib.lib()
+
+    def timed(kernel, call):
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize()
+        k_us, h_us = [], []
+        for _ in range(GEODESIC_GROUPS):
+            L.vlfm_profile_enable(1)
+            t0 = time.perf_counter()
+            for _ in range(GEODESIC_LAUNCHES):
+                call()
+                torch.cuda.synchronize()
+            h_us.append((time.perf_counter() - t0) / GEODESIC_LAUNCHES * 1e6)
+            ms, got = _lib.profile_read(kernel)
+            assert got == GEODESIC_LAUNCHES, (kernel, got)
+            k_us.append(ms * 1e3)
+        L.vlfm_profile_enable(0)
+        return stats(k_us), stats(h_us)
+
+    handle = rr.geodesic_fields(objects, targets, 1.0)
+    counts, n_src = handle.counts.cpu().numpy(), handle.source_counts.cpu().numpy()
+    fk, fh = timed("geodesic_fields_kernel", lambda: rr.geodesic_fields(objects, targets, 1.0))
+    qk, qh = timed("geodesic_query_kernel", lambda: rr.geodesic_distances(handle, field_of, xy))
+    d = rr.geodesic_distances(handle, field_of, xy).cpu().numpy()
+    # the host statement for the first environments (every environment is the same amount of work: same walls, two objects)
+    t_field = t_query = 0.0
+    for e in range(GEODESIC_HOST_ENVS):
+        t0 = time.perf_counter()
+        rects = S.inflated_rects(objects[e])
+        src = S.goal_viewpoints(targets[e], rects, 1.0)
+        nodes, dist = S.geodesic_field_numpy(rects, src)
+        t1 = time.perf_counter()
+        want = S.geodesic_query_numpy(rects, src, nodes, dist, xy[e:e + 1])
+        t2 = time.perf_counter()
+        t_field, t_query = t_field + (t1 - t0), t_query + (t2 - t1)
+        assert want.view(np.int64)[0] == d[e:e + 1].view(np.int64)[0], (e, want, d[e])
+    lines.append("geodesic n=%d fields  rooms world + 2 objects: %d-%d rectangles, %d-%d nodes, %d-%d view points   "
+                 "geodesic_fields_kernel %8.1f us (%.1f-%.1f)   host call with uploads and synchronise %8.1f us (%.1f-%.1f)   "
+                 "%d groups of %d launches   host statement (NumPy) %.1f ms per environment = %.2f s for %d"
+                 % (n, counts[:, 0].min(), counts[:, 0].max(), counts[:, 1].min(), counts[:, 1].max(), n_src.min(), n_src.max(),
+                    *fk, *fh, GEODESIC_GROUPS, GEODESIC_LAUNCHES, 1e3 * t_field / GEODESIC_HOST_ENVS,
+                    t_field / GEODESIC_HOST_ENVS * n, n))
+    print(lines[-1], flush=True)
+    lines.append("geodesic m=%d queries (one per field)   geodesic_query_kernel %8.1f us (%.1f-%.1f)   host call with upload, "
+                 "synchronise and read-back %8.1f us (%.1f-%.1f)   host statement (NumPy) %.2f ms per point = %.1f ms for %d; "
+                 "%d of %d distances finite, mean %.2f m; the first %d bit-equal to the host statement"
+                 % (n, *qk, *qh, 1e3 * t_query / GEODESIC_HOST_ENVS, 1e3 * t_query / GEODESIC_HOST_ENVS * n, n,
+                    int(np.isfinite(d).sum()), n, float(d[np.isfinite(d)].mean()), GEODESIC_HOST_ENVS))
+    print(lines[-1], flush=True)
+
+
+def probe_steps(steps: int, lines, batch: str = "on", clouds: str = "on", metrics: bool = False) -> None:
     import time
 
     import torch
@@ -312,6 +390,8 @@ def probe_steps(steps: int, lines, batch: str = "on", clouds: str = "on") -> Non
             if batch in ("off", "both"):
                 sims[("with world_objects" if batch == "off" else "world_objects one by one") + where] = BatchedEpisodes(
                     E, world_objects=WorldObjects(), batch_object_maps=False, device_object_clouds=device_clouds, **kw)
+        if metrics:
+            sims["world_objects, objectnav_metrics"] = BatchedEpisodes(E, world_objects=WorldObjects(), objectnav_metrics=True, **kw)
         sims["without"] = BatchedEpisodes(E, **kw)
         rate = {k: [] for k in sims}
         # object-cloud kernel launches, host read-backs, cloud-query launches, uploaded bytes, band points inside the windows
@@ -349,6 +429,10 @@ def probe_steps(steps: int, lines, batch: str = "on", clouds: str = "on") -> Non
             lines.append("steps  E=%3d  %-40s %8.1f env-steps/s (%.1f-%.1f over 3 windows of %d steps)%s"
                          % (E, name, *stats(rate[name]), steps, extra))
             print(lines[-1], flush=True)
+            if getattr(s, "objectnav_metrics", False):
+                lines.append("summary E=%3d  %s" % (E, "  ".join("%s %s" % (k, ("%.4f" % v) if isinstance(v, float) else v)
+                                                                  for k, v in s.objectnav_summary().items())))
+                print(lines[-1], flush=True)
         del sims
         torch.cuda.empty_cache()
 
@@ -367,6 +451,8 @@ def main() -> None:
     ap.add_argument("--batch-trace-child", action="store_true")
     ap.add_argument("--cloud-trace", action="store_true", help="leg (d): kernel time of the cloud queries, a trace of its own")
     ap.add_argument("--cloud-trace-child", action="store_true")
+    ap.add_argument("--objectnav-metrics", action="store_true",
+                    help="leg (e): the geodesic kernels; leg (b) also runs a harness with objectnav_metrics=True and prints its summary")
     ap.add_argument("--workdir", default=os.path.join(ROOT, "scratch", "world_objects_trace"),
                     help="where the kernel trace of leg (a) is written (removed and rewritten by every run)")
     ap.add_argument("--out", default=None)
@@ -389,8 +475,10 @@ def main() -> None:
     assert torch.cuda.is_available(), "world_objects_probe measures on the GPU; there is no CPU path"
     lines.insert(0, "world_objects_probe: device %s; (a) rocprofv3 kernel trace, median (min-max); (b) stub cosines, no detector, "
                     "object_maps=True" % torch.cuda.get_device_name(0))
+    if a.objectnav_metrics:
+        probe_geodesic(lines)
     if not a.skip_steps:
-        probe_steps(a.steps, lines, a.batch_object_maps, a.device_object_clouds)
+        probe_steps(a.steps, lines, a.batch_object_maps, a.device_object_clouds, a.objectnav_metrics)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

@@ -13,7 +13,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlfm_amd.so")
-SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "qformer_attention.hip", "detect_ops.hip", "object_cloud.hip", "cloud_query.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "world_render.hip", "host.cpp"]
+SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "qformer_attention.hip", "detect_ops.hip", "object_cloud.hip", "cloud_query.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "world_render.hip", "geodesic.hip", "host.cpp"]
 
 VLFM_OK = 0
 VLFM_ERR_INVALID = -1
@@ -236,6 +236,8 @@ def lib() -> ctypes.CDLL:
                                                ctypes.c_size_t, ci, vp, vp, vp, ctypes.c_size_t, vp]
         L.vlfm_rooms_raycast.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp]
         L.vlfm_rooms_raycast_objects.argtypes = [vp, ci, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp]
+        L.vlfm_geodesic_fields.argtypes = [vp, ci, cd, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
+        L.vlfm_geodesic_query.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp]
         _lib = L
     return _lib
 

@@ -34,7 +34,8 @@ from .mapping.base_map import require_gpu
 from .mapping.value_map import ValueMapBatch
 from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TURN_RIGHT, BOXES, CAMERA_HEIGHT, HEADINGS, \
     MAX_DEPTH, MIN_DEPTH, YAWS, BangBangController, ReplayController, Trajectory, camera_intrinsics, depth_frame, integrate, \
-    WORLD_MAX_OBJECTS, object_layout, plan_actions, pose_to_tf, rect_distance, rgb_frame, step_poses, tf_of
+    GEODESIC_MAX_SOURCES, STEP_MARGIN, WORLD_MAX_OBJECTS, goal_viewpoints, inflated_rects, object_layout, plan_actions, \
+    pose_to_tf, rect_distance, rgb_frame, soft_spl, spl, step_poses, tf_of
 
 PROMPT = "Seems like there is a target_object ahead."  # vlfm/policy/base_objectnav_policy.py:377
 TARGETS = ["chair", "bed", "potted plant", "toilet", "tv", "couch"]  # HM3D ObjectNav categories
@@ -225,6 +226,36 @@ class CameraRig:
         return np.matmul(robot_tf[..., None, :, :], self.offsets)
 
 
+@dataclass
+class GeodesicFields:
+    """Device handle of ``n`` geodesic fields (RoomsRenderer.geodesic_fields): the tables vlfm_geodesic_fields wrote and the
+    source lists it read, all f64 / int32 device tensors with the strides of include/vlfm_amd.h (R = walls + 8 rectangles, 4R
+    nodes per field).  ``has_target`` [n] bool on the host: False for a field built without a target (no source)."""
+    n: int
+    max_sources: int
+    rects: torch.Tensor          # [n,R,4]
+    nodes: torch.Tensor          # [n,4R,2]
+    dist: torch.Tensor           # [n,4R]
+    counts: torch.Tensor         # [n,2] int32: rectangles, nodes
+    sources: torch.Tensor        # [n,max_sources,2]
+    source_counts: torch.Tensor  # [n] int32
+    has_target: np.ndarray
+
+    def assign(self, rows, other: "GeodesicFields") -> None:
+        """Overwrite the fields ``rows`` of this handle with the fields of ``other`` (len(rows) == other.n), on the device."""
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        if len(rows) != other.n or other.max_sources != self.max_sources or other.rects.shape[1:] != self.rects.shape[1:]:
+            raise ValueError("GeodesicFields.assign: the other handle must hold one field of the same shape per row")
+        if np.any((rows < 0) | (rows >= self.n)):
+            raise ValueError("GeodesicFields.assign: row out of range")
+        if not len(rows):
+            return
+        idx = torch.from_numpy(rows).to(self.rects.device)
+        for name in ("rects", "nodes", "dist", "counts", "sources", "source_counts"):
+            getattr(self, name).index_copy_(0, idx, getattr(other, name))
+        self.has_target[rows] = other.has_target
+
+
 class RoomsRenderer:
     """Depth frames of the consistent rooms-and-pillars world (vlfm_amd/synthetic.py) for E environments at once, ray-cast ON
     THE DEVICE (f64, the arithmetic of synthetic.wall_profile / depth_from_profile batched over environments): environment
@@ -381,6 +412,71 @@ class RoomsRenderer:
                        "rooms_raycast_objects")
         return out, ids, stats
 
+    @torch.no_grad()
+    def geodesic_fields(self, objects: np.ndarray, targets_boxes, success_distance: float,
+                        max_sources: int = GEODESIC_MAX_SOURCES) -> GeodesicFields:
+        """The geodesic fields of n environments in ONE launch on the current stream (vlfm_geodesic_fields, bit for bit
+        synthetic.geodesic_field_numpy): ``objects`` [n,8,8] f64 on the host, the ray caster's records -- walls and valid
+        footprints, inflated by STEP_MARGIN, are the obstacles; ``targets_boxes`` [n,>=4] the footprint each environment has to
+        reach within ``success_distance`` (a NaN row: no target, every distance in that field is inf).  The view points
+        (synthetic.goal_viewpoints) are worked out on the host; they, their counts and the records cross in one small copy each."""
+        objects = np.ascontiguousarray(objects, np.float64)
+        if objects.ndim != 3 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
+            raise ValueError(f"geodesic_fields: objects must be [n, {WORLD_MAX_OBJECTS}, 8]")
+        n = len(objects)
+        boxes = np.asarray(targets_boxes, np.float64).reshape(n, -1)[:, :4] if n else np.zeros((0, 4))
+        src = np.zeros((n, max_sources, 2))
+        cnt = np.zeros(n, np.int32)
+        has = np.zeros(n, bool)
+        for e in range(n):
+            if np.all(np.isfinite(boxes[e])):
+                pts = goal_viewpoints(boxes[e], inflated_rects(objects[e]), success_distance, max_sources)
+                src[e, :len(pts)], cnt[e], has[e] = pts, len(pts), True
+        dev = self.boxes.device
+        R = len(self.boxes) + WORLD_MAX_OBJECTS
+        f64 = dict(dtype=torch.float64, device=dev)
+        h = GeodesicFields(n, max_sources, torch.empty((n, R, 4), **f64), torch.empty((n, 4 * R, 2), **f64),
+                           torch.empty((n, 4 * R), **f64), torch.empty((n, 2), dtype=torch.int32, device=dev),
+                           torch.empty((n, max_sources, 2), **f64), torch.empty((n,), dtype=torch.int32, device=dev), has)
+        if n == 0:
+            return h
+        with torch.cuda.device(dev):
+            d_obj = torch.from_numpy(objects).to(dev)
+            h.sources.copy_(torch.from_numpy(src))
+            h.source_counts.copy_(torch.from_numpy(cnt))
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().vlfm_geodesic_fields(self.boxes.data_ptr(), len(self.boxes), STEP_MARGIN, d_obj.data_ptr(),
+                                                       h.sources.data_ptr(), h.source_counts.data_ptr(), n, max_sources,
+                                                       h.rects.data_ptr(), h.nodes.data_ptr(), h.dist.data_ptr(),
+                                                       h.counts.data_ptr(), stream), "geodesic_fields")
+        return h
+
+    @torch.no_grad()
+    def geodesic_distances(self, handle: GeodesicFields, field_of, xy) -> torch.Tensor:
+        """f64 [m] on the device: the geodesic distance to the goal of the points ``xy`` [m,2], point i in the field
+        ``field_of[i]`` of ``handle`` (-1: no field, the answer is NaN), ONE launch on the current stream
+        (vlfm_geodesic_query, bit for bit synthetic.geodesic_query_numpy).  inf: no way to the goal."""
+        xy = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
+        m = len(xy)
+        field_of = np.ascontiguousarray(np.asarray(field_of).reshape(-1), np.int32)
+        if len(field_of) != m or np.any((field_of < -1) | (field_of >= handle.n)):
+            raise ValueError("geodesic_distances: field_of must name one field of the handle (or -1) per point")
+        dev = self.boxes.device
+        out = torch.empty((m,), dtype=torch.float64, device=dev)
+        if m == 0:
+            return out
+        with torch.cuda.device(dev):
+            blob = np.concatenate([xy.reshape(-1), np.zeros((m + 1) // 2, np.float64)])     # points and field_of: one copy
+            blob[2 * m:].view(np.int32)[:m] = field_of
+            d_blob = torch.from_numpy(blob).to(dev)
+            p = d_blob.data_ptr()
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().vlfm_geodesic_query(p, p + 16 * m, m, handle.n, len(self.boxes), handle.rects.data_ptr(),
+                                                      handle.nodes.data_ptr(), handle.dist.data_ptr(), handle.counts.data_ptr(),
+                                                      handle.sources.data_ptr(), handle.source_counts.data_ptr(),
+                                                      handle.max_sources, out.data_ptr(), stream), "geodesic_query")
+        return out
+
     def prepare(self, t0: int, n: int) -> None:
         self.window = torch.stack([self.render((t0 + i) % self.L) for i in range(n)])
         self.window_t0 = t0
@@ -414,7 +510,7 @@ class BatchedEpisodes:
                  render_trajectories: bool = False, emulate_jpeg: bool = False, rig: Optional[CameraRig] = None,
                  text_prompt: str = PROMPT, exploration_thresh: Optional[float] = None, closed_loop: bool = False,
                  controller=None, world_objects: Optional[WorldObjects] = None, batch_object_maps: bool = True,
-                 device_object_clouds: bool = True) -> None:
+                 device_object_clouds: bool = True, objectnav_metrics: bool = False) -> None:
         # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
         # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -457,6 +553,12 @@ class BatchedEpisodes:
                 raise ValueError("world_objects replaces the scripted sightings: give one of the two")
             if rig is not None:
                 raise ValueError("world_objects renders the robot's own camera: it cannot be combined with a camera rig")
+        # objectnav_metrics: the episodes are also scored by SPL, SoftSPL and the geodesic distance_to_goal (geodesic fields on
+        # the device: one launch when episodes start, one query launch and read-back per step); nothing reads them back into the
+        # policy, the controller or the world.  Off: every step and every key of objectnav_stats is what it always was
+        self.objectnav_metrics = bool(objectnav_metrics)
+        if self.objectnav_metrics and world_objects is None:
+            raise ValueError("objectnav_metrics scores ObjectNav episodes: it needs world_objects")
         self.device = require_gpu(device)
         # rig: K cameras per environment (CameraRig) fused into the environment's maps by ONE ingest_cameras / update_cameras per
         # step (step() -> _step_rig()); None = one camera at the robot pose, the step as it always was
@@ -536,6 +638,12 @@ class BatchedEpisodes:
                                             "no_frontier_stops": z(np.int64), "timeouts": z(np.int64), "episode_env": [],
                                             "episode_outcome": [], "episode_steps": [], "episode_path_length": [],
                                             "episode_first_sighting": []}
+                    if self.objectnav_metrics:
+                        self.objectnav_stats.update({"episode_geodesic": [], "episode_distance_to_goal": [],
+                                                     "episode_spl": [], "episode_soft_spl": []})
+                        self.distance_to_goal = np.full(n_envs, np.nan)     # of the poses the last step judged
+                        self._ep_geodesic = np.full(n_envs, np.nan)         # l: from where each running episode started
+                        self._geodesic = None                               # GeodesicFields of all E environments
                     self._draw_layouts(range(n_envs))
         else:
             trajs = [Trajectory(i) for i in self.env_ids]
@@ -871,6 +979,41 @@ class BatchedEpisodes:
             self._object_classes[e] = [cls for cls, _ in lay]
             self._target_slot[e] = next((k for k, (cls, _) in enumerate(lay) if cls == self.targets[e]), -1)
             self._ep_clock[e], self._ep_path[e], self._ep_first[e] = 0, 0.0, -1
+        if self.objectnav_metrics:
+            self._start_geodesics(np.array(list(envs), np.int64))
+
+    def _start_geodesics(self, envs: np.ndarray) -> None:
+        """objectnav_metrics: the geodesic fields of the episodes ``envs`` start now, ONE launch, and ``l`` of each -- the
+        distance to the goal from where its robot stands (nan: the layout has no target; inf: no way to it)."""
+        if not len(envs):
+            return
+        slots = self._target_slot[envs]
+        boxes = np.where((slots >= 0)[:, None], self._objects[envs, np.maximum(slots, 0), :4], np.nan)
+        fresh = self.rooms.geodesic_fields(self._objects[envs], boxes, self.world_objects.success_distance)
+        if self._geodesic is None:              # (the first call starts every environment's episode)
+            assert len(envs) == self.E and np.array_equal(envs, np.arange(self.E))
+            self._geodesic = fresh
+        else:
+            self._geodesic.assign(envs, fresh)
+        field_of = np.where(fresh.has_target, np.arange(len(envs)), -1)
+        self._ep_geodesic[envs] = self.rooms.geodesic_distances(fresh, field_of, self.world_xy[envs]).cpu().numpy()
+        self.distance_to_goal[envs] = self._ep_geodesic[envs]
+
+    def objectnav_summary(self) -> Dict:
+        """The ObjectNav table of the episodes scored so far: ``episodes``, ``success_rate`` and, with objectnav_metrics,
+        Habitat's ``spl``, ``soft_spl`` and mean final ``distance_to_goal`` over the episodes that have a finite geodesic
+        start distance; the others are counted in ``excluded_no_target`` / ``excluded_unreachable`` and in no mean."""
+        st = self.objectnav_stats
+        n = len(st["episode_outcome"])
+        success = np.array([o == "success" for o in st["episode_outcome"]], bool)
+        if not self.objectnav_metrics:
+            return {"episodes": n, "success_rate": float(success.mean()) if n else float("nan")}
+        l = np.asarray(st["episode_geodesic"], np.float64)
+        ok = np.isfinite(l)
+        mean = lambda v: float(np.asarray(v, np.float64)[ok].mean()) if ok.any() else float("nan")   # noqa: E731
+        return {"episodes": n, "scored": int(ok.sum()), "excluded_no_target": int(np.isnan(l).sum()),
+                "excluded_unreachable": int(np.isinf(l).sum()), "success_rate": mean(success), "spl": mean(st["episode_spl"]),
+                "soft_spl": mean(st["episode_soft_spl"]), "distance_to_goal": mean(st["episode_distance_to_goal"])}
 
     def _instance_of(self, e: int, box_px: np.ndarray) -> int:
         """The object slot behind a detection of environment ``e``'s target class with the pixel box ``box_px`` (xyxy): the
@@ -893,11 +1036,20 @@ class BatchedEpisodes:
         st["episode_steps"].append(int(self._ep_clock[e]))
         st["episode_path_length"].append(float(self._ep_path[e]))
         st["episode_first_sighting"].append(int(self._ep_first[e]))
+        if self.objectnav_metrics:
+            l, d_end, p = float(self._ep_geodesic[e]), float(self.distance_to_goal[e]), float(self._ep_path[e])
+            st["episode_geodesic"].append(l)
+            st["episode_distance_to_goal"].append(d_end)
+            st["episode_spl"].append(spl(outcome == "success", l, p))
+            st["episode_soft_spl"].append(soft_spl(d_end, l, p))
 
     def _objectnav_ends(self) -> List[int]:
         """Decided after ``_navigate``: the environments whose ObjectNav episode ends with this step (objectnav_outcome), scored."""
         wo, done = self.world_objects, []
         self._ep_clock += 1                          # this step is taken
+        if self.objectnav_metrics:                   # one launch, one read-back: where every robot is judged
+            field_of = np.where(self._geodesic.has_target, np.arange(self.E), -1)
+            self.distance_to_goal = self.rooms.geodesic_distances(self._geodesic, field_of, self.world_xy).cpu().numpy()
         for e in range(self.E):
             navigating = bool(self.last_modes) and self.last_modes[e] == "navigate"
             exploring = bool(self.last_modes) and self.last_modes[e] == "explore"

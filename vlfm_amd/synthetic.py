@@ -449,3 +449,182 @@ def object_stats_numpy(ids, K: int = WORLD_MAX_OBJECTS) -> np.ndarray:
         r, c = np.nonzero(ids == k + 1)
         out[k] = (len(r), c.min(), c.max(), r.min(), r.max()) if len(r) else (0, W, -1, H, -1)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- ObjectNav metrics
+# The length of the shortest collision-free path to an episode's goal, which SPL, SoftSPL and Habitat's distance_to_goal are
+# made of (the reference reads them off Habitat's navmesh).  This section is the HOST STATEMENT of the rule; the device
+# (csrc/geodesic.hip: vlfm_geodesic_fields / vlfm_geodesic_query) matches it bit for bit.  Everything is f64 with one rounding
+# per operation (+ - * / sqrt, comparisons), no fused multiply-add, the expressions exactly as written here.
+#
+#   obstacles  the walls BOXES and the environment's valid object footprints, each inflated by STEP_MARGIN with the expressions
+#              of `step_poses` (x0 - m, y0 - m, x1 + m, y1 + m): the doubles are the kinematics' own.  For the geodesic every
+#              inflated rectangle is an OPEN set: a path may run along its boundary.
+#   blocked    the segment p -> q is blocked by a rectangle iff some t in (0, 1) puts p + t (q - p) strictly inside it.  Per
+#              axis, with d = q - p:  d == 0: the interval is everything if lo < p < hi, else empty;  otherwise
+#              t0 = (lo - p) / d, t1 = (hi - p) / d and the interval is (min(t0, t1), max(t0, t1)).  Blocked iff
+#              max(enter_x, enter_y, 0) < min(exit_x, exit_y, 1).  A segment along an edge or through a corner is free.  The
+#              test is evaluated FROM p TO q as given (the roundings of the two directions may differ):
+#              source -> corner, corner of lower index -> corner of higher index (one verdict per pair), query point -> source
+#              or corner.
+#   nodes      the corners (x0,y0) (x1,y0) (x1,y1) (x0,y1) of every inflated rectangle, in rectangle order, without those that
+#              lie strictly inside some rectangle.  Edge weight w(a, b) = sqrt(dx*dx + dy*dy) (not hypot).
+#   sources    Habitat's "view points": `goal_viewpoints`.
+#   field      dist[c] = the least value with dist[c] <= w(s, c) for every source s that sees c and
+#              dist[c] <= fl(dist[u] + w(u, c)) for every corner u that sees c, attained by one of them (inf: unreachable).
+#              Adding a non-negative weight never decreases a value, so this least fixed point is unique, a heap Dijkstra with
+#              the same additions returns it, and so does relaxing until nothing changes (the kernel).
+#   query      d(p) = min(min over the sources p sees of w(p, s), min over the corners p sees of fl(w(p, c) + dist[c]));
+#              inf when nothing is reachable -- every segment out of a p strictly inside a rectangle is blocked.
+#
+# Known looseness: two inflated rectangles that exactly abut leave a slit of zero width, which the open-set rule lets a path
+# through.  That can only SHORTEN l, so SPL stays at or below its true value.  Among the built-in layouts it concerns four
+# (class, spot) pairs -- a bed or a couch against the east wall or a pillar (tests/test_geodesic_cpu.py counts them).
+GEODESIC_MAX_SOURCES = 256
+
+
+def inflated_rects(objects=None, margin: float = STEP_MARGIN, boxes=None) -> np.ndarray:
+    """[R,4] f64 (x0 - m, y0 - m, x1 + m, y1 + m): the walls ``boxes`` (default BOXES), then the objects in slot order.
+    ``objects``: [K,8] ray-caster records (a slot counts iff its ``valid`` field, column 6, is non-zero) or [K,4] / [K,6]
+    boxes (all count)."""
+    b = np.asarray(BOXES if boxes is None else boxes, np.float64).reshape(-1, 4)
+    if objects is not None and len(objects):
+        o = np.asarray(objects, np.float64)
+        o = o.reshape(-1, o.shape[-1])
+        if o.shape[1] not in (4, 6, 8):
+            raise ValueError("inflated_rects: objects must be [K,8] records or [K,4] / [K,6] boxes")
+        if o.shape[1] == 8:
+            o = o[o[:, 6] != 0.0]
+        b = np.concatenate([b, o[:, :4]])
+    m = float(margin)
+    return np.stack([b[:, 0] - m, b[:, 1] - m, b[:, 2] + m, b[:, 3] + m], axis=1)
+
+
+def segments_blocked_numpy(p, q, rects) -> np.ndarray:
+    """bool [len(p), len(q)]: is the segment p[i] -> q[j] blocked by one of the OPEN rectangles ``rects`` [R,4] (the rule
+    above, evaluated from p to q)."""
+    p = np.asarray(p, np.float64).reshape(-1, 1, 1, 2)
+    q = np.asarray(q, np.float64).reshape(1, -1, 1, 2)
+    r = np.asarray(rects, np.float64).reshape(1, 1, -1, 4)
+    out = np.zeros((p.shape[0], q.shape[1]), bool)
+    rows = max(1, (1 << 21) // max(1, q.shape[1] * r.shape[2]))         # [rows, len(q), R] temporaries of 16 MB at the most
+    for i in range(0, p.shape[0], rows):
+        enter, leave = 0.0, 1.0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for ax in (0, 1):
+                pa, lo, hi = p[i:i + rows, ..., ax], r[..., ax], r[..., ax + 2]
+                d = q[..., ax] - pa
+                t0, t1 = (lo - pa) / d, (hi - pa) / d
+                inside = (lo < pa) & (pa < hi)
+                a = np.where(d == 0.0, np.where(inside, -np.inf, np.inf), np.minimum(t0, t1))
+                b = np.where(d == 0.0, np.where(inside, np.inf, -np.inf), np.maximum(t0, t1))
+                enter, leave = np.maximum(enter, a), np.minimum(leave, b)
+        out[i:i + rows] = np.any(enter < leave, axis=2)
+    return out
+
+
+def _edge_weights(a, b) -> np.ndarray:
+    a, b = np.asarray(a, np.float64).reshape(-1, 1, 2), np.asarray(b, np.float64).reshape(1, -1, 2)
+    dx, dy = a[..., 0] - b[..., 0], a[..., 1] - b[..., 1]
+    return np.sqrt(dx * dx + dy * dy)
+
+
+def goal_viewpoints(target_box, rects, success_distance: float, max_points: int = GEODESIC_MAX_SOURCES) -> np.ndarray:
+    """[S,2] f64, the sources of a geodesic field: the points (0.25 i, 0.25 j), i and j integers, with
+    dx*dx + dy*dy <= r*r for `rect_distance`'s clamped offsets (dx, dy) to ``target_box[:4]`` and r = ``success_distance``,
+    that `step_poses`' CLOSED test against the inflated rectangles ``rects`` does not block -- where a robot can stand and
+    have succeeded.  Ordered by (i, j).  More than ``max_points`` of them: ValueError."""
+    x0, y0, x1, y1 = (float(v) for v in np.asarray(target_box, np.float64).reshape(-1)[:4])
+    r = float(success_distance)
+    i = np.arange(int(np.floor((x0 - r) / 0.25)), int(np.ceil((x1 + r) / 0.25)) + 1, dtype=np.float64)
+    j = np.arange(int(np.floor((y0 - r) / 0.25)), int(np.ceil((y1 + r) / 0.25)) + 1, dtype=np.float64)
+    px, py = np.meshgrid(0.25 * i, 0.25 * j, indexing="ij")
+    px, py = px.reshape(-1), py.reshape(-1)
+    dx = np.maximum(np.maximum(x0 - px, 0.0), px - x1)
+    dy = np.maximum(np.maximum(y0 - py, 0.0), py - y1)
+    keep = dx * dx + dy * dy <= r * r
+    b = np.asarray(rects, np.float64).reshape(-1, 4)
+    keep &= ~np.any((b[None, :, 0] <= px[:, None]) & (px[:, None] <= b[None, :, 2]) &
+                    (b[None, :, 1] <= py[:, None]) & (py[:, None] <= b[None, :, 3]), axis=1)
+    pts = np.stack([px[keep], py[keep]], axis=1)
+    if len(pts) > max_points:
+        raise ValueError(f"goal_viewpoints: {len(pts)} view points, at most {max_points} fit a geodesic field")
+    return pts
+
+
+def geodesic_nodes_numpy(rects) -> np.ndarray:
+    """[N,2] the corner nodes of the rectangles ``rects`` [R,4]: (x0,y0) (x1,y0) (x1,y1) (x0,y1) per rectangle, in order,
+    without the corners strictly inside some rectangle."""
+    r = np.asarray(rects, np.float64).reshape(-1, 4)
+    c = r[:, [0, 1, 2, 1, 2, 3, 0, 3]].reshape(-1, 2)
+    inside = np.any((r[None, :, 0] < c[:, None, 0]) & (c[:, None, 0] < r[None, :, 2]) &
+                    (r[None, :, 1] < c[:, None, 1]) & (c[:, None, 1] < r[None, :, 3]), axis=1)
+    return c[~inside]
+
+
+def geodesic_field_numpy(rects, sources):
+    """(nodes [N,2], dist [N]) f64: the geodesic field of the OPEN rectangles ``rects`` [R,4] around the ``sources`` [S,2]
+    (the rule above), by a heap Dijkstra from the goal outwards."""
+    import heapq
+
+    rects = np.asarray(rects, np.float64).reshape(-1, 4)
+    sources = np.asarray(sources, np.float64).reshape(-1, 2)
+    nodes = geodesic_nodes_numpy(rects)
+    N = len(nodes)
+    dist = np.full(N, np.inf)
+    if N == 0:
+        return nodes, dist
+    if len(sources):
+        w = np.where(segments_blocked_numpy(sources, nodes, rects), np.inf, _edge_weights(sources, nodes))
+        dist = w.min(axis=0)
+    up = np.triu(segments_blocked_numpy(nodes, nodes, rects), 1)         # lower index -> higher index, one verdict per pair
+    sees = ~(up | up.T)
+    np.fill_diagonal(sees, False)
+    w = _edge_weights(nodes, nodes)
+    heap = [(float(d), c) for c, d in enumerate(dist) if np.isfinite(d)]
+    heapq.heapify(heap)
+    done = np.zeros(N, bool)
+    while heap:
+        d, u = heapq.heappop(heap)
+        if done[u] or d > dist[u]:
+            continue
+        done[u] = True
+        for c in np.flatnonzero(sees[u] & ~done):
+            cand = d + float(w[u, c])
+            if cand < dist[c]:
+                dist[c] = cand
+                heapq.heappush(heap, (cand, int(c)))
+    return nodes, dist
+
+
+def geodesic_query_numpy(rects, sources, nodes, dist, points) -> np.ndarray:
+    """[m] f64: d(p) of the rule above for the ``points`` [m,2] in the field (``nodes``, ``dist``) of ``rects``, ``sources``."""
+    rects = np.asarray(rects, np.float64).reshape(-1, 4)
+    sources = np.asarray(sources, np.float64).reshape(-1, 2)
+    nodes, dist = np.asarray(nodes, np.float64).reshape(-1, 2), np.asarray(dist, np.float64).reshape(-1)
+    points = np.asarray(points, np.float64).reshape(-1, 2)
+    out = np.full(len(points), np.inf)
+    if len(sources) and len(points):
+        out = np.where(segments_blocked_numpy(points, sources, rects), np.inf, _edge_weights(points, sources)).min(axis=1)
+    if len(nodes) and len(points):
+        via = np.where(segments_blocked_numpy(points, nodes, rects), np.inf, _edge_weights(points, nodes) + dist[None, :])
+        out = np.minimum(out, via.min(axis=1))
+    return out
+
+
+def spl(success, l: float, p: float) -> float:
+    """Habitat's SPL of one episode: S * l / max(p, l) for the geodesic start-to-goal distance ``l`` and the path length
+    ``p``; the ratio is 1 when l == 0.  An episode without a finite ``l`` (no target, or no way to it) contributes 0."""
+    if not success or not np.isfinite(l):
+        return 0.0
+    return 1.0 if l == 0.0 else float(l / max(p, l))
+
+
+def soft_spl(d_end: float, l: float, p: float) -> float:
+    """Habitat's SoftSPL of one episode: max(0, 1 - d_end / l) * l / max(p, l) with the geodesic distance ``d_end`` left at
+    the end; with l == 0 the progress term is 1 iff d_end == 0.  0 without a finite ``l`` or ``d_end``."""
+    if not np.isfinite(l) or not np.isfinite(d_end):
+        return 0.0
+    if l == 0.0:
+        return 1.0 if d_end == 0.0 else 0.0
+    return float(max(0.0, 1.0 - d_end / l) * (l / max(p, l)))
