@@ -513,27 +513,12 @@ int vlfm_dwconv3x3_f32(const float* d_x, const float* d_w, const float* d_bias, 
 int vlfm_bias_act_nchw(void* d_y, const void* d_bias, int n, int channels, long long hw, int dtype, int act, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * ObjectPointCloudMap._extract_object_cloud (vlfm/mapping/object_point_cloud_map.py:150-170,186-212)
+ * ObjectPointCloudMap._extract_object_cloud (vlfm/mapping/object_point_cloud_map.py:150-170,186-212) for ALL detections of a
+ * step at once; a single detection is a batch of one job.  The number of kernel launches does not depend on the number of jobs.
  * ------------------------------------------------------------------------------------------- */
 
-/* cv2.erode(mask, None, iterations) -> valid_depth -> get_point_cloud over the eroded mask, in np.where order.
- * d_depth [H][W] f32, d_mask [H][W] u8 (non-zero = object).  d_cloud [capacity][3] f64 (z, -x, -y); *d_count = number of
- * masked pixels (may exceed capacity: only the first `capacity` are written).  d_scratch:
- * vlfm_object_cloud_scratch_bytes(H, W). */
-size_t vlfm_object_cloud_scratch_bytes(int height, int width);
-int vlfm_object_cloud_extract(const float* d_depth, const uint8_t* d_mask, int height, int width, int erosion_iterations,
-                              double min_depth, double max_depth, double fx, double fy, void* d_scratch, double* d_cloud,
-                              int capacity, int32_t* d_count, void* stream);
-
-/* open3d cluster_dbscan(eps, min_points) + "largest non-noise cluster" (object_point_cloud_map.py:186-212) for n <= 8192
- * f64 points.  d_labels [n] receives the cluster root index of every point (INT32_MAX = noise), d_keep the indices of the
- * largest cluster in ascending order, d_num_keep their count (0 = only noise). */
-size_t vlfm_dbscan_scratch_bytes(int n);
-int vlfm_dbscan_largest_cluster(const double* d_points, int n, double eps, int min_points, void* d_scratch,
-                                size_t scratch_bytes, int32_t* d_labels, int32_t* d_keep, int32_t* d_num_keep, void* stream);
-
-/* The same three stages for ALL detections of a step (ABI 17).  The number of kernel launches does not depend on the number of
- * jobs.  Results are bit-identical to the per-detection functions above.
+/* Three stages: cv2.erode(mask, None, iterations) and the point counts; valid_depth -> get_point_cloud over the eroded mask in
+ * np.where order, sub-sampled by rank; open3d cluster_dbscan(eps, min_points) + "largest non-noise cluster" (:186-212).
  *
  * Stage 1, vlfm_object_cloud_batch_stats: d_masks [jobs][H][W] u8, d_erosion [jobs] i32 on the device (erosion iterations per job;
  * max_erosion = their maximum, known to the host).  d_stats [jobs][4] i32 = (points of the eroded mask, first and last occupied
@@ -549,6 +534,9 @@ int vlfm_dbscan_largest_cluster(const double* d_points, int n, double eps, int m
  * the job's scratch: a multiple of 256, vlfm_dbscan_batch_scratch_bytes(n) bytes); max_n = the largest n (<= 8192).  The points
  * of job j's largest cluster are written in order to d_kept at the job's own first point, their number to d_num_keep[j]
  * (0 = only noise, or n == 0).
+ * After the call a job's scratch holds, behind its n * ceil(n / 64) adjacency words (u64; bit j of word (i, cb) = point 64 cb + j
+ * lies within eps of point i), four [n] i32 arrays: degree, sizes, label, keep.  label = the cluster root index of every point
+ * (INT32_MAX = noise); keep[0 : d_num_keep[j]] = the indices of the largest cluster in ascending order.
  *
  * vlfm_object_cloud_launch_count: kernels launched so far by every function of this section (diagnostics, tests). */
 size_t vlfm_object_cloud_batch_scratch_bytes(int jobs, int height, int width);

@@ -1,6 +1,7 @@
 """-m gpu: ObjectPointCloudMap (HIP erosion + masked back-projection + DBSCAN) against the fixture produced by the
 reference's own object_point_cloud_map.py (tests/golden/make_golden.py: cv2.erode/boundingRect and open3d stand-ins), and
 the device kernels against their oracle restatements.  Clouds must match BIT-EXACTLY (f64) including order."""
+import functools
 import hashlib
 import os
 import sys
@@ -80,40 +81,74 @@ def test_object_map_replays_random_reference_sessions(gpu_device, seed):
             assert np.array_equal(np.asarray(m.clouds[name], np.float64), g[f"final_{name}"])
 
 
-@pytest.mark.parametrize("n,seed", [(300, 0), (1500, 1), (5000, 2), (64, 3), (129, 4)])
-def test_dbscan_matches_sequential_oracle(gpu_device, n, seed):
-    """Clustered + noisy point sets: labels up to renaming are checked through the selected largest cluster, which must be
-    the same index set in the same order as the sequential Open3D-style algorithm picks."""
-    import ctypes
+DBSCAN_SETS = [(300, 0), (1500, 1), (5000, 2), (64, 3), (129, 4)]    # (n, seed): 64 = one adjacency word per row, 129 = two plus one
 
-    from oracle.ref_object_map import cluster_dbscan
-    from vlfm_amd import _lib
 
+@functools.lru_cache(maxsize=None)
+def _dbscan_points(n, seed):
+    """Clustered + noisy points; the stragglers are copies of ONE point, so indices say more than coordinates."""
     rng = np.random.default_rng(seed)
     k = max(1, n // 400)
     centres = rng.uniform(-2, 2, (k + 1, 3))
     pts = np.concatenate([centres[i % (k + 1)] + rng.normal(0, 0.12, 3) for i in range(n)]).reshape(n, 3)
     pts[rng.random(n) < 0.1] = rng.uniform(-3, 3, (int((rng.random(n) < 0.1).sum()) or 1, 3))[:1]  # a few stragglers
+    pts.setflags(write=False)
+    return pts
+
+
+@functools.lru_cache(maxsize=None)
+def _dbscan_batch(device, eps, mp):
+    """The five point sets as five jobs of ONE vlfm_dbscan_largest_cluster_batch call (a different n per job), shared by the five
+    cases below.  Per job, as host arrays: (label, keep) read from the job's scratch by the layout include/vlfm_amd.h states --
+    n * ceil(n / 64) adjacency words, then degree, sizes, label, keep ([n] i32 each) --, the job's rows of d_kept, d_num_keep[j]."""
+    from vlfm_amd import _lib
+
+    L = _lib.lib()
+    sets = [_dbscan_points(n, seed) for n, seed in DBSCAN_SETS]
+    ns = [len(p) for p in sets]
+    first = np.concatenate(([0], np.cumsum(ns)))
+    sc_first = np.concatenate(([0], np.cumsum([L.vlfm_dbscan_batch_scratch_bytes(n) for n in ns])))
+    total = int(first[-1])
+    points = torch.from_numpy(np.concatenate(sets)).to(device)
+    jobs = torch.from_numpy(np.array([(n, first[j], sc_first[j]) for j, n in enumerate(ns)], np.int64)).to(device)
+    sc = torch.empty(int(sc_first[-1]), dtype=torch.uint8, device=device)
+    kept = torch.full((total, 3), float("nan"), dtype=torch.float64, device=device)
+    num = torch.full((len(ns),), -1, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(L.vlfm_dbscan_largest_cluster_batch(points.data_ptr(), total, jobs.data_ptr(), len(ns), max(ns), eps, mp,
+                                                       sc.data_ptr(), sc.numel(), kept.data_ptr(), num.data_ptr(),
+                                                       torch.cuda.current_stream().cuda_stream), "dbscan_batch")
+    scratch, kept, num = sc.cpu().numpy(), kept.cpu().numpy(), num.cpu().numpy()
+    out = []
+    for j, n in enumerate(ns):
+        arrays = scratch[sc_first[j] + n * ((n + 63) // 64) * 8:][:16 * n].view(np.int32).reshape(4, n)
+        out.append((arrays[2], arrays[3], kept[first[j]:first[j + 1]], int(num[j])))
+    return out
+
+
+@pytest.mark.parametrize("n,seed", DBSCAN_SETS)
+def test_dbscan_matches_sequential_oracle(gpu_device, n, seed):
+    """Clustered + noisy point sets: labels up to renaming are checked through the selected largest cluster, which must be
+    the same index set in the same order as the sequential Open3D-style algorithm picks; the points written out must be those of
+    the wanted indices, bit for bit."""
+    from oracle.ref_object_map import cluster_dbscan
+
+    pts = _dbscan_points(n, seed)
     for eps, mp in ((0.2, 100), (0.15, 20), (0.3, 5)):
         labels = cluster_dbscan(pts, eps, mp)
         uniq, cnt = np.unique(labels[labels >= 0], return_counts=True)
         want = np.where(labels == uniq[np.argmax(cnt)])[0] if len(uniq) else np.zeros(0, np.int64)
-        d = torch.from_numpy(pts).to(gpu_device)
-        L = _lib.lib()
-        sc = torch.empty(L.vlfm_dbscan_scratch_bytes(n), dtype=torch.uint8, device=gpu_device)
-        lab = torch.empty(n, dtype=torch.int32, device=gpu_device)
-        keep = torch.empty(n, dtype=torch.int32, device=gpu_device)
-        num = torch.zeros(1, dtype=torch.int32, device=gpu_device)
-        _lib.check(L.vlfm_dbscan_largest_cluster(d.data_ptr(), n, eps, mp, sc.data_ptr(), sc.numel(), lab.data_ptr(),
-                                                 keep.data_ptr(), num.data_ptr(), torch.cuda.current_stream().cuda_stream))
-        got = keep[: int(num.item())].cpu().numpy()
+        lab, keep, kept, num = _dbscan_batch(str(gpu_device), eps, mp)[DBSCAN_SETS.index((n, seed))]
+        assert num == len(want), (n, eps, mp, num, len(want))
+        got = keep[:num]
         assert np.array_equal(got, want), (n, eps, mp, len(got), len(want))
         # full labelling: same partition (noise <-> INT32_MAX; clusters in the same order)
-        gl = lab.cpu().numpy().astype(np.int64)
+        gl = lab.astype(np.int64)
         roots = np.unique(gl[gl != 0x7FFFFFFF])
         remap = {r: i for i, r in enumerate(roots)}
         mapped = np.array([remap.get(x, -1) for x in gl])
         assert np.array_equal(mapped, labels), (n, eps, mp)
+        assert kept[:num].tobytes() == pts[want].tobytes(), (n, eps, mp)
 
 
 def test_erosion_and_cloud_order(gpu_device):

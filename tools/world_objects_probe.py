@@ -6,12 +6,12 @@
       rooms_raycast_kernel (walls only) on the same cameras in the same session.
   (b) env-steps/s of a closed-loop harness with and without world_objects at 8 and 256 environments: stub cosines, no
       detector, object_maps=True, alternating windows; --batch-object-maps on | off | both runs the world_objects harness with
-      the batched object-map update, with one update_map per detection, or both side by side, and reports the object-cloud
+      all detections of a step in one object-map update, with one update_map per detection, or both side by side, and reports the object-cloud
       kernel launches and host read-backs per step of each; --device-object-clouds on | off | both does the same for the device
       mirrors of the clouds (update_explored_batch / get_best_objects_batch against one NumPy pass per environment) and adds the
       cloud-query launches, the bytes uploaded to the mirrors and the points re-evaluated on the host per step.
-  (c) --batch-trace: kernel time of the batched object-map update for 1 / 16 / 64 detections (objects in view of the tour poses) at 640x480
-      next to the per-detection kernels for the same detections, from one `rocprofv3 --kernel-trace --stats` run of its own.
+  (c) --batch-trace: kernel time of the object-map update for 1 / 16 / 64 detections in one call (objects in view of the tour poses)
+      at 640x480, from one `rocprofv3 --kernel-trace --stats` run of its own.
 
   (d) --cloud-trace: kernel time of the two cloud queries (csrc/cloud_query.hip) over 256 mirrored clouds of 20 000 and of
       100 000 points, from one `rocprofv3 --kernel-trace --stats` run of its own, against the bytes of the mirrors.
@@ -135,13 +135,11 @@ def probe_trace(lines, workdir: str) -> None:
 BATCH_TRACE_JOBS, BATCH_TRACE_REPS, BATCH_TRACE_WARMUP = (1, 16, 64), 10, 2
 BATCH_KERNELS = ("mask_pack_batch_kernel", "mask_erode_batch_kernel", "mask_stats_batch_kernel", "cloud_expand_batch_kernel",
                  "dbscan_adjacency_batch_kernel", "dbscan_cluster_batch_kernel")
-SINGLE_KERNELS = ("mask_pack_kernel", "mask_erode_kernel", "cloud_extract_kernel", "dbscan_adjacency_kernel",
-                  "dbscan_cluster_kernel")
 
 
 def batch_trace_child() -> None:
     """64 objects as the cameras of `scene` see them; per D in BATCH_TRACE_JOBS: warm-up + BATCH_TRACE_REPS
-    batched updates of the first D detections, then as many rounds of D per-detection updates."""
+    updates of the first D detections in one call."""
     import numpy as np
     import torch
 
@@ -171,10 +169,6 @@ def batch_trace_child() -> None:
         for _ in range(BATCH_TRACE_WARMUP + BATCH_TRACE_REPS):
             list(opm.extract_object_clouds_batch(maps, depth, frames[:D], masks, MIN_DEPTH, MAX_DEPTH, fx, fy))
         torch.cuda.synchronize()
-        for _ in range(BATCH_TRACE_WARMUP + BATCH_TRACE_REPS):
-            for j in range(D):
-                maps[j]._extract_object_cloud(depth[frames[j]], masks[j], MIN_DEPTH, MAX_DEPTH, fx, fy)
-        torch.cuda.synchronize()
 
 
 def probe_batch_trace(lines, workdir: str) -> None:
@@ -199,33 +193,27 @@ def probe_batch_trace(lines, workdir: str) -> None:
 
     rows = [(short(n), (e - s) * 1e-3) for n, s, e in rows]
     # calls end with their clustering kernel (every traced detection keeps >= 100 points, one wave, one chunk)
-    calls = {"batch": [], "single": []}
-    for kind, names, last in (("batch", BATCH_KERNELS, "dbscan_cluster_batch_kernel"), ("single", SINGLE_KERNELS, "dbscan_cluster_kernel")):
-        cur = {}
-        for n, us in rows:
-            if n not in names:
-                continue
-            cur[n] = cur.get(n, 0.0) + us
-            if n == last:
-                calls[kind].append(cur)
-                cur = {}
+    calls, cur = [], {}
+    for n, us in rows:
+        if n not in BATCH_KERNELS:
+            continue
+        cur[n] = cur.get(n, 0.0) + us
+        if n == "dbscan_cluster_batch_kernel":
+            calls.append(cur)
+            cur = {}
     per = BATCH_TRACE_WARMUP + BATCH_TRACE_REPS
-    want = (per * len(BATCH_TRACE_JOBS), per * sum(BATCH_TRACE_JOBS))
-    if (len(calls["batch"]), len(calls["single"])) != want:
-        raise RuntimeError(f"expected {want} batched calls / detections in the trace, found {len(calls['batch'])} and {len(calls['single'])}")
-    b0 = s0 = 0
-    for D in BATCH_TRACE_JOBS:
-        batch = calls["batch"][b0 + BATCH_TRACE_WARMUP:b0 + per]
-        single = [calls["single"][s0 + r * D:s0 + (r + 1) * D] for r in range(BATCH_TRACE_WARMUP, per)]
-        b0, s0 = b0 + per, s0 + per * D
+    # (the first call in the trace is the child's own mask_stats_batch, which never reaches the clustering kernel: its stage-1
+    # kernels are counted with the first warm-up call)
+    if len(calls) != per * len(BATCH_TRACE_JOBS):
+        raise RuntimeError(f"expected {per * len(BATCH_TRACE_JOBS)} calls in the trace, found {len(calls)}")
+    for i, D in enumerate(BATCH_TRACE_JOBS):
+        batch = calls[i * per + BATCH_TRACE_WARMUP:(i + 1) * per]
         stage = lambda c: (c.get("mask_pack_batch_kernel", 0) + c.get("mask_erode_batch_kernel", 0) + c["mask_stats_batch_kernel"],
                            c["cloud_expand_batch_kernel"], c["dbscan_adjacency_batch_kernel"], c["dbscan_cluster_batch_kernel"])
         med = [float(np.median([stage(c)[i] for c in batch])) for i in range(4)]
         tot = [sum(stage(c)) for c in batch]
-        one = [sum(sum(c.values()) for c in rnd) for rnd in single]
         lines.append("batch-kernels D=%2d 640x480  stage 1 %8.1f us  expansion %7.1f us  adjacency %8.1f us  clusters %8.1f us  "
-                     "sum %9.1f us (%.1f-%.1f)   per-detection kernels for the same %d detections %9.1f us (%.1f-%.1f)   %d rounds each"
-                     % (D, *med, *stats(tot), D, *stats(one), len(batch)))
+                     "sum %9.1f us (%.1f-%.1f)   %d rounds" % (D, *med, *stats(tot), len(batch)))
         print(lines[-1], flush=True)
 
 

@@ -171,12 +171,6 @@ def lib() -> ctypes.CDLL:
         L.vlfm_nms.argtypes = [vp, vp, ci, cf, vp, ctypes.c_size_t, vp, vp, ci, vp]
         L.vlfm_ms_deform_attn.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]
         L.vlfm_ms_deform_attn_fused.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]
-        L.vlfm_object_cloud_scratch_bytes.argtypes = [ci, ci]
-        L.vlfm_object_cloud_scratch_bytes.restype = ctypes.c_size_t
-        L.vlfm_object_cloud_extract.argtypes = [vp, vp, ci, ci, ci, cd, cd, cd, cd, vp, vp, ci, vp, vp]
-        L.vlfm_dbscan_scratch_bytes.argtypes = [ci]
-        L.vlfm_dbscan_scratch_bytes.restype = ctypes.c_size_t
-        L.vlfm_dbscan_largest_cluster.argtypes = [vp, ci, cd, ci, vp, ctypes.c_size_t, vp, vp, vp, vp]
         L.vlfm_object_cloud_batch_scratch_bytes.argtypes = [ci, ci, ci]
         L.vlfm_object_cloud_batch_scratch_bytes.restype = ctypes.c_size_t
         L.vlfm_object_cloud_batch_stats.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]

@@ -1,25 +1,23 @@
 // object_cloud.hip -- gfx950 kernels for vlfm.mapping.ObjectPointCloudMap._extract_object_cloud
 // (reference: /root/reference/vlfm/mapping/object_point_cloud_map.py:150-170, :186-212).
 //
-//   mask_erode_kernel      cv2.erode(mask * 255, None, iterations=k): 3x3 minimum, image border does not erode
-//                          (morphologyDefaultBorderValue) -- on a bit-packed mask, one AND of nine shifted words per word
-//   cloud_extract_kernel   valid_depth (0 -> 1), scale, get_point_cloud (geometry_utils.py:216-236) over the eroded mask in
-//                          np.where order (row-major): per-row popcounts, an LDS scan, then an ordered expansion -> f64
-//                          points (z, -x, -y)
-//   dbscan_*               open3d PointCloud.cluster_dbscan(eps, min_points) [ext] for n <= ~5000 points, restated for a
-//                          data-parallel machine: eps-adjacency as an n x n bit matrix (64 columns per word: a wavefront
-//                          ballot), core = degree >= min_points (the point itself counts), clusters = connected components
-//                          of the core-core graph labelled in order of their smallest core index (the order in which the
-//                          sequential scan seeds them), border points join the lowest-labelled neighbouring cluster (the
-//                          first one to reach them), everything else is noise; then the largest cluster (first maximum) in
-//                          original point order (object_point_cloud_map.py:186-212).
+//   mask_*_batch_kernel       cv2.erode(mask * 255, None, iterations=k): 3x3 minimum, image border does not erode
+//                             (morphologyDefaultBorderValue) -- on a bit-packed mask, one AND of nine shifted words per word;
+//                             then per-row popcounts and their scan: the row offsets of the masked pixels in np.where order
+//   cloud_expand_batch_kernel valid_depth (0 -> 1), scale, get_point_cloud (geometry_utils.py:216-236) -> f64 points (z, -x, -y).
+//                             One thread per OUTPUT slot finds its pixel by rank (binary search in the row offsets, popcount walk
+//                             within the row), so the 5000-point subsample is taken while expanding and device memory is bounded
+//                             by the number of points kept, not by the mask area
+//   dbscan_*_batch_kernel     open3d PointCloud.cluster_dbscan(eps, min_points) [ext] for n <= ~5000 points, restated for a
+//                             data-parallel machine: eps-adjacency as an n x n bit matrix (64 columns per word: a wavefront
+//                             ballot), core = degree >= min_points (the point itself counts), clusters = connected components
+//                             of the core-core graph labelled in order of their smallest core index (the order in which the
+//                             sequential scan seeds them), border points join the lowest-labelled neighbouring cluster (the
+//                             first one to reach them), everything else is noise; then the largest cluster (first maximum) in
+//                             original point order (object_point_cloud_map.py:186-212).
 // Latency-bound integer/f64 work on a few thousand points; no MFMA.
 //
-// The *_batch_* kernels run the same stages for ALL detections of a step at once (grid.y = job, or one workgroup per job): the
-// per-job bodies are the device functions the single-job kernels call, so the two paths cannot drift apart.  What differs is the
-// expansion: instead of writing every masked pixel and gathering the 5000-point subsample afterwards, one thread per OUTPUT slot
-// finds its pixel by rank (binary search in the row offsets, popcount walk within the row), so device memory is bounded by the
-// number of points kept, not by the mask area.
+// Every kernel takes ALL detections of a step at once (grid.y = job, or one workgroup per job); a single detection is a batch of one.
 #include <atomic>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,19 +29,6 @@
 namespace vlfm {
 
 // ------------------------------------------------------------------------------------------------ mask -> bits, erosion
-__global__ __launch_bounds__(256) void mask_pack_kernel(const unsigned char* __restrict__ mask, int H, int W, int hw,
-                                                        unsigned* __restrict__ bits) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= H * hw) return;
-    const int y = i / hw, w = i - y * hw;
-    unsigned v = 0u;
-    for (int b = 0; b < 32; b++) {
-        const int x = w * 32 + b;
-        if (x < W && mask[(size_t)y * W + x] != 0) v |= 1u << b;
-    }
-    bits[i] = v;
-}
-
 // one eroded word of a packed plane: the AND of the nine shifted neighbours
 __device__ __forceinline__ unsigned erode_word(const unsigned* __restrict__ src, int y, int w, int H, int W, int hw) {
     const unsigned tail = (W & 31) && w == hw - 1 ? ~((1u << (W & 31)) - 1u) : 0u;  // columns >= W count as set
@@ -58,14 +43,6 @@ __device__ __forceinline__ unsigned erode_word(const unsigned* __restrict__ src,
         acc &= m & ((m << 1) | left) & ((m >> 1) | (right << 31));
     }
     return acc & ~tail;
-}
-
-__global__ __launch_bounds__(256) void mask_erode_kernel(const unsigned* __restrict__ src, int H, int W, int hw,
-                                                         unsigned* __restrict__ dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= H * hw) return;
-    const int y = i / hw, w = i - y * hw;
-    dst[i] = erode_word(src, y, w, H, W, hw);
 }
 
 // grid.y = job.  The packed plane of every job, and the OR of its rows (which columns the UN-eroded mask occupies: the x-extent
@@ -143,49 +120,6 @@ __device__ __forceinline__ void unproject_pixel(float d, int u, int y, int H, in
     out[2] = -yc;
 }
 
-__global__ __launch_bounds__(1024) void cloud_extract_kernel(const float* __restrict__ depth, const unsigned* __restrict__ bits,
-                                                             int H, int W, int hw, float scale, float offset, double fx,
-                                                             double fy, double* __restrict__ cloud, int cap,
-                                                             int* __restrict__ count) {
-    extern __shared__ int row_off[];  // [H + 1]
-    const int tid = threadIdx.x, nth = blockDim.x;
-    for (int y = tid; y < H; y += nth) {
-        int c = 0;
-        for (int w = 0; w < hw; w++) c += __popc(bits[(size_t)y * hw + w]);
-        row_off[y + 1] = c;
-    }
-    if (tid == 0) row_off[0] = 0;
-    __syncthreads();
-    if (tid == 0) {  // H <= a few thousand: a serial scan is microseconds
-        for (int y = 0; y < H; y++) row_off[y + 1] += row_off[y];
-        *count = row_off[H];
-    }
-    __syncthreads();
-    // one wavefront per row: lanes own words, ranks come from a wave prefix over the word popcounts
-    const int lane = tid & 63, wave = tid >> 6, n_waves = nth >> 6;
-    for (int y = wave; y < H; y += n_waves) {
-        int base = row_off[y];
-        for (int w0 = 0; w0 < hw; w0 += 64) {
-            const int w = w0 + lane;
-            unsigned v = w < hw ? bits[(size_t)y * hw + w] : 0u;
-            int pc = __popc(v), incl = pc;
-            for (int off = 1; off < 64; off <<= 1) {
-                const int t = __shfl_up(incl, off, 64);
-                if (lane >= off) incl += t;
-            }
-            int rank = base + incl - pc;
-            while (v) {
-                const int b = __builtin_ctz(v);
-                v &= v - 1;
-                const int u = w * 32 + b;
-                if (rank < cap) unproject_pixel(depth[(size_t)y * W + u], u, y, H, W, scale, offset, fx, fy, cloud + (size_t)rank * 3);
-                rank++;
-            }
-            base += __shfl(incl, 63, 64);
-        }
-    }
-}
-
 // grid.y = entry of `jobs`; one thread per OUTPUT point.  jobs [n][6] = (stage-1 job, depth frame, points to write, first output
 // point, first entry of `ranks` or -1, 0).  Output slot s holds the masked pixel of rank ranks[first + s] (np.where order), or of
 // rank s without a rank list: the row by binary search in the row offsets, the column by a popcount walk along the row.
@@ -245,13 +179,7 @@ __device__ __forceinline__ void dbscan_adjacency_row(const double* __restrict__ 
     if (lane == 0) degree[i] = deg;
 }
 
-__global__ __launch_bounds__(256) void dbscan_adjacency_kernel(const double* __restrict__ pts, int n, double eps2,
-                                                               unsigned long long* __restrict__ adj, int cb_count,
-                                                               int* __restrict__ degree) {
-    dbscan_adjacency_row(pts, n, eps2, adj, cb_count, degree);
-}
-
-// Per-job scratch of the batched DBSCAN: adjacency words, then degree, sizes, label, keep ([n] i32 each).
+// Per-job scratch of the DBSCAN: adjacency words, then degree, sizes, label, keep ([n] i32 each) -- the layout include/vlfm_amd.h states.
 struct DbscanJob {
     const double* pts;
     unsigned long long* adj;
@@ -434,13 +362,6 @@ __device__ __forceinline__ void dbscan_cluster_block(const unsigned long long* _
     }
 }
 
-__global__ __launch_bounds__(1024) void dbscan_cluster_kernel(const unsigned long long* __restrict__ adj, const int* __restrict__ degree,
-                                                              int n, int cb_count, int min_points, int* __restrict__ label,
-                                                              int* __restrict__ sizes /* [n] scratch */, int* __restrict__ keep,
-                                                              int* __restrict__ num_keep) {
-    dbscan_cluster_block(adj, degree, n, cb_count, min_points, label, sizes, keep, num_keep);
-}
-
 // One workgroup per job, each with its own n; then the points of the largest cluster, in order, at the job's own place in `kept`
 // (the same offsets as `points`: a job keeps at most what it had).
 __global__ __launch_bounds__(1024) void dbscan_cluster_batch_kernel(const double* __restrict__ points, int capacity,
@@ -464,8 +385,8 @@ __global__ __launch_bounds__(1024) void dbscan_cluster_batch_kernel(const double
 
 using namespace vlfm;
 
-// every kernel this file launches is counted (vlfm_object_cloud_launch_count): the batched path's claim is that the count per call
-// does not depend on the number of detections
+// every kernel this file launches is counted (vlfm_object_cloud_launch_count): the count per call does not depend on the number of
+// detections, and the tests hold it to that
 static std::atomic<long long> g_launches{0};
 #define OC_LAUNCH(...)           \
     do {                         \
@@ -474,60 +395,6 @@ static std::atomic<long long> g_launches{0};
     } while (0)
 
 extern "C" long long vlfm_object_cloud_launch_count(void) { return g_launches.load(); }
-
-extern "C" size_t vlfm_object_cloud_scratch_bytes(int height, int width) {
-    if (height <= 0 || width <= 0) return 0;
-    return (size_t)2 * height * ((width + 31) / 32) * sizeof(uint32_t);
-}
-
-extern "C" int vlfm_object_cloud_extract(const float* d_depth, const uint8_t* d_mask, int height, int width,
-                                         int erosion_iterations, double min_depth, double max_depth, double fx, double fy,
-                                         void* d_scratch, double* d_cloud, int capacity, int32_t* d_count, void* stream) {
-    if (!d_depth || !d_mask || !d_scratch || !d_cloud || !d_count || height <= 0 || width <= 0 || erosion_iterations < 0 ||
-        capacity <= 0 || height > 8192)
-        return fail(VLFM_ERR_INVALID, "object_cloud_extract: bad argument");
-    const int hw = (width + 31) / 32, words = height * hw;
-    unsigned* a = (unsigned*)d_scratch;
-    unsigned* b = a + words;
-    OC_LAUNCH(mask_pack_kernel, dim3((words + 255) / 256), dim3(256), 0, stream, d_mask, height, width, hw, a);
-    for (int k = 0; k < erosion_iterations; k++) {
-        OC_LAUNCH(mask_erode_kernel, dim3((words + 255) / 256), dim3(256), 0, stream, a, height, width, hw, b);
-        unsigned* t = a; a = b; b = t;
-    }
-    // NumPy: f32 image * Python float -> f32 (object_point_cloud_map.py:162)
-    VLFM_TIMED("cloud_extract_kernel", stream);
-    OC_LAUNCH(cloud_extract_kernel, dim3(1), dim3(1024), (size_t)(height + 1) * sizeof(int), stream, d_depth, a, height,
-                 width, hw, (float)(max_depth - min_depth), (float)min_depth, fx, fy, d_cloud, capacity, d_count);
-    return check_launch("cloud_extract_kernel");
-}
-
-extern "C" size_t vlfm_dbscan_scratch_bytes(int n) {
-    if (n <= 0) return 0;
-    const size_t cb = ((size_t)n + 63) / 64;
-    return (size_t)n * cb * 8 + (size_t)2 * n * sizeof(int32_t) + 256;
-}
-
-extern "C" int vlfm_dbscan_largest_cluster(const double* d_points, int n, double eps, int min_points, void* d_scratch,
-                                           size_t scratch_bytes, int32_t* d_labels, int32_t* d_keep, int32_t* d_num_keep,
-                                           void* stream) {
-    if (!d_num_keep) return fail(VLFM_ERR_INVALID, "dbscan: d_num_keep is null");
-    if (n == 0) return hipMemsetAsync(d_num_keep, 0, sizeof(int32_t), (hipStream_t)stream) == hipSuccess ? VLFM_OK : VLFM_ERR_HIP;
-    if (!d_points || !d_scratch || !d_labels || !d_keep || n < 0 || n > 8192 || min_points < 1 || !(eps > 0))
-        return fail(VLFM_ERR_INVALID, "dbscan: bad argument (n <= 8192)");
-    if (scratch_bytes < vlfm_dbscan_scratch_bytes(n)) return fail(VLFM_ERR_CAPACITY, "dbscan: scratch too small");
-    const int cb = (n + 63) / 64;
-    unsigned long long* adj = (unsigned long long*)d_scratch;
-    int* degree = (int*)((unsigned char*)d_scratch + (size_t)n * cb * 8);
-    int* sizes = degree + n;
-    {
-        VLFM_TIMED("dbscan_adjacency_kernel", stream);
-        OC_LAUNCH(dbscan_adjacency_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, d_points, n, eps * eps, adj, cb, degree);
-    }
-    VLFM_TIMED("dbscan_cluster_kernel", stream);
-    OC_LAUNCH(dbscan_cluster_kernel, dim3(1), dim3(1024), 0, stream, (const unsigned long long*)adj, (const int*)degree, n,
-                 cb, min_points, d_labels, sizes, d_keep, d_num_keep);
-    return check_launch("dbscan_cluster_kernel");
-}
 
 // ------------------------------------------------------------------------------------------------ all detections of a step
 extern "C" size_t vlfm_object_cloud_batch_scratch_bytes(int jobs, int height, int width) {

@@ -524,7 +524,8 @@ class BatchedEpisodes:
         # act(modes, rho_theta [E,2], stops [E], collided [E]) -> int64 [E] action ids (default: BangBangController)
         self.closed_loop = bool(closed_loop)
         # batch_object_maps: all detections of a step go through the object-cloud kernels together (update_maps_batch); False =
-        # one ObjectPointCloudMap.update_map after the other -- same clouds, same random draws, kept for comparison
+        # one ObjectPointCloudMap.update_map per detection, each a batch of one job -- same clouds, same random draws, more launches
+        # and read-backs, kept for comparison
         self.batch_object_maps = bool(batch_object_maps)
         # device_object_clouds: update_explored and the object goals of all environments are asked of device mirrors of the clouds,
         # one launch and one read-back each per step (update_explored_batch, get_best_objects_batch); False = one NumPy pass per
@@ -849,8 +850,9 @@ class BatchedEpisodes:
     def _update_object_maps(self, dets, rgb: torch.Tensor, depth: torch.Tensor, tf: np.ndarray) -> None:
         """BaseObjectNavPolicy._update_object_map for every environment (base_objectnav_policy.py:285-352): class + confidence
         filters, ONE MobileSAM call for all surviving boxes of the batch (the reference re-encodes the frame per box too),
-        ObjectPointCloudMap.update_map per mask (csrc/object_cloud.hip: erosion, back-projection, DBSCAN) -- all masks of the step
-        in one update_maps_batch unless batch_object_maps=False -- update_explored per environment and step (one
+        the reference's ObjectPointCloudMap.update_map per mask (csrc/object_cloud.hip: erosion, back-projection, DBSCAN) -- all
+        masks of the step as the jobs of one update_maps_batch, or with batch_object_maps=False one job per call -- update_explored
+        per environment and step (one
         update_explored_batch over the environments that have clouds unless device_object_clouds=False)."""
         jobs = []
         for e, det in enumerate(dets):

@@ -1,9 +1,10 @@
 """vlfm.mapping.object_point_cloud_map.ObjectPointCloudMap, MI355X-native
 (reference: /root/reference/vlfm/mapping/object_point_cloud_map.py:17-297).
 
-The per-detection heavy lifting -- mask erosion, masked back-projection, DBSCAN + largest-cluster selection
-(``_extract_object_cloud``, :150-170) -- runs in HIP kernels (csrc/object_cloud.hip); the bookkeeping around it (range ids,
-closest point, ``get_best_object`` hysteresis, ``update_explored``) is O(points kept) NumPy on the host exactly as in the
+The heavy lifting of a detection -- mask erosion, masked back-projection, DBSCAN + largest-cluster selection
+(``_extract_object_cloud``, :150-170) -- runs in HIP kernels (csrc/object_cloud.hip) that take all detections of a step at once
+(``extract_object_clouds_batch`` / ``update_maps_batch``); ``update_map`` is a batch of one job.  The bookkeeping around it (range
+ids, closest point, ``get_best_object`` hysteresis, ``update_explored``) is O(points kept) NumPy on the host exactly as in the
 reference, INCLUDING its draws from NumPy's global RNG (``np.random.choice`` for the 5000-point subsample,
 ``np.random.rand`` for the out-of-range ids), so that a seeded run reproduces the reference's clouds.
 
@@ -46,14 +47,9 @@ def within_fov_cone(cone_origin, cone_angle, cone_fov, cone_range, points) -> np
 def too_offset(mask) -> bool:
     """Does the detection hug the left or right image border (object_point_cloud_map.py:272-297)?  A mask whose column
     extent lies wholly in the outer third of the image AND reaches within 5 % of that border is "too offset": its
-    points get an out-of-range tag because the object is probably cut off by the image edge.  ``mask``: (H,W) ndarray, or a
-    device tensor (the column occupancy is reduced on the device; W bytes cross to the host)."""
+    points get an out-of-range tag because the object is probably cut off by the image edge.  ``mask``: (H,W) ndarray."""
     width = mask.shape[1]
-    if hasattr(mask, "is_cuda"):
-        SYNCS[0] += 1
-        occupied = np.flatnonzero((mask != 0).any(dim=0).cpu().numpy())
-    else:
-        occupied = np.flatnonzero(np.asarray(mask).any(axis=0))       # cv2.boundingRect's x-extent
+    occupied = np.flatnonzero(np.asarray(mask).any(axis=0))           # cv2.boundingRect's x-extent
     left, right = (int(occupied[0]), int(occupied[-1]) + 1) if len(occupied) else (0, 0)
     return extent_too_offset(left, right, width)
 
@@ -192,14 +188,14 @@ class ObjectPointCloudMap:
 
     def update_map(self, object_name: str, depth_img: np.ndarray, object_mask: np.ndarray,
                    tf_camera_to_episodic: np.ndarray, min_depth: float, max_depth: float, fx: float, fy: float) -> None:
-        """object_point_cloud_map.py:29-75."""
-        camera_frame = self._extract_object_cloud(depth_img, object_mask, min_depth, max_depth, fx, fy)
-        self._commit(object_name, camera_frame, lambda: too_offset(object_mask), tf_camera_to_episodic, max_depth)
+        """object_point_cloud_map.py:29-75: ``update_maps_batch`` with this detection as its one job."""
+        update_maps_batch([self], [object_name], *_one_job(depth_img, object_mask), [tf_camera_to_episodic], min_depth, max_depth,
+                          fx, fy)
 
     def _commit(self, object_name: str, camera_frame: np.ndarray, is_too_offset, tf_camera_to_episodic: np.ndarray,
                 max_depth: float) -> None:
-        """Everything of ``update_map`` after the camera-frame cloud is on the host (:40-75) -- shared by the per-detection and the
-        batched path.  ``is_too_offset``: called (once) only for a non-empty cloud."""
+        """Everything of ``update_map`` after the camera-frame cloud is on the host (:40-75).  ``is_too_offset``: called (once) only
+        for a non-empty cloud."""
         if len(camera_frame) == 0:
             return
         # exactly ONE draw from the global generator per non-empty observation, whichever branch is taken (the reference
@@ -336,49 +332,10 @@ class ObjectPointCloudMap:
     # ------------------------------------------------------------------------------------------ :150-170 on the GPU
     def _extract_object_cloud(self, depth: np.ndarray, object_mask: np.ndarray, min_depth: float, max_depth: float,
                               fx: float, fy: float) -> np.ndarray:
-        import torch
-
-        L = _lib.lib()
-        dev = self.device
-        d = torch.from_numpy(np.ascontiguousarray(depth, np.float32)).to(dev) if not torch.is_tensor(depth) else depth
-        d = d.reshape(d.shape[-2], d.shape[-1]).contiguous()
-        H, W = d.shape
-        m = torch.from_numpy(np.ascontiguousarray(np.asarray(object_mask) != 0).astype(np.uint8)).to(dev) \
-            if not torch.is_tensor(object_mask) else (object_mask != 0).to(torch.uint8).contiguous()
-        cap = H * W
-        scratch = torch.empty(L.vlfm_object_cloud_scratch_bytes(H, W), dtype=torch.uint8, device=dev)
-        cloud = torch.empty((cap, 3), dtype=torch.float64, device=dev)
-        count = torch.zeros(1, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.vlfm_object_cloud_extract(d.data_ptr(), m.data_ptr(), H, W, int(self._erosion_size),
-                                                   float(min_depth), float(max_depth), float(fx), float(fy),
-                                                   scratch.data_ptr(), cloud.data_ptr(), cap, count.data_ptr(),
-                                                   _stream_ptr()), "object_cloud_extract")
-            SYNCS[0] += 1
-            n = int(count.item())
-            cloud = cloud[:n]
-            if n > 5000:  # get_random_subarray: NumPy's global RNG picks, the device gathers
-                idx = self._rng.choice(n, 5000, replace=False)
-                cloud = cloud[torch.from_numpy(idx).to(dev)].contiguous()
-                n = 5000
-            if not self.use_dbscan:
-                SYNCS[0] += 1
-                return cloud.cpu().numpy()
-            if n == 0:
-                return np.array([])  # open3d_dbscan_filtering of an empty cloud: no non-noise label (:200-201), shape (0,) like the reference
-            sc = torch.empty(L.vlfm_dbscan_scratch_bytes(n), dtype=torch.uint8, device=dev)
-            labels = torch.empty(n, dtype=torch.int32, device=dev)
-            keep = torch.empty(n, dtype=torch.int32, device=dev)
-            num = torch.zeros(1, dtype=torch.int32, device=dev)
-            _lib.check(L.vlfm_dbscan_largest_cluster(cloud.data_ptr(), n, 0.2, 100, sc.data_ptr(), sc.numel(),
-                                                     labels.data_ptr(), keep.data_ptr(), num.data_ptr(), _stream_ptr()),
-                       "dbscan")
-            SYNCS[0] += 1
-            k = int(num.item())
-            if k == 0:
-                return np.array([])  # only noise was detected (:200-201)
-            SYNCS[0] += 1
-            return cloud[keep[:k].to(torch.int64)].cpu().numpy()
+        """The camera-frame cloud of one detection: ``extract_object_clouds_batch`` with one job.  ``depth``: H x W values (leading
+        unit axes allowed), ``object_mask``: (H, W), non-zero = object; NumPy arrays or device tensors."""
+        (_, cloud, _), = extract_object_clouds_batch([self], *_one_job(depth, object_mask), min_depth, max_depth, fx, fy)
+        return cloud
 
     # ------------------------------------------------------------------------------------------ :172-183
     def _get_closest_point(self, cloud: np.ndarray, curr_position: np.ndarray) -> np.ndarray:
@@ -395,12 +352,25 @@ class ObjectPointCloudMap:
 
 
 # ---------------------------------------------------------------------------------------------- all detections of a step
+def _one_job(depth, mask):
+    """(depth_frames, frame_index, masks) of the batch that holds one detection: the depth as one H x W frame, H and W being the
+    mask's."""
+    import torch
+
+    H, W = mask.shape
+    if not torch.is_tensor(mask):
+        mask = np.asarray(mask) != 0
+    if not torch.is_tensor(depth):
+        depth = np.asarray(depth)
+    return depth.reshape(1, H, W), [0], mask[None]
+
+
 def plan_waves(generators: Sequence[int], needs_choice: Sequence[bool]) -> List[List[int]]:
     """Split jobs 0..D-1, in order, into waves whose random draws can be made as "all ``choice``s of the wave in job order, then
-    all ``rand``s in job order" and still leave every generator with the draws of the per-detection path in the same order
-    (per job: ``choice`` if the mask has more than 5000 points, then ``rand`` if the final cloud is not empty).  ``generators``:
-    one key per job, equal for jobs that share a generator (``id(rng)``).  A new wave starts at a job that needs a ``choice``
-    and whose generator already has an earlier job in the current wave -- that job's ``rand`` has to come first."""
+    all ``rand``s in job order" and still leave every generator with the draws of the reference's ``update_map`` calls made one
+    after the other (per job: ``choice`` if the mask has more than 5000 points, then ``rand`` if the final cloud is not empty).
+    ``generators``: one key per job, equal for jobs that share a generator (``id(rng)``).  A new wave starts at a job that needs
+    a ``choice`` and whose generator already has an earlier job in the current wave -- that job's ``rand`` has to come first."""
     if len(generators) != len(needs_choice):
         raise ValueError("plan_waves: one generator key and one flag per job")
     waves: List[List[int]] = []
@@ -479,14 +449,16 @@ def mask_stats_batch(masks_u8, erosion: Sequence[float], device):
 def extract_object_clouds_batch(maps: Sequence[ObjectPointCloudMap], depth_frames, frame_index: Sequence[int], masks,
                                 min_depth: float, max_depth: float, fx: float, fy: float,
                                 scratch_budget_bytes: int = DEFAULT_SCRATCH_BUDGET) -> Iterator[Tuple[int, np.ndarray, bool]]:
-    """``maps[j]._extract_object_cloud(depth_frames[frame_index[j]], masks[j], ...)`` for every job j, all jobs going through the
-    kernels together; yields ``(j, cloud, too_offset(masks[j]))`` in job order, with bit-identical clouds.  A generator, because
-    the random draws have to interleave with the caller's: the ``choice``s of a wave (``plan_waves``) are drawn when its first job
-    is asked for, and whoever consumes a job makes that job's other draws before asking for the next one.
+    """The reference's ``_extract_object_cloud`` (:150-170) of ``depth_frames[frame_index[j]]`` under ``masks[j]`` with the erosion
+    size, ``use_dbscan`` and generator of ``maps[j]``, for every job j, all jobs going through the kernels together; yields
+    ``(j, cloud, too_offset(masks[j]))`` in job order.  A job's cloud and draws do not depend on what else is in the batch.  A
+    generator, because the random draws have to interleave with the caller's: the ``choice``s of a wave (``plan_waves``) are drawn
+    when its first job is asked for, and whoever consumes a job makes that job's other draws before asking for the next one.
 
     Launches and host synchronisations: one synchronisation for the point counts of all jobs, then one per (wave, scratch chunk);
-    pack, max(erosion) erosions and the statistics kernel for the counts, then expansion, adjacency and clustering per chunk.  Device memory: 2 bit planes per job, at most 5000 points per job
-    twice, and at most ``scratch_budget_bytes`` of adjacency scratch."""
+    pack, max(erosion) erosions and the statistics kernel for the counts, then expansion, adjacency and clustering per chunk.
+    Device memory: 2 bit planes per job, at most 5000 points per job twice, and at most ``scratch_budget_bytes`` of adjacency
+    scratch."""
     import torch
 
     D, F, H, W = _check_batch(maps, frame_index, masks, depth_frames, scratch_budget_bytes)
@@ -564,11 +536,11 @@ def extract_object_clouds_batch(maps: Sequence[ObjectPointCloudMap], depth_frame
 def update_maps_batch(maps: Sequence[ObjectPointCloudMap], object_names: Sequence[str], depth_frames, frame_index: Sequence[int],
                       masks, tfs: Sequence[np.ndarray], min_depth: float, max_depth: float, fx: float, fy: float,
                       scratch_budget_bytes: int = DEFAULT_SCRATCH_BUDGET) -> List[bool]:
-    """``maps[j].update_map(object_names[j], depth_frames[frame_index[j]], masks[j], tfs[j], ...)`` for j = 0..D-1 with all D
-    detections going through erosion, back-projection, sub-sampling and DBSCAN together (``extract_object_clouds_batch``).
-    ``maps[j]`` may repeat, several jobs may share a depth frame, maps may differ in erosion size and share generators: clouds and
-    every draw of every generator are those of the D calls made one after the other.  Returns, per job, whether it changed the
-    number of points its map holds for its class."""
+    """The reference's ``update_map`` (:29-75) of ``depth_frames[frame_index[j]]`` under ``masks[j]`` into class
+    ``object_names[j]`` of ``maps[j]``, for j = 0..D-1 in order, with all D detections going through erosion, back-projection,
+    sub-sampling and DBSCAN together (``extract_object_clouds_batch``).  ``maps[j]`` may repeat, several jobs may share a depth
+    frame, maps may differ in erosion size and share generators: clouds and every draw of every generator are those of D calls
+    of one job each.  Returns, per job, whether it changed the number of points its map holds for its class."""
     _check_batch(maps, frame_index, masks, depth_frames, scratch_budget_bytes, object_names, tfs)
     changed = []
     for j, cloud, off in extract_object_clouds_batch(maps, depth_frames, frame_index, masks, min_depth, max_depth, fx, fy,
