@@ -13,7 +13,9 @@ measured against f64, plus an allowance for the hardware exponential.  The NARRO
 within [-2, 2]) puts most pre-activations of a short K into GELU's interesting range, the negative tail included.
 Two evaluations of the same expectations: numpy on the CPU (conv_ref.f16_bits / ordered: the definition), and torch f64 in row chunks
 on the device for the cases too large for that (``rn16``: round-to-nearest-even onto the f16 grid by integer arithmetic in f64;
-tests/test_gemm_ref_cpu.py holds the two against each other).  Everything cached here is shared between tests: read-only."""
+tests/test_gemm_ref_cpu.py holds the two against each other).  Everything cached here is shared between tests: read-only.
+``work_items`` / ``tile_order`` are the library's own description of the persistent walk (evaluated on the host: no device needed)."""
+import ctypes
 import functools
 from types import SimpleNamespace
 
@@ -29,6 +31,35 @@ UNIT = 2.0 ** -7                 # every product, bias and residual is a multipl
 GELU_RANGE = 12.0                # beyond it gelu_f16.h returns max(v, 0) exactly (tests/test_gemm_ref_cpu.py)
 F16_TIE_TO_INF = 65520.0         # the tie between 65504 and 2^16: rounds to even, i.e. to inf
 CPU_LIMIT = 1 << 21              # outputs up to which a case is checked with numpy on the CPU
+
+
+# ------------------------------------------------------------------------------------------------ the kernel's schedule
+def _tiles(m, n):
+    return ((m + 255) // 256) * ((n + 255) // 256)
+
+
+def work_items(m, n, grid):
+    """[items, 2] = (list position of the tile, n-half 0 / 1 or -1 for the whole tile) of the persistent walk of ``grid`` workgroups;
+    workgroup w runs items w, w + grid, ..."""
+    from vlfm_amd import _lib
+
+    L = _lib.lib()
+    L.vlfm_gemm_f16_work_items.restype = ctypes.c_int
+    out = np.full((2 * _tiles(m, n), 2), -7, np.int32)
+    items = L.vlfm_gemm_f16_work_items(m, n, grid, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(out))
+    assert items >= _tiles(m, n)
+    return out[:items]
+
+
+def tile_order(m, n, group_m=0):
+    """[tiles, 2] = (m-tile, n-tile) of every list position; group_m = 0: the grouping the launcher uses."""
+    from vlfm_amd import _lib
+
+    L = _lib.lib()
+    L.vlfm_gemm_f16_tile_order.restype = ctypes.c_int
+    out = np.full((_tiles(m, n), 2), -7, np.int32)
+    assert L.vlfm_gemm_f16_tile_order(m, n, group_m, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(out)) == len(out)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ operands

@@ -14,8 +14,6 @@ vlfm_gemm_f16_tile_order that it has the structure it is named for.  Every outpu
 Around them: f16 saturation, subnormal results, ties and NaN confinement on hand-made operands, a 10-launch repeat screen, and the
 refusal of pointers that are not 16-byte aligned.  Subnormal f16 INPUTS are out of scope: what the matrix cores do with them is not
 established."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -37,29 +35,6 @@ def _grid(tiles):
 
 def _tiles(M, N):
     return (M + 255) // 256, (N + 255) // 256
-
-
-def _work_items(M, N, grid):
-    from vlfm_amd import _lib
-
-    L = _lib.lib()
-    L.vlfm_gemm_f16_work_items.restype = ctypes.c_int
-    tm, tn = _tiles(M, N)
-    out = np.full((2 * tm * tn, 2), -7, np.int32)
-    items = L.vlfm_gemm_f16_work_items(M, N, grid, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 2 * tm * tn)
-    assert items >= tm * tn
-    return out[:items]
-
-
-def _tile_order(M, N):
-    from vlfm_amd import _lib
-
-    L = _lib.lib()
-    L.vlfm_gemm_f16_tile_order.restype = ctypes.c_int
-    tm, tn = _tiles(M, N)
-    out = np.full((tm * tn, 2), -7, np.int32)
-    assert L.vlfm_gemm_f16_tile_order(M, N, 0, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), tm * tn) == tm * tn
-    return out
 
 
 def _launch(x, w, b, epi, r0):
@@ -153,7 +128,7 @@ def run_case(M, N, K, dev, repeats=1, runs=RUNS):
 def _few_tiles(M, N, K):
     tm, tn = _tiles(M, N)
     assert tm * tn <= _grid(1 << 30)
-    items = _work_items(M, N, _grid(tm * tn))
+    items = G.work_items(M, N, _grid(tm * tn))
     assert len(items) == tm * tn and (items[:, 1] == -1).all()          # one whole tile per workgroup
     return tm, tn, K // 64
 
@@ -172,7 +147,7 @@ def _s_two_ktiles(M, N, K):
 
 def _s_four_ragged(M, N, K):
     assert _few_tiles(M, N, K) == (2, 2, 3) and M % 256 == 1 and N % 256 == 8
-    assert sorted(map(tuple, _tile_order(M, N))) == [(0, 0), (0, 1), (1, 0), (1, 1)]
+    assert sorted(map(tuple, G.tile_order(M, N))) == [(0, 0), (0, 1), (1, 0), (1, 1)]
 
 
 def _s_second_group_8(M, N, K):
@@ -181,12 +156,12 @@ def _s_second_group_8(M, N, K):
 
 def _s_half_empty(M, N, K):
     assert _few_tiles(M, N, K) == (1, 2, 5) and N - 256 == 128              # wavefronts 4-7 of the last n-tile are inactive
-    assert tuple(_tile_order(M, N)[-1]) == (0, 1)
+    assert tuple(G.tile_order(M, N)[-1]) == (0, 1)
 
 
 def _s_vit_half_tile(M, N, K):
     assert _few_tiles(M, N, K) == (2, 6, 22) and N - 5 * 256 == 128
-    order = _tile_order(M, N)
+    order = G.tile_order(M, N)
     assert (order[:, 1] == 5).sum() == 2 and set(order[-2:, 1]) == {5}       # the half tiles close the list of their XCDs
 
 
@@ -212,32 +187,32 @@ def _walk_shape(name):
     assert g >= 16 and g % 8 == 0
     if name == "one_leftover_tile_as_two_halves":
         M, N = 256 * g + 1, 200
-        items = _work_items(M, N, g)
+        items = G.work_items(M, N, g)
         assert len(items) == g + 2 and (items[:g, 1] == -1).all()
         assert [tuple(i) for i in items[g:]] == [(g, 0), (g, 1)]
     elif name == "three_whole_rounds":
         M, N = 256 * 3 * g, 256
-        items = _work_items(M, N, g)
+        items = G.work_items(M, N, g)
         assert len(items) == 3 * g and (items[:, 1] == -1).all()
     elif name == "leftover_half_a_round_is_split":
         M, N = 256 * (2 * g + g // 2), 256
-        items = _work_items(M, N, g)
+        items = G.work_items(M, N, g)
         assert len(items) == 3 * g and (items[:2 * g, 1] == -1).all() and sorted(items[2 * g:, 1]) == [0] * (g // 2) + [1] * (g // 2)
     elif name == "leftover_above_half_a_round_is_not":
         M, N = 256 * (2 * g + g // 2 + 1), 256
-        items = _work_items(M, N, g)
+        items = G.work_items(M, N, g)
         assert len(items) == 2 * g + g // 2 + 1 and (items[:, 1] == -1).all()
     else:
         assert name == "three_n_tiles_ragged_groups"
         tm = (g + 17 + 2) // 3
         M, N = 256 * tm - 5, 520
         assert _tiles(M, N) == (tm, 3) and tm % 4 != 0 and 3 * tm > g and N - 512 == 8
-        order = _tile_order(M, N)
+        order = G.tile_order(M, N)
         assert sorted(map(tuple, order)) == [(m, n) for m in range(tm) for n in range(3)]
         for xcd in range(8):                                                # the 8-column tiles close every XCD's share of the list
             tn = order[xcd::8, 1]
             assert (tn[:int((tn < 2).sum())] < 2).all()
-        assert len(_work_items(M, N, g)) >= 3 * tm
+        assert len(G.work_items(M, N, g)) >= 3 * tm
     return M, N
 
 
@@ -293,7 +268,7 @@ def test_pair_gemm_is_exact(gpu_device, which, with_bias):
         assert (N // 64) % 2 == 1 and 2 * N - 256 == 128
     if which == "walk":
         g = _grid(1 << 30)
-        items = _work_items(M, 2 * N, g)
+        items = G.work_items(M, 2 * N, g)
         assert len(items) == g + 2 and [tuple(i) for i in items[g:]] == [(g, 0), (g, 1)]
     g = torch.Generator().manual_seed(M * 7 + N * 3 + K)
     x, w1, w2 = G._dyadic(g, (M, K), G.WIDE.x), G._dyadic(g, (N, K), G.WIDE.w), G._dyadic(g, (N, K), G.WIDE.w)

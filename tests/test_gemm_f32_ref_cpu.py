@@ -144,9 +144,11 @@ def test_a_chain_in_another_k_order_is_reported():
 
 # ------------------------------------------------------------------------------------------------ GELU coefficients
 def test_kernel_gelu_coefficients_are_the_reference_polynomial():
-    """gemm_ref.gelu_tolerance() is derived from _Q; it applies to gemm_f32.hip only while its gelu_erf holds the same eight numbers,
-    in the same Horner order."""
-    body = re.search(r"float gelu_erf\(float v\) \{(.*?)\n\}", KERNEL.read_text(), re.S).group(1)
+    """gemm_ref.gelu_tolerance() is derived from _Q; it applies to gemm_f32.hip only while its gelu_erf -- the one of gelu_f16.h, which
+    it shares with gemm_f16.hip -- holds the same eight numbers, in the same Horner order."""
+    kernel = KERNEL.read_text()
+    assert '#include "gelu_f16.h"' in kernel and "t = gelu_erf(t);" in kernel and "float gelu_erf(" not in kernel
+    body = re.search(r"float gelu_erf\(float v\) \{(.*?)\n\}", (KERNEL.parent / "gelu_f16.h").read_text(), re.S).group(1)
     first = re.findall(r"float q = ([-+0-9.e]+)f;", body)
     rest = re.findall(r"q = fmaf\(q, u, ([-+0-9.e]+)f\);", body)
     assert len(first) == 1 and len(rest) == 7

@@ -7,6 +7,8 @@ import ctypes
 import numpy as np
 import pytest
 
+import gemm_ref as G
+
 SHAPES = [(65792, 6144), (65792, 4224), (65792, 1408), (8224, 6144), (257, 6144), (7000, 2568), (5000, 4224), (300, 264), (130, 8),
           (256, 256), (2049, 640), (100000, 1408), (33 * 256, 129), (256 * 9, 256 * 3 + 128), (1, 8)]
 
@@ -15,13 +17,14 @@ def _order(m, n, gm):
     from vlfm_amd import _lib
 
     _lib.build()
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    L.vlfm_gemm_f16_tile_order.restype = ctypes.c_int
-    tiles = ((m + 255) // 256) * ((n + 255) // 256)
-    out = np.zeros((tiles, 2), np.int32)
-    got = L.vlfm_gemm_f16_tile_order(m, n, gm, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), tiles)
-    assert got == tiles
-    return out
+    return G.tile_order(m, n, gm)
+
+
+def _items(m, n, grid):
+    from vlfm_amd import _lib
+
+    _lib.build()
+    return G.work_items(m, n, grid)
 
 
 @pytest.mark.parametrize("gm", [0, 1, 2, 4, 8, 32])
@@ -78,17 +81,11 @@ def test_tile_order_rejects_bad_arguments():
 @pytest.mark.parametrize("grid", [256, 304, 32, 8])
 @pytest.mark.parametrize("shape", SHAPES)
 def test_work_items_cover_every_tile_once_whole_or_as_two_halves(shape, grid):
-    from vlfm_amd import _lib
-
-    _lib.build()
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    L.vlfm_gemm_f16_work_items.restype = ctypes.c_int
     m, n = shape
     tiles = ((m + 255) // 256) * ((n + 255) // 256)
-    out = np.full((2 * tiles, 2), -7, np.int32)
-    items = L.vlfm_gemm_f16_work_items(m, n, grid, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 2 * tiles)
+    it = _items(m, n, grid)
+    items = len(it)
     assert tiles <= items <= tiles + grid // 2
-    it = out[:items]
     whole = np.zeros(tiles, np.int32)
     halves = np.zeros((tiles, 2), np.int32)
     for pos, h in it:
@@ -112,14 +109,8 @@ def test_work_items_cover_every_tile_once_whole_or_as_two_halves(shape, grid):
 
 def test_the_vit_fc1_shapes_end_in_split_rounds():
     """fc1 at 256 / 128 / 64 / 32 images: 24.1 / 12.1 / 6.1 / 3.1 rounds of 256 workgroups -- the 24 leftover tiles become 48 half items."""
-    from vlfm_amd import _lib
-
-    _lib.build()
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    L.vlfm_gemm_f16_work_items.restype = ctypes.c_int
     for images in (256, 128, 64, 32):
         m = images * 257
         tiles = ((m + 255) // 256) * 24
-        out = np.zeros((2 * tiles, 2), np.int32)
-        assert L.vlfm_gemm_f16_work_items(m, 6144, 256, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 2 * tiles) == tiles + tiles % 256
+        assert len(_items(m, 6144, 256)) == tiles + tiles % 256
         assert tiles % 256 == 24

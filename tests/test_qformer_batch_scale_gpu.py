@@ -14,12 +14,12 @@ vlfm_gemm_f16_tile_order) and from a restatement of the attention launcher's, wi
 figures in the comments are those of 256 CUs).  Bounds: those of the two one-item test files, relative to a yardstick evaluated on
 the same inputs.  A result must also not depend on the schedule at all: the same rows / images computed alone, one item per workgroup,
 give identical bits."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import gemm_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -58,19 +58,8 @@ PAIR_CASES = ["split", "split_one_ktile", "odd_blocks", "no_split", "steady"]
 def _walk(m, n, grid):
     """(items [n, 2] = (list position, n-half or -1), order [tiles, 2] = (m-tile, n-tile) of a list position) for ``grid`` workgroups;
     workgroup w runs items w, w + grid, ..."""
-    from vlfm_amd import _lib
-
-    L = _lib.lib()
-    L.vlfm_gemm_f16_work_items.restype = ctypes.c_int
-    L.vlfm_gemm_f16_tile_order.restype = ctypes.c_int
-    tiles = _ceil_div(m, 256) * _ceil_div(n, 256)
-    assert grid == min(grid, tiles)
-    items = np.full((2 * tiles, 2), -7, np.int32)
-    n_items = L.vlfm_gemm_f16_work_items(m, n, grid, items.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 2 * tiles)
-    assert n_items >= tiles
-    order = np.full((tiles, 2), -7, np.int32)
-    assert L.vlfm_gemm_f16_tile_order(m, n, 0, order.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), tiles) == tiles
-    return items[:n_items], order
+    assert grid == min(grid, _ceil_div(m, 256) * _ceil_div(n, 256))
+    return gemm_ref.work_items(m, n, grid), gemm_ref.tile_order(m, n)
 
 
 def _assert_pair_schedule(case, shape, cus):

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+import gemm_ref
+
 pytestmark = pytest.mark.gpu
 
 _BITS = {torch.float16: torch.int16, torch.float32: torch.int32}
@@ -208,18 +210,6 @@ def test_vit_attention_item_result_is_independent_of_the_schedule(gpu_device):
 
 
 # ------------------------------------------------------------------------------------------------ fc1 / fc2 GEMM
-def _work_items(m, n, grid):
-    from vlfm_amd import _lib
-
-    L = _lib.lib()
-    L.vlfm_gemm_f16_work_items.restype = ctypes.c_int
-    tiles = ((m + 255) // 256) * ((n + 255) // 256)
-    out = np.full((2 * tiles, 2), -7, np.int32)
-    items = L.vlfm_gemm_f16_work_items(m, n, grid, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 2 * tiles)
-    assert items >= tiles
-    return out[:items]
-
-
 def _check_gemm(got, x, w, b, r0, gelu):
     """|got - ref| <= 2e-3 * max(1, max|ref|) with ref = [gelu](x . w^T + b) [+ r0] in float64, 8192 rows at a time"""
     wd = w.double().t()
@@ -245,7 +235,7 @@ def test_fc1_gelu_gemm_at_batch_vs_f64(gpu_device, M):
 
     N, K = 6144, 1408
     grid = min(_cu_count() & ~7, ((M + 255) // 256) * 24)           # the launcher's grid: one workgroup per CU
-    items = _work_items(M, N, grid)
+    items = gemm_ref.work_items(M, N, grid)
     assert (items[:, 1] >= 0).any()                                  # the leftover round runs as n-halves
     if M == 65792:
         whole = np.bincount(np.arange(len(items))[items[:, 1] < 0] % grid, minlength=grid)
@@ -269,7 +259,7 @@ def test_fc2_accumulate_gemm_at_batch_vs_f64(gpu_device):
 
     M, N, K = 65792, 1408, 6144
     grid = min(_cu_count() & ~7, 257 * 6)
-    assert (_work_items(M, N, grid)[:, 1] >= 0).any()
+    assert (gemm_ref.work_items(M, N, grid)[:, 1] >= 0).any()
     g = torch.Generator(device=gpu_device).manual_seed(65)
     x = (torch.randn(M, K, generator=g, device=gpu_device) * 0.5).half()
     w = (torch.randn(N, K, generator=g, device=gpu_device) * 0.05).half()

@@ -21,17 +21,12 @@
 #include <stdint.h>
 
 #include "../../include/vlfm_amd.h"
+#include "mfma.h"
 #include "profile.h"
 #include "status.h"
 
 namespace vlfm {
 namespace conv {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-using lds_ptr = __attribute__((address_space(3))) unsigned char*;
-using gbl_ptr = const __attribute__((address_space(1))) unsigned char*;
 
 constexpr int GK = 64;             // channels per K-tile
 constexpr int ROWB = GK * 2;       // bytes per staged row
@@ -70,14 +65,9 @@ __global__ __launch_bounds__(512) void conv_nhwc_kernel(ConvArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave % WAVES_M, wn = wave / WAVES_M;
-    // XCD-aware tile order (as in gemm_f16.hip): every XCD works on a contiguous range of tiles, n fastest, so that the tiles sharing
+    // XCD-aware tile order (as in gemm_f32.hip): every XCD works on a contiguous range of tiles, n fastest, so that the tiles sharing
     // an activation panel (and, for 3x3 layers, the image rows above and below it) meet in one L2
-    const int nwg = a.tiles_m * a.tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_contiguous(blockIdx.x, a.tiles_m * a.tiles_n);
     const int tm = bid / a.tiles_n, tn = bid - tm * a.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     const int Ktot = GEN ? (a.taps * a.Cin + GK - 1) / GK * GK : a.taps * a.Cin;   // filter row stride
@@ -105,7 +95,7 @@ __global__ __launch_bounds__(512) void conv_nhwc_kernel(ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < WCH; j++) {
         const int r = (wave * WCH + j) * 8 + sub;
-        w_off[j] = min(n0 + r, a.Cout - 1) * Ktot + (p ^ ((r >> 1) & 7)) * 8;
+        w_off[j] = min(n0 + r, a.Cout - 1) * Ktot + (swz128(r, p) >> 1);      // (elements: 8 per 16-byte slot)
     }
 
     const int cin8 = a.Cin >> 3;
@@ -147,12 +137,12 @@ __global__ __launch_bounds__(512) void conv_nhwc_kernel(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < FA; i++) {
             const int R = wn * WN + i * 16 + r16;
-            fa[i] = *reinterpret_cast<const half8*>(smem + buf + R * ROWB + ((s ^ ((R >> 1) & 7)) << 4));
+            fa[i] = *reinterpret_cast<const half8*>(smem + buf + R * ROWB + swz128(R, s));
         }
 #pragma unroll
         for (int j = 0; j < FB; j++) {
             const int R = wm * WM + j * 16 + r16;
-            fb[j] = *reinterpret_cast<const half8*>(smem + buf + WOPER + R * ROWB + ((s ^ ((R >> 1) & 7)) << 4));
+            fb[j] = *reinterpret_cast<const half8*>(smem + buf + WOPER + R * ROWB + swz128(R, s));
         }
     };
 
@@ -170,12 +160,12 @@ __global__ __launch_bounds__(512) void conv_nhwc_kernel(ConvArgs a) {
     };
 
     stage(0, 0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0)
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (NT > 1) stage(BUF, 1);
     read_frags(0, 0, fa0, fb0);
-    __builtin_amdgcn_s_waitcnt(0xC07F);     // lgkmcnt(0)
+    wait_lgkmcnt0();
 
     for (int t = 0; t < NT; t++) {
         const int cur = (t & 1) * BUF;
@@ -183,9 +173,9 @@ __global__ __launch_bounds__(512) void conv_nhwc_kernel(ConvArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         mma(fa0, fb0);
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0xC07F);                // every LDS read of tile t by this wavefront has returned
+        wait_lgkmcnt0();                                   // every LDS read of tile t by this wavefront has returned
         if (t + 1 < NT) {
-            __builtin_amdgcn_s_waitcnt(0x0F70);            // ... and its share of tile t + 1 has landed
+            wait_vmcnt<0>();                               // ... and its share of tile t + 1 has landed
             __builtin_amdgcn_s_barrier();                  // ... for everybody: buffer `cur` is free, the other one is complete
             asm volatile("" ::: "memory");
             if (t + 2 < NT) stage(cur, t + 2);
@@ -194,7 +184,7 @@ __global__ __launch_bounds__(512) void conv_nhwc_kernel(ConvArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         mma(fa1, fb1);
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        wait_lgkmcnt0();
     }
     __builtin_amdgcn_s_barrier();   // every wavefront is done with the operand buffers: the epilogue staging aliases them
     asm volatile("" ::: "memory");
@@ -224,7 +214,7 @@ __global__ __launch_bounds__(512) void conv_nhwc_kernel(ConvArgs a) {
             *reinterpret_cast<half4*>(stg + (j * 16 + c16) * EPI_ROW + nl * 2) = h;
         }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // wavefront-private region: no workgroup barrier needed
+    wait_lgkmcnt0();   // wavefront-private region: no workgroup barrier needed
     constexpr int CHUNKS = WN / 8, ROWS_PER_IT = 64 / CHUNKS, ITS = WM / ROWS_PER_IT;
     const int rsub = lane / CHUNKS, chunk = lane % CHUNKS;
     uint4 v[ITS];

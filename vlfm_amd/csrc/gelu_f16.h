@@ -1,4 +1,4 @@
-// GELU of the f16 GEMM epilogues (csrc/gemm_f16.hip): scalar form and the packed-f32 form the kernels use.
+// Exact (erf) GELU of the GEMM epilogues: the scalar form (csrc/gemm_f32.hip) and the packed-f32 form (csrc/gemm_f16.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 namespace vlfm {

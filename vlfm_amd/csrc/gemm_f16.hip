@@ -12,8 +12,8 @@
 //     groups: conflict-free, while the 8 lanes of a row still read one whole 128-byte line of global memory.
 //   * two LDS buffers (128 KB, one workgroup per CU, two wavefronts per SIMD).
 //   * operand roles are swapped (A-operand = W rows, B-operand = X rows): a lane then holds 4 CONSECUTIVE n of one m, i.e.
-//     8 contiguous bytes of the output row after conversion; the epilogue transposes through LDS (row stride 272 B:
-//     conflict-free 8-byte writes, 16-byte reads) and stores 256-byte row segments with 16 B per lane.
+//     8 contiguous bytes of the output row after conversion; the epilogue transposes through LDS (row stride 144 B:
+//     conflict-free 8-byte writes, 16-byte reads) and stores 128-byte row segments with 16 B per lane.
 //   * the schedule is a PING-PONG between the two wavefronts of a SIMD in the 8-phase form (Gemm8p: four phases of 16 MFMAs per K-tile,
 //     half-tile staging, counted vmcnt waits) as a PERSISTENT kernel (gemm_f16_8pp_kernel: one workgroup per CU walks the tile list,
 //     the next tile's first K-tile is requested before the epilogue, the stores drain under the next tile) with the GELU in packed
@@ -22,33 +22,25 @@
 //     tree (git history: round 5; their numbers: DESIGN.md section 6c / 6g).
 // Measured at 256 images (tools/gemm_f16_probe.py, tools/mlp_probe.py; DESIGN.md section 6c has the table): fc1 + GELU 1.11-1.16 ms
 // against 1.41-1.45 ms for hipBLASLt + the GELU pass on random data, 1.19 against 1.24 ms on the network's own activations; as a
-// plain GEMM 1.0-1.1 PFLOP/s, i.e. 5-10 % BELOW hipBLASLt -- so only the fused fc1 uses it (vlfm_amd/vlm/ops.py:linear_gelu).
+// plain GEMM 1.0-1.1 PFLOP/s, i.e. 5-10 % BELOW hipBLASLt.  Users (vlfm_amd/vlm/ops.py): the ViT block's fused fc1 by default
+// (linear_gelu); qkv, projection and fc2 when a block's hip_gemms selects them (linear_f16); and the Q-Former's cross-attention
+// K / V projection in the two-piece f32 form (linear_pair_f32, EPI_PAIR_F32).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/vlfm_amd.h"
 #include "gelu_f16.h"
+#include "mfma.h"
 #include "profile.h"
 #include "status.h"
 
 namespace vlfm {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-// s_waitcnt through the builtin (the compiler's own scoreboard sees it; beside inline-asm waits it re-waits for everything at
-// the loop head): simm16 = vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14]; 0xC07F = lgkmcnt(0), 0x0F70 =
-// vmcnt(0), 0x0F78 = vmcnt(8)
-
 constexpr int GB = 256;            // tile rows (both m and n)
 constexpr int GK = 64;             // K per tile
 constexpr int ROWB = GK * 2;       // bytes per staged row
-constexpr int OPER = GB * ROWB;    // bytes per operand tile (32 KB)
-constexpr int BUF = 2 * OPER;      // W tile + X tile
-constexpr int EPI_ROW = 272;       // epilogue staging row stride (128 n x 2 B + 16)
-constexpr int EPI_WAVE = 64 * EPI_ROW;
-constexpr int GEMM_LDS = 8 * EPI_WAVE > 2 * BUF ? 8 * EPI_WAVE : 2 * BUF;
+constexpr int SLOT = 128 * ROWB;   // half an operand tile: 16 KB
+constexpr int KBUF = 4 * SLOT;     // one K-tile of both operands: 64 KB
 enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_ACCUM = 2,     // 2: C += X . W^T (+ bias): the residual-stream GEMMs (projection, fc2)
        EPI_PAIR_F32 = 3 };   // 3: W holds the two f16 pieces of an f32 weight, interleaved by 64-channel blocks; f32 block-major result
 
@@ -59,56 +51,48 @@ struct GemmArgs {
     _Float16* c;           // [M][N]
     int M, N, K;
     int tiles_m, tiles_n;
-    int group_m;          // tile order of the ping-pong kernel: m-tiles per group (1 = plain n-fastest order)
-    int split_ragged;     // persistent kernel: split the tiles of a ragged last round into n-halves (the launcher sets 1)
+    int group_m;          // tile order: m-tiles per group (1 = plain n-fastest order)
 };
-
-using lds_ptr = __attribute__((address_space(3))) unsigned char*;
-using gbl_ptr = const __attribute__((address_space(1))) unsigned char*;
 
 // ------------------------------------------------------------------------------------------------ 8-phase schedule
 // The two wavefronts of a SIMD (w and w + 4) never do the same thing at the same time (wavefronts 4-7 run one barrier behind 0-3).
 // A K-tile is FOUR phases of 16 MFMAs (one quadrant of the wavefront's 128 x 64 accumulator block each) instead of
 // two of 32, an operand tile is staged as two HALF-tiles, one half-tile (2 global_load_lds per wavefront) per phase, and the loads
-// are never drained inside the loop: ONE counted s_waitcnt vmcnt(4) per K-tile leaves the two half-tiles issued last in flight across
-// every barrier (the guide's 256^2 8-phase template; a schedule that waits vmcnt(0) once per K-tile needs every load of the next tile to land
-// inside ~3 phases of the current one, with the wait on the critical path of all 8 wavefronts).
+// are never drained inside the loop: two counted waits per K-tile (vmcnt(8) in phase 3, vmcnt(4) in phase 4) leave the half-tiles
+// issued last in flight across every barrier (the guide's 256^2 8-phase template; a schedule that waits vmcnt(0) once per K-tile
+// needs every load of the next tile to land inside ~3 phases of the current one, with the wait on the critical path of all 8
+// wavefronts).
 //
 // LDS: two K-tile buffers of four 16 KB slots, in the order the phases need them:
-//     slot 0 = Q_H0   X rows {wm * 64 + [ 0, 32)}  for the four wm      read in phase 1 (4 ds_read_b128 per wavefront)
+//     slot 0 = Q_H0   X rows {wm * 64 + [ 0, 32)}  for the four wm      read in phase 4 of the tile BEFORE (4 ds_read_b128 each)
 //     slot 1 = P_H0   W rows {wn * 128 + [ 0, 64)} for the two wn       read in phase 1 (8)
 //     slot 2 = Q_H1   X rows {wm * 64 + [32, 64)}                       read in phase 2 (4)
 //     slot 3 = P_H1   W rows {wn * 128 + [64,128)}                      read in phase 3 (8)
 //   (a "half" is the same half of EVERY wavefront's rows, so one slot serves all eight wavefronts in one phase.)
-// Quadrants: phase 1 (P_H0, Q_H0), phase 2 (P_H0, Q_H1), phase 3 (P_H1, Q_H1), phase 4 (P_H1, Q_H0): one new fragment set per phase,
-// none in phase 4; P fragments 32 VGPRs, Q_H0 and Q_H1 16 each.
+// Quadrants: phase 1 (P_H0, Q_H0), phase 2 (P_H0, Q_H1), phase 3 (P_H1, Q_H1), phase 4 (P_H1, Q_H0): one new fragment set per phase
+// (phase 4: Q_H0 of the next tile, into the other of its two register sets); P fragments 32 VGPRs, Q_H0 2 x 16, Q_H1 16.
 // Staging while tile t (buffer b) is computed:    phase 1: slot 2 of tile t + 1 (buffer b ^ 1)   phase 2: slot 3 of tile t + 1
 //                                                 phase 3: slot 0 of tile t + 2 (buffer b)       phase 4: slot 1 of tile t + 2
-//   WAR: a slot is re-staged >= 2 phases after the phase that read it last (slot 0 / 1: read in 1, staged in 3 / 4; slot 2: read in
-//        2 of tile t - 1, staged in 1 of tile t; slot 3: read in 3, staged in 2), and every wavefront retires its reads of phase p
-//        (lgkmcnt(0)) right behind the first barrier of phase p -- the late group one barrier later, still before phase p + 2.
+//   WAR: a slot is re-staged >= 2 phases after the phase that read it last (slot 0: read in 4 of tile t - 1, staged in 3 of tile
+//        t; slot 1: read in 1, staged in 4; slot 2: read in 2 of tile t - 1, staged in 1 of tile t; slot 3: read in 3, staged in
+//        2), and every wavefront retires its reads of phase p (lgkmcnt(0)) right behind the first barrier of phase p -- the late
+//        group one barrier later, still before phase p + 2.
 //   RAW: the wait of phase 4 -- before that phase's FIRST barrier -- leaves only the 4 loads of phases 3 and 4 (tile t + 2) in flight:
 //        tile t + 1 is complete as far as this wavefront's shares go; the early group reads it two barriers later, the late group
 //        three, and by then every wavefront has executed its own wait (the late group's sits one barrier behind the early group's).
+//        Slot 0 of tile t + 1 is read one phase earlier, so it has a wait of its own: vmcnt(8) in phase 3, again in front of the
+//        phase's first barrier and two barriers ahead of the read.
 // (Round 5 instrumented this schedule with per-workgroup and per-barrier clock stamps -- tools/gemm_stamp_probe.py of that tree,
 // profiles/r05_gemm_stamps.txt; the instrumentation left with the one-tile kernel it was written for.)
-template <int EPI, int BAL, int SYNC = 2>
 struct Gemm8p {
-    static constexpr int SLOT = 128 * ROWB;      // 16 KB
-    static constexpr int KBUF = 4 * SLOT;        // one K-tile: 64 KB
-
     const GemmArgs& a;
     lds_ptr lds;
     const unsigned char* smem;
     int wave, lane;
-    bool half;                  // half tile: at most 128 valid W rows (the last n-tile of N = 1408 / 4224).  The two wavefront groups
-                                // then take 64 rows each (P_H0 only) and phases 3 and 4 carry no work -- with the full-tile mapping
-                                // one group would own all 128 rows, the other none, and the ping-pong would degenerate to "read, then
-                                // compute" at three quarters of a full tile's time for half the work
     bool active;                // this wavefront's W rows are not all beyond N
     uint32_t voff[4][2];        // per slot and chunk: byte offset of this lane's 16 B inside the operand, without the K-tile term
     uint32_t rdP[2], rdQ[2];    // fragment read offsets inside a slot, by kk (the swizzle turns kk into an XOR of 64 B)
-    half8 fp[4][2], fq0[BAL ? 2 : 1][2][2], fq1[2][2];   // BAL: Q_H0 of the NEXT tile is read in phase 4 into the other set
+    half8 fp[4][2], fq0[2][2][2], fq1[2][2];   // fq0: two sets, Q_H0 of the NEXT tile is read in phase 4 into the other one
     floatx4 acc[8][4];
 
     __device__ Gemm8p(const GemmArgs& a_, unsigned char* smem_, int m0, int n0) : a(a_), lds((lds_ptr)smem_), smem(smem_) {
@@ -116,12 +100,11 @@ struct Gemm8p {
         lane = tid & 63;
         wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         const int wn = wave >> 2, wm = wave & 3;
-        half = false;   // (half-tile mode: measured, no gain -- see tile())
-        active = n0 + wn * (half ? 64 : 128) < a.N;
+        active = n0 + wn * 128 < a.N;
         offsets(m0, n0, voff);
-        const int r16 = lane & 15, swz = (r16 >> 1) & 7, s0 = lane >> 4;
-        const uint32_t bp = (uint32_t)(wn * 64 + r16) * ROWB + (uint32_t)((s0 ^ swz) << 4);
-        const uint32_t bq = (uint32_t)(wm * 32 + r16) * ROWB + (uint32_t)((s0 ^ swz) << 4);
+        const int r16 = lane & 15, s0 = lane >> 4;      // (rows wn * 64 and wm * 32 are multiples of 16: the swizzle sees r16 alone)
+        const uint32_t bp = (uint32_t)(wn * 64 + r16) * ROWB + (uint32_t)swz128(r16, s0);
+        const uint32_t bq = (uint32_t)(wm * 32 + r16) * ROWB + (uint32_t)swz128(r16, s0);
         rdP[0] = bp; rdP[1] = bp ^ 64u;
         rdQ[0] = bq; rdQ[1] = bq ^ 64u;
         zero_acc();
@@ -144,7 +127,7 @@ struct Gemm8p {
             for (int k = 0; k < 2; k++) {
                 fq1[g][k] = z;
 #pragma unroll
-                for (int q = 0; q < (BAL ? 2 : 1); q++) fq0[q][g][k] = z;
+                for (int q = 0; q < 2; q++) fq0[q][g][k] = z;
             }
     }
     // staging offsets of this lane for the tile at (m0, n0)
@@ -153,13 +136,13 @@ struct Gemm8p {
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             const int rho = (wave * 2 + j) * 8 + sub;            // row inside the slot
-            const int s = p ^ ((rho >> 1) & 7);                  // the 16-byte slot of the row this lane FETCHES (lands at p)
+            const uint32_t sb = (uint32_t)swz128(rho, p);        // the 16 bytes of the row this lane FETCHES (they land at slot p)
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const int rq = min(m0 + (rho >> 5) * 64 + h * 32 + (rho & 31), a.M - 1);
-                const int rp = min(n0 + (half ? rho + h * 128 : (rho >> 6) * 128 + h * 64 + (rho & 63)), a.N - 1);
-                vo[2 * h][j] = (uint32_t)rq * (uint32_t)a.K * 2u + (uint32_t)s * 16u;
-                vo[2 * h + 1][j] = (uint32_t)rp * (uint32_t)a.K * 2u + (uint32_t)s * 16u;
+                const int rp = min(n0 + (rho >> 6) * 128 + h * 64 + (rho & 63), a.N - 1);
+                vo[2 * h][j] = (uint32_t)rq * (uint32_t)a.K * 2u + sb;
+                vo[2 * h + 1][j] = (uint32_t)rp * (uint32_t)a.K * 2u + sb;
             }
         }
     }
@@ -209,44 +192,41 @@ struct Gemm8p {
     }
     // [fragments + staging issued by the caller] | barrier | fragments have arrived | 16 MFMAs | barrier
     template <int PI, int QJ>
-    __device__ inline void compute(const half8 (&fq)[2][2], bool work = true) {
+    __device__ inline void compute(const half8 (&fq)[2][2]) {
         bar();
-        __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0): this phase's reads are in registers -- and out of the slot
+        wait_lgkmcnt0();          // this phase's reads are in registers -- and out of the slot
         __builtin_amdgcn_sched_barrier(0);
-        if (active && work) {
+        if (active) {
             __builtin_amdgcn_s_setprio(1);
             mma<PI, QJ>(fq);
             __builtin_amdgcn_s_setprio(0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        // SYNC 2: a second barrier closes the phase, and the late group runs one barrier behind: strict alternation of the two
-        // wavefronts of a SIMD between "read" and "MFMA".  SYNC 1: ONE barrier per phase and no stagger -- the two wavefronts of a
-        // SIMD leave the barrier together, one gets the matrix pipe first, the other follows, and each reads its next fragments
-        // when it is done: the offset re-creates itself every phase.  Same hazards: a slot is re-staged two barriers after the
-        // barrier that followed its last read (whose lgkmcnt(0) every wavefront executes before it can arrive at the next one),
-        // and the counted vmcnt wait precedes the barrier in front of the first read.
-        if (SYNC == 2) bar();
+        // a second barrier closes the phase, and the late group runs one barrier behind: strict alternation of the two wavefronts
+        // of a SIMD between "read" and "MFMA"
+        bar();
     }
 
     // K-tile t in buffer B (compile-time: the buffer term of every ds_read offset is an immediate).
-    // BAL = 1 ("balanced"): the Q_H0 fragments of tile t + 1 are read in phase 4 of tile t (which has no reads of its own) instead
-    // of in phase 1 of tile t + 1 (which has the 8 P reads): 8 / 4 / 8 / 4 ds_read_b128 per phase instead of 12 / 4 / 8 / 0.  Slot 0 of
-    // tile t + 1 therefore has to be complete one phase earlier: a second counted wait, vmcnt(8), in phase 3.
-    // Measured and dropped (round 5, profiles/r05_gemm_*): a counted wait in EVERY phase (vmcnt(8): each half-tile gets four
-    // phases to land instead of two to five) -- no gain on the N = 4224 / 6144 shapes, 7 % slower on fc2: the K-tile time is not a
-    // memory-latency effect (see the barrier stamps in DESIGN.md); a half-tile mode that splits the 128 valid W rows of the last
-    // n-tile over both wavefront groups and leaves phases 3 and 4 empty -- no gain either, the barriers cost what they cost.
+    // The read schedule is balanced: the Q_H0 fragments of tile t + 1 are read in phase 4 of tile t (which has no reads of its
+    // own), not in phase 1 of tile t + 1 (which has the 8 P reads): 8 / 4 / 8 / 4 ds_read_b128 per phase.  Slot 0 of tile t + 1
+    // therefore has to be complete one phase earlier: a second counted wait, vmcnt(8), in phase 3.
+    // Measured and dropped (round 5, profiles/r05_gemm_*):
+    //   * Q_H0 read in phase 1 of its own tile (12 / 4 / 8 / 0 reads per phase, one counted wait per K-tile): 1-2 % slower.
+    //   * ONE barrier per phase without the stagger (the two wavefronts of a SIMD leave the barrier together and one follows the
+    //     other through the matrix pipe): qkv 712 against 685 us -- the second wavefront's reads stand behind its MFMAs.
+    //   * a half-tile mode that splits the 128 valid W rows of the last n-tile of N = 1408 / 4224 over both wavefront groups and
+    //     leaves phases 3 and 4 empty: no gain, the barriers cost what they cost.
+    //   * a counted wait in EVERY phase (vmcnt(8): each half-tile gets four phases to land instead of two to five) -- no gain on
+    //     the N = 4224 / 6144 shapes, 7 % slower on fc2: the K-tile time is not a memory-latency effect (see the barrier stamps in
+    //     DESIGN.md).
     template <int B>
     __device__ inline void tile(int t, int NT) {
-        constexpr int QS = BAL ? B : 0;
         // ---- phase 1
-        if (active) {
-            if (!BAL) read_q<B, 0>(fq0[QS]);
-            read_p<B, 1>();
-        }
+        if (active) read_p<B, 1>();
         __builtin_amdgcn_sched_barrier(0);
         if (t + 1 < NT) stage<2>(B ^ 1, t + 1);
-        compute<0, 0>(fq0[QS]);
+        compute<0, 0>(fq0[B]);
         // ---- phase 2
         if (active) read_q<B, 2>(fq1);
         __builtin_amdgcn_sched_barrier(0);
@@ -257,21 +237,21 @@ struct Gemm8p {
         __builtin_amdgcn_sched_barrier(0);
         if (t + 2 < NT) {
             stage<0>(B, t + 2);
-            if (BAL) __builtin_amdgcn_s_waitcnt(0x0F78);     // vmcnt(8): slot 0 of tile t + 1 has landed (slots 1-3 of t + 1 and
-        } else if (BAL) {                                     //           slot 0 of t + 2 may still be in flight)
-            __builtin_amdgcn_s_waitcnt(0x0F76);              // vmcnt(6): no slot 0 of t + 2 behind it
+            wait_vmcnt<8>();      // slot 0 of tile t + 1 has landed (slots 1-3 of t + 1 and slot 0 of t + 2 may still be in flight)
+        } else {
+            wait_vmcnt<6>();      // no slot 0 of t + 2 behind it
         }
         compute<1, 1>(fq1);
         // ---- phase 4: tile t + 1 must be complete when this phase's first barrier is passed
-        if (BAL && active && t + 1 < NT) read_q<B ^ 1, 0>(fq0[BAL ? (B ^ 1) : 0]);
+        if (active && t + 1 < NT) read_q<B ^ 1, 0>(fq0[B ^ 1]);
         __builtin_amdgcn_sched_barrier(0);
         if (t + 2 < NT) {
             stage<1>(B, t + 2);
-            __builtin_amdgcn_s_waitcnt(0x0F74);      // vmcnt(4): only the loads of phases 3 and 4 (tile t + 2) stay in flight
+            wait_vmcnt<4>();      // only the loads of phases 3 and 4 (tile t + 2) stay in flight
         } else {
-            __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): nothing newer was issued
+            wait_vmcnt<0>();      // nothing newer was issued
         }
-        compute<1, 0>(fq0[QS]);
+        compute<1, 0>(fq0[B]);
     }
 };
 
@@ -318,14 +298,16 @@ __host__ __device__ inline void tile_of(const GemmArgs& a, int bid, int& tm, int
 //     EPI_ACCUM and the prefetch: everything this wavefront asked for) and the 16 stores back to back;
 //   * the stores drain under the next tile's first phases: on gfx9 they share vmcnt with the LDS-DMA loads and retire IN ISSUE ORDER
 //     with them (the assumption every counted wait of this file rests on; tests/test_gemm_f16_gpu.py's 30-repeat bitwise screen is
-//     what covers it), so the first counted wait behind them -- vmcnt(8) in phase 3 of K-tile 0, BAL form -- also waits for all 16
+//     what covers it), so the first counted wait behind them -- vmcnt(8) in phase 3 of K-tile 0 -- also waits for all 16
 //     stores of the previous tile; nothing waits for them earlier.
 // After the epilogue one barrier (every wavefront's staging reads are over and its share of K-tile 0 is in LDS), then slots 0 / 1
 // of K-tile 1 are requested and the phases start; the wait of phase 4 of K-tile 0 covers them as it does in the steady state.
 constexpr int EPI2_ROW = 144;                 // 64 n x 2 B + 16
 constexpr int EPI2_WAVE = 64 * EPI2_ROW;      // 9216 B; 8 wavefronts: 72 KB behind buffer 0
-constexpr int PBIAS_OFF = GEMM_LDS;           // 256 bias halves behind everything else
-constexpr int GEMM_LDS_P = GEMM_LDS + 512;
+constexpr int PBIAS_OFF = KBUF + 8 * EPI2_WAVE;      // 256 bias halves behind the staging rows
+constexpr int GEMM_LDS = PBIAS_OFF + 512;
+static_assert(PBIAS_OFF >= 2 * KBUF, "the bias lies behind both operand buffers");
+static_assert(GEMM_LDS == 139776, "LDS per workgroup: 2 x 64 KB of operands, 8 KB more of staging rows, 512 B of bias");
 
 // (plain vector values, not HIP's uint4 struct: its copies are memcpy calls between address spaces that pin the arrays in scratch)
 __device__ __forceinline__ half8 add_half8(half8 a, const half8 b) {       // 8 halves + 8 halves, summed in f32
@@ -349,7 +331,7 @@ __device__ __forceinline__ void epi2_pass(const floatx4 (&acc)[8][4], const half
             *reinterpret_cast<half4*>(stg + (j * 16 + c16) * EPI2_ROW + (ii * 16 + g4) * 2) = hv;
         }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // wavefront-private rows: no workgroup barrier
+    wait_lgkmcnt0();   // wavefront-private rows: no workgroup barrier
 #pragma unroll
     for (int it = 0; it < 8; it++) v[it] = *reinterpret_cast<const half8*>(stg + (it * 8 + rsub) * EPI2_ROW + chunk * 16);
 }
@@ -379,7 +361,7 @@ __device__ __forceinline__ void epi_pair_pass(const floatx4 (&acc)[8][4], const 
             *reinterpret_cast<floatx4*>(stg + (j * 16 + c16) * EPI2_ROW + (i2 * 16 + g4) * 4) = r;
         }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // wavefront-private rows: no workgroup barrier
+    wait_lgkmcnt0();   // wavefront-private rows: no workgroup barrier
 #pragma unroll
     for (int it = 0; it < 8; it++) v[it] = *reinterpret_cast<const floatx4*>(stg + (it * 8 + rsub) * EPI2_ROW + chunk * 16);
 }
@@ -398,9 +380,9 @@ __device__ __forceinline__ void stage_bias(const GemmArgs& a, lds_ptr lds, int w
 // tile's time on twice as many workgroups.  item -> (list position of the tile, half or -1)
 struct WorkList {
     int nwg, first_split, nitems;
-    __host__ __device__ WorkList(int nwg_, int grid, bool allow = true) : nwg(nwg_) {
+    __host__ __device__ WorkList(int nwg_, int grid) : nwg(nwg_) {
         const int left = nwg > grid ? nwg % grid : 0;
-        const bool split = allow && left > 0 && 2 * left <= grid;
+        const bool split = left > 0 && 2 * left <= grid;
         first_split = split ? nwg - left : nwg;
         nitems = nwg + (split ? left : 0);
     }
@@ -413,40 +395,39 @@ struct WorkList {
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm_f16_8pp_kernel(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using G = Gemm8p<EPI, 1, 2>;
     const int stride = gridDim.x;
-    const WorkList work(a.tiles_m * a.tiles_n, stride, a.split_ragged != 0);
+    const WorkList work(a.tiles_m * a.tiles_n, stride);
     int bid = blockIdx.x;        // work item
     int tm, tn, pos, half;
     work.item(bid, pos, half);
     tile_of(a, pos, tm, tn);
     int m0 = tm * GB, n0 = tn * GB;
-    G g(a, smem, m0, n0);
+    Gemm8p g(a, smem, m0, n0);
     g.active = g.active && (half < 0 || half == (g.wave >> 2));
     const int NT = a.K / GK;
     const int wave = g.wave, lane = g.lane, wn = wave >> 2, wm = wave & 3, late = wn;
     const int g4 = (lane >> 4) * 4, c16 = lane & 15;      // accumulator layout: 4 consecutive n at g4, m = c16
     const int rsub = lane >> 3, chunk = lane & 7;         // store layout: 8 rows x 8 chunks of 16 B per instruction
-    unsigned char* stg = smem + G::KBUF + wave * EPI2_WAVE;
+    unsigned char* stg = smem + KBUF + wave * EPI2_WAVE;
     const bool has_bias = a.bias != nullptr;
     // bias[n0 .. n0 + 256) -> LDS behind the staging rows: one 16-byte LDS-DMA load by lanes 0-31 of wavefront 0.  Issued BEFORE the
     // tile's first operand loads, so every counted wait that covers those covers it
     stage_bias(a, g.lds, wave, lane, n0);
-    g.template stage<0>(0, 0); g.template stage<1>(0, 0); g.template stage<2>(0, 0); g.template stage<3>(0, 0);
+    g.stage<0>(0, 0); g.stage<1>(0, 0); g.stage<2>(0, 0); g.stage<3>(0, 0);
     if (NT > 1) {
-        g.template stage<0>(1, 1); g.template stage<1>(1, 1);
-        __builtin_amdgcn_s_waitcnt(0x0F74);
+        g.stage<0>(1, 1); g.stage<1>(1, 1);
+        wait_vmcnt<4>();
     } else {
-        __builtin_amdgcn_s_waitcnt(0x0F70);
+        wait_vmcnt<0>();
     }
     g.bar();
     for (;;) {
         g.kill_fragments();
         if (late) g.bar();
-        if (g.active) g.template read_q<0, 0>(g.fq0[0]);
+        if (g.active) g.read_q<0, 0>(g.fq0[0]);
         for (int t = 0; t < NT; t += 2) {
-            g.template tile<0>(t, NT);
-            if (t + 1 < NT) g.template tile<1>(t + 1, NT);
+            g.tile<0>(t, NT);
+            if (t + 1 < NT) g.tile<1>(t + 1, NT);
         }
         if (!late) g.bar();       // behind it nobody reads the operand buffers any more
 
@@ -479,8 +460,8 @@ __global__ __launch_bounds__(512) void gemm_f16_8pp_kernel(GemmArgs a) {
         const int m1 = tm * GB, n1 = tn * GB;
         uint32_t von[4][2];
         g.offsets(m1, n1, von);
-        g.template stage_at<0>(0, 0, von); g.template stage_at<1>(0, 0, von);
-        g.template stage_at<2>(0, 0, von); g.template stage_at<3>(0, 0, von);
+        g.stage_at<0>(0, 0, von); g.stage_at<1>(0, 0, von);
+        g.stage_at<2>(0, 0, von); g.stage_at<3>(0, 0, von);
         __builtin_amdgcn_sched_barrier(0);
         half8 old[EPI == EPI_ACCUM ? 16 : 1];       // the residual stream's row segments: used behind the vmcnt(0) below
         if (EPI == EPI_ACCUM) {
@@ -502,7 +483,7 @@ __global__ __launch_bounds__(512) void gemm_f16_8pp_kernel(GemmArgs a) {
             epi_pair_pass<0>(g.acc, biasf, stg, g4, c16, rsub, chunk, p0);
             epi_pair_pass<1>(g.acc, biasf, stg, g4, c16, rsub, chunk, p1);
             __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0x0F70);   // this wavefront's share of the next K-tile 0 is in LDS (no store is in flight yet)
+            wait_vmcnt<0>();   // this wavefront's share of the next K-tile 0 is in LDS (no store is in flight yet)
             __builtin_amdgcn_sched_barrier(0);
             const int nblk = n0 + wn * 128;       // first of the block's 128 interleaved W rows; the block is nblk / 128
             if (store && nblk + 128 <= a.N) {
@@ -531,7 +512,7 @@ __global__ __launch_bounds__(512) void gemm_f16_8pp_kernel(GemmArgs a) {
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0x0F70);       // this wavefront's share of the next K-tile 0 is in LDS (no store is in flight yet)
+        wait_vmcnt<0>();       // this wavefront's share of the next K-tile 0 is in LDS (no store is in flight yet)
         __builtin_amdgcn_sched_barrier(0);
         {
             const int n = n0 + wn * 128 + chunk * 8;
@@ -559,7 +540,7 @@ __global__ __launch_bounds__(512) void gemm_f16_8pp_kernel(GemmArgs a) {
         g.zero_acc();
         g.bar();      // staging rows are free again (they lie in buffer 1), K-tile 0 is complete for everybody
         stage_bias(a, g.lds, wave, lane, n0);
-        if (NT > 1) { g.template stage<0>(1, 1); g.template stage<1>(1, 1); }
+        if (NT > 1) { g.stage<0>(1, 1); g.stage<1>(1, 1); }
     }
 }
 
@@ -578,7 +559,7 @@ template <int EPI>
 static int launch_gemm(const GemmArgs& a, hipStream_t stream) {
     const void* fn = reinterpret_cast<const void*>(gemm_f16_8pp_kernel<EPI>);
     static LdsOptIn optp;
-    if (!optp.ensure(fn, GEMM_LDS_P)) return fail(VLFM_ERR_HIP, "gemm_f16_nt: cannot opt in to the LDS size");
+    if (!optp.ensure(fn, GEMM_LDS)) return fail(VLFM_ERR_HIP, "gemm_f16_nt: cannot opt in to the LDS size");
     const int n_cu = device_cu_count() & ~7;       // per device (status.h): the grid and the XCD walk follow the CURRENT device
     const int nwg = a.tiles_m * a.tiles_n;
     const dim3 grid(nwg < n_cu ? nwg : n_cu), block(512);
@@ -586,7 +567,7 @@ static int launch_gemm(const GemmArgs& a, hipStream_t stream) {
     // (3 = the Q-Former's cross-attention K / V projection, once per forward)
     VLFM_TIMED(EPI == EPI_BIAS ? "gemm_f16_8pp_kernel<0>" : EPI == EPI_BIAS_GELU ? "gemm_f16_8pp_kernel<1>" :
                EPI == EPI_ACCUM ? "gemm_f16_8pp_kernel<2>" : "gemm_f16_8pp_kernel<3>", stream);
-    VLFM_KLAUNCH((gemm_f16_8pp_kernel<EPI>), grid, block, GEMM_LDS_P, stream, a);
+    VLFM_KLAUNCH((gemm_f16_8pp_kernel<EPI>), grid, block, GEMM_LDS, stream, a);
     return check_launch("gemm_f16_8pp_kernel");
 }
 
@@ -604,9 +585,8 @@ extern "C" int vlfm_gemm_f16_nt(const void* d_x, const void* d_w, const void* d_
     a.M = m; a.N = n; a.K = k;
     a.tiles_m = (m + GB - 1) / GB; a.tiles_n = (n + GB - 1) / GB;
     // tile order of the persistent walk: groups of 4 m-tiles on every ViT shape (probe: 2-8 within 1 %, 1 and 16+ behind); the
-    // tiles of a ragged last round are split into n-halves
+    // tiles of a ragged last round are split into n-halves (WorkList)
     a.group_m = 4;
-    a.split_ragged = 1;
     if (epilogue == 0) return launch_gemm<EPI_BIAS>(a, (hipStream_t)stream);
     if (epilogue == 1) return launch_gemm<EPI_BIAS_GELU>(a, (hipStream_t)stream);
     return launch_gemm<EPI_ACCUM>(a, (hipStream_t)stream);
@@ -632,7 +612,6 @@ extern "C" int vlfm_gemm_f16_pair_f32_nt(const void* d_x, const void* d_w_pair, 
     a.M = m; a.N = 2 * n_out; a.K = k;
     a.tiles_m = (m + GB - 1) / GB; a.tiles_n = (a.N + GB - 1) / GB;
     a.group_m = 4;
-    a.split_ragged = 1;
     return launch_gemm<EPI_PAIR_F32>(a, (hipStream_t)stream);
 }
 

@@ -31,16 +31,13 @@
 #include <stdlib.h>
 
 #include "../../include/vlfm_amd.h"
+#include "gelu_f16.h"
+#include "mfma.h"
 #include "profile.h"
 #include "status.h"
 
 namespace vlfm {
 namespace g32 {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 constexpr int TB = 128;            // tile rows (m and n)
 constexpr int TK = 32;             // floats of K per tile
@@ -66,31 +63,10 @@ struct Args {
     const _Float16* w_lo;
 };
 
-// exact-form GELU as in gemm_f16.hip (|gelu - f64| <= 2.8e-7)
-__device__ inline float gelu_erf(float v) {
-    const float u = fabsf(v);
-    float q = 2.834908400e-06f;
-    q = fmaf(q, u, -3.937762449e-05f);
-    q = fmaf(q, u, 1.861798810e-04f);
-    q = fmaf(q, u, 1.369373058e-04f);
-    q = fmaf(q, u, -7.063421421e-03f);
-    q = fmaf(q, u, 5.249617994e-02f);
-    q = fmaf(q, u, 4.592081904e-01f);
-    q = fmaf(q, u, 1.151105165e+00f);
-    const float e = __builtin_amdgcn_exp2f(-(q * u));
-    return fmaf(-0.5f * u, e, fmaxf(v, 0.0f));
-}
-
-using lds_ptr = __attribute__((address_space(3))) unsigned char*;
-using gbl_ptr = const __attribute__((address_space(1))) unsigned char*;
-
 __device__ inline void tile_of_block(const Args& a, int& tm, int& tn) {
-    // XCD-aware order: consecutive workgroup ids go round-robin over the 8 XCDs; give every XCD a contiguous range of tiles
-    // (n fastest) so that the tiles sharing an X row panel and the (small) W matrix meet in one L2
-    const int nwg = a.tiles_m * a.tiles_n;
-    int bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    // XCD-aware order: every XCD gets a contiguous range of tiles (n fastest) so that the tiles sharing an X row panel and the
+    // (small) W matrix meet in one L2
+    const int bid = xcd_contiguous(blockIdx.x, a.tiles_m * a.tiles_n);
     tm = bid / a.tiles_n;
     tn = bid - tm * a.tiles_n;
 }
@@ -102,10 +78,10 @@ __device__ inline void stage_tile(const Args& a, lds_ptr lds, int buf, int n0, i
     for (int j = 0; j < 4; j++) {
         const int chunk = wave * 4 + j;
         const int r = chunk * 8 + sub;
-        const int s = p ^ ((r >> 1) & 7);
+        const int s4 = swz128(r, p) >> 2;      // first of the 4 floats of the row this lane FETCHES (they land at slot p)
         const int rn = min(n0 + r, a.N - 1), rm = min(m0 + r, a.M - 1);
-        const float* gw = a.w + (size_t)rn * a.K + k0 + s * 4;
-        const float* gx = a.x + (size_t)rm * a.K + k0 + s * 4;
+        const float* gw = a.w + (size_t)rn * a.K + k0 + s4;
+        const float* gx = a.x + (size_t)rm * a.K + k0 + s4;
         const int dst = __builtin_amdgcn_readfirstlane(buf + chunk * 1024);
         __builtin_amdgcn_global_load_lds((gbl_ptr)gw, lds + dst, 16, 0, 0);
         __builtin_amdgcn_global_load_lds((gbl_ptr)gx, lds + dst + OPER, 16, 0, 0);
@@ -148,13 +124,13 @@ __device__ inline void store_tile(const Args& a, unsigned char* smem, const floa
                     if (SPLIT) t = fmaf(cross[i][j][g * 4 + e], 0x1p-11f, t);
                     t += b[e];
                     if (act == ACT_RELU) t = fmaxf(t, 0.f);
-                    else if (act == ACT_GELU) t = gelu_erf(t);
+                    else if (act == ACT_GELU) t = gelu_erf(t);      // (gelu_f16.h: |gelu - f64| <= 2.8e-7)
                     v[e] = t;
                 }
                 *reinterpret_cast<floatx4*>(stg + (j * 32 + c32) * EPI_ROW + nl * 4) = v;
             }
         }
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // wavefront-private area
+    wait_lgkmcnt0();   // wavefront-private area
     const int rsub = lane >> 4, chunk = lane & 15;
     const bool vec = (a.N & 3) == 0;      // rows of C / residual are 16-byte aligned
     // Round 5 (as in gemm_f16.hip): all 16 residual loads first, then all 16 LDS reads, then the stores -- the loop that loaded,
@@ -207,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_exact_kernel(Args a, int act)
             for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
 
     stage_tile(a, lds, 0, n0, m0, 0, wave, lane);
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
@@ -222,12 +198,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_exact_kernel(Args a, int act)
 #pragma unroll
             for (int i = 0; i < 2; i++) {
                 const int R = wn * 64 + i * 32 + r32;
-                fa[i] = *reinterpret_cast<const floatx4*>(smem + cur + R * ROWB + ((s ^ ((R >> 1) & 7)) << 4));
+                fa[i] = *reinterpret_cast<const floatx4*>(smem + cur + R * ROWB + swz128(R, s));
             }
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 const int R = wm * 64 + j * 32 + r32;
-                fb[j] = *reinterpret_cast<const floatx4*>(smem + cur + OPER + R * ROWB + ((s ^ ((R >> 1) & 7)) << 4));
+                fb[j] = *reinterpret_cast<const floatx4*>(smem + cur + OPER + R * ROWB + swz128(R, s));
             }
 #pragma unroll
             for (int q = 0; q < 4; q++)
@@ -237,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_exact_kernel(Args a, int act)
                     for (int j = 0; j < 2; j++)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][q], fb[j][q], acc[i][j], 0, 0, 0);
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // this wavefront's share of tile t + 1 has landed
+        wait_vmcnt<0>();                      // this wavefront's share of tile t + 1 has landed
         __builtin_amdgcn_s_barrier();         // ... everybody's, and everybody is done reading tile t
         asm volatile("" ::: "memory");
     }
@@ -266,22 +242,12 @@ __device__ inline void split4(const floatx4 v, half4& hi, half4& lo, bool& over)
     }
 }
 
-// NI = 32-row MFMA tiles of W per wavefront: 2 -> the 128 (n) x 128 (m) workgroup tile above, two workgroups per CU;
-// 4 -> a 256 (n) x 128 (m) tile (wavefronts of 128 x 64 = 4 x 2 MFMA tiles, 256 accumulator registers, ONE workgroup per CU): every
-// X tile is converted and staged for twice as many MFMAs (the conversion of X is repeated by every workgroup along n), and a k-step's
-// 12 fragment reads feed 24 MFMAs instead of 8 feeding 12 -- the LDS read rate, not the matrix pipe, bounds the small tile.
-template <int NI>
-struct SplitGeom {
-    static constexpr int TN = 64 * NI;               // workgroup tile along n (two wavefronts)
-    static constexpr int WOPER = TN * SROWB;         // bytes of one W plane tile
-    static constexpr int XO = 0, WO = 2 * SOPER;     // X hi | X lo | W hi | W lo
-    static constexpr int BUF = 2 * SOPER + 2 * WOPER;
-    static constexpr int LDS = 4 * EPI_WAVE > 2 * BUF ? 4 * EPI_WAVE : 2 * BUF;
-};
+// The 128 (n) x 128 (m) workgroup tile of the exact form: a k-step's 8 fragment reads feed 12 MFMAs, two workgroups per CU (the wider
+// tile that was measured and dropped: see the launcher).
+constexpr int XO = 0, WO = 2 * SOPER;  // X hi | X lo | W hi | W lo
+constexpr int LDS_SPLIT = 4 * EPI_WAVE > 2 * SBUF ? 4 * EPI_WAVE : 2 * SBUF;
 
-template <int NI>
-__device__ __forceinline__ void gemm_f32_split_body(const Args& a, int act) {
-    using G = SplitGeom<NI>;
+__global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(Args a, int act) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     lds_ptr lds = (lds_ptr)smem;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -289,12 +255,12 @@ __device__ __forceinline__ void gemm_f32_split_body(const Args& a, int act) {
     const int wn = wave >> 1, wm = wave & 1;
     int tm, tn;
     tile_of_block(a, tm, tn);
-    const int m0 = tm * TB, n0 = tn * G::TN;
+    const int m0 = tm * TB, n0 = tn * TB;
     const int NT = a.K / TK;
 
-    floatx16 acc[NI][2], crs[NI][2];
+    floatx16 acc[2][2], crs[2][2];
 #pragma unroll
-    for (int i = 0; i < NI; i++)
+    for (int i = 0; i < 2; i++)
 #pragma unroll
         for (int j = 0; j < 2; j++)
 #pragma unroll
@@ -319,59 +285,59 @@ __device__ __forceinline__ void gemm_f32_split_body(const Args& a, int act) {
             half4 hi, lo;
             split4(xr[u], hi, lo, over);
             const int off = r * SROWB + sslot(r, pc >> 1) + (pc & 1) * 8;
-            *reinterpret_cast<half4*>(smem + buf + G::XO + off) = hi;
-            *reinterpret_cast<half4*>(smem + buf + G::XO + SOPER + off) = lo;
+            *reinterpret_cast<half4*>(smem + buf + XO + off) = hi;
+            *reinterpret_cast<half4*>(smem + buf + XO + SOPER + off) = lo;
         }
     };
-    // W hi / lo: TN rows x 64 B per plane; one global_load_lds instruction covers 16 rows (4 lanes per row), NI per wavefront and plane
+    // W hi / lo: 128 rows x 64 B per plane; one global_load_lds instruction covers 16 rows (4 lanes per row), 2 per wavefront and plane
     auto stage_w = [&](int buf, int k0) {
         const int sub = lane >> 2, p = lane & 3;
 #pragma unroll
-        for (int j = 0; j < NI; j++) {
-            const int chunk = wave * NI + j;                // 16 rows each
+        for (int j = 0; j < 2; j++) {
+            const int chunk = wave * 2 + j;                 // 16 rows each
             const int r = chunk * 16 + sub;
             const int s = p ^ ((r >> 2) & 3);
             const int rn = min(n0 + r, a.N - 1);
             const size_t g = (size_t)rn * a.K + k0 + s * 8;
-            const int dst = __builtin_amdgcn_readfirstlane(buf + G::WO + chunk * 1024);
+            const int dst = __builtin_amdgcn_readfirstlane(buf + WO + chunk * 1024);
             __builtin_amdgcn_global_load_lds((gbl_ptr)(a.w_hi + g), lds + dst, 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_ptr)(a.w_lo + g), lds + dst + G::WOPER, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_ptr)(a.w_lo + g), lds + dst + SOPER, 16, 0, 0);
         }
     };
 
     load_x(0);
     stage_w(0, 0);
     put_x(0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    __builtin_amdgcn_s_waitcnt(0xC07F);
+    wait_vmcnt<0>();
+    wait_lgkmcnt0();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
     const int r32 = lane & 31, h = lane >> 5;
     for (int t = 0; t < NT; t++) {
-        const int cur = (t & 1) * G::BUF;
+        const int cur = (t & 1) * SBUF;
         if (t + 1 < NT) {
             load_x((t + 1) * TK);
-            stage_w(cur ^ G::BUF, (t + 1) * TK);
+            stage_w(cur ^ SBUF, (t + 1) * TK);
         }
 #pragma unroll
         for (int kk = 0; kk < 2; kk++) {
             const int s = kk * 2 + h;                      // 16 k per step: lanes 0-31 take k 0-7, lanes 32-63 k 8-15
-            half8 whi[NI], wlo[NI], xhi[2], xlo[2];
+            half8 whi[2], wlo[2], xhi[2], xlo[2];
 #pragma unroll
-            for (int i = 0; i < NI; i++) {
-                const int R = wn * 32 * NI + i * 32 + r32, o = cur + G::WO + R * SROWB + sslot(R, s);
+            for (int i = 0; i < 2; i++) {
+                const int R = wn * 64 + i * 32 + r32, o = cur + WO + R * SROWB + sslot(R, s);
                 whi[i] = *reinterpret_cast<const half8*>(smem + o);
-                wlo[i] = *reinterpret_cast<const half8*>(smem + o + G::WOPER);
+                wlo[i] = *reinterpret_cast<const half8*>(smem + o + SOPER);
             }
 #pragma unroll
             for (int j = 0; j < 2; j++) {
-                const int R = wm * 64 + j * 32 + r32, o = cur + G::XO + R * SROWB + sslot(R, s);
+                const int R = wm * 64 + j * 32 + r32, o = cur + XO + R * SROWB + sslot(R, s);
                 xhi[j] = *reinterpret_cast<const half8*>(smem + o);
                 xlo[j] = *reinterpret_cast<const half8*>(smem + o + SOPER);
             }
 #pragma unroll
-            for (int i = 0; i < NI; i++)
+            for (int i = 0; i < 2; i++)
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whi[i], xhi[j], acc[i][j], 0, 0, 0);
@@ -379,22 +345,15 @@ __device__ __forceinline__ void gemm_f32_split_body(const Args& a, int act) {
                     crs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo[i], xhi[j], crs[i][j], 0, 0, 0);
                 }
         }
-        if (t + 1 < NT) put_x(cur ^ G::BUF);      // (the other buffer: everybody left it before the previous barrier)
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        if (t + 1 < NT) put_x(cur ^ SBUF);      // (the other buffer: everybody left it before the previous barrier)
+        wait_vmcnt<0>();
+        wait_lgkmcnt0();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     }
     if (over && a.overflow) atomicOr(a.overflow, 1);
-    // epilogue: 64 (n) x 64 (m) per wavefront and pass through the wavefront's staging area
-#pragma unroll
-    for (int half = 0; half < NI / 2; half++)
-        store_tile<true>(a, smem, reinterpret_cast<const floatx16(&)[2][2]>(acc[2 * half]),
-                         reinterpret_cast<const floatx16(&)[2][2]>(crs[2 * half]), act, wave, 0, wm, lane, m0,
-                         n0 + wn * 32 * NI + half * 64);
+    store_tile<true>(a, smem, acc, crs, act, wave, wn, wm, lane, m0, n0);
 }
-
-__global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(Args a, int act) { gemm_f32_split_body<2>(a, act); }
 
 // f32 [rows][cols] -> hi / lo f16 planes (the weights, once per layer)
 __global__ void split_f32_kernel(const float* __restrict__ src, _Float16* __restrict__ hi, _Float16* __restrict__ lo, long long n,
@@ -449,13 +408,14 @@ extern "C" int vlfm_gemm_f32_nt(const float* d_x, const float* d_w, const float*
         VLFM_KLAUNCH(gemm_f32_exact_kernel, grid, block, LDS_EXACT, (hipStream_t)stream, a, activation);
         return check_launch("gemm_f32_exact_kernel");
     }
-    // (a 256-wide tile with one workgroup per CU -- gemm_f32_split_body<4>, 512 registers per wavefront -- was measured and is NOT
-    // dispatched: with one wavefront per SIMD nothing covers the barrier, the X conversion and the fragment reads between the MFMA
-    // groups: 145 / 177 / 141 TFLOP/s-equivalent on the encoder FFN / Swin stage-3 MLP / 256 -> 256 shapes against 186 / 223 / 180 for
-    // two 128-wide workgroups per CU, tools/gemm_f32_probe.py, profiles/r04_gemm_f32_probe_wide_tile.txt)
-    if (SplitGeom<2>::LDS > 64 * 1024 && !opt_split.ensure(reinterpret_cast<const void*>(gemm_f32_split_kernel), SplitGeom<2>::LDS))
+    // (a 256 (n) x 128 (m) tile with ONE workgroup per CU -- wavefronts of 128 x 64 = 4 x 2 MFMA tiles, 512 registers each, every X
+    // tile converted and staged for twice as many MFMAs, a k-step's 12 fragment reads feeding 24 MFMAs instead of 8 feeding 12 -- was
+    // measured and dropped: with one wavefront per SIMD nothing covers the barrier, the X conversion and the fragment reads between
+    // the MFMA groups: 145 / 177 / 141 TFLOP/s-equivalent on the encoder FFN / Swin stage-3 MLP / 256 -> 256 shapes against 186 /
+    // 223 / 180 for two 128-wide workgroups per CU, profiles/r04_gemm_f32_probe_wide_tile.txt)
+    if (LDS_SPLIT > 64 * 1024 && !opt_split.ensure(reinterpret_cast<const void*>(gemm_f32_split_kernel), LDS_SPLIT))
         return fail(VLFM_ERR_HIP, "gemm_f32_nt: cannot opt in to the LDS size");
     VLFM_TIMED("gemm_f32_split_kernel", stream);
-    VLFM_KLAUNCH(gemm_f32_split_kernel, grid, block, SplitGeom<2>::LDS, (hipStream_t)stream, a, activation);
+    VLFM_KLAUNCH(gemm_f32_split_kernel, grid, block, LDS_SPLIT, (hipStream_t)stream, a, activation);
     return check_launch("gemm_f32_split_kernel");
 }

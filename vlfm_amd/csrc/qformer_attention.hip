@@ -28,15 +28,11 @@
 #include <stdint.h>
 
 #include "../../include/vlfm_amd.h"
+#include "mfma.h"
 #include "profile.h"
 #include "status.h"
 
 namespace vlfm {
-
-typedef float qa_f32x16 __attribute__((ext_vector_type(16)));
-typedef float qa_f32x4 __attribute__((ext_vector_type(4)));
-using qa_lds_ptr = __attribute__((address_space(3))) unsigned char*;
-using qa_gbl_ptr = const __attribute__((address_space(1))) unsigned char*;
 
 constexpr int QA_ROWB = 256;                       // one key / value row of a head: 64 f32
 constexpr int QA_MERGE_REGS = 34;                  // 32 output registers + m + l
@@ -55,10 +51,10 @@ struct QaArgs {
 struct QaKernel {
     const QaArgs& a;
     unsigned char* smem;
-    qa_lds_ptr lds;
+    lds_ptr lds;
     int lane, wave, col, g, voff;
 
-    __device__ QaKernel(const QaArgs& a_, unsigned char* smem_) : a(a_), smem(smem_), lds((qa_lds_ptr)smem_) {
+    __device__ QaKernel(const QaArgs& a_, unsigned char* smem_) : a(a_), smem(smem_), lds((lds_ptr)smem_) {
         lane = threadIdx.x & 63;
         wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         col = lane & 31;
@@ -74,7 +70,7 @@ struct QaKernel {
         for (int ins = 0; ins < n_ins; ins++) {
             const int row = row0 + 4 * ins + r4, src_row = min(row, a.T - 1);
             const int dst = __builtin_amdgcn_readfirstlane((row0 + 4 * ins) * QA_ROWB);
-            __builtin_amdgcn_global_load_lds((qa_gbl_ptr)(kg + (size_t)src_row * QA_ROWB + ((p ^ (row & 15)) << 4)), lds + dst, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_ptr)(kg + (size_t)src_row * QA_ROWB + ((p ^ (row & 15)) << 4)), lds + dst, 16, 0, 0);
         }
     }
     __device__ inline void issue_v(const unsigned char* vg, int row0, int n_ins) const {
@@ -82,7 +78,7 @@ struct QaKernel {
         for (int ins = 0; ins < n_ins; ins++) {
             const int row = row0 + 4 * ins + r4, src_row = min(row, a.T - 1);
             const int dst = __builtin_amdgcn_readfirstlane(voff + (row0 + 4 * ins) * QA_ROWB);
-            __builtin_amdgcn_global_load_lds((qa_gbl_ptr)(vg + (size_t)src_row * QA_ROWB + ((p ^ (((row >> 2) & 1) << 3)) << 4)),
+            __builtin_amdgcn_global_load_lds((gbl_ptr)(vg + (size_t)src_row * QA_ROWB + ((p ^ (((row >> 2) & 1) << 3)) << 4)),
                                              lds + dst, 16, 0, 0);
         }
     }
@@ -95,7 +91,7 @@ struct QaKernel {
         const float* src = a.q + ((size_t)b * a.Q + min(col, a.Q - 1)) * ((size_t)a.heads * 64) + (size_t)h * 64 + 32 * g;
 #pragma unroll
         for (int c = 0; c < 8; c++) {
-            const qa_f32x4 v = *reinterpret_cast<const qa_f32x4*>(src + 4 * c);
+            const floatx4 v = *reinterpret_cast<const floatx4*>(src + 4 * c);
             qn[4 * c] = v[0]; qn[4 * c + 1] = v[1]; qn[4 * c + 2] = v[2]; qn[4 * c + 3] = v[3];
         }
     }
@@ -127,7 +123,7 @@ __global__ __launch_bounds__(256) void qformer_cross_attention_kernel(QaArgs a) 
         if (n_left != 0 && wave == left_wave) k.issue_rows(kg, vg, 32 * n_full, left_ins);
     }
     for (;;) {
-        __builtin_amdgcn_s_waitcnt(0x0F70);       // vmcnt(0): this wavefront's tiles of the item and its query row
+        wait_vmcnt<0>();       // this wavefront's tiles of the item and its query row
         asm volatile("" ::: "memory");
         float qf[32];
 #pragma unroll
@@ -141,7 +137,7 @@ __global__ __launch_bounds__(256) void qformer_cross_attention_kernel(QaArgs a) 
         if (more) k.load_q(nb, nh, qn);
 
         float m = -INFINITY, l = 0.f;
-        qa_f32x16 o0, o1;
+        floatx16 o0, o1;
 #pragma unroll
         for (int r = 0; r < 16; r++) { o0[r] = 0.f; o1[r] = 0.f; }
         for (int t = wave; t < n_full; t += 4) {
@@ -150,15 +146,15 @@ __global__ __launch_bounds__(256) void qformer_cross_attention_kernel(QaArgs a) 
             float kf[32];
 #pragma unroll
             for (int c = 0; c < 8; c++) {
-                const qa_f32x4 v = *reinterpret_cast<const qa_f32x4*>(kb + (((8 * g + c) ^ (col & 15)) << 4));
+                const floatx4 v = *reinterpret_cast<const floatx4*>(kb + (((8 * g + c) ^ (col & 15)) << 4));
                 kf[4 * c] = v[0]; kf[4 * c + 1] = v[1]; kf[4 * c + 2] = v[2]; kf[4 * c + 3] = v[3];
             }
             // the K rows are in registers: the same tile of the next item's K takes their place while this one is multiplied
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            wait_lgkmcnt0();
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("" ::: "memory");
             if (more) k.issue_k(kg, 32 * t, 8);
-            qa_f32x16 acc;
+            floatx16 acc;
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[r] = 0.f;
 #pragma unroll
@@ -187,7 +183,7 @@ __global__ __launch_bounds__(256) void qformer_cross_attention_kernel(QaArgs a) 
                 o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vb[ro + c1], acc[r], o1, 0, 0, 0);
             }
             // ... and so are the V rows now
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            wait_lgkmcnt0();
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("" ::: "memory");
             if (more) k.issue_v(vg, 32 * t, 8);
@@ -199,7 +195,7 @@ __global__ __launch_bounds__(256) void qformer_cross_attention_kernel(QaArgs a) 
                 float part = 0.f;
 #pragma unroll
                 for (int c = 0; c < 8; c++) {
-                    const qa_f32x4 v = *reinterpret_cast<const qa_f32x4*>(kr + (((8 * g + c) ^ (j & 15)) << 4));
+                    const floatx4 v = *reinterpret_cast<const floatx4*>(kr + (((8 * g + c) ^ (j & 15)) << 4));
 #pragma unroll
                     for (int e = 0; e < 4; e++) part = fmaf(v[e], qf[4 * c + e], part);
                 }
@@ -212,8 +208,8 @@ __global__ __launch_bounds__(256) void qformer_cross_attention_kernel(QaArgs a) 
                 const int sw = ((j >> 2) & 1) << 3;
 #pragma unroll
                 for (int q4 = 0; q4 < 4; q4++) {
-                    const qa_f32x4 v0 = *reinterpret_cast<const qa_f32x4*>(vr + (((2 * q4 + g) ^ sw) << 4));
-                    const qa_f32x4 v1 = *reinterpret_cast<const qa_f32x4*>(vr + (((8 + 2 * q4 + g) ^ sw) << 4));
+                    const floatx4 v0 = *reinterpret_cast<const floatx4*>(vr + (((2 * q4 + g) ^ sw) << 4));
+                    const floatx4 v1 = *reinterpret_cast<const floatx4*>(vr + (((8 + 2 * q4 + g) ^ sw) << 4));
 #pragma unroll
                     for (int e = 0; e < 4; e++) {
                         o0[4 * q4 + e] = fmaf(pj, v0[e], o0[4 * q4 + e] * alpha);
@@ -221,7 +217,7 @@ __global__ __launch_bounds__(256) void qformer_cross_attention_kernel(QaArgs a) 
                     }
                 }
             }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            wait_lgkmcnt0();
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("" ::: "memory");
             if (more) k.issue_rows(kg, vg, 32 * n_full, left_ins);
@@ -236,7 +232,7 @@ __global__ __launch_bounds__(256) void qformer_cross_attention_kernel(QaArgs a) 
             for (int r = 0; r < 16; r++) { mine[r * 64] = o0[r]; mine[(16 + r) * 64] = o1[r]; }
             mine[32 * 64] = m;
             mine[33 * 64] = l;
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            wait_lgkmcnt0();
         }
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -263,13 +259,13 @@ __global__ __launch_bounds__(256) void qformer_cross_attention_kernel(QaArgs a) 
                 float* orow = a.out + ((size_t)b * a.Q + col) * ((size_t)a.heads * 64) + (size_t)h * 64 + 4 * g;
 #pragma unroll
                 for (int q4 = 0; q4 < 4; q4++) {
-                    const qa_f32x4 s0 = {o0[4 * q4] * inv, o0[4 * q4 + 1] * inv, o0[4 * q4 + 2] * inv, o0[4 * q4 + 3] * inv};
-                    const qa_f32x4 s1 = {o1[4 * q4] * inv, o1[4 * q4 + 1] * inv, o1[4 * q4 + 2] * inv, o1[4 * q4 + 3] * inv};
-                    *reinterpret_cast<qa_f32x4*>(orow + 8 * q4) = s0;
-                    *reinterpret_cast<qa_f32x4*>(orow + 32 + 8 * q4) = s1;
+                    const floatx4 s0 = {o0[4 * q4] * inv, o0[4 * q4 + 1] * inv, o0[4 * q4 + 2] * inv, o0[4 * q4 + 3] * inv};
+                    const floatx4 s1 = {o1[4 * q4] * inv, o1[4 * q4 + 1] * inv, o1[4 * q4 + 2] * inv, o1[4 * q4 + 3] * inv};
+                    *reinterpret_cast<floatx4*>(orow + 8 * q4) = s0;
+                    *reinterpret_cast<floatx4*>(orow + 32 + 8 * q4) = s1;
                 }
             }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            wait_lgkmcnt0();
         }
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();      // the partials are read: the next item's may be written

@@ -29,14 +29,11 @@
 #include <stdint.h>
 
 #include "../../include/vlfm_amd.h"
+#include "mfma.h"
 #include "profile.h"
 #include "status.h"
 
 namespace vlfm {
-
-using half4_t = __attribute__((ext_vector_type(4))) _Float16;
-using half8_t = __attribute__((ext_vector_type(8))) _Float16;
-using f32x16_t = __attribute__((ext_vector_type(16))) float;
 
 constexpr int AT_D = 96;                  // head width as the MFMAs see it (88 real channels + zeros in the Q registers)
 constexpr int AT_NT = 8;                  // full 32-token tiles
@@ -82,14 +79,10 @@ constexpr int PA_KSLOTS = AT_S * 11, PA_VSLOTS = AT_S * 12;
 static_assert(32 * 11 * (AT_WAVES - 1) + 64 * (PA_QPIECES - 1) < PA_KSLOTS, "a Q piece with no active lane");
 static_assert(64 * 5 < 32 * 11, "a store_out instruction with no active lane");
 
-using lds_ptr = __attribute__((address_space(3))) unsigned char*;
-using gbl_ptr = const __attribute__((address_space(1))) unsigned char*;
 typedef short short4v __attribute__((__vector_size__(4 * sizeof(short))));
 typedef short short8v __attribute__((__vector_size__(8 * sizeof(short))));
 using half2_t = __attribute__((ext_vector_type(2))) _Float16;
 
-#define PA_WAIT_VM(n) __builtin_amdgcn_s_waitcnt(0x0F70 | ((n) & 15) | (((n) >> 4) << 14))   /* vmcnt(n), n < 64 */
-#define PA_WAIT_LGKM0() __builtin_amdgcn_s_waitcnt(0xC07F)
 #define PA_BARRIER()                               \
     do {                                           \
         asm volatile("" ::: "memory");             \
@@ -112,11 +105,11 @@ __device__ inline float row16_sum(float x) {
     return x + PA_DPP(x, 0x140);
 }
 
-__device__ inline half8_t tr_pair(const unsigned char* p0, const unsigned char* p1) {
+__device__ inline half8 tr_pair(const unsigned char* p0, const unsigned char* p1) {
     const short4v a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(lds_ptr)p0);
     const short4v b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(lds_ptr)p1);
     const short8v ab = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(half8_t, ab);
+    return __builtin_bit_cast(half8, ab);
 }
 
 __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _Float16* __restrict__ qkv,
@@ -136,7 +129,7 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
     const int row_halfs = 3 * H * DH, row_bytes = 2 * row_halfs, part_bytes = 2 * H * DH;
     // ---- zero the whole LDS once (over-read bytes must be finite)
     for (int i = tid; i < PA_LDS / 16; i += 64 * AT_WAVES) *reinterpret_cast<uint4*>(at_lds + 16 * i) = uint4{0, 0, 0, 0};
-    PA_WAIT_LGKM0();
+    wait_lgkmcnt0();
     PA_BARRIER();
     auto item_base = [&](int tt) {
         const int b = image_of(tt), h = tt % H;
@@ -217,12 +210,12 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
                 *reinterpret_cast<half2_t*>(out + ((size_t)(b * AT_S) * H + h) * DH + 2 * lane) = half2_t{(_Float16)(o0 * inv), (_Float16)(o1 * inv)};
         }
     };
-    half4_t of[11];          // the wavefront's 32 output rows of the previous item (f16, accumulator layout) until they are staged
+    half4 of[11];          // the wavefront's 32 output rows of the previous item (f16, accumulator layout) until they are staged
     // rows of the accumulator layout -> LDS: lane (col, grp) holds channels 32 dt + 8 q4 + 4 grp .. + 3 of row col
     auto stage_rows = [&](int bo) {
         unsigned char* st = at_lds + bo + (1 + 32 * wave + col) * PA_KROW + 8 * grp;
 #pragma unroll
-        for (int i = 0; i < 11; i++) *reinterpret_cast<half4_t*>(st + 16 * i) = of[i];
+        for (int i = 0; i < 11; i++) *reinterpret_cast<half4*>(st + 16 * i) = of[i];
     };
     int n = 0, t_prev = -1;
     for (;;) {
@@ -233,15 +226,15 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
         const unsigned char* base_n = has_next ? item_base(tn) : base;
         const int kb = (n & 1) * PA_KB, ob = PA_KB - kb;
         // ---- A: K and Q of this item are in LDS (this wavefront's pieces: the last vector-memory operations of the previous item)
-        PA_WAIT_VM(0);
+        wait_vmcnt<0>();
         PA_BARRIER();
         // the B operand (Q^T) of the wavefront's 32 queries: lane (col, grp) = channels 16 kk + 8 grp .. of row 1 + 32 wave + col;
         // channels 88..95 (kk = 5, upper half) read 16 B of the next row: zeroed
-        half8_t qf[AT_D / 16];
+        half8 qf[AT_D / 16];
         {
             const unsigned char* qr = at_lds + ob + (1 + 32 * wave + col) * PA_KROW + 16 * grp;
 #pragma unroll
-            for (int kk = 0; kk < AT_D / 16; kk++) qf[kk] = *reinterpret_cast<const half8_t*>(qr + 32 * kk);
+            for (int kk = 0; kk < AT_D / 16; kk++) qf[kk] = *reinterpret_cast<const half8*>(qr + 32 * kk);
             if (grp) {
 #pragma unroll
                 for (int j = 0; j < 8; j++) qf[AT_D / 16 - 1][j] = (_Float16)0.0f;
@@ -262,13 +255,13 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
         const unsigned char* okl = at_lds + kb + 256 * PA_KROW + 96 * grp;
         float os = 0.0f, os2 = 0.0f;
         auto odd_score_slot = [&](int i) {
-            half8_t qv = *reinterpret_cast<const half8_t*>(oq0 + 16 * i);
+            half8 qv = *reinterpret_cast<const half8*>(oq0 + 16 * i);
             if (i == 5 && grp) {
 #pragma unroll
                 for (int j = 0; j < 8; j++) qv[j] = (_Float16)0.0f;
             }
-            const half8_t kv = *reinterpret_cast<const half8_t*>(okr + 16 * i);
-            const half8_t k2 = *reinterpret_cast<const half8_t*>(okl + 16 * i);
+            const half8 kv = *reinterpret_cast<const half8*>(okr + 16 * i);
+            const half8 k2 = *reinterpret_cast<const half8*>(okl + 16 * i);
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 os = __builtin_amdgcn_fdot2(half2_t{qv[2 * e], qv[2 * e + 1]}, half2_t{kv[2 * e], kv[2 * e + 1]}, os, false);
@@ -276,7 +269,7 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
             }
         };
         // ---- S^T = K Q^T for the wavefront's 32 queries: 9 key tiles x 6 contraction steps; the 7 V pieces of this item in between
-        f32x16_t acc[AT_KT];
+        floatx16 acc[AT_KT];
 #pragma unroll
         for (int tt = 0; tt < AT_KT; tt++)
 #pragma unroll
@@ -285,14 +278,14 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
             const unsigned char* kbase = at_lds + kb + col * PA_KROW + 16 * grp;
 #pragma unroll
             for (int g0 = 0; g0 < AT_KT; g0 += 3) {
-                half8_t a_cur[3], a_nxt[3];
+                half8 a_cur[3], a_nxt[3];
 #pragma unroll
-                for (int u = 0; u < 3; u++) a_cur[u] = *reinterpret_cast<const half8_t*>(kbase + 32 * (g0 + u) * PA_KROW);
+                for (int u = 0; u < 3; u++) a_cur[u] = *reinterpret_cast<const half8*>(kbase + 32 * (g0 + u) * PA_KROW);
 #pragma unroll
                 for (int kk = 0; kk < AT_D / 16; kk++) {
                     if (kk + 1 < AT_D / 16) {
 #pragma unroll
-                        for (int u = 0; u < 3; u++) a_nxt[u] = *reinterpret_cast<const half8_t*>(kbase + 32 * (g0 + u) * PA_KROW + 32 * (kk + 1));
+                        for (int u = 0; u < 3; u++) a_nxt[u] = *reinterpret_cast<const half8*>(kbase + 32 * (g0 + u) * PA_KROW + 32 * (kk + 1));
                     }
 #pragma unroll
                     for (int u = 0; u < 3; u++) acc[g0 + u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[u], qf[kk], acc[g0 + u], 0, 0, 0);
@@ -336,7 +329,7 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
         // probabilities go to f16 at once (the B operands of the PV MFMAs: chunk ch = 16 keys = registers 8 (ch & 1) .. + 7 of tile
         // ch >> 1): 72 registers instead of 144; the previous item's rows leave LDS in between (6 x 16 B per lane)
         constexpr int NCH = 2 * AT_KT - 1;      // 17 chunks of 16 keys: keys 272.. do not exist
-        half8_t pb[NCH];
+        half8 pb[NCH];
 #pragma unroll
         for (int ch = 0; ch < NCH; ch++) {
 #pragma unroll
@@ -349,8 +342,8 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
         }
         l += __shfl_xor(l, 32, 64);
         // ---- B: V of this item is in LDS (this wavefront's pieces: older than the 6 Q pieces)
-        PA_WAIT_VM(6);
-        PA_WAIT_LGKM0();
+        wait_vmcnt<6>();
+        wait_lgkmcnt0();
         PA_BARRIER();
         // ---- the odd query's share of P V runs BETWEEN the PV MFMAs below (two keys per 16-key chunk): lane = channel pair, its 32
         // probabilities are read back from LDS (one address per instruction: a broadcast)
@@ -368,7 +361,7 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
         // by two ds_read_b64_tr_b16: a 16-lane group addresses a [4 keys][16 channels] block (lane j: key j >> 2, channels 4 (j & 3) ..)
         // and lane j receives channel j of the 4 keys.  Keys behind the 8 operand elements: 16 ch + 4 grp + (0..3), then + 8.
         // In between: the 6 K pieces (-> the other buffer) and the 6 Q pieces (-> this item's K buffer) of the next item.
-        f32x16_t o[AT_D / 32];
+        floatx16 o[AT_D / 32];
 #pragma unroll
         for (int dt = 0; dt < AT_D / 32; dt++)
 #pragma unroll
@@ -376,7 +369,7 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
         {
             const int j16 = lane & 15, g16 = (lane >> 4) & 1;
             const unsigned char* vb = at_lds + PA_V_OFF + (4 * grp + (j16 >> 2)) * PA_VROW + 2 * (16 * g16 + 4 * (j16 & 3));
-            half8_t v_cur[AT_D / 32], v_nxt[AT_D / 32];
+            half8 v_cur[AT_D / 32], v_nxt[AT_D / 32];
 #pragma unroll
             for (int dt = 0; dt < AT_D / 32; dt++) v_cur[dt] = tr_pair(vb + 64 * dt, vb + 64 * dt + 8 * PA_VROW);
 #pragma unroll
@@ -410,14 +403,14 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
 #pragma unroll
                 for (int q4 = 0; q4 < 4; q4++) {
                     if (32 * dt + 8 * q4 + 8 <= DH) {      // 11 x 4 channels per lane
-                        of[i] = half4_t{(_Float16)(o[dt][4 * q4] * inv), (_Float16)(o[dt][4 * q4 + 1] * inv),
+                        of[i] = half4{(_Float16)(o[dt][4 * q4] * inv), (_Float16)(o[dt][4 * q4 + 1] * inv),
                                         (_Float16)(o[dt][4 * q4 + 2] * inv), (_Float16)(o[dt][4 * q4 + 3] * inv)};
                         i++;
                     }
                 }
             }
         }
-        PA_WAIT_LGKM0();     // the partials are written before the next barrier A
+        wait_lgkmcnt0();     // the partials are written before the next barrier A
         t_prev = t;
         if (!has_next) break;
         t = tn;
@@ -425,7 +418,7 @@ __global__ __launch_bounds__(64 * AT_WAVES, 2) void vit_attention_kernel(const _
         n++;
     }
     // the last item's rows: through this item's K buffer, once the (unused) pieces that were still aimed at it have landed
-    PA_WAIT_VM(0);
+    wait_vmcnt<0>();
     PA_BARRIER();
     stage_rows((n & 1) * PA_KB);
 #pragma unroll
