@@ -917,6 +917,73 @@ int vlfm_geodesic_query(const double* d_points, const int32_t* d_field_of, int m
                         const double* d_rects, const double* d_nodes, const double* d_dist, const int32_t* d_counts,
                         const double* d_sources, const int32_t* d_source_counts, int max_sources, double* d_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Map planner (ABI 21, csrc/map_planner.hip): shortest paths over the navigable planes of the obstacle maps (the reference's
+ * _navigable_map: obstacles dilated by the robot's footprint, unexplored cells free), n jobs in ONE launch, one workgroup per
+ * job.  Integers only; bit for bit vlfm_amd.synthetic.plan_paths_numpy (Dijkstra with a heap over the same rule).
+ *
+ * A JOB plans one path in one environment's plane.  Cells are (x, y) = (bit, row) of the bit-packed plane (row = ceil(size / 32)
+ * 32-bit words, bit x of a row in word x >> 5 at position x & 31); metres become cells by BaseMap._xy_to_px.
+ *   env          the slot.  Two jobs may name the same slot.
+ *   window       y0, y1, x0, x1, inclusive.  Everything outside it is blocked.
+ *   start        (sx, sy) with a free radius start_free, in cells;  goal: (gx, gy) with goal_free.  Radii in [0, 4096].
+ *   free         a cell of the window is free if its navigable bit is set, or if dx*dx + dy*dy <= r*r (integers) about `start`
+ *                with r = start_free, or about `goal` with r = goal_free (r = 0: the cell itself -- start and goal are always
+ *                free).  The discs exist because a robot legally stands inside the inflated zone next to a wall, and an object
+ *                goal lies inside its own obstacle.
+ *   moves        8-connected; cost 2 for E/N/W/S, 3 for diagonals.  a -> b is allowed iff both cells are free; a diagonal move
+ *                also needs the two cells that share an edge with both a and b to be free (no corner cutting, no squeezing
+ *                through a diagonal gap).  The rule is symmetric: a field grown from the goal is the distance TO the goal.
+ *   field        dist[c] = the least cost from `goal` to c, uint16; 0xFFFF: blocked, outside the window, not reached, or cost
+ *                above max_cost (an argument: at most 65534).
+ *   descent      cur = start; while dist[cur] > 0 and fewer than `lookahead` steps were taken: try the chain codes s = 0..7
+ *                (dx = {1,1,0,-1,-1,-1,0,1}, dy = {0,-1,-1,-1,0,1,1,1}: E NE N NW W SW S SE, y grows downwards) and take the
+ *                first whose move is allowed and has dist[next] + cost(s) == dist[cur] (one always exists).  The waypoint is
+ *                the final cur, `steps` the number of moves taken.
+ *   result       status, cost, waypoint_x, waypoint_y, steps.  The status is the first that applies:
+ *                  VLFM_PLAN_INVALID      env outside [0, n_envs), empty window, window outside the map or larger than
+ *                                         field_h x field_w, start or goal outside the window, a radius outside [0, 4096].
+ *                                         Nothing else is computed; a bad job never faults.
+ *                  VLFM_PLAN_TOO_LONG     start has no cost <= max_cost and some cell has a finite cost above max_cost
+ *                                         (the search reached max_cost with cells still to expand)
+ *                  VLFM_PLAN_UNREACHABLE  the search ran dry without reaching start
+ *                  VLFM_PLAN_OK           cost = dist[start], waypoint and steps as above
+ *                Every status but VLFM_PLAN_OK: cost = 0xFFFF, waypoint = start, steps = 0.
+ * cost * 0.5 / pixels_per_meter is the path length in metres; it overstates pure diagonals by 6 % (3/2 against sqrt 2).
+ *
+ * vlfm_plan_paths, on `stream` (a memset node presets the dist planes, then ONE kernel):
+ *   d_navigable   [n_envs][size][ceil(size / 32)] words, size <= 2048
+ *   d_jobs        [n_jobs] VlfmPlanJob;  d_results [n_jobs] VlfmPlanResult out
+ *   lookahead     >= 0, steps of the descent;  max_cost in [0, 65534]
+ *   d_fields      NULL, or [n_jobs][field_h][field_w] uint16 out: row / column 0 are the window's y0 / x0, cells beyond the
+ *                 window (and the whole field of an invalid job) are 0xFFFF.  NULL: no field is kept and the search stops
+ *                 after the level that settles `start` (every cell of a shortest path from it is settled by then): the
+ *                 results are those of the full run.
+ *   field_h, field_w   in [1, size]: the bound every job's window keeps to, with or without d_fields (the dist planes and the
+ *                 LDS planes are laid out for it).  The jobs are device memory, which the host call cannot inspect, so a
+ *                 window beyond the bound is answered per job (VLFM_PLAN_INVALID); the Python layer derives the bound from
+ *                 the jobs it uploads.
+ *   d_scratch     at least vlfm_plan_scratch_bytes(n_jobs, size) bytes (VLFM_ERR_CAPACITY otherwise); no state between calls
+ * Returns VLFM_PLAN_IN_LDS (0) when the six bit planes of a field_h x field_w window fit 160 KB of LDS (e.g. 400 x 400), else
+ * VLFM_PLAN_IN_SCRATCH (1): they then live in d_scratch.  Same results either way.  Negative: vlfm_status, nothing launched.
+ * n_jobs == 0 returns 0 without a launch. */
+enum { VLFM_PLAN_OK = 0, VLFM_PLAN_UNREACHABLE = 1, VLFM_PLAN_TOO_LONG = 2, VLFM_PLAN_INVALID = 3 };
+enum { VLFM_PLAN_IN_LDS = 0, VLFM_PLAN_IN_SCRATCH = 1 };
+typedef struct VlfmPlanJob {
+    int32_t env, y0, y1, x0, x1;
+    int32_t sx, sy, start_free;
+    int32_t gx, gy, goal_free;
+    int32_t reserved;
+} VlfmPlanJob; /* 48 bytes */
+typedef struct VlfmPlanResult {
+    int32_t status, cost, waypoint_x, waypoint_y, steps;
+    int32_t reserved[3];
+} VlfmPlanResult; /* 32 bytes */
+size_t vlfm_plan_scratch_bytes(int n_jobs, int size);
+int vlfm_plan_paths(const int32_t* d_navigable, int n_envs, int size, const VlfmPlanJob* d_jobs, int n_jobs, int lookahead,
+                    int max_cost, uint16_t* d_fields, int field_h, int field_w, VlfmPlanResult* d_results, void* d_scratch,
+                    size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlfm_amd.so")
-SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "qformer_attention.hip", "detect_ops.hip", "object_cloud.hip", "cloud_query.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "world_render.hip", "geodesic.hip", "host.cpp"]
+SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "qformer_attention.hip", "detect_ops.hip", "object_cloud.hip", "cloud_query.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "world_render.hip", "geodesic.hip", "map_planner.hip", "host.cpp"]
 
 VLFM_OK = 0
 VLFM_ERR_INVALID = -1
@@ -63,6 +63,21 @@ class CloudQuery(ctypes.Structure):
                 ("n", ctypes.c_int32), ("k", ctypes.c_int32), ("flag_offset", ctypes.c_int32), ("n_slots", ctypes.c_int32)]
 
 
+class PlanJob(ctypes.Structure):          # VlfmPlanJob
+    _fields_ = [("env", ctypes.c_int32), ("y0", ctypes.c_int32), ("y1", ctypes.c_int32), ("x0", ctypes.c_int32),
+                ("x1", ctypes.c_int32), ("sx", ctypes.c_int32), ("sy", ctypes.c_int32), ("start_free", ctypes.c_int32),
+                ("gx", ctypes.c_int32), ("gy", ctypes.c_int32), ("goal_free", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class PlanResult(ctypes.Structure):       # VlfmPlanResult
+    _fields_ = [("status", ctypes.c_int32), ("cost", ctypes.c_int32), ("waypoint_x", ctypes.c_int32),
+                ("waypoint_y", ctypes.c_int32), ("steps", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+PLAN_OK, PLAN_UNREACHABLE, PLAN_TOO_LONG, PLAN_INVALID = 0, 1, 2, 3
+PLAN_IN_LDS, PLAN_IN_SCRATCH = 0, 1
+
+assert ctypes.sizeof(PlanJob) == 48 and ctypes.sizeof(PlanResult) == 32
 assert ctypes.sizeof(CloudQuery) == 80
 assert ctypes.sizeof(ScatterJournal) == 24 and ctypes.sizeof(VmOptics) == 48
 assert ctypes.sizeof(VmPose) == 64 and ctypes.sizeof(IngestParams) == 152 and ctypes.sizeof(FogParams) == 48 + 16 * FOG_MAX_POLY
@@ -232,6 +247,9 @@ def lib() -> ctypes.CDLL:
         L.vlfm_rooms_raycast_objects.argtypes = [vp, ci, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp]
         L.vlfm_geodesic_fields.argtypes = [vp, ci, cd, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
         L.vlfm_geodesic_query.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp]
+        L.vlfm_plan_scratch_bytes.argtypes = [ci, ci]
+        L.vlfm_plan_scratch_bytes.restype = ctypes.c_size_t
+        L.vlfm_plan_paths.argtypes = [vp, ci, ci, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.c_size_t, vp]
         _lib = L
     return _lib
 

@@ -35,7 +35,8 @@ from .mapping.value_map import ValueMapBatch
 from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TURN_RIGHT, BOXES, CAMERA_HEIGHT, HEADINGS, \
     MAX_DEPTH, MIN_DEPTH, YAWS, BangBangController, ReplayController, Trajectory, camera_intrinsics, depth_frame, integrate, \
     GEODESIC_MAX_SOURCES, STEP_MARGIN, WORLD_MAX_OBJECTS, goal_viewpoints, inflated_rects, object_layout, plan_actions, \
-    pose_to_tf, rect_distance, rgb_frame, soft_spl, spl, step_poses, tf_of
+    pose_to_tf, rect_distance, rgb_frame, soft_spl, spl, step_poses, tf_of, PLAN_INVALID, PLAN_OK, PLAN_TOO_LONG, \
+    PLAN_UNREACHABLE
 
 PROMPT = "Seems like there is a target_object ahead."  # vlfm/policy/base_objectnav_policy.py:377
 TARGETS = ["chair", "bed", "potted plant", "toilet", "tv", "couch"]  # HM3D ObjectNav categories
@@ -630,6 +631,10 @@ class BatchedEpisodes:
                 self.closed_loop_stats = {"path_length": z(np.float64), "collisions": z(np.int64), "forward_steps": z(np.int64),
                                           "turn_steps": z(np.int64), "stops": z(np.int64)}
                 self.last_poses = self.last_world_actions = None
+                # of a controller with act_on_map (MapPlannerController), per environment: plans = ok + unreachable + too_long
+                # + invalid (a robot or goal off the map)
+                self.planner_stats = {"plans": z(np.int64), "ok": z(np.int64), "unreachable": z(np.int64),
+                                      "too_long": z(np.int64), "invalid": z(np.int64)}
                 if world_objects is not None:
                     self._ep_index, self._ep_clock = z(np.int64), z(np.int64)
                     self._ep_path, self._ep_first = z(np.float64), np.full(n_envs, -1, np.int64)
@@ -1362,6 +1367,21 @@ class BatchedEpisodes:
         the step observed from."""
         if self.pointnav is not None and self.last_actions is not None:
             acts = self.last_actions.detach().reshape(self.E).cpu().numpy().astype(np.int64)
+        elif hasattr(self.controller, "act_on_map"):
+            # a controller that plans over the navigable planes (synthetic.MapPlannerController): on the main stream, which
+            # joined the map stream before the value update; an object goal may be entered up to the stop radius
+            navigate = np.array([m == "navigate" for m in self.last_modes], bool)
+            goal_free = [self.stop_radius if nav else None for nav in navigate]
+            acts = np.asarray(self.controller.act_on_map(self.obstacles, poses, self.last_goals, goal_free, self.last_modes,
+                                                         self.last_rho_theta, self.last_stops, self._collided),
+                              np.int64).reshape(self.E)
+            status = np.asarray(self.controller.last_status)
+            ps = self.planner_stats
+            ps["plans"] += status >= 0
+            ps["ok"] += status == PLAN_OK
+            ps["unreachable"] += status == PLAN_UNREACHABLE
+            ps["too_long"] += status == PLAN_TOO_LONG
+            ps["invalid"] += status == PLAN_INVALID
         else:
             acts = np.asarray(self.controller.act(self.last_modes, self.last_rho_theta, self.last_stops, self._collided),
                               np.int64).reshape(self.E)

@@ -22,6 +22,9 @@ from .base_map import BaseMap, require_gpu
 from .value_map import INGEST_DTYPE, UploadRing, _stream_ptr, wait_stream
 
 
+PLAN_JOB_DTYPE = np.dtype(_lib.PlanJob)     # the NumPy view of VlfmPlanJob the host layer fills
+
+
 def _wrap_heading(theta):
     return (theta + np.pi) % (2 * np.pi) - np.pi
 
@@ -496,6 +499,126 @@ class ObstacleMapBatch:
             if (hc[:, 2] != 0).any():
                 raise RuntimeError("fill_small_holes scratch capacity exceeded (HOLE_CAP_PTS/HOLE_CAP_CONTOURS or the "
                                    "scatter journal)")
+
+    # ------------------------------------------------------------------------------------------ planning
+    def cells_of(self, xy) -> np.ndarray:
+        """[n,2] int64 cells (x, y) = (column, row) of the points ``xy`` [n,2] in metres: BaseMap._xy_to_px's arithmetic."""
+        xy = np.asarray(xy, np.float64).reshape(-1, 2)
+        px = np.rint(xy[:, ::-1] * self.pixels_per_meter) + self.size // 2
+        px[:, 0] = self.size - px[:, 0]
+        return px.astype(np.int64)
+
+    def plan_windows(self, env: np.ndarray, start_px: np.ndarray, goal_px: np.ndarray) -> np.ndarray:
+        """[n,4] int32 default windows (y0, y1, x0, x1) of ``plan_paths``: the host mirror of everything ever revealed in the
+        slot (``_bbox_host``) unioned with the start and goal cells, padded by 2 * kernel_size, clipped to the map."""
+        S, pad = self.size, 2 * self.kernel_size
+        box = self._bbox_host[env].astype(np.int64)
+        pts_y = np.stack([start_px[:, 1], goal_px[:, 1]], axis=1)
+        pts_x = np.stack([start_px[:, 0], goal_px[:, 0]], axis=1)
+        live = box[:, 1] >= box[:, 0]
+        y0 = np.where(live, np.minimum(box[:, 0], pts_y.min(axis=1)), pts_y.min(axis=1))
+        y1 = np.where(live, np.maximum(box[:, 1], pts_y.max(axis=1)), pts_y.max(axis=1))
+        x0 = np.where(live, np.minimum(box[:, 2], pts_x.min(axis=1)), pts_x.min(axis=1))
+        x1 = np.where(live, np.maximum(box[:, 3], pts_x.max(axis=1)), pts_x.max(axis=1))
+        win = np.stack([y0 - pad, y1 + pad, x0 - pad, x1 + pad], axis=1)
+        return np.clip(win, 0, S - 1).astype(np.int32)
+
+    def _plan_jobs(self, starts_xy, goals_xy, env_ids, start_free_m, goal_free_m, windows):
+        """(jobs [n] PLAN_JOB_DTYPE, goal cells [n,2], windows [n,4] int32) of a ``plan_paths`` call: host arithmetic only."""
+        start_px, goal_px = self.cells_of(starts_xy), self.cells_of(goals_xy)
+        n = len(start_px)
+        if len(goal_px) != n:
+            raise ValueError("plan_paths: one goal per start")
+        env = np.arange(n, dtype=np.int64) if env_ids is None else np.asarray(env_ids, np.int64).reshape(-1)
+        if env.shape != (n,):
+            raise ValueError("plan_paths: one slot id per job")
+
+        def radius(r_m):
+            out = np.full(n, self.kernel_size // 2, np.int64)
+            if r_m is not None:
+                r = np.broadcast_to(np.asarray(r_m, np.float64), (n,))
+                out = np.where(np.isfinite(r), np.rint(np.where(np.isfinite(r), r, 0.0) * self.pixels_per_meter), out)
+            return out.astype(np.int64)
+
+        i32 = lambda a: np.clip(np.asarray(a, np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32)   # noqa: E731
+        if windows is None:
+            # (a slot out of range gets a window anyway: its job comes back PLAN_INVALID)
+            win = self.plan_windows(np.clip(env, 0, self.n_envs - 1), start_px, goal_px) if n else np.zeros((0, 4), np.int32)
+        else:
+            win = i32(np.asarray(windows, np.int64).reshape(n, 4))
+        jobs = np.zeros(n, PLAN_JOB_DTYPE)
+        jobs["env"] = i32(env)
+        jobs["y0"], jobs["y1"], jobs["x0"], jobs["x1"] = (win[:, k] for k in range(4))
+        jobs["sx"], jobs["sy"], jobs["start_free"] = i32(start_px[:, 0]), i32(start_px[:, 1]), i32(radius(start_free_m))
+        jobs["gx"], jobs["gy"], jobs["goal_free"] = i32(goal_px[:, 0]), i32(goal_px[:, 1]), i32(radius(goal_free_m))
+        return jobs, goal_px, win
+
+    def plan_paths(self, starts_xy, goals_xy, env_ids=None, start_free_m=None, goal_free_m=None, lookahead_m: float = 0.75,
+                   max_cost: int = 65534, windows=None, return_fields: bool = False):
+        """Shortest paths over the navigable planes (csrc/map_planner.hip: vlfm_plan_paths; include/vlfm_amd.h states the
+        contract; bit for bit synthetic.plan_paths_numpy): job i goes from ``starts_xy[i]`` to ``goals_xy[i]`` (metres,
+        converted by ``cells_of``) in slot ``env_ids[i]`` (default: i; slots may repeat).  ``start_free_m`` / ``goal_free_m``:
+        None, a scalar or one value per job (NaN: the default) -- radii in metres about start and goal inside which every cell
+        counts as free (default kernel_size // 2 cells each: the robot stands legally inside the inflated zone, an object goal
+        inside its own obstacle).  ``lookahead_m``: how far along the path the waypoint lies.  ``windows`` [n,4] (y0, y1, x0, x1)
+        in cells, inclusive (default: ``plan_windows``); everything outside a job's window is blocked.
+
+        ONE launch and ONE read-back whatever the number of jobs (``return_fields`` adds the copy of the fields).  Returns a
+        dict: ``status`` [n] (PLAN_OK / PLAN_UNREACHABLE / PLAN_TOO_LONG / PLAN_INVALID), ``cost`` [n] (0xFFFF unless OK),
+        ``path_m`` [n] = cost * 0.5 / pixels_per_meter (inf unless OK; overstates pure diagonals by 6 %: 3/2 against sqrt 2),
+        ``waypoints`` [n,2] metres (``px_to_xy``'s convention; the start cell unless OK), ``waypoints_px`` [n,2] cells (x, y),
+        ``steps`` [n], ``at_goal`` [n] (the waypoint is the goal's cell), ``windows`` [n,4], ``residence`` ("lds" or "scratch":
+        where the kernel kept its bit planes) and, with ``return_fields``, ``fields`` [n,fh,fw] uint16 (row / column 0 = the
+        window's y0 / x0, 0xFFFF beyond it), whose search is not cut short.
+
+        Stream: the call launches on the CURRENT stream and waits for it.  The navigable bits are written by
+        ``update_after_ingest`` on the stream that was current for IT (the harness: its map stream, which the main stream
+        joins before the value update), so call this on that stream or on one that has waited for it."""
+        import torch
+
+        jobs, goal_px, win = self._plan_jobs(starts_xy, goals_xy, env_ids, start_free_m, goal_free_m, windows)
+        n, ppm = len(jobs), self.pixels_per_meter
+        lookahead = max(1, int(round(float(lookahead_m) * ppm)))
+        if not 0 <= int(max_cost) <= 65534:
+            raise ValueError("plan_paths: max_cost in [0, 65534]")
+        out = {"status": np.zeros(n, np.int64), "cost": np.zeros(n, np.int64), "path_m": np.zeros(n), "steps": np.zeros(n, np.int64),
+               "waypoints": np.zeros((n, 2)), "waypoints_px": np.zeros((n, 2), np.int64), "at_goal": np.zeros(n, bool),
+               "windows": win, "residence": None}
+        if n == 0:
+            if return_fields:
+                out["fields"] = np.zeros((0, 1, 1), np.uint16)
+            return out
+        # the bound of the call's windows (a window that is empty or leaves the map is answered PLAN_INVALID by the kernel)
+        fh = int(np.clip(win[:, 1].astype(np.int64) - win[:, 0] + 1, 1, self.size).max())
+        fw = int(np.clip(win[:, 3].astype(np.int64) - win[:, 2] + 1, 1, self.size).max())
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            if getattr(self, "_plan_cap", 0) < n:
+                cap = max(n, self.n_envs)
+                self._plan_cap = cap
+                self._plan_scratch = torch.empty(L.vlfm_plan_scratch_bytes(cap, self.size), dtype=torch.uint8, device=self.device)
+                self._plan_results = torch.empty((cap, 8), dtype=torch.int32, device=self.device)
+                self._h_plan = torch.empty((cap, 8), dtype=torch.int32).pin_memory()
+                self._ring_plan = UploadRing(self.device, cap * PLAN_JOB_DTYPE.itemsize, slots=4)
+            fields = torch.empty((n, fh, fw), dtype=torch.int16, device=self.device) if return_fields else None
+            d_jobs = self._ring_plan.upload(jobs)
+            rc = _lib.check(L.vlfm_plan_paths(self.navigable_bits.data_ptr(), self.n_envs, self.size, d_jobs.data_ptr(), n,
+                                              lookahead, int(max_cost), fields.data_ptr() if fields is not None else None,
+                                              fh, fw, self._plan_results.data_ptr(), self._plan_scratch.data_ptr(),
+                                              self._plan_scratch.numel(), _stream_ptr()), "plan_paths")
+            self._h_plan[:n].copy_(self._plan_results[:n], non_blocking=True)
+            wait_stream()
+            res = self._h_plan[:n].numpy().astype(np.int64)
+            if fields is not None:
+                out["fields"] = fields.cpu().numpy().view(np.uint16)
+        ok = res[:, 0] == _lib.PLAN_OK
+        out["status"], out["cost"], out["steps"] = res[:, 0], res[:, 1], res[:, 4]
+        out["path_m"] = np.where(ok, res[:, 1] * 0.5 / ppm, np.inf)
+        out["waypoints_px"] = res[:, 2:4]
+        out["waypoints"] = self.px_to_xy(res[:, 2:4].astype(np.float64))
+        out["at_goal"] = ok & (res[:, 2] == goal_px[:, 0]) & (res[:, 3] == goal_px[:, 1])
+        out["residence"] = "lds" if rc == _lib.PLAN_IN_LDS else "scratch"
+        return out
 
     # ------------------------------------------------------------------------------------------ rendering
     def update_agent_traj(self, env_ids: Sequence[int], xy, yaw) -> None:

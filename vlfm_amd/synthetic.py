@@ -628,3 +628,159 @@ def soft_spl(d_end: float, l: float, p: float) -> float:
     if l == 0.0:
         return 1.0 if d_end == 0.0 else 0.0
     return float(max(0.0, 1.0 - d_end / l) * (l / max(p, l)))
+
+
+# ---------------------------------------------------------------------------------------------- map planner
+# Shortest paths over a navigable plane (ObstacleMapBatch.navigable_bits: the reference's _navigable_map, obstacles dilated by
+# the robot's footprint, unexplored cells free).  `plan_paths_numpy` is the host statement of the rule; the device path
+# (csrc/map_planner.hip: vlfm_plan_paths, ObstacleMapBatch.plan_paths) matches it bit for bit.  Integers only.  The contract is
+# stated in full in include/vlfm_amd.h ("Map planner"); in short, per JOB (env, y0, y1, x0, x1, sx, sy, start_free, gx, gy,
+# goal_free), cells (x, y) = (column, row):
+#   free     inside the inclusive window: navigable, or dx*dx + dy*dy <= r*r about start (r = start_free) or goal (goal_free)
+#   moves    8-connected, cost 2 (E/N/W/S) or 3 (diagonals); both cells free, and for a diagonal the two cells that share an
+#            edge with both (no corner cutting, no squeezing through a diagonal gap)
+#   field    dist[c]: least cost from the goal, uint16, 0xFFFF = none (blocked, outside, not reached, above max_cost)
+#   descent  from start, at most `lookahead` steps, each to the FIRST chain code s = 0..7 (E NE N NW W SW S SE, y down) whose
+#            move is allowed and has dist[next] + cost(s) == dist[cur]
+# cost * 0.5 / pixels_per_meter is the path length in metres; it overstates pure diagonals by 6 % (3/2 against sqrt 2).
+PLAN_OK, PLAN_UNREACHABLE, PLAN_TOO_LONG, PLAN_INVALID = 0, 1, 2, 3
+PLAN_NONE = 0xFFFF
+PLAN_MAX_RADIUS = 4096
+PLAN_JOB_FIELDS = ("env", "y0", "y1", "x0", "x1", "sx", "sy", "start_free", "gx", "gy", "goal_free")
+PLAN_CODE_DX = (1, 1, 0, -1, -1, -1, 0, 1)      # csrc/bitmap.h: code_dx / code_dy
+PLAN_CODE_DY = (0, -1, -1, -1, 0, 1, 1, 1)
+
+
+def plan_jobs_array(jobs) -> np.ndarray:
+    """[n,11] int64 rows in PLAN_JOB_FIELDS order, from such rows or from a structured array with those field names."""
+    a = np.asarray(jobs)
+    if a.dtype.names:
+        a = np.stack([a[f].astype(np.int64) for f in PLAN_JOB_FIELDS], axis=-1)
+    return np.asarray(a, np.int64).reshape(-1, len(PLAN_JOB_FIELDS))
+
+
+def plan_allowed_moves(free: np.ndarray) -> np.ndarray:
+    """[8,h,w] bool: is the move with chain code s out of cell (x, y) = [s, y, x] of the window's ``free`` [h,w] allowed."""
+    h, w = free.shape
+    f = np.zeros((h + 2, w + 2), bool)              # everything outside the window is blocked
+    f[1:-1, 1:-1] = free
+    at = lambda dx, dy: f[1 + dy:1 + dy + h, 1 + dx:1 + dx + w]   # noqa: E731  free[y + dy, x + dx]
+    out = np.zeros((8, h, w), bool)
+    for s in range(8):
+        dx, dy = PLAN_CODE_DX[s], PLAN_CODE_DY[s]
+        out[s] = free & at(dx, dy)
+        if s & 1:                                   # a diagonal: the two cells that share an edge with both ends
+            out[s] &= at(dx, 0) & at(0, dy)
+    return out
+
+
+def plan_paths_numpy(free_or_navigable, jobs, lookahead: int = 15, max_cost: int = 65534):
+    """(results [n,5] int64: status, cost, waypoint_x, waypoint_y, steps;  fields: per job the uint16 [h,w] field of its window,
+    None for an invalid job).  ``free_or_navigable``: [n_envs,S,S] or [S,S] (one slot) of truth values, rows y, columns x.
+    Plain Dijkstra with a heap over the allowed moves, then the descent: slow, and the yardstick."""
+    import heapq
+
+    planes = np.asarray(free_or_navigable).astype(bool)
+    if planes.ndim == 2:
+        planes = planes[None]
+    n_envs, S = planes.shape[0], planes.shape[1]
+    if not 0 <= max_cost <= 65534 or lookahead < 0:
+        raise ValueError("plan_paths_numpy: max_cost in [0, 65534], lookahead >= 0")
+    jobs = plan_jobs_array(jobs)
+    results = np.zeros((len(jobs), 5), np.int64)
+    fields = []
+    for n, (env, y0, y1, x0, x1, sx, sy, rs, gx, gy, rg) in enumerate(jobs.tolist()):
+        results[n] = (PLAN_INVALID, PLAN_NONE, sx, sy, 0)
+        if not (0 <= env < n_envs and 0 <= y0 <= y1 < S and 0 <= x0 <= x1 < S and x0 <= sx <= x1 and y0 <= sy <= y1 and
+                x0 <= gx <= x1 and y0 <= gy <= y1 and 0 <= rs <= PLAN_MAX_RADIUS and 0 <= rg <= PLAN_MAX_RADIUS):
+            fields.append(None)
+            continue
+        free = planes[env, y0:y1 + 1, x0:x1 + 1].copy()
+        h, w = free.shape
+        yy, xx = np.mgrid[y0:y1 + 1, x0:x1 + 1]
+        free |= (xx - sx) ** 2 + (yy - sy) ** 2 <= rs * rs
+        free |= (xx - gx) ** 2 + (yy - gy) ** 2 <= rg * rg
+        # per cell a byte whose bit s says that the move with chain code s is allowed
+        allowed = np.bitwise_or.reduce(plan_allowed_moves(free).astype(np.uint8) << np.arange(8, dtype=np.uint8)[:, None, None],
+                                       axis=0).tobytes()
+        step = [(1 << s, PLAN_CODE_DY[s] * w + PLAN_CODE_DX[s], 3 if s & 1 else 2) for s in range(8)]
+        dist = [PLAN_NONE] * (h * w)                # settled costs
+        best = {(gy - y0) * w + gx - x0: 0}         # tentative costs
+        heap = [(0, (gy - y0) * w + gx - x0)]
+        too_long = False
+        while heap:
+            c, i = heapq.heappop(heap)
+            if dist[i] != PLAN_NONE or best[i] != c:
+                continue                            # (settled already, or a stale entry)
+            if c > max_cost:
+                too_long = True                     # a cell with a finite cost above max_cost: still to expand
+                break
+            dist[i] = c
+            moves = allowed[i]
+            for bit, di, dc in step:
+                if moves & bit and dist[i + di] == PLAN_NONE and c + dc < best.get(i + di, 1 << 30):
+                    best[i + di] = c + dc
+                    heapq.heappush(heap, (c + dc, i + di))
+        fields.append(np.array(dist, np.uint16).reshape(h, w))
+        cur = (sy - y0) * w + sx - x0
+        if dist[cur] == PLAN_NONE:
+            results[n, 0] = PLAN_TOO_LONG if too_long else PLAN_UNREACHABLE
+            continue
+        cost, steps = dist[cur], 0
+        while dist[cur] > 0 and steps < lookahead:
+            for bit, di, dc in step:
+                if allowed[cur] & bit and dist[cur + di] + dc == dist[cur]:
+                    cur, steps = cur + di, steps + 1
+                    break
+            else:
+                raise AssertionError("plan_paths_numpy: a settled cell without a predecessor")
+        results[n] = (PLAN_OK, cost, cur % w + x0, cur // w + y0, steps)
+    return results, fields
+
+
+class MapPlannerController:
+    """Steers by the map: every environment that has a finite goal and neither stops nor initialises plans a shortest path over
+    its navigable plane (``obstacles.plan_paths``: ONE launch and ONE read-back for all of them) and walks towards the cell
+    ``lookahead_m`` along it instead of towards the goal's bearing.  The waypoint's (rho, theta) in the robot frame (the
+    expression of BatchedEpisodes._navigate) replace the goal's; they stay as they are where the plan is not PLAN_OK, and where
+    the descent ends in the goal's own cell (the goal's bearing is exact there, the cell centre's is not).  The action is then
+    ``inner``'s (default: BangBangController): the turn threshold and the detour after a refused move are that rule, stated
+    once.  ``act`` without maps is ``inner.act``.
+
+    ``last_status`` [E]: the plan status of each environment in the last ``act_on_map`` (-1: it did not plan), ``last_cost_m``
+    [E]: cost * 0.5 / pixels_per_meter of the PLAN_OK ones (NaN otherwise; overstates pure diagonals by 6 %)."""
+
+    def __init__(self, lookahead_m: float = 0.75, inner=None) -> None:
+        self.lookahead_m = float(lookahead_m)
+        self.inner = inner if inner is not None else BangBangController()
+        self.last_status = self.last_cost_m = None
+
+    def reset(self, envs=None) -> None:
+        if hasattr(self.inner, "reset"):
+            self.inner.reset(envs)
+
+    def act(self, modes, rho_theta, stops, collided) -> np.ndarray:
+        return self.inner.act(modes, rho_theta, stops, collided)
+
+    def act_on_map(self, obstacles, poses, goals, goal_free_m, modes, rho_theta, stops, collided) -> np.ndarray:
+        E = len(modes)
+        poses = np.asarray(poses, np.float64).reshape(E, 3)
+        goals = np.asarray(goals, np.float64).reshape(E, 2)
+        rt = np.array(rho_theta, np.float64).reshape(E, 2)
+        plan = np.isfinite(goals).all(axis=1) & ~np.asarray(stops, bool) & np.array([m != "initialize" for m in modes], bool)
+        self.last_status, self.last_cost_m = np.full(E, -1, np.int64), np.full(E, np.nan)
+        idx = np.flatnonzero(plan)
+        if len(idx):
+            gf = None
+            if goal_free_m is not None:
+                gf = np.array([np.nan if g is None else g for g in np.asarray(goal_free_m, object).reshape(E)], np.float64)[idx]
+            out = obstacles.plan_paths(poses[idx, :2], goals[idx], env_ids=idx, goal_free_m=gf, lookahead_m=self.lookahead_m)
+            status = np.asarray(out["status"], np.int64)
+            self.last_status[idx] = status
+            self.last_cost_m[idx] = np.where(status == PLAN_OK, out["path_m"], np.nan)
+            use = (status == PLAN_OK) & ~np.asarray(out["at_goal"], bool)
+            d = np.asarray(out["waypoints"], np.float64)[use] - poses[idx[use], :2]
+            c, s = np.cos(-poses[idx[use], 2]), np.sin(-poses[idx[use], 2])
+            lx, ly = c * d[:, 0] - s * d[:, 1], s * d[:, 0] + c * d[:, 1]
+            rt[idx[use]] = np.stack([np.hypot(lx, ly), np.arctan2(ly, lx)], axis=1)
+        return self.inner.act(modes, rt, stops, collided)
