@@ -918,6 +918,34 @@ int vlfm_geodesic_query(const double* d_points, const int32_t* d_field_of, int m
                         const double* d_sources, const int32_t* d_source_counts, int max_sources, double* d_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Procedural worlds (ABI 22): a world per camera / per field instead of one shared box table (vlfm_amd.synthetic.
+ * ProceduralWorlds generates the floor plans; harness.WorldTable keeps the table).
+ *   d_world_boxes  [n_worlds][max_boxes][4] doubles: x0, y0, x1, y1
+ *   d_box_counts   [n_worlds] int32: the boxes of each world, clamped to [0, max_boxes] by the kernels; rows beyond a world's
+ *                  count are never read as boxes, whatever they hold
+ *   d_world_of     [n] int32: the world (row of the table) of each camera / field.  An index outside [0, n_worlds) is an EMPTY
+ *                  world; the kernels never read out of bounds for it (the Python wrappers refuse it before any launch).
+ *
+ * vlfm_worlds_raycast: vlfm_rooms_raycast_objects with the walls of each camera's own world, ONE launch plus the fill of d_stats,
+ * bit for bit synthetic.render_objects_numpy(..., boxes = that world's boxes) / object_stats_numpy.  d_objects == NULL: walls
+ * only -- d_env_of, n_envs, d_ids and d_stats are ignored and the frames are vlfm_rooms_raycast's, i.e.
+ * depth_from_profile(wall_profile(..., boxes = ...)).  Grid, row bands, LDS layout and store paths are those of the shared-table
+ * entries; a workgroup stages the `count` boxes of its camera's world.  The LDS budget is that of the shared-table entries with
+ * n_boxes = max_boxes (VLFM_ERR_INVALID otherwise, nothing launched, nothing written); n <= 65535, and H <= 32768 with objects.
+ *
+ * vlfm_geodesic_fields_worlds: vlfm_geodesic_fields with the rectangles of field i = the `count` boxes of world d_world_of[i], then
+ * the valid objects of d_objects[i] -- synthetic.inflated_rects(objects, margin, boxes) -- ONE launch, one workgroup per field,
+ * bit for bit synthetic.geodesic_field_numpy.  The outputs are strided by R = max_boxes + 8 whatever the counts, so
+ * vlfm_geodesic_query reads them unchanged when called with n_boxes = max_boxes.  R <= 141 (VLFM_ERR_INVALID otherwise). */
+int vlfm_worlds_raycast(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts, int n_worlds,
+                        int max_boxes, const int32_t* d_world_of, const double* d_objects, const int32_t* d_env_of, int n_envs,
+                        int H, int W, float* d_depth, uint8_t* d_ids, int32_t* d_stats, void* stream);
+int vlfm_geodesic_fields_worlds(const double* d_world_boxes, const int32_t* d_box_counts, int n_worlds, int max_boxes,
+                                const int32_t* d_world_of, double margin, const double* d_objects, const double* d_sources,
+                                const int32_t* d_source_counts, int n, int max_sources, double* d_rects, double* d_nodes,
+                                double* d_dist, int32_t* d_counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Map planner (ABI 21, csrc/map_planner.hip): shortest paths over the navigable planes of the obstacle maps (the reference's
  * _navigable_map: obstacles dilated by the robot's footprint, unexplored cells free), n jobs in ONE launch, one workgroup per
  * job.  Integers only; bit for bit vlfm_amd.synthetic.plan_paths_numpy (Dijkstra with a heap over the same rule).

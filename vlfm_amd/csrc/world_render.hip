@@ -17,12 +17,15 @@
 // normalised floor values of its band of rows in LDS; the column profile is recomputed per band (W * B * 4 divisions) so that a
 // handful of cameras still spreads over the chip.  With W a multiple of 4 and a 16-byte aligned output every lane owns 4
 // adjacent columns and a band leaves as consecutive 16-byte stores; any other W takes the scalar store loop.
+// The kernels are templates over where a workgroup finds its boxes: one shared table (vlfm_rooms_raycast, vlfm_rooms_raycast_objects)
+// or the row of its camera's world in a table of worlds (vlfm_worlds_raycast, at the end of the file).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/vlfm_amd.h"
 #include "profile.h"
 #include "status.h"
+#include "world_table.h"
 
 namespace vlfm {
 namespace world {
@@ -41,16 +44,18 @@ __device__ __forceinline__ float normalise(double d, double lo, double span) {
     return (float)v;
 }
 
-__global__ __launch_bounds__(THREADS) void rooms_raycast_kernel(const CameraRec* __restrict__ cameras,
-                                                                const double* __restrict__ boxes, int n_boxes, int H, int W,
-                                                                int band, int vec4, float* __restrict__ out) {
+template <class Table>
+__global__ __launch_bounds__(THREADS) void rooms_raycast_kernel(const CameraRec* __restrict__ cameras, const Table table, int H,
+                                                                int W, int band, int vec4, float* __restrict__ out) {
     extern __shared__ double smem[];
     const int r0 = blockIdx.x * band;
     if (r0 >= H) return;                                   // (uniform for the workgroup: before any barrier)
     const int rows = min(band, H - r0);
     const int tid = threadIdx.x;
-    double* sbox = smem;                                   // [n_boxes][4]
-    float* ncol = reinterpret_cast<float*>(smem + 4 * n_boxes);   // [W rounded up to 4]: 16-byte aligned (32 * n_boxes bytes in)
+    int n_boxes;
+    const double* __restrict__ boxes = table.find(blockIdx.y, n_boxes);
+    double* sbox = smem;                                   // [capacity][4], n_boxes of them staged
+    float* ncol = reinterpret_cast<float*>(smem + 4 * table.capacity());   // [W rounded up to 4]: 16-byte aligned (32 * capacity bytes in)
     float* nrow = ncol + ((W + 3) & ~3);                   // [band]
     const CameraRec cam = cameras[blockIdx.y];
     for (int i = tid; i < 4 * n_boxes; i += THREADS) sbox[i] = boxes[i];
@@ -138,8 +143,8 @@ extern "C" int vlfm_rooms_raycast(const double* d_cameras, int n, const double* 
     const int vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_out) % 16 == 0);
     hipStream_t st = (hipStream_t)stream;
     VLFM_TIMED("rooms_raycast_kernel", st);
-    VLFM_KLAUNCH(rooms_raycast_kernel, dim3(grid_x, n), dim3(THREADS), lds, st,
-                 reinterpret_cast<const CameraRec*>(d_cameras), d_boxes, n_boxes, H, W, band, vec4, d_out);
+    VLFM_KLAUNCH(rooms_raycast_kernel<SharedBoxes>, dim3(grid_x, n), dim3(THREADS), lds, st,
+                 reinterpret_cast<const CameraRec*>(d_cameras), SharedBoxes{d_boxes, n_boxes}, H, W, band, vec4, d_out);
     return check_launch("rooms_raycast_kernel");
 }
 
@@ -216,8 +221,9 @@ __device__ __forceinline__ float shade(float bg, unsigned mask, const ObjCol* __
     return fminf(bg, best);
 }
 
+template <class Table>
 __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
-    const CameraRec* __restrict__ cameras, const double* __restrict__ boxes, int n_boxes, const double* __restrict__ objects,
+    const CameraRec* __restrict__ cameras, const Table table, const double* __restrict__ objects,
     const int32_t* __restrict__ env_of, int n_envs, int H, int W, int band, int vec4, float* __restrict__ out,
     uint8_t* __restrict__ ids, int32_t* __restrict__ stats) {
     extern __shared__ double smem[];
@@ -226,10 +232,12 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
     const int rows = min(band, H - r0);
     const int tid = threadIdx.x;
     const int wp = (W + 3) & ~3;
-    double* sbox = smem;                                   // [n_boxes][4]
-    double* sobj = sbox + 4 * n_boxes;                     // [8][8]
+    int n_boxes;
+    const double* __restrict__ boxes = table.find(blockIdx.y, n_boxes);
+    double* sbox = smem;                                   // [capacity][4], n_boxes of them staged
+    double* sobj = sbox + 4 * table.capacity();            // [8][8]
     ObjCol* ent = reinterpret_cast<ObjCol*>(sobj + MAX_OBJECTS * OBJ_REC);      // [8][wp]
-    float* ncol = reinterpret_cast<float*>(ent + MAX_OBJECTS * wp);            // [wp]: 16-byte aligned (32 * n_boxes + 512 + 64 * wp in)
+    float* ncol = reinterpret_cast<float*>(ent + MAX_OBJECTS * wp);            // [wp]: 16-byte aligned (32 * capacity + 512 + 64 * wp in)
     float* nrow = ncol + wp;                               // [band]
     int* sstat = reinterpret_cast<int*>(nrow + band);      // [8][5]
     uint8_t* cmask = reinterpret_cast<uint8_t*>(sstat + 5 * MAX_OBJECTS);       // [wp]: 4-byte aligned
@@ -403,8 +411,56 @@ extern "C" int vlfm_rooms_raycast_objects(const double* d_cameras, int n, const 
     int rc = check_launch("rooms_stats_init_kernel");
     if (rc != VLFM_OK) return rc;
     VLFM_TIMED("rooms_raycast_objects_kernel", st);
-    VLFM_KLAUNCH(rooms_raycast_objects_kernel, dim3(grid_x, n), dim3(THREADS), lds, st,
-                 reinterpret_cast<const CameraRec*>(d_cameras), d_boxes, n_boxes, d_objects, d_env_of, n_envs, H, W, band, vec4,
-                 d_depth, d_ids, d_stats);
+    VLFM_KLAUNCH(rooms_raycast_objects_kernel<SharedBoxes>, dim3(grid_x, n), dim3(THREADS), lds, st,
+                 reinterpret_cast<const CameraRec*>(d_cameras), SharedBoxes{d_boxes, n_boxes}, d_objects, d_env_of, n_envs, H, W,
+                 band, vec4, d_depth, d_ids, d_stats);
     return check_launch("rooms_raycast_objects_kernel");
+}
+
+// ------------------------------------------------------------------------------------------------------------ a world per camera
+// vlfm_worlds_raycast: the two kernels above with the boxes looked up per camera in a table of worlds (WorldBoxes): a workgroup
+// stages the `count` boxes of ITS camera's world.  Grid, bands, LDS layout (sized by max_boxes) and store paths are those of the
+// shared-table entries; d_objects == NULL renders walls only.
+extern "C" int vlfm_worlds_raycast(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts,
+                                   int n_worlds, int max_boxes, const int32_t* d_world_of, const double* d_objects,
+                                   const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids,
+                                   int32_t* d_stats, void* stream) {
+    const bool with_objects = d_objects != nullptr;
+    if (n < 0 || n > 65535 || n_worlds < 0 || max_boxes < 0 || H <= 0 || W <= 0 || (n > 0 && (!d_cameras || !d_world_of || !d_depth)) ||
+        (n_worlds > 0 && (!d_box_counts || (max_boxes > 0 && !d_world_boxes))) ||
+        (with_objects && (n_envs <= 0 || H > 32768 || (n > 0 && (!d_env_of || !d_ids || !d_stats)))))
+        return fail(VLFM_ERR_INVALID, "worlds_raycast: bad argument");
+    if (n == 0) return VLFM_OK;
+    const long long want = 4LL * device_cu_count();         // row bands: as in vlfm_rooms_raycast
+    long long bands = (want + n - 1) / n;
+    const long long most = (H + MIN_BAND_ROWS - 1) / MIN_BAND_ROWS;
+    bands = bands < 1 ? 1 : (bands > most ? most : bands);
+    const int band = (int)((H + bands - 1) / bands);
+    const int grid_x = (H + band - 1) / band;
+    const size_t wp = (size_t)((W + 3) & ~3);
+    const WorldBoxes table{d_world_boxes, d_box_counts, d_world_of, n_worlds, max_boxes};
+    hipStream_t st = (hipStream_t)stream;
+    if (!with_objects) {
+        const size_t lds = (size_t)max_boxes * 32 + wp * 4 + (size_t)band * 4;
+        if (lds > 64 * 1024) return fail(VLFM_ERR_INVALID, "worlds_raycast: max_boxes + one image row + one row band exceed 64 KB of LDS");
+        const int vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_depth) % 16 == 0);
+        VLFM_TIMED("worlds_raycast_kernel", st);
+        VLFM_KLAUNCH(rooms_raycast_kernel<WorldBoxes>, dim3(grid_x, n), dim3(THREADS), lds, st,
+                     reinterpret_cast<const CameraRec*>(d_cameras), table, H, W, band, vec4, d_depth);
+        return check_launch("worlds_raycast_kernel");
+    }
+    const size_t lds = (size_t)max_boxes * 32 + MAX_OBJECTS * OBJ_REC * 8 + wp * MAX_OBJECTS * sizeof(ObjCol) + wp * 4 +
+                       (size_t)band * 4 + 5 * MAX_OBJECTS * 4 + wp;
+    if (lds > 64 * 1024)
+        return fail(VLFM_ERR_INVALID, "worlds_raycast: max_boxes + 69 bytes per image column + one row band exceed 64 KB of LDS");
+    const int vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_depth) % 16 == 0) && (reinterpret_cast<uintptr_t>(d_ids) % 4 == 0);
+    const int total = n * 5 * MAX_OBJECTS;
+    VLFM_KLAUNCH(rooms_stats_init_kernel, dim3((total + THREADS - 1) / THREADS), dim3(THREADS), 0, st, d_stats, total, H, W);
+    int rc = check_launch("rooms_stats_init_kernel");
+    if (rc != VLFM_OK) return rc;
+    VLFM_TIMED("worlds_raycast_objects_kernel", st);
+    VLFM_KLAUNCH(rooms_raycast_objects_kernel<WorldBoxes>, dim3(grid_x, n), dim3(THREADS), lds, st,
+                 reinterpret_cast<const CameraRec*>(d_cameras), table, d_objects, d_env_of, n_envs, H, W, band, vec4, d_depth, d_ids,
+                 d_stats);
+    return check_launch("worlds_raycast_objects_kernel");
 }

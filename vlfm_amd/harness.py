@@ -34,7 +34,7 @@ from .mapping.base_map import require_gpu
 from .mapping.value_map import ValueMapBatch
 from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TURN_RIGHT, BOXES, CAMERA_HEIGHT, HEADINGS, \
     MAX_DEPTH, MIN_DEPTH, YAWS, BangBangController, ReplayController, Trajectory, camera_intrinsics, depth_frame, integrate, \
-    GEODESIC_MAX_SOURCES, STEP_MARGIN, WORLD_MAX_OBJECTS, goal_viewpoints, inflated_rects, object_layout, plan_actions, \
+    GEODESIC_MAX_SOURCES, STEP_MARGIN, WORLD_MAX_BOXES, WORLD_MAX_OBJECTS, ProceduralWorlds, goal_viewpoints, inflated_rects, object_layout, plan_actions, \
     pose_to_tf, rect_distance, rgb_frame, soft_spl, spl, step_poses, tf_of, PLAN_INVALID, PLAN_OK, PLAN_TOO_LONG, \
     PLAN_UNREACHABLE
 
@@ -257,6 +257,54 @@ class GeodesicFields:
         self.has_target[rows] = other.has_target
 
 
+class WorldTable:
+    """A table of ``n_worlds`` floor plans for the per-world entries (RoomsRenderer.cast_worlds / geodesic_fields_worlds): the
+    host mirror -- ``boxes`` [n_worlds,max_boxes,4] f64, NaN beyond each world's ``counts`` [n_worlds] int32 (what
+    synthetic.step_poses takes as ``boxes``) -- and its copy on ``device`` (``d_boxes``, ``d_counts``).  Every world starts
+    empty."""
+
+    def __init__(self, n_worlds: int, device, max_boxes: int = WORLD_MAX_BOXES) -> None:
+        if n_worlds < 0 or max_boxes < 0:
+            raise ValueError("WorldTable: n_worlds and max_boxes must not be negative")
+        self.n_worlds, self.max_boxes, self.device = int(n_worlds), int(max_boxes), torch.device(device)
+        self.boxes = np.full((self.n_worlds, self.max_boxes, 4), np.nan)
+        self.counts = np.zeros(self.n_worlds, np.int32)
+        self.d_boxes = torch.full((self.n_worlds, self.max_boxes, 4), float("nan"), dtype=torch.float64, device=self.device)
+        self.d_counts = torch.zeros((self.n_worlds,), dtype=torch.int32, device=self.device)
+
+    def world(self, row: int) -> np.ndarray:
+        """[count,4] f64: the boxes of world ``row`` (a copy of the host mirror's)."""
+        return self.boxes[row, :self.counts[row]].copy()
+
+    def assign(self, rows, list_of_boxes) -> None:
+        """World ``rows[i]`` becomes the boxes ``list_of_boxes[i]`` [B_i,4] (finite, B_i <= max_boxes).  Only these rows cross,
+        in ONE host-to-device copy (boxes, counts and row indices in one buffer), and are scattered into the table on the
+        device, on the current stream."""
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        worlds = [np.asarray(b, np.float64).reshape(-1, 4) for b in list_of_boxes]
+        if len(rows) != len(worlds):
+            raise ValueError("WorldTable.assign: one list of boxes per row")
+        if np.any((rows < 0) | (rows >= self.n_worlds)) or len(np.unique(rows)) != len(rows):
+            raise ValueError("WorldTable.assign: rows must be distinct rows of the table")
+        for b in worlds:
+            if len(b) > self.max_boxes:
+                raise ValueError(f"WorldTable.assign: a world of {len(b)} boxes, the table holds {self.max_boxes} per world")
+            if not np.all(np.isfinite(b)):
+                raise ValueError("WorldTable.assign: boxes must be finite")
+        if not len(rows):
+            return
+        blob = np.full((len(rows), 4 * self.max_boxes + 2), np.nan)
+        for i, b in enumerate(worlds):
+            blob[i, :4 * len(b)] = b.reshape(-1)
+            blob[i, -2:] = len(b), rows[i]
+        self.boxes[rows] = blob[:, :-2].reshape(len(rows), self.max_boxes, 4)
+        self.counts[rows] = [len(b) for b in worlds]
+        d_blob = torch.from_numpy(blob).to(self.device)
+        idx = d_blob[:, -1].long()
+        self.d_boxes.index_copy_(0, idx, d_blob[:, :-2].reshape(len(rows), self.max_boxes, 4))
+        self.d_counts.index_copy_(0, idx, d_blob[:, -2].to(torch.int32))
+
+
 class RoomsRenderer:
     """Depth frames of the consistent rooms-and-pillars world (vlfm_amd/synthetic.py) for E environments at once, ray-cast ON
     THE DEVICE (f64, the arithmetic of synthetic.wall_profile / depth_from_profile batched over environments): environment
@@ -453,6 +501,115 @@ class RoomsRenderer:
         return h
 
     @torch.no_grad()
+    def cast_worlds(self, tf: np.ndarray, table: WorldTable, world_of, objects: Optional[np.ndarray] = None, env_of=None,
+                    hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None, out: Optional[torch.Tensor] = None):
+        """``cast_cameras_objects`` with a floor plan per camera (vlfm_worlds_raycast, one launch on the current stream): camera i
+        stands in world ``world_of[i]`` of ``table`` and sees the objects ``objects[env_of[i]]``.  Returns (depth, ids, stats) as
+        ``cast_cameras_objects`` does, bit for bit synthetic.render_objects_numpy(..., boxes=table.world(world_of[i])); with
+        ``objects=None`` the walls-only frames, as ``cast_cameras`` returns them.  Camera records, object records and both index
+        lists cross in one small copy."""
+        tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
+        n = len(tf)
+        dev = self.boxes.device
+        if table.device != dev:
+            raise ValueError(f"cast_worlds: the world table must live on {dev}")
+        world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
+        if len(world_of) != n or np.any((world_of < 0) | (world_of >= table.n_worlds)):
+            raise ValueError("cast_worlds: world_of must name one world of the table per camera")
+        if objects is None:
+            objects, env_of = np.zeros((0, WORLD_MAX_OBJECTS, 8)), np.zeros(n, np.int32)
+        else:
+            objects = np.ascontiguousarray(objects, np.float64)
+            if objects.ndim != 3 or objects.shape[0] < 1 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
+                raise ValueError(f"cast_worlds: objects must be [n_envs >= 1, {WORLD_MAX_OBJECTS}, 8]")
+            env_of = np.ascontiguousarray(np.asarray(env_of).reshape(-1), np.int32)
+            if len(env_of) != n or np.any((env_of < 0) | (env_of >= len(objects))):
+                raise ValueError("cast_worlds: env_of must name one row of objects per camera")
+        with_objects = len(objects) > 0
+        rec = np.empty((n, 8), np.float64)
+        rec[:, 0:2], rec[:, 2:4], rec[:, 4] = tf[:, :2, 3], tf[:, :2, 0], tf[:, 2, 3]
+        rec[:, 5] = camera_intrinsics(self.W)[0] if hfov is None else self.W / (2 * np.tan(np.asarray(hfov, np.float64) / 2))
+        rec[:, 6] = MIN_DEPTH if min_depth is None else np.asarray(min_depth, np.float64)
+        rec[:, 7] = MAX_DEPTH if max_depth is None else np.asarray(max_depth, np.float64)
+        if not np.all(rec[:, 7] > rec[:, 6]):
+            raise ValueError("cast_worlds: every camera needs max_depth > min_depth")
+        if out is None:
+            out = torch.empty((n, self.H, self.W), dtype=torch.float32, device=dev)
+        elif out.shape != (n, self.H, self.W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"cast_worlds: out must be a contiguous f32 [{n},{self.H},{self.W}] tensor on {dev}")
+        ids = stats = None
+        if with_objects:
+            ids = torch.empty((n, self.H, self.W), dtype=torch.uint8, device=dev)
+            stats = torch.empty((n, WORLD_MAX_OBJECTS, 5), dtype=torch.int32, device=dev)
+        if n > 0:
+            with torch.cuda.device(dev):
+                # camera records, object records, world_of and env_of in ONE host buffer and one copy (all 8-byte aligned pieces)
+                pad = (n + 1) // 2
+                blob = np.concatenate([rec.reshape(-1), objects.reshape(-1), np.zeros(2 * pad, np.float64)])
+                blob[rec.size + objects.size:].view(np.int32)[:n] = world_of
+                blob[rec.size + objects.size + pad:].view(np.int32)[:n] = env_of
+                d_blob = torch.from_numpy(blob).to(dev)
+                p = d_blob.data_ptr()
+                p_world_of = p + 8 * (rec.size + objects.size)
+                stream = torch.cuda.current_stream().cuda_stream
+                _lib.check(_lib.lib().vlfm_worlds_raycast(
+                    p, n, table.d_boxes.data_ptr(), table.d_counts.data_ptr(), table.n_worlds, table.max_boxes, p_world_of,
+                    p + 8 * rec.size if with_objects else None, p_world_of + 8 * pad, len(objects), self.H, self.W,
+                    out.data_ptr(), ids.data_ptr() if with_objects else None, stats.data_ptr() if with_objects else None,
+                    stream), "worlds_raycast")
+        return (out, ids, stats) if with_objects else out
+
+    @torch.no_grad()
+    def geodesic_fields_worlds(self, table: WorldTable, world_of, objects: np.ndarray, targets_boxes, success_distance: float,
+                               max_sources: int = GEODESIC_MAX_SOURCES) -> GeodesicFields:
+        """``geodesic_fields`` with a floor plan per field (vlfm_geodesic_fields_worlds, ONE launch on the current stream): the
+        obstacles of field i are the walls of world ``world_of[i]`` of ``table`` and the valid footprints of ``objects[i]``,
+        i.e. synthetic.inflated_rects(objects[i], STEP_MARGIN, table.world(world_of[i])).  The handle is strided by
+        R = table.max_boxes + 8; ``geodesic_distances`` and ``GeodesicFields.assign`` take it as they take any other."""
+        objects = np.ascontiguousarray(objects, np.float64)
+        if objects.ndim != 3 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
+            raise ValueError(f"geodesic_fields_worlds: objects must be [n, {WORLD_MAX_OBJECTS}, 8]")
+        n = len(objects)
+        dev = self.boxes.device
+        if table.device != dev:
+            raise ValueError(f"geodesic_fields_worlds: the world table must live on {dev}")
+        world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
+        if len(world_of) != n or np.any((world_of < 0) | (world_of >= table.n_worlds)):
+            raise ValueError("geodesic_fields_worlds: world_of must name one world of the table per field")
+        boxes = np.asarray(targets_boxes, np.float64).reshape(n, -1)[:, :4] if n else np.zeros((0, 4))
+        # sources, their counts and world_of in one host buffer: [n][max_sources][2] doubles, then two int32 lists
+        pad = (n + 1) // 2
+        blob = np.zeros(n * max_sources * 2 + 2 * pad)
+        src = blob[:n * max_sources * 2].reshape(n, max_sources, 2)
+        cnt = blob[n * max_sources * 2:].view(np.int32)[:n]
+        blob[n * max_sources * 2 + pad:].view(np.int32)[:n] = world_of
+        has = np.zeros(n, bool)
+        for e in range(n):
+            if np.all(np.isfinite(boxes[e])):
+                pts = goal_viewpoints(boxes[e], inflated_rects(objects[e], STEP_MARGIN, table.world(world_of[e])),
+                                      success_distance, max_sources)
+                src[e, :len(pts)], cnt[e], has[e] = pts, len(pts), True
+        R = table.max_boxes + WORLD_MAX_OBJECTS
+        f64 = dict(dtype=torch.float64, device=dev)
+        h = GeodesicFields(n, max_sources, torch.empty((n, R, 4), **f64), torch.empty((n, 4 * R, 2), **f64),
+                           torch.empty((n, 4 * R), **f64), torch.empty((n, 2), dtype=torch.int32, device=dev),
+                           torch.empty((n, max_sources, 2), **f64), torch.empty((n,), dtype=torch.int32, device=dev), has)
+        if n == 0:
+            return h
+        with torch.cuda.device(dev):
+            d_obj = torch.from_numpy(objects).to(dev)
+            d_blob = torch.from_numpy(blob).to(dev)
+            h.sources.copy_(d_blob[:n * max_sources * 2].view(n, max_sources, 2))
+            h.source_counts.copy_(d_blob[n * max_sources * 2:].view(torch.int32)[:n])
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().vlfm_geodesic_fields_worlds(
+                table.d_boxes.data_ptr(), table.d_counts.data_ptr(), table.n_worlds, table.max_boxes,
+                d_blob.data_ptr() + 8 * (n * max_sources * 2 + pad), STEP_MARGIN, d_obj.data_ptr(), h.sources.data_ptr(),
+                h.source_counts.data_ptr(), n, max_sources, h.rects.data_ptr(), h.nodes.data_ptr(), h.dist.data_ptr(),
+                h.counts.data_ptr(), stream), "geodesic_fields_worlds")
+        return h
+
+    @torch.no_grad()
     def geodesic_distances(self, handle: GeodesicFields, field_of, xy) -> torch.Tensor:
         """f64 [m] on the device: the geodesic distance to the goal of the points ``xy`` [m,2], point i in the field
         ``field_of[i]`` of ``handle`` (-1: no field, the answer is NaN), ONE launch on the current stream
@@ -472,7 +629,8 @@ class RoomsRenderer:
             d_blob = torch.from_numpy(blob).to(dev)
             p = d_blob.data_ptr()
             stream = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().vlfm_geodesic_query(p, p + 16 * m, m, handle.n, len(self.boxes), handle.rects.data_ptr(),
+            n_boxes = handle.rects.shape[1] - WORLD_MAX_OBJECTS     # the stride the handle was built with (walls + 8)
+            _lib.check(_lib.lib().vlfm_geodesic_query(p, p + 16 * m, m, handle.n, n_boxes, handle.rects.data_ptr(),
                                                       handle.nodes.data_ptr(), handle.dist.data_ptr(), handle.counts.data_ptr(),
                                                       handle.sources.data_ptr(), handle.source_counts.data_ptr(),
                                                       handle.max_sources, out.data_ptr(), stream), "geodesic_query")
@@ -511,7 +669,8 @@ class BatchedEpisodes:
                  render_trajectories: bool = False, emulate_jpeg: bool = False, rig: Optional[CameraRig] = None,
                  text_prompt: str = PROMPT, exploration_thresh: Optional[float] = None, closed_loop: bool = False,
                  controller=None, world_objects: Optional[WorldObjects] = None, batch_object_maps: bool = True,
-                 device_object_clouds: bool = True, objectnav_metrics: bool = False) -> None:
+                 device_object_clouds: bool = True, objectnav_metrics: bool = False,
+                 worlds: Optional[ProceduralWorlds] = None) -> None:
         # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
         # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -561,6 +720,18 @@ class BatchedEpisodes:
         self.objectnav_metrics = bool(objectnav_metrics)
         if self.objectnav_metrics and world_objects is None:
             raise ValueError("objectnav_metrics scores ObjectNav episodes: it needs world_objects")
+        # worlds: environment e lives in its OWN floor plan, worlds.world(env_ids[e], episode) -- its robot starts at that world's
+        # start pose, its depth is ray-cast against that world's walls (RoomsRenderer.cast_worlds, still one launch per step), its
+        # moves are refused by them, and with world_objects every episode end draws the NEXT world (layouts from the world's own
+        # spots, geodesics over its own walls); without world_objects it stays in episode 0's.  None: the one rooms world
+        self.worlds = worlds
+        if worlds is not None:
+            if not self.closed_loop:
+                raise ValueError("worlds needs closed_loop=True: the open-loop tour is planned through the rooms world")
+            if rig is not None:
+                raise ValueError("worlds renders the robot's own camera: it cannot be combined with a camera rig")
+            if sightings is not None:
+                raise ValueError("worlds cannot be combined with the scripted sightings, which are painted along the rooms tour")
         self.device = require_gpu(device)
         # rig: K cameras per environment (CameraRig) fused into the environment's maps by ONE ingest_cameras / update_cameras per
         # step (step() -> _step_rig()); None = one camera at the robot pose, the step as it always was
@@ -627,6 +798,11 @@ class BatchedEpisodes:
                 self.world_xy, self.world_k = self._start_xy.copy(), self._start_k.copy()
                 self._collided = np.zeros(n_envs, bool)
                 self._live_frames = None
+                if worlds is not None:
+                    self.world_table = WorldTable(n_envs, self.device)
+                    self.world_episode = np.full(n_envs, -1, np.int64)      # the episode whose world each environment is in
+                    if world_objects is None:
+                        self._enter_worlds(range(n_envs), np.zeros(n_envs, np.int64))
                 z = lambda dt: np.zeros(n_envs, dt)   # noqa: E731
                 self.closed_loop_stats = {"path_length": z(np.float64), "collisions": z(np.int64), "forward_steps": z(np.int64),
                                           "turn_steps": z(np.int64), "stops": z(np.int64)}
@@ -976,8 +1152,14 @@ class BatchedEpisodes:
             self._objects = np.zeros((self.E, WORLD_MAX_OBJECTS, 8))
             self._object_classes: List[List[str]] = [[] for _ in range(self.E)]
             self._target_slot = np.full(self.E, -1, np.int64)
+        envs = list(envs)
+        layout = self.world_objects.layout
+        if self.worlds is not None:                 # the episode's own world first: the layout is drawn around ITS start
+            self._enter_worlds(envs, self._ep_index[envs])
+            if layout is object_layout:
+                layout = self.worlds.layout
         for e in envs:
-            lay = list(self.world_objects.layout(self.env_ids[e], int(self._ep_index[e]), self.world_xy[e].copy()))
+            lay = list(layout(self.env_ids[e], int(self._ep_index[e]), self.world_xy[e].copy()))
             if len(lay) > WORLD_MAX_OBJECTS:
                 raise ValueError(f"a layout may hold at most {WORLD_MAX_OBJECTS} objects")
             self._objects[e] = 0.0
@@ -989,6 +1171,18 @@ class BatchedEpisodes:
         if self.objectnav_metrics:
             self._start_geodesics(np.array(list(envs), np.int64))
 
+    def _enter_worlds(self, envs, episodes) -> None:
+        """worlds: the environments ``envs`` move into the worlds of their ``episodes`` -- the table rows cross in one copy -- and
+        their robots stand at those worlds' start poses, nothing refused yet."""
+        envs = list(envs)
+        made = [self.worlds.world(self.env_ids[e], int(k)) for e, k in zip(envs, episodes)]
+        self.world_table.assign(envs, [w.boxes for w in made])
+        for e, k, w in zip(envs, episodes, made):
+            self._start_xy[e], self._start_k[e] = w.start_xy, w.start_k
+            self.world_xy[e], self.world_k[e] = w.start_xy, w.start_k
+            self._collided[e] = False
+            self.world_episode[e] = int(k)
+
     def _start_geodesics(self, envs: np.ndarray) -> None:
         """objectnav_metrics: the geodesic fields of the episodes ``envs`` start now, ONE launch, and ``l`` of each -- the
         distance to the goal from where its robot stands (nan: the layout has no target; inf: no way to it)."""
@@ -996,7 +1190,11 @@ class BatchedEpisodes:
             return
         slots = self._target_slot[envs]
         boxes = np.where((slots >= 0)[:, None], self._objects[envs, np.maximum(slots, 0), :4], np.nan)
-        fresh = self.rooms.geodesic_fields(self._objects[envs], boxes, self.world_objects.success_distance)
+        if self.worlds is not None:
+            fresh = self.rooms.geodesic_fields_worlds(self.world_table, envs, self._objects[envs], boxes,
+                                                      self.world_objects.success_distance)
+        else:
+            fresh = self.rooms.geodesic_fields(self._objects[envs], boxes, self.world_objects.success_distance)
         if self._geodesic is None:              # (the first call starts every environment's episode)
             assert len(envs) == self.E and np.array_equal(envs, np.arange(self.E))
             self._geodesic = fresh
@@ -1346,9 +1544,15 @@ class BatchedEpisodes:
         renders into one buffer it keeps (every reader of the previous step's frames was joined back into the main stream)."""
         if self._live_frames is None and not fresh:
             self._live_frames = torch.empty((self.E, self.H, self.W), dtype=torch.float32, device=self.device)
+        if self.worlds is not None and self.world_objects is None:
+            return self.rooms.cast_worlds(tf, self.world_table, np.arange(self.E), out=None if fresh else self._live_frames)
         if self.world_objects is not None:
-            d, ids, stats = self.rooms.cast_cameras_objects(tf, self._objects, np.arange(self.E),
-                                                            out=None if fresh else self._live_frames)
+            if self.worlds is not None:
+                d, ids, stats = self.rooms.cast_worlds(tf, self.world_table, np.arange(self.E), self._objects, np.arange(self.E),
+                                                       out=None if fresh else self._live_frames)
+            else:
+                d, ids, stats = self.rooms.cast_cameras_objects(tf, self._objects, np.arange(self.E),
+                                                                out=None if fresh else self._live_frames)
             if not fresh:
                 wo = self.world_objects
                 self._live_ids, self._live_stats = ids, stats.cpu().numpy()     # the one extra D2H copy of this mode
@@ -1389,7 +1593,8 @@ class BatchedEpisodes:
         if self.world_objects is not None:
             acts = np.where(self.last_episode_end, ACTION_STOP, acts)     # an episode that ended: the robot stays where it is
             extra = np.where(self._objects[:, :, 6:7] != 0.0, self._objects[:, :, :4], np.nan)
-        self.world_xy, self.world_k, self._collided = step_poses(self.world_xy, self.world_k, acts, extra)
+        self.world_xy, self.world_k, self._collided = step_poses(self.world_xy, self.world_k, acts, extra,
+                                                                 None if self.worlds is None else self.world_table.boxes)
         st = self.closed_loop_stats
         fwd = acts == ACTION_FORWARD
         st["forward_steps"] += fwd

@@ -3,6 +3,8 @@ scripted trajectories and stub values.  Used by bench.py, the harness and the pa
 oracle are fed from here, so they see identical inputs)."""
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 
 HFOV_DEG = 79.0
@@ -134,8 +136,15 @@ WAYPOINTS = [(0.6, 2.0), (3.4, 2.0), (5.4, 2.0), (6.9, 3.9), (8.9, 4.2), (8.9, 7
              (8.6, -5.9), (9.2, -5.7), (9.2, -2.2), (5.4, -2.0), (3.4, -2.0), (3.0, -0.6), (0.0, 0.0)]
 
 
-def wall_profile(x: float, y: float, k: int, width: int = ROOMS_W) -> np.ndarray:
-    """(width,) f32 depth along the optical axis of the nearest box face per image column (inf where nothing is hit)."""
+def _walls_of(boxes) -> np.ndarray:
+    """[B,4] f64: the walls a host statement works on -- ``boxes``, or the rooms world's BOXES for None."""
+    return BOXES if boxes is None else np.asarray(boxes, np.float64).reshape(-1, 4)
+
+
+def wall_profile(x: float, y: float, k: int, width: int = ROOMS_W, boxes=None) -> np.ndarray:
+    """(width,) f32 depth along the optical axis of the nearest box face per image column (inf where nothing is hit).
+    ``boxes`` [B,4]: the walls of the world (None: BOXES)."""
+    b = _walls_of(boxes)
     fx = camera_intrinsics(width)[0]
     c, s = HEADINGS[k]
     m = -(np.arange(width, dtype=np.float64) - width // 2) / fx        # geometry_utils.py:216-236: y_cam = -(u - W//2) z / fx
@@ -143,12 +152,12 @@ def wall_profile(x: float, y: float, k: int, width: int = ROOMS_W) -> np.ndarray
     tiny = 1e-12
     dx = np.where(np.abs(dx) < tiny, tiny, dx)
     dy = np.where(np.abs(dy) < tiny, tiny, dy)
-    tx0, tx1 = (BOXES[None, :, 0] - x) / dx, (BOXES[None, :, 2] - x) / dx
-    ty0, ty1 = (BOXES[None, :, 1] - y) / dy, (BOXES[None, :, 3] - y) / dy
+    tx0, tx1 = (b[None, :, 0] - x) / dx, (b[None, :, 2] - x) / dx
+    ty0, ty1 = (b[None, :, 1] - y) / dy, (b[None, :, 3] - y) / dy
     tmin = np.maximum(np.minimum(tx0, tx1), np.minimum(ty0, ty1))
     tmax = np.minimum(np.maximum(tx0, tx1), np.maximum(ty0, ty1))
     hit = (tmax >= np.maximum(tmin, 0.0)) & (tmin > 0.0)
-    return np.where(hit, tmin, np.inf).min(axis=1).astype(np.float32)
+    return np.where(hit, tmin, np.inf).min(axis=1, initial=np.inf).astype(np.float32)      # (initial: a world without boxes)
 
 
 def depth_from_profile(wall: np.ndarray, height: int = ROOMS_H) -> np.ndarray:
@@ -165,9 +174,9 @@ def tf_of(x: float, y: float, k: int) -> np.ndarray:
     return np.array([[c, -s, 0.0, x], [s, c, 0.0, y], [0.0, 0.0, 1.0, CAMERA_HEIGHT], [0.0, 0.0, 0.0, 1.0]])
 
 
-def _blocked(x: float, y: float, margin: float = 0.3) -> bool:
-    return bool(np.any((BOXES[:, 0] - margin <= x) & (x <= BOXES[:, 2] + margin) &
-                       (BOXES[:, 1] - margin <= y) & (y <= BOXES[:, 3] + margin)))
+def _blocked(x: float, y: float, margin: float = 0.3, boxes=None) -> bool:
+    b = _walls_of(boxes)
+    return bool(np.any((b[:, 0] - margin <= x) & (x <= b[:, 2] + margin) & (b[:, 1] - margin <= y) & (y <= b[:, 3] + margin)))
 
 
 def integrate(actions):
@@ -229,13 +238,14 @@ ACTION_STOP, ACTION_FORWARD, ACTION_TURN_LEFT, ACTION_TURN_RIGHT = 0, 1, 2, 3
 STEP_MARGIN = 0.2          # the clearance plan_actions asserts for every pose of the tour
 
 
-def step_poses(xy, k, actions, extra_boxes=None):
+def step_poses(xy, k, actions, extra_boxes=None, boxes=None):
     """Apply one action per robot: ``xy`` [E,2] f64 positions, ``k`` [E] heading indices (multiples of 30 degrees),
     ``actions`` [E] action ids -> (xy, k, collided [E] bool), new arrays.  A turn changes k by +-1 mod 12; FORWARD adds
     0.25 * HEADINGS[k] (the expression of `integrate`) unless the new position lies within STEP_MARGIN of a box, in which case
     the move is refused (pose unchanged, ``collided`` set: no sliding along walls); STOP changes nothing.  ``extra_boxes``
     [E,K,4] f64: per robot up to K more boxes (x0, y0, x1, y1; a NaN row is "none") that refuse its moves like the walls do:
-    the objects of its own environment (world objects section below)."""
+    the objects of its own environment (world objects section below).  ``boxes`` [E,B,4] f64: per robot the walls of ITS world
+    instead of the shared BOXES (a NaN row blocks nothing: the padding of a world table)."""
     xy = np.array(xy, np.float64).reshape(-1, 2)
     k = np.array(k, np.int64).reshape(-1)
     a = np.asarray(actions).reshape(-1).astype(np.int64)
@@ -247,8 +257,14 @@ def step_poses(xy, k, actions, extra_boxes=None):
     heading = np.array(HEADINGS, np.float64)[k]
     new = xy + 0.25 * heading
     m = STEP_MARGIN
-    blocked = np.any((BOXES[None, :, 0] - m <= new[:, None, 0]) & (new[:, None, 0] <= BOXES[None, :, 2] + m) &
-                     (BOXES[None, :, 1] - m <= new[:, None, 1]) & (new[:, None, 1] <= BOXES[None, :, 3] + m), axis=1)
+    if boxes is None:
+        w = BOXES[None]
+    else:
+        w = np.asarray(boxes, np.float64)
+        if w.ndim != 3 or w.shape[0] != len(xy) or w.shape[2] != 4:
+            raise ValueError("step_poses: boxes must be [E,B,4]")
+    blocked = np.any((w[:, :, 0] - m <= new[:, None, 0]) & (new[:, None, 0] <= w[:, :, 2] + m) &
+                     (w[:, :, 1] - m <= new[:, None, 1]) & (new[:, None, 1] <= w[:, :, 3] + m), axis=1)
     if extra_boxes is not None:
         x = np.asarray(extra_boxes, np.float64)
         if x.ndim != 3 or x.shape[0] != len(xy) or x.shape[2] != 4:
@@ -404,13 +420,14 @@ def _normalise(d, lo, hi):
     return np.clip((d - lo) / (hi - lo), 1e-3, 1.0).astype(np.float32)
 
 
-def render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6):
+def render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6, boxes=None):
     """(depth f32 [H,W], ids u8 [H,W]) seen by ONE camera at (x, y), heading (c, s) = (cos, sin), ``height`` above the floor,
     focal length ``fx`` pixels, range [lo, hi]: the walls and the floor of `wall_profile` / `depth_from_profile`, and the
     objects ``boxes6`` [K,6] in front of them.  Per column u an object is hit at t = f64(f32(tmin)) of the walls' slab test
     and covers the rows rr = r - H//2 with ceil((height - z1) fx / t) <= rr <= floor((height - z0) fx / t); the pixel's depth
     is the f32 minimum of the normalised wall, floor and covering objects, its id is k + 1 of the nearest covering object
-    (lowest k among equals) where that is STRICTLY nearer than wall and floor, else 0.  Whole-array f64 NumPy."""
+    (lowest k among equals) where that is STRICTLY nearer than wall and floor, else 0.  ``boxes`` [B,4]: the walls (None: BOXES).
+    Whole-array f64 NumPy."""
     boxes6 = np.asarray(boxes6, np.float64).reshape(-1, 6)
     m = -(np.arange(W, dtype=np.float64) - W // 2) / fx
     dx, dy = c - s * m, s + c * m
@@ -425,7 +442,7 @@ def render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6):
         return np.where((tmax >= np.maximum(tmin, 0.0)) & (tmin > 0.0), tmin, np.inf)
 
     with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
-        wall = slab(BOXES).min(axis=1).astype(np.float32).astype(np.float64)
+        wall = slab(_walls_of(boxes)).min(axis=1, initial=np.inf).astype(np.float32).astype(np.float64)
         rr = (np.arange(H) - H // 2)[:, None]
         floor = np.where(rr > 0, (height * fx) / np.maximum(rr, 1), np.inf)
         bg = np.minimum(_normalise(wall, lo, hi)[None, :], _normalise(floor, lo, hi))              # [H,W] f32
@@ -628,6 +645,167 @@ def soft_spl(d_end: float, l: float, p: float) -> float:
     if l == 0.0:
         return 1.0 if d_end == 0.0 else 0.0
     return float(max(0.0, 1.0 - d_end / l) * (l / max(p, l)))
+
+
+# ---------------------------------------------------------------------------------------------- procedural worlds
+# A floor plan per (seed, env_id, episode) instead of the one hand-built BOXES: rooms on a jittered grid, doorways, pillars, and
+# the spots objects may stand on.  Everything is drawn with `_mix32` (no global RNG) and laid out in INTEGER units of 0.05 m; a
+# coordinate becomes a float by one division by 20, so a world is the same bytes on every platform.
+#
+#   plan     the square [-10, 10] m with a 0.3 m boundary wall, cut into nx x ny cells, nx, ny in {2, 3, 4}; the partition lines
+#            sit at the even split, jittered in 0.1 m steps by up to +-1 m (+-0.7 m with four cells: every wall keeps room for a
+#            doorway 1 m from both of its ends)
+#   walls    between two adjacent cells a 0.3 m wall.  The edges of a spanning tree of the cell graph (Kruskal over hashed
+#            weights) carry a 1.2 m doorway at least 1 m from either end; every other edge is solid (1/4), has a doorway (1/2) or
+#            is absent (1/4).  A piece runs from partition line to partition line -- half a wall thickness past the cell at both
+#            ends -- so pieces OVERLAP at junctions instead of abutting
+#   pillars  a cell at least 4.5 m wide both ways gets, with probability 1/2, a free-standing square pillar of half extent
+#            0.3-0.5 m within 0.5 m of its centre, while the box budget WORLD_MAX_BOXES lasts
+#   spots    the quarter points of every cell, snapped to 0.25 m, that keep 0.65 m to every box and 1.6 m to every doorway centre
+#            (no object can close a door) and on which no object class's inflated footprint exactly abuts an inflated wall (the
+#            zero-width slit of the geodesic rule above does not arise)
+#   start    a hashed spot, a hashed heading
+# `tests/test_procedural_worlds_cpu.py` checks what the harness relies on: the box budget, the start's clearance, at least 12
+# spots, every spot reachable from the start, no abutting inflated rectangles.
+WORLD_MAX_BOXES = 64
+_WORLD_HALF, _WORLD_WALL, _WORLD_DOOR, _WORLD_DOOR_END = 200, 6, 24, 20       # units of 0.05 m: 10 m, 0.3 m, 1.2 m, 1 m
+
+
+class World(NamedTuple):
+    boxes: np.ndarray        # [B,4] f64 walls and pillars (x0, y0, x1, y1), B <= WORLD_MAX_BOXES
+    start_xy: np.ndarray     # [2] f64
+    start_k: int             # heading index into HEADINGS
+    spots: np.ndarray        # [S,2] f64 object centres
+    doors: np.ndarray        # [D,2] f64 doorway centres
+
+
+def rects_abut(a, b) -> np.ndarray:
+    """bool [len(a), len(b)]: do the rectangles a[i] and b[j] (x0, y0, x1, y1) exactly abut -- one ends on an axis where the
+    other begins (equal doubles) while they overlap by a positive length on the other axis."""
+    a, b = np.asarray(a, np.float64).reshape(-1, 1, 4), np.asarray(b, np.float64).reshape(1, -1, 4)
+    ox = np.minimum(a[..., 2], b[..., 2]) - np.maximum(a[..., 0], b[..., 0])
+    oy = np.minimum(a[..., 3], b[..., 3]) - np.maximum(a[..., 1], b[..., 1])
+    return (((a[..., 2] == b[..., 0]) | (a[..., 0] == b[..., 2])) & (oy > 0)) | \
+           (((a[..., 3] == b[..., 1]) | (a[..., 1] == b[..., 3])) & (ox > 0))
+
+
+class ProceduralWorlds:
+    """``worlds.world(env_id, episode)``: the floor plan of that environment's episode, a pure function of (seed, env_id, episode)
+    (the rule above).  ``worlds.layout(env_id, episode, robot_xy)``: `object_layout`'s rule over the world's own spots."""
+
+    def __init__(self, seed: int = 0) -> None:
+        self.seed = int(seed)
+        self._made = {}          # (env_id, episode) -> World: the harness asks for an episode's world more than once
+
+    def world(self, env_id: int, episode: int) -> World:
+        key = (int(env_id), int(episode))
+        if key not in self._made:
+            if len(self._made) >= 1024:
+                self._made.clear()
+            w = self._generate(*key)
+            for a in (w.boxes, w.start_xy, w.spots, w.doors):
+                a.setflags(write=False)
+            self._made[key] = w
+        return self._made[key]
+
+    def _generate(self, env_id: int, episode: int) -> World:
+        base = _mix32(_mix32(self.seed, int(env_id), 101), int(episode), 102)
+        draws = iter(range(1 << 30))
+        rnd = lambda n: _mix32(base, next(draws), 103) % n      # noqa: E731  the next draw, uniform over range(n)
+        half, t, h = _WORLD_HALF, _WORLD_WALL, _WORLD_WALL // 2
+
+        def lines(n):        # centre lines of the n + 1 walls across one axis, boundary included
+            jitter = 10 if n < 4 else 7                         # in steps of 0.1 m = 2 units
+            inner = [-half + 2 * ((half * i) // n) + 2 * (rnd(2 * jitter + 1) - jitter) for i in range(1, n)]
+            return [-half + h] + inner + [half - h]
+
+        nx, ny = 2 + rnd(3), 2 + rnd(3)
+        X, Y = lines(nx), lines(ny)
+        boxes = [(-half, -half, half, -half + t), (-half, half - t, half, half), (-half, -half, -half + t, half),
+                 (half - t, -half, half, half)]
+        # the cell graph: edge (a, b, vertical?) between cell a = (i, j) and its east / north neighbour
+        edges = [((i, j), (i + 1, j), True) for j in range(ny) for i in range(nx - 1)] + \
+                [((i, j), (i, j + 1), False) for j in range(ny - 1) for i in range(nx)]
+        weight = [rnd(1 << 20) for _ in edges]
+        kind = [rnd(4) for _ in edges]                           # off the tree: 0 solid, 1 / 2 doorway, 3 absent
+        root = {(i, j): (i, j) for i in range(nx) for j in range(ny)}
+
+        def find(c):
+            while root[c] != c:
+                c = root[c]
+            return c
+
+        for n in sorted(range(len(edges)), key=lambda n: (weight[n], n)):
+            ra, rb = find(edges[n][0]), find(edges[n][1])
+            if ra != rb:
+                root[ra] = rb
+                kind[n] = 1
+        doors = []
+        for n, ((i, j), _, vertical) in enumerate(edges):
+            if kind[n] == 3:
+                continue
+            line = X[i + 1] if vertical else Y[j + 1]
+            p0, p1 = (Y[j], Y[j + 1]) if vertical else (X[i], X[i + 1])   # the piece: partition line to partition line
+            room = (p1 - h) - (p0 + h) - _WORLD_DOOR - 2 * _WORLD_DOOR_END
+            assert room >= 0
+            off = 2 * rnd(room // 2 + 1)                         # (drawn for a solid wall too: one draw per edge)
+            pieces = [(p0, p1)]
+            if kind[n] != 0:
+                d0 = p0 + h + _WORLD_DOOR_END + off
+                pieces = [(p0, d0), (d0 + _WORLD_DOOR, p1)]
+                doors.append((line, d0 + _WORLD_DOOR // 2) if vertical else (d0 + _WORLD_DOOR // 2, line))
+            for (a, b) in pieces:
+                boxes.append((line - h, a, line + h, b) if vertical else (a, line - h, b, line + h))
+        for j in range(ny):
+            for i in range(nx):
+                want, r, ox, oy = rnd(2), 6 + rnd(5), rnd(21) - 10, rnd(21) - 10
+                x0, x1, y0, y1 = X[i] + h, X[i + 1] - h, Y[j] + h, Y[j + 1] - h
+                if want and min(x1 - x0, y1 - y0) >= 90 and len(boxes) < WORLD_MAX_BOXES:
+                    cx, cy = (x0 + x1) // 2 + ox, (y0 + y1) // 2 + oy
+                    boxes.append((cx - r, cy - r, cx + r, cy + r))
+        assert len(boxes) <= WORLD_MAX_BOXES
+        fboxes = np.array(boxes, np.float64) / 20.0
+        walls = inflated_rects(boxes=fboxes)
+        sizes = list(OBJECT_SIZES.values())
+        spots = []
+        for j in range(ny):
+            for i in range(nx):
+                x0, x1, y0, y1 = X[i] + h, X[i + 1] - h, Y[j] + h, Y[j + 1] - h
+                for qy in (1, 2, 3):
+                    for qx in (1, 2, 3):
+                        sx = 5 * ((2 * (4 * x0 + qx * (x1 - x0)) + 20) // 40)     # the quarter point, rounded to 0.25 m
+                        sy = 5 * ((2 * (4 * y0 + qy * (y1 - y0)) + 20) // 40)
+                        if (sx, sy) in spots:
+                            continue
+                        if any(max(b[0] - sx, 0, sx - b[2]) ** 2 + max(b[1] - sy, 0, sy - b[3]) ** 2 < 13 * 13 for b in boxes):
+                            continue
+                        if any((dx - sx) ** 2 + (dy - sy) ** 2 < 32 * 32 for (dx, dy) in doors):
+                            continue
+                        # the doubles the geodesic sees: object_box, then inflated_rects
+                        obj = inflated_rects([(sx / 20.0 - hx, sy / 20.0 - hy, sx / 20.0 + hx, sy / 20.0 + hy)
+                                              for (hx, hy, _, _) in sizes], boxes=np.zeros((0, 4)))
+                        if rects_abut(obj, walls).any():
+                            continue
+                        spots.append((sx, sy))
+        assert len(spots) >= 12
+        start = spots[rnd(len(spots))]
+        return World(fboxes, np.array(start, np.float64) / 20.0, rnd(12), np.array(spots, np.float64) / 20.0,
+                     np.array(doors, np.float64).reshape(-1, 2) / 20.0)
+
+    def layout(self, env_id: int, episode: int, robot_xy):
+        """`object_layout` over the spots of ``world(env_id, episode)``: the target (class ``env_id mod 6``) and one distractor,
+        both farther than OBJECT_START_CLEARANCE from the robot and more than 1.5 m apart."""
+        spots = [tuple(p) for p in self.world(env_id, episode).spots.tolist()]
+        classes = list(OBJECT_SIZES)
+        target = classes[env_id % len(classes)]
+        rx, ry = float(robot_xy[0]), float(robot_xy[1])
+        free = [p for p in spots if (p[0] - rx) ** 2 + (p[1] - ry) ** 2 > OBJECT_START_CLEARANCE ** 2]
+        a = free[_mix32(env_id, episode, 21) % len(free)]
+        apart = [p for p in free if (p[0] - a[0]) ** 2 + (p[1] - a[1]) ** 2 > 1.5 ** 2]
+        b = apart[_mix32(env_id, episode, 22) % len(apart)]
+        other = [c for c in classes if c != target]
+        distractor = other[_mix32(env_id, episode, 23) % len(other)]
+        return [(target, object_box(target, *a)), (distractor, object_box(distractor, *b))]
 
 
 # ---------------------------------------------------------------------------------------------- map planner
