@@ -945,6 +945,28 @@ int vlfm_geodesic_fields_worlds(const double* d_world_boxes, const int32_t* d_bo
                                 const int32_t* d_source_counts, int n, int max_sources, double* d_rects, double* d_nodes,
                                 double* d_dist, int32_t* d_counts, void* stream);
 
+/* World colours (ABI 23): vlfm_worlds_raycast with objects, and the camera's RGB view of the same world, ONE launch plus the
+ * fill of d_stats (csrc/world_render.hip), every byte what vlfm_amd.synthetic.render_rgb_numpy computes.  d_depth, d_ids and
+ * d_stats are always written and are bit for bit vlfm_worlds_raycast's.  Colours are packed 0x00RRGGBB (the top byte is ignored).
+ *   d_object_colours  [n_envs][8] int32: the colour of each object slot of d_objects
+ *   d_palette         [12] int32: 8 wall colours, 2 floor colours, the void, one spare entry
+ *   d_rgb             [n][H][W][3] uint8: R, G, B
+ * Per column: the wall is the box b_w with the least tmin among the hit boxes (lowest index among equals, counted inside the
+ * camera's own world) at t_w = f64(f32(tmin)); it shows a y-face iff min(ty0, ty1) > min(tx0, tx1); q = x + dx t_w on a y-face,
+ * y + dy t_w on an x-face; panel = floor(2 q) & 1; r_sk = ceil(((height - 0.12) fx) / t_w) clamped to int16.  Per pixel, with
+ * rr = r - H/2, the first that holds:
+ *   object  id > 0: the slot's colour; its footprint shows a y-face: ch -= ch >> 2
+ *   floor   floor_d < t_w (f64): palette[8 + ((floor(2 px) + floor(2 py)) & 1)], (px, py) = (x, y) + (dx, dy) floor_d
+ *   wall    t_w finite: palette[mix32(b_w, 0, 31) % 8]; an odd panel: ch -= ch >> 3; a y-face: ch -= ch >> 2; rr >= r_sk: ch >>= 1
+ *   void    palette[10], as it is
+ * and on the first three the depth cue g = int(depth * 128.0f), ch = (ch * (256 - g)) >> 8.  One rounding per f64 operation.
+ * The world table's max_boxes, 95 bytes per image column and one band of at most 128 rows (12 bytes each) must fit 64 KB of LDS;
+ * n <= 65535, n_envs >= 1, H <= 32768; every pointer is required (VLFM_ERR_INVALID otherwise, nothing launched). */
+int vlfm_worlds_raycast_rgb(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts, int n_worlds,
+                            int max_boxes, const int32_t* d_world_of, const double* d_objects, const int32_t* d_env_of, int n_envs,
+                            int H, int W, float* d_depth, uint8_t* d_ids, int32_t* d_stats, const int32_t* d_object_colours,
+                            const int32_t* d_palette, uint8_t* d_rgb, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Map planner (ABI 21, csrc/map_planner.hip): shortest paths over the navigable planes of the obstacle maps (the reference's
  * _navigable_map: obstacles dilated by the robot's footprint, unexplored cells free), n jobs in ONE launch, one workgroup per

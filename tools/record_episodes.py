@@ -1,7 +1,9 @@
 """Steps a small BatchedEpisodes harness (no BLIP-2: stub cosines) and records its maps: one raw Motion-JPEG file per
 environment and map, every frame encoded on the device (BatchedEpisodes.render_jpeg).  Play one with
-`ffplay -f mjpeg out/env0_value_map.mjpeg`.
-Usage: python tools/record_episodes.py [--envs 4] [--steps 50] [--every 1] [--quality 90] [--out recordings]"""
+`ffplay -f mjpeg out/env0_value_map.mjpeg`.  `--first-person` steps a closed-loop harness that renders the robots' RGB view of the
+world (BatchedEpisodes(closed_loop=True, render_rgb=True)) and writes one more file per environment, env<e>_first_person.mjpeg:
+what the robot saw (last_rgb), through the same encoder.
+Usage: python tools/record_episodes.py [--envs 4] [--steps 50] [--every 1] [--quality 90] [--out recordings] [--first-person]"""
 import argparse
 import os
 import sys
@@ -16,22 +18,28 @@ def main():
     ap.add_argument("--every", type=int, default=1, help="record every n-th step")
     ap.add_argument("--quality", type=int, default=90)
     ap.add_argument("--out", default="recordings")
+    ap.add_argument("--first-person", action="store_true", help="closed loop; also record what each robot saw")
     args = ap.parse_args()
     import torch
 
     from vlfm_amd.harness import BatchedEpisodes
     from vlfm_amd.utils.mjpeg import MjpegWriter
+    from vlfm_amd.vlm.transport import jpeg_encode_batch_bytes
 
     device = torch.device("cuda:0")
     os.makedirs(args.out, exist_ok=True)
-    sim = BatchedEpisodes(args.envs, device=device, use_blip2=False, world="rooms", render_trajectories=True)
+    first_person = dict(closed_loop=True, select_frontiers=True, render_rgb=True) if args.first_person else {}
+    sim = BatchedEpisodes(args.envs, device=device, use_blip2=False, world="rooms", render_trajectories=True, **first_person)
     writers = {}
     try:
         for t in range(args.steps):
             sim.step()
             if t % args.every:
                 continue
-            for name, files in sim.render_jpeg(quality=args.quality).items():
+            frames = sim.render_jpeg(quality=args.quality)
+            if args.first_person:
+                frames["first_person"] = jpeg_encode_batch_bytes(sim.last_rgb, args.quality, "rgb")
+            for name, files in frames.items():
                 for e, data in enumerate(files):
                     key = (e, name)
                     if key not in writers:

@@ -248,6 +248,7 @@ def lib() -> ctypes.CDLL:
         L.vlfm_geodesic_fields.argtypes = [vp, ci, cd, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
         L.vlfm_geodesic_query.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp]
         L.vlfm_worlds_raycast.argtypes = [vp, ci, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]
+        L.vlfm_worlds_raycast_rgb.argtypes = [vp, ci, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
         L.vlfm_geodesic_fields_worlds.argtypes = [vp, vp, ci, ci, vp, cd, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
         L.vlfm_plan_scratch_bytes.argtypes = [ci, ci]
         L.vlfm_plan_scratch_bytes.restype = ctypes.c_size_t

@@ -18,7 +18,8 @@
 // handful of cameras still spreads over the chip.  With W a multiple of 4 and a 16-byte aligned output every lane owns 4
 // adjacent columns and a band leaves as consecutive 16-byte stores; any other W takes the scalar store loop.
 // The kernels are templates over where a workgroup finds its boxes: one shared table (vlfm_rooms_raycast, vlfm_rooms_raycast_objects)
-// or the row of its camera's world in a table of worlds (vlfm_worlds_raycast, at the end of the file).
+// or the row of its camera's world in a table of worlds (vlfm_worlds_raycast, at the end of the file).  The objects kernel is also
+// a template over "with colour": vlfm_worlds_raycast_rgb, the last entry, adds the camera's RGB view from the same geometry.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -221,11 +222,87 @@ __device__ __forceinline__ float shade(float bg, unsigned mask, const ObjCol* __
     return fminf(bg, best);
 }
 
-template <class Table>
+// ---- world colours (vlfm_worlds_raycast_rgb; the rule is stated with the entry point at the end of the file) ----------------
+// Colours are packed 0x00RRGGBB; the per-channel steps of the rule run on all three channels of a packed colour at once (the
+// subtrahend of a channel never exceeds the channel: no borrow crosses into the next one).
+constexpr int RGB_COL_BYTES = 26;             // per image column: dx, dy (f64), the wall (f32), wall colour | face bits, r_sk (int16)
+constexpr int RGB_ROW_BYTES = 8;              // per row of the band: floor_d (f64)
+constexpr int RGB_FIXED_BYTES = 16 + 12 * 4 + MAX_OBJECTS * 4;   // alignment slack, the palette, the environment's object colours
+constexpr int RGB_MAX_BAND_ROWS = 128;        // keeps 64 boxes + 640 columns + one band inside 64 KB whatever the camera count
+constexpr int PALETTE_FLOOR = 8, PALETTE_VOID = 10;
+constexpr double SKIRTING_HEIGHT = 0.12;      // synthetic.SKIRTING_HEIGHT
+
+struct RgbLds {                               // the colour tables of a workgroup, all in LDS
+    double *dx, *dy;                          // [wp] the clamped ray direction of each column
+    float* wall;                              // [wp] t_w as the depth profile keeps it (inf: nothing hit)
+    uint32_t* wrgb;                           // [wp] bits 0-23 the wall's colour after panel and face, bit 24 + k: object k shows a y-face
+    short* rsk;                               // [wp] first row (relative to H/2) of the skirting
+    double* frow;                             // [band] floor_d of each row
+    uint32_t* pal;                            // [12]
+    uint32_t* ocol;                           // [8] colours of the environment's object slots
+};
+
+__device__ __forceinline__ uint32_t mix32(uint32_t a, uint32_t b, uint32_t salt) {      // synthetic._mix32
+    uint32_t h = a * 2654435761u + b * 40503u + salt * 97u + 0x9E3779B9u;
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    return h ^ (h >> 16);
+}
+
+// int64(floor(2 v)) & 1 without the 64-bit conversion: floor(2 v) is odd iff the fractional part of v is at least one half, and
+// v - floor(v) is exact for every finite f64 (zero from 2^52 on, where 2 v is an even integer)
+__device__ __forceinline__ uint32_t floor_twice_is_odd(double v) { return __dsub_rn(v, floor(v)) >= 0.5 ? 1u : 0u; }
+
+// the floor's checker bit where the ray of direction (dx, dy) from the camera meets the floor at floor_d
+__device__ __forceinline__ uint32_t floor_check(double cam_x, double cam_y, double dx, double dy, double floor_d) {
+    const double px = __dadd_rn(cam_x, __dmul_rn(dx, floor_d));
+    const double py = __dadd_rn(cam_y, __dmul_rn(dy, floor_d));
+    return floor_twice_is_odd(px) ^ floor_twice_is_odd(py);
+}
+
+__device__ __forceinline__ uint32_t dim_quarter(uint32_t c) { return c - ((c >> 2) & 0x3f3f3fu); }   // ch -= ch >> 2
+__device__ __forceinline__ uint32_t dim_eighth(uint32_t c) { return c - ((c >> 3) & 0x1f1f1fu); }    // ch -= ch >> 3
+__device__ __forceinline__ uint32_t halve(uint32_t c) { return (c >> 1) & 0x7f7f7fu; }               // ch >>= 1
+
+struct Paint {                                // a pixel before the depth cue: its colour, and whether the cue applies (not the void)
+    uint32_t c;
+    bool lit;
+};
+
+// what stands behind the objects in one pixel, without a branch: floor, wall (skirting from `rsk` down) or void.  `w`, `wall`,
+// `rsk`: the column's entries; `check`: the floor's checker bit (read only where the pixel is floor); f0, f1, v: palette[8..10]
+__device__ __forceinline__ Paint background(uint32_t w, float wall, int rsk, int rr, double floor_d, uint32_t check, uint32_t f0,
+                                            uint32_t f1, uint32_t v) {
+    const bool is_floor = floor_d < (double)wall;
+    const bool lit = is_floor || wall < __builtin_inff();
+    const uint32_t cw = w & 0xffffffu;
+    const uint32_t c = is_floor ? (check ? f1 : f0) : (rr >= rsk ? halve(cw) : cw);
+    return Paint{lit ? c : v, lit};
+}
+
+// object `id` (> 0) in a column whose entry is `w`
+__device__ __forceinline__ Paint object_paint(const uint32_t* __restrict__ ocol, uint32_t w, int id) {
+    const uint32_t c = ocol[id - 1];
+    return Paint{(w >> (23 + id)) & 1u ? dim_quarter(c) : c, true};
+}
+
+// the depth cue, then the three bytes R, G, B from the lowest up
+__device__ __forceinline__ uint32_t finish(Paint p, float depth) {
+    const uint32_t k = p.lit ? 256u - (uint32_t)(int)(depth * 128.0f) : 256u;   // 128 .. 256: neither product leaves its 16 bits
+    const uint32_t c = ((((p.c & 0xff00ffu) * k) >> 8) & 0xff00ffu) | ((((p.c & 0x00ff00u) * k) >> 8) & 0x00ff00u);
+    return __builtin_bswap32(c) >> 8;
+}
+
+// RGB = false: vlfm_rooms_raycast_objects / vlfm_worlds_raycast as they always were (`object_colours`, `palette`, `rgb` unused);
+// RGB = true: the colour plane as well, from the same per-column geometry (vlfm_worlds_raycast_rgb).
+template <class Table, bool RGB>
 __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
     const CameraRec* __restrict__ cameras, const Table table, const double* __restrict__ objects,
     const int32_t* __restrict__ env_of, int n_envs, int H, int W, int band, int vec4, float* __restrict__ out,
-    uint8_t* __restrict__ ids, int32_t* __restrict__ stats) {
+    uint8_t* __restrict__ ids, int32_t* __restrict__ stats, const int32_t* __restrict__ object_colours,
+    const int32_t* __restrict__ palette, uint8_t* __restrict__ rgb) {
     extern __shared__ double smem[];
     const int r0 = blockIdx.x * band;
     if (r0 >= H) return;                                   // (uniform for the workgroup: before any barrier)
@@ -244,6 +321,21 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
     const CameraRec cam = cameras[blockIdx.y];
     const int env = env_of[blockIdx.y];
     const bool has_env = env >= 0 && env < n_envs;         // (the host wrapper refuses anything else; never read out of bounds)
+    RgbLds L{};
+    if constexpr (RGB) {                                   // behind cmask, from the next 16-byte boundary (wp is a multiple of 4)
+        const uintptr_t end = reinterpret_cast<uintptr_t>(cmask + wp), base0 = reinterpret_cast<uintptr_t>(smem);
+        L.dx = reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + (((end - base0) + 15) & ~(uintptr_t)15));
+        L.dy = L.dx + wp;
+        L.wall = reinterpret_cast<float*>(L.dy + wp);
+        L.wrgb = reinterpret_cast<uint32_t*>(L.wall + wp);
+        L.rsk = reinterpret_cast<short*>(L.wrgb + wp);
+        L.frow = reinterpret_cast<double*>(L.rsk + wp);    // 2 * wp bytes on: 8-byte aligned
+        L.pal = reinterpret_cast<uint32_t*>(L.frow + band);
+        L.ocol = L.pal + 12;
+        for (int i = tid; i < 12; i += THREADS) L.pal[i] = (uint32_t)palette[i] & 0xffffffu;
+        for (int i = tid; i < MAX_OBJECTS; i += THREADS)
+            L.ocol[i] = has_env ? (uint32_t)object_colours[(size_t)env * MAX_OBJECTS + i] & 0xffffffu : 0u;
+    }
     for (int i = tid; i < 4 * n_boxes; i += THREADS) sbox[i] = boxes[i];
     for (int i = tid; i < MAX_OBJECTS * OBJ_REC; i += THREADS) sobj[i] = has_env ? objects[(size_t)env * MAX_OBJECTS * OBJ_REC + i] : 0.0;
     for (int i = tid; i < 5 * MAX_OBJECTS; i += THREADS) {
@@ -256,6 +348,7 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
         const int rr = r0 + i - H / 2;
         const double floor_d = rr > 0 ? __dmul_rn(cam.height, cam.fx) / (double)rr : inf;
         nrow[i] = normalise(floor_d, cam.lo, span);
+        if constexpr (RGB) L.frow[i] = floor_d;
     }
     __syncthreads();
     const int rr_first = r0 - H / 2, rr_last = r0 + rows - 1 - H / 2;
@@ -270,16 +363,43 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
         if (fabs(dx) < 1e-12) dx = 1e-12;
         if (fabs(dy) < 1e-12) dy = 1e-12;
         double best = inf;
+        int best_b = 0;                                    // RGB: the box `best` came from and the face it shows
+        bool best_y = false;
         for (int b = 0; b < n_boxes; ++b) {
             const double tx0 = (sbox[4 * b + 0] - cam.x) / dx, tx1 = (sbox[4 * b + 2] - cam.x) / dx;
             const double ty0 = (sbox[4 * b + 1] - cam.y) / dy, ty1 = (sbox[4 * b + 3] - cam.y) / dy;
             const double tmin = fmax(fmin(tx0, tx1), fmin(ty0, ty1));
             const double tmax = fmin(fmax(tx0, tx1), fmax(ty0, ty1));
-            if (tmax >= fmax(tmin, 0.0) && tmin > 0.0) best = fmin(best, tmin);
+            if (tmax >= fmax(tmin, 0.0) && tmin > 0.0) {
+                if constexpr (RGB) {
+                    if (tmin < best) {                     // (a hit's tmin is no NaN: the same minimum; strict <: the lowest index)
+                        best = tmin;
+                        best_b = b;
+                        best_y = fmin(ty0, ty1) > fmin(tx0, tx1);
+                    }
+                } else {
+                    best = fmin(best, tmin);
+                }
+            }
         }
         const float wall = (float)best;                    // the host path keeps the profile in f32
         const float nwall = normalise((double)wall, cam.lo, span);
         ncol[u] = nwall;
+        uint32_t wrgb = 0;
+        if constexpr (RGB) {
+            const double tw = (double)wall;
+            L.dx[u] = dx;
+            L.dy[u] = dy;
+            L.wall[u] = wall;
+            if (wall < __builtin_inff()) {
+                const double q = best_y ? __dadd_rn(cam.x, __dmul_rn(dx, tw)) : __dadd_rn(cam.y, __dmul_rn(dy, tw));
+                wrgb = L.pal[mix32((uint32_t)best_b, 0u, 31u) & 7u];
+                if (floor_twice_is_odd(q)) wrgb = dim_eighth(wrgb);
+                if (best_y) wrgb = dim_quarter(wrgb);
+            }
+            const double sk = ceil(__dmul_rn(__dsub_rn(cam.height, SKIRTING_HEIGHT), cam.fx) / tw);
+            L.rsk[u] = !(sk <= 32767.0) ? (short)32767 : (sk < -32768.0 ? (short)-32768 : (short)sk);      // (a NaN: never)
+        }
         unsigned mask = 0;
         for (int k = 0; k < MAX_OBJECTS; ++k) {
             const double* o = sobj + OBJ_REC * k;
@@ -289,6 +409,7 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
             const double tmin = fmax(fmin(tx0, tx1), fmin(ty0, ty1));
             const double tmax = fmin(fmax(tx0, tx1), fmax(ty0, ty1));
             if (!(tmax >= fmax(tmin, 0.0) && tmin > 0.0)) continue;
+            if constexpr (RGB) wrgb |= (fmin(ty0, ty1) > fmin(tx0, tx1) ? 1u : 0u) << (24 + k);
             const double t = (double)(float)tmin;
             const double lo_r = ceil(__dmul_rn(__dsub_rn(cam.height, o[5]), cam.fx) / t);
             const double hi_r = floor(__dmul_rn(__dsub_rn(cam.height, o[4]), cam.fx) / t);
@@ -304,12 +425,15 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
             mask |= 1u << k;
         }
         cmask[u] = (uint8_t)mask;
+        if constexpr (RGB) L.wrgb[u] = wrgb;
     }
     __syncthreads();
     const size_t base = ((size_t)blockIdx.y * H + r0) * (size_t)W;     // the band's rows are contiguous
     float* dst = out + base;
     uint8_t* idst = ids + base;
     LaneStats acc{0, 0, 0, 0, 0, 0};
+    uint32_t pal_f0 = 0, pal_f1 = 0, pal_v = 0;            // RGB: the two floor colours and the void
+    if constexpr (RGB) pal_f0 = L.pal[PALETTE_FLOOR], pal_f1 = L.pal[PALETTE_FLOOR + 1], pal_v = L.pal[PALETTE_VOID];
     if (vec4) {
         const int ng = W >> 2, total = rows * ng;
         const int dr = THREADS / ng, dg = THREADS % ng;
@@ -334,6 +458,38 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
             }
             dst4[idx] = d;
             idst4[idx] = id4;
+            if constexpr (RGB) {                           // 4 pixels = 12 bytes = three dwords
+                const int rr = r0 + r - H / 2;
+                const double fd = L.frow[r];
+                const float4 wl = reinterpret_cast<const float4*>(L.wall)[g];
+                const uint4 wc = reinterpret_cast<const uint4*>(L.wrgb)[g];
+                const short4 sk = reinterpret_cast<const short4*>(L.rsk)[g];
+                uint32_t k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+                if (fd < fmaxf(fmaxf(wl.x, wl.y), fmaxf(wl.z, wl.w))) {         // some of the four are floor (never above the horizon)
+                    const double2* dx2 = reinterpret_cast<const double2*>(L.dx) + 2 * g;
+                    const double2* dy2 = reinterpret_cast<const double2*>(L.dy) + 2 * g;
+                    const double2 xa = dx2[0], xb = dx2[1], ya = dy2[0], yb = dy2[1];
+                    k0 = floor_check(cam.x, cam.y, xa.x, ya.x, fd);
+                    k1 = floor_check(cam.x, cam.y, xa.y, ya.y, fd);
+                    k2 = floor_check(cam.x, cam.y, xb.x, yb.x, fd);
+                    k3 = floor_check(cam.x, cam.y, xb.y, yb.y, fd);
+                }
+                Paint q0 = background(wc.x, wl.x, sk.x, rr, fd, k0, pal_f0, pal_f1, pal_v);
+                Paint q1 = background(wc.y, wl.y, sk.y, rr, fd, k1, pal_f0, pal_f1, pal_v);
+                Paint q2 = background(wc.z, wl.z, sk.z, rr, fd, k2, pal_f0, pal_f1, pal_v);
+                Paint q3 = background(wc.w, wl.w, sk.w, rr, fd, k3, pal_f0, pal_f1, pal_v);
+                if (id4) {                                 // (objects are a small part of most frames)
+                    if (id4 & 0xffu) q0 = object_paint(L.ocol, wc.x, (int)(id4 & 0xffu));
+                    if ((id4 >> 8) & 0xffu) q1 = object_paint(L.ocol, wc.y, (int)((id4 >> 8) & 0xffu));
+                    if ((id4 >> 16) & 0xffu) q2 = object_paint(L.ocol, wc.z, (int)((id4 >> 16) & 0xffu));
+                    if (id4 >> 24) q3 = object_paint(L.ocol, wc.w, (int)(id4 >> 24));
+                }
+                const uint32_t p0 = finish(q0, d.x), p1 = finish(q1, d.y), p2 = finish(q2, d.z), p3 = finish(q3, d.w);
+                uint32_t* rgb3 = reinterpret_cast<uint32_t*>(rgb + 3 * base) + 3 * (size_t)idx;
+                rgb3[0] = p0 | (p1 << 24);
+                rgb3[1] = (p1 >> 8) | (p2 << 16);
+                rgb3[2] = (p2 >> 16) | (p3 << 8);
+            }
             r += dr;
             g += dg;
             if (g >= ng) {
@@ -355,6 +511,19 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
             }
             dst[idx] = d;
             idst[idx] = (uint8_t)id;
+            if constexpr (RGB) {
+                const double fd = L.frow[r];
+                const uint32_t w = L.wrgb[c];
+                const float wall = L.wall[c];
+                const uint32_t check = fd < (double)wall ? floor_check(cam.x, cam.y, L.dx[c], L.dy[c], fd) : 0u;
+                Paint q = background(w, wall, (int)L.rsk[c], r0 + r - H / 2, fd, check, pal_f0, pal_f1, pal_v);
+                if (id) q = object_paint(L.ocol, w, id);
+                const uint32_t p = finish(q, d);
+                uint8_t* px = rgb + 3 * (base + (size_t)idx);
+                px[0] = (uint8_t)p;
+                px[1] = (uint8_t)(p >> 8);
+                px[2] = (uint8_t)(p >> 16);
+            }
             r += dr;
             c += dc;
             if (c >= W) {
@@ -411,9 +580,10 @@ extern "C" int vlfm_rooms_raycast_objects(const double* d_cameras, int n, const 
     int rc = check_launch("rooms_stats_init_kernel");
     if (rc != VLFM_OK) return rc;
     VLFM_TIMED("rooms_raycast_objects_kernel", st);
-    VLFM_KLAUNCH(rooms_raycast_objects_kernel<SharedBoxes>, dim3(grid_x, n), dim3(THREADS), lds, st,
-                 reinterpret_cast<const CameraRec*>(d_cameras), SharedBoxes{d_boxes, n_boxes}, d_objects, d_env_of, n_envs, H, W,
-                 band, vec4, d_depth, d_ids, d_stats);
+    constexpr auto kernel = rooms_raycast_objects_kernel<SharedBoxes, false>;
+    VLFM_KLAUNCH(kernel, dim3(grid_x, n), dim3(THREADS), lds, st, reinterpret_cast<const CameraRec*>(d_cameras),
+                 SharedBoxes{d_boxes, n_boxes}, d_objects, d_env_of, n_envs, H, W, band, vec4, d_depth, d_ids, d_stats,
+                 (const int32_t*)nullptr, (const int32_t*)nullptr, (uint8_t*)nullptr);
     return check_launch("rooms_raycast_objects_kernel");
 }
 
@@ -459,8 +629,68 @@ extern "C" int vlfm_worlds_raycast(const double* d_cameras, int n, const double*
     int rc = check_launch("rooms_stats_init_kernel");
     if (rc != VLFM_OK) return rc;
     VLFM_TIMED("worlds_raycast_objects_kernel", st);
-    VLFM_KLAUNCH(rooms_raycast_objects_kernel<WorldBoxes>, dim3(grid_x, n), dim3(THREADS), lds, st,
-                 reinterpret_cast<const CameraRec*>(d_cameras), table, d_objects, d_env_of, n_envs, H, W, band, vec4, d_depth, d_ids,
-                 d_stats);
+    constexpr auto kernel = rooms_raycast_objects_kernel<WorldBoxes, false>;
+    VLFM_KLAUNCH(kernel, dim3(grid_x, n), dim3(THREADS), lds, st, reinterpret_cast<const CameraRec*>(d_cameras), table, d_objects,
+                 d_env_of, n_envs, H, W, band, vec4, d_depth, d_ids, d_stats, (const int32_t*)nullptr, (const int32_t*)nullptr,
+                 (uint8_t*)nullptr);
     return check_launch("worlds_raycast_objects_kernel");
+}
+
+// ------------------------------------------------------------------------------------------------------------ world colours
+// vlfm_worlds_raycast_rgb: vlfm_worlds_raycast with objects, and the camera's RGB view of the same world from the same launch
+// (synthetic.render_rgb_numpy is the host statement; every byte agrees).  Colours are packed 0x00RRGGBB and arrive as arguments.
+//
+//   column u:  b_w = the box the wall's tmin came from (lowest index among equals), t_w = f64(f32(tmin))
+//              y-face iff min(ty0, ty1) > min(tx0, tx1) at b_w;  q = x + dx*t_w (y-face) | y + dy*t_w;  panel = floor(2q) & 1
+//              wall colour = palette[mix32(b_w, 0, 31) % 8];  odd panel: ch -= ch >> 3;  y-face: ch -= ch >> 2
+//              r_sk = ceil(((height - 0.12) * fx) / t_w) clamped to int16;  per object slot a face bit from its own footprint
+//   pixel:     object (id > 0): the slot's colour, y-face: ch -= ch >> 2
+//              floor (floor_d < t_w in f64): palette[8 + ((floor(2 px) + floor(2 py)) & 1)], p = camera + d * floor_d
+//              wall (t_w finite): the column's wall colour, rr >= r_sk: ch >>= 1
+//              void: palette[10], as it is
+//              depth cue on the first three: g = int(depth * 128.0f), ch = (ch * (256 - g)) >> 8
+//
+// Layout: the kernel above with RGB = true.  A column costs 26 more bytes of LDS (dx, dy, the f32 wall, one dword with the wall's
+// colour AFTER panel and face in bits 0-23 and the objects' face bits above them, r_sk) and a row of the band 8 (floor_d): box
+// index, face and panel parity are only ever used for that colour, so the column pass resolves them once and a wall pixel costs
+// one LDS dword, one compare and the depth cue.  The pixel pass is selects, not branches (a first version that branched per
+// pixel on object / floor / wall / void took 317 us for 256 frames of 640x480 against 220 us for this one): per group of four
+// pixels one branch around the floor's f64 checker ("is any of the four floor") and one around the objects' colours.  Bands
+// are capped at RGB_MAX_BAND_ROWS rows so that the LDS need does not grow with the camera count.  Stores: with W % 4 == 0 and
+// aligned outputs a lane's 4 pixels leave as three dwords (one 12-byte store); else bytes.
+extern "C" int vlfm_worlds_raycast_rgb(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts,
+                                       int n_worlds, int max_boxes, const int32_t* d_world_of, const double* d_objects,
+                                       const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids,
+                                       int32_t* d_stats, const int32_t* d_object_colours, const int32_t* d_palette, uint8_t* d_rgb,
+                                       void* stream) {
+    if (n < 0 || n > 65535 || n_worlds < 0 || max_boxes < 0 || n_envs <= 0 || H <= 0 || W <= 0 || H > 32768 ||
+        (n > 0 && (!d_cameras || !d_world_of || !d_objects || !d_env_of || !d_depth || !d_ids || !d_stats || !d_object_colours ||
+                   !d_palette || !d_rgb)) ||
+        (n_worlds > 0 && (!d_box_counts || (max_boxes > 0 && !d_world_boxes))))
+        return fail(VLFM_ERR_INVALID, "worlds_raycast_rgb: bad argument");
+    if (n == 0) return VLFM_OK;
+    const long long want = 4LL * device_cu_count();         // row bands: as in vlfm_rooms_raycast, and no taller than the cap
+    long long bands = (want + n - 1) / n;
+    const long long most = (H + MIN_BAND_ROWS - 1) / MIN_BAND_ROWS, least = (H + RGB_MAX_BAND_ROWS - 1) / RGB_MAX_BAND_ROWS;
+    bands = bands < least ? least : (bands > most ? most : bands);
+    const int band = (int)((H + bands - 1) / bands);
+    const int grid_x = (H + band - 1) / band;
+    const size_t wp = (size_t)((W + 3) & ~3);
+    const WorldBoxes table{d_world_boxes, d_box_counts, d_world_of, n_worlds, max_boxes};
+    const size_t lds = (size_t)max_boxes * 32 + MAX_OBJECTS * OBJ_REC * 8 + wp * MAX_OBJECTS * sizeof(ObjCol) + wp * 4 +
+                       (size_t)band * 4 + 5 * MAX_OBJECTS * 4 + wp + wp * RGB_COL_BYTES + (size_t)band * RGB_ROW_BYTES + RGB_FIXED_BYTES;
+    if (lds > 64 * 1024)
+        return fail(VLFM_ERR_INVALID, "worlds_raycast_rgb: max_boxes + 95 bytes per image column + one row band exceed 64 KB of LDS");
+    const int vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_depth) % 16 == 0) && (reinterpret_cast<uintptr_t>(d_ids) % 4 == 0) &&
+                     (reinterpret_cast<uintptr_t>(d_rgb) % 4 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    const int total = n * 5 * MAX_OBJECTS;
+    VLFM_KLAUNCH(rooms_stats_init_kernel, dim3((total + THREADS - 1) / THREADS), dim3(THREADS), 0, st, d_stats, total, H, W);
+    int rc = check_launch("rooms_stats_init_kernel");
+    if (rc != VLFM_OK) return rc;
+    VLFM_TIMED("worlds_raycast_rgb_kernel", st);
+    constexpr auto kernel = rooms_raycast_objects_kernel<WorldBoxes, true>;
+    VLFM_KLAUNCH(kernel, dim3(grid_x, n), dim3(THREADS), lds, st, reinterpret_cast<const CameraRec*>(d_cameras), table, d_objects,
+                 d_env_of, n_envs, H, W, band, vec4, d_depth, d_ids, d_stats, d_object_colours, d_palette, d_rgb);
+    return check_launch("worlds_raycast_rgb_kernel");
 }

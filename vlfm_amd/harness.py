@@ -36,7 +36,7 @@ from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TUR
     MAX_DEPTH, MIN_DEPTH, YAWS, BangBangController, ReplayController, Trajectory, camera_intrinsics, depth_frame, integrate, \
     GEODESIC_MAX_SOURCES, STEP_MARGIN, WORLD_MAX_BOXES, WORLD_MAX_OBJECTS, ProceduralWorlds, goal_viewpoints, inflated_rects, object_layout, plan_actions, \
     pose_to_tf, rect_distance, rgb_frame, soft_spl, spl, step_poses, tf_of, PLAN_INVALID, PLAN_OK, PLAN_TOO_LONG, \
-    PLAN_UNREACHABLE
+    PLAN_UNREACHABLE, OBJECT_COLOURS, WORLD_PALETTE
 
 PROMPT = "Seems like there is a target_object ahead."  # vlfm/policy/base_objectnav_policy.py:377
 TARGETS = ["chair", "bed", "potted plant", "toilet", "tv", "couch"]  # HM3D ObjectNav categories
@@ -332,6 +332,7 @@ class RoomsRenderer:
         self.window = None
         self.window_t0 = 0
         self.painter = None      # optional (t, frames [E,H,W]) -> frames: scripted objects in front of the walls
+        self._rooms_table = None  # cast_cameras_rgb: BOXES as the one row of a world table
 
     @torch.no_grad()
     def render(self, t: int) -> torch.Tensor:
@@ -560,6 +561,90 @@ class RoomsRenderer:
         return (out, ids, stats) if with_objects else out
 
     @torch.no_grad()
+    def cast_worlds_rgb(self, tf: np.ndarray, table: WorldTable, world_of, objects: Optional[np.ndarray] = None, env_of=None,
+                        colours=None, palette=None, hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None,
+                        out: Optional[torch.Tensor] = None, rgb_out: Optional[torch.Tensor] = None):
+        """``cast_worlds`` and the cameras' RGB view of the same worlds from the same launch (vlfm_worlds_raycast_rgb, on the
+        current stream).  Returns (depth, ids, stats, rgb u8 [n,H,W,3]) -- always all four; ``objects=None`` is a world without
+        objects: ids of zeros -- with (depth, ids, stats) bit for bit ``cast_worlds``' and rgb every byte
+        synthetic.render_rgb_numpy's.  ``colours`` int [n_envs,8]: packed 0x00RRGGBB of each slot of ``objects`` (None: zeros);
+        ``palette`` int [12] (None: synthetic.WORLD_PALETTE).  ``rgb_out``: a contiguous u8 [n,H,W,3] device tensor to render
+        into.  Camera records, object records, index lists, colours and palette cross in one small copy."""
+        tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
+        n = len(tf)
+        dev = self.boxes.device
+        if table.device != dev:
+            raise ValueError(f"cast_worlds_rgb: the world table must live on {dev}")
+        world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
+        if len(world_of) != n or np.any((world_of < 0) | (world_of >= table.n_worlds)):
+            raise ValueError("cast_worlds_rgb: world_of must name one world of the table per camera")
+        if objects is None:
+            if env_of is not None or colours is not None:
+                raise ValueError("cast_worlds_rgb: env_of and colours belong to objects")
+            objects, env_of = np.zeros((1, WORLD_MAX_OBJECTS, 8)), np.zeros(n, np.int32)
+        else:
+            objects = np.ascontiguousarray(objects, np.float64)
+            if objects.ndim != 3 or objects.shape[0] < 1 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
+                raise ValueError(f"cast_worlds_rgb: objects must be [n_envs >= 1, {WORLD_MAX_OBJECTS}, 8]")
+            env_of = np.ascontiguousarray(np.asarray(env_of).reshape(-1), np.int32)
+            if len(env_of) != n or np.any((env_of < 0) | (env_of >= len(objects))):
+                raise ValueError("cast_worlds_rgb: env_of must name one row of objects per camera")
+        colours = np.zeros((len(objects), WORLD_MAX_OBJECTS), np.int32) if colours is None else np.asarray(colours)
+        if colours.shape != (len(objects), WORLD_MAX_OBJECTS) or colours.dtype.kind not in "iu":
+            raise ValueError(f"cast_worlds_rgb: colours must be integers [{len(objects)}, {WORLD_MAX_OBJECTS}], one per object slot")
+        palette = np.asarray(WORLD_PALETTE if palette is None else palette)
+        if palette.shape != (12,) or palette.dtype.kind not in "iu":
+            raise ValueError("cast_worlds_rgb: palette must be 12 integers")
+        rec = np.empty((n, 8), np.float64)
+        rec[:, 0:2], rec[:, 2:4], rec[:, 4] = tf[:, :2, 3], tf[:, :2, 0], tf[:, 2, 3]
+        rec[:, 5] = camera_intrinsics(self.W)[0] if hfov is None else self.W / (2 * np.tan(np.asarray(hfov, np.float64) / 2))
+        rec[:, 6] = MIN_DEPTH if min_depth is None else np.asarray(min_depth, np.float64)
+        rec[:, 7] = MAX_DEPTH if max_depth is None else np.asarray(max_depth, np.float64)
+        if not np.all(rec[:, 7] > rec[:, 6]):
+            raise ValueError("cast_worlds_rgb: every camera needs max_depth > min_depth")
+        if out is None:
+            out = torch.empty((n, self.H, self.W), dtype=torch.float32, device=dev)
+        elif out.shape != (n, self.H, self.W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"cast_worlds_rgb: out must be a contiguous f32 [{n},{self.H},{self.W}] tensor on {dev}")
+        if rgb_out is None:
+            rgb_out = torch.empty((n, self.H, self.W, 3), dtype=torch.uint8, device=dev)
+        elif rgb_out.shape != (n, self.H, self.W, 3) or rgb_out.dtype != torch.uint8 or not rgb_out.is_contiguous() \
+                or rgb_out.device != dev:
+            raise ValueError(f"cast_worlds_rgb: rgb_out must be a contiguous u8 [{n},{self.H},{self.W},3] tensor on {dev}")
+        ids = torch.empty((n, self.H, self.W), dtype=torch.uint8, device=dev)
+        stats = torch.empty((n, WORLD_MAX_OBJECTS, 5), dtype=torch.int32, device=dev)
+        if n > 0:
+            with torch.cuda.device(dev):
+                # camera and object records, then the int32 lists (world_of, env_of, colours, palette), in ONE host buffer
+                ints = np.concatenate([world_of, env_of, (colours.astype(np.int64) & 0xFFFFFF).astype(np.int32).reshape(-1),
+                                       (palette.astype(np.int64) & 0xFFFFFF).astype(np.int32)])
+                blob = np.concatenate([rec.reshape(-1), objects.reshape(-1), np.zeros((len(ints) + 1) // 2, np.float64)])
+                blob[rec.size + objects.size:].view(np.int32)[:len(ints)] = ints
+                d_blob = torch.from_numpy(blob).to(dev)
+                p = d_blob.data_ptr()
+                p_ints = p + 8 * (rec.size + objects.size)
+                stream = torch.cuda.current_stream().cuda_stream
+                _lib.check(_lib.lib().vlfm_worlds_raycast_rgb(
+                    p, n, table.d_boxes.data_ptr(), table.d_counts.data_ptr(), table.n_worlds, table.max_boxes, p_ints,
+                    p + 8 * rec.size, p_ints + 4 * n, len(objects), self.H, self.W, out.data_ptr(), ids.data_ptr(),
+                    stats.data_ptr(), p_ints + 8 * n, p_ints + 8 * n + 4 * colours.size, rgb_out.data_ptr(), stream),
+                    "worlds_raycast_rgb")
+        return out, ids, stats, rgb_out
+
+    @torch.no_grad()
+    def cast_cameras_rgb(self, tf: np.ndarray, objects: Optional[np.ndarray] = None, env_of=None, colours=None, palette=None,
+                         hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None, out: Optional[torch.Tensor] = None,
+                         rgb_out: Optional[torch.Tensor] = None):
+        """``cast_worlds_rgb`` for the rooms world: every camera stands in the one row of a world table the renderer keeps (BOXES).
+        (depth, ids, stats) are bit for bit ``cast_cameras_objects``'."""
+        if self._rooms_table is None:
+            self._rooms_table = WorldTable(1, self.boxes.device, len(BOXES))
+            self._rooms_table.assign([0], [BOXES])
+        n = len(np.asarray(tf, np.float64).reshape(-1, 4, 4))
+        return self.cast_worlds_rgb(tf, self._rooms_table, np.zeros(n, np.int32), objects, env_of, colours, palette, hfov,
+                                    min_depth, max_depth, out, rgb_out)
+
+    @torch.no_grad()
     def geodesic_fields_worlds(self, table: WorldTable, world_of, objects: np.ndarray, targets_boxes, success_distance: float,
                                max_sources: int = GEODESIC_MAX_SOURCES) -> GeodesicFields:
         """``geodesic_fields`` with a floor plan per field (vlfm_geodesic_fields_worlds, ONE launch on the current stream): the
@@ -670,7 +755,7 @@ class BatchedEpisodes:
                  text_prompt: str = PROMPT, exploration_thresh: Optional[float] = None, closed_loop: bool = False,
                  controller=None, world_objects: Optional[WorldObjects] = None, batch_object_maps: bool = True,
                  device_object_clouds: bool = True, objectnav_metrics: bool = False,
-                 worlds: Optional[ProceduralWorlds] = None) -> None:
+                 worlds: Optional[ProceduralWorlds] = None, render_rgb: bool = False) -> None:
         # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
         # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -732,6 +817,16 @@ class BatchedEpisodes:
                 raise ValueError("worlds renders the robot's own camera: it cannot be combined with a camera rig")
             if sightings is not None:
                 raise ValueError("worlds cannot be combined with the scripted sightings, which are painted along the rooms tour")
+        # render_rgb: the step's RGB frames are the camera's view of the world the depth frame shows (RoomsRenderer.cast_worlds_rgb /
+        # cast_cameras_rgb: depth, ids, stats and colours from ONE launch) instead of the pool's noise -- what the transport hop,
+        # BLIP-2, the detector and the segmenter then see; they stay readable as ``last_rgb``.  Off: every step is the step it was
+        self.render_rgb = bool(render_rgb)
+        self.last_rgb: Optional[torch.Tensor] = None
+        if self.render_rgb:
+            if not self.closed_loop:
+                raise ValueError("render_rgb needs closed_loop=True: the frames are rendered from where the robot is")
+            if rig is not None:
+                raise ValueError("render_rgb renders the robot's own camera: it cannot be combined with a camera rig")
         self.device = require_gpu(device)
         # rig: K cameras per environment (CameraRig) fused into the environment's maps by ONE ingest_cameras / update_cameras per
         # step (step() -> _step_rig()); None = one camera at the robot pose, the step as it always was
@@ -1544,6 +1639,8 @@ class BatchedEpisodes:
         renders into one buffer it keeps (every reader of the previous step's frames was joined back into the main stream)."""
         if self._live_frames is None and not fresh:
             self._live_frames = torch.empty((self.E, self.H, self.W), dtype=torch.float32, device=self.device)
+        if self.render_rgb and not fresh:
+            return self._live_depth_rgb(t_ep, tf)
         if self.worlds is not None and self.world_objects is None:
             return self.rooms.cast_worlds(tf, self.world_table, np.arange(self.E), out=None if fresh else self._live_frames)
         if self.world_objects is not None:
@@ -1554,15 +1651,40 @@ class BatchedEpisodes:
                 d, ids, stats = self.rooms.cast_cameras_objects(tf, self._objects, np.arange(self.E),
                                                                 out=None if fresh else self._live_frames)
             if not fresh:
-                wo = self.world_objects
-                self._live_ids, self._live_stats = ids, stats.cpu().numpy()     # the one extra D2H copy of this mode
-                self._live_sightings = sightings_from_stats(self._live_stats, self._object_classes, wo.min_pixels, wo.confidence,
-                                                            wo.faint_confidence)
-                for (e, _, conf, _, k) in self._live_sightings:
-                    if k == self._target_slot[e] and conf == wo.confidence and self._ep_first[e] < 0:
-                        self._ep_first[e] = self._ep_clock[e]
+                self._note_sightings(ids, stats)
             return d
         d = self.rooms.cast_cameras(tf, out=None if fresh else self._live_frames)
+        return self.rooms.painter(t_ep, d) if self.rooms.painter is not None else d
+
+    def _note_sightings(self, ids: torch.Tensor, stats: torch.Tensor) -> None:
+        """world_objects: what the ray caster saw of the objects this step (the one extra D2H copy of this mode)."""
+        wo = self.world_objects
+        self._live_ids, self._live_stats = ids, stats.cpu().numpy()
+        self._live_sightings = sightings_from_stats(self._live_stats, self._object_classes, wo.min_pixels, wo.confidence,
+                                                    wo.faint_confidence)
+        for (e, _, conf, _, k) in self._live_sightings:
+            if k == self._target_slot[e] and conf == wo.confidence and self._ep_first[e] < 0:
+                self._ep_first[e] = self._ep_clock[e]
+
+    def _live_depth_rgb(self, t_ep: int, tf: np.ndarray) -> torch.Tensor:
+        """render_rgb: ``_live_depth`` with the step's RGB frames (``last_rgb``) from the same launch; the objects wear
+        OBJECT_COLOURS of their classes (a class without one: mid grey)."""
+        if self.last_rgb is None:
+            self.last_rgb = torch.empty((self.E, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
+        objects = env_of = colours = None
+        if self.world_objects is not None:
+            objects, env_of = self._objects, np.arange(self.E)
+            colours = np.zeros((self.E, WORLD_MAX_OBJECTS), np.int32)
+            for e, classes in enumerate(self._object_classes):
+                colours[e, :len(classes)] = [OBJECT_COLOURS.get(c, 0x808080) for c in classes]
+        if self.worlds is not None:
+            d, ids, stats, _ = self.rooms.cast_worlds_rgb(tf, self.world_table, np.arange(self.E), objects, env_of, colours,
+                                                          out=self._live_frames, rgb_out=self.last_rgb)
+        else:
+            d, ids, stats, _ = self.rooms.cast_cameras_rgb(tf, objects, env_of, colours, out=self._live_frames, rgb_out=self.last_rgb)
+        if self.world_objects is not None:
+            self._note_sightings(ids, stats)
+            return d
         return self.rooms.painter(t_ep, d) if self.rooms.painter is not None else d
 
     def _advance_world(self, poses: np.ndarray) -> None:
@@ -1753,11 +1875,14 @@ class BatchedEpisodes:
             depth, rgb = self.rooms.frame(self.t % self.episode_len), self.rgb_pool[kr]
         else:
             depth, rgb = self.depth_pool[k], self.rgb_pool[kr]
-        rgb = self._transported(rgb)
+        if not self.render_rgb:
+            rgb = self._transported(rgb)
         t_ep = self.t % self.episode_len
         poses, tf = self._poses_tf(t_ep)
         if self.closed_loop:
             depth = self._live_depth(t_ep, tf)
+            if self.render_rgb:                        # the frames of the launch that gave the depth, then the transport hop
+                rgb = self._transported(self.last_rgb)
         # ---- mapping, part 1 (side stream): one depth pass feeds both maps, then the obstacle/frontier pipeline
         main, side = self._open_step(poses)
         with torch.cuda.stream(side):

@@ -468,6 +468,131 @@ def object_stats_numpy(ids, K: int = WORLD_MAX_OBJECTS) -> np.ndarray:
     return out
 
 
+# ---------------------------------------------------------------------------------------------- world colours
+# What the camera's RGB frame shows of the same world (csrc/world_render.hip: vlfm_worlds_raycast_rgb; `render_rgb_numpy` is the
+# host statement).  Colours are packed 0x00RRGGBB integers and reach the kernel as arguments: it holds no colour constants.
+WORLD_PALETTE = np.array([0xC8B7A6, 0xB5C4B1, 0xA9B8C8, 0xD6C58F, 0xC49A8A, 0x9FB7AD, 0xBFAFCB, 0xD9D4C7,      # 8 wall colours
+                          0x8A6F4E, 0x6F5B41,                                                                  # 2 floor colours
+                          0x87B5E8,                                                                            # sky
+                          0], np.int32)                                                                        # spare: nothing reads it
+OBJECT_COLOURS = {"chair": 0xB03A2E, "bed": 0x2E6FB0, "potted plant": 0x2F8F3A, "toilet": 0xE8E8F0, "tv": 0x202428,
+                  "couch": 0x8E44AD}
+assert set(OBJECT_COLOURS) == set(OBJECT_SIZES)
+SKIRTING_HEIGHT = 0.12      # metres: below it a wall is drawn at half brightness
+
+
+def _channels(packed) -> np.ndarray:
+    """int64 [..., 3] = (R, G, B) of packed 0x00RRGGBB colours."""
+    p = np.asarray(packed, np.int64)
+    return np.stack([(p >> 16) & 255, (p >> 8) & 255, p & 255], axis=-1)
+
+
+def render_rgb_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6, colours, boxes=None, palette=WORLD_PALETTE):
+    """(depth f32 [H,W], ids u8 [H,W], rgb u8 [H,W,3]) seen by ONE camera: the depth and id planes of `render_objects_numpy`
+    for the same arguments, and the colour of every pixel.  ``colours`` [K] int: packed 0x00RRGGBB, one per object slot of
+    ``boxes6``; ``palette`` int [12]: 8 wall colours, 2 floor colours, sky, one spare entry.
+
+    Per column u (dx, dy clamped as in `wall_profile`): the wall is the box b_w with the least f64 tmin among the hit boxes
+    (lowest index among equals) at t_w = f64(f32(tmin)); it shows a y-face iff min(ty0, ty1) > min(tx0, tx1) there (ties: an
+    x-face); q = x + dx * t_w on a y-face, y + dy * t_w on an x-face, panel = int64(floor(q * 2.0)) & 1; the skirting starts at
+    r_sk = ceil(((height - 0.12) * fx) / t_w), clamped to the int16 range (a NaN: never).  Every object slot has a face bit by
+    the same rule from its own footprint.  Per pixel, rr = r - H//2, floor_d as in `render_objects_numpy`, the first that holds:
+      object   ids > 0: colours[ids - 1]; on a y-face ch -= ch >> 2
+      floor    floor_d < t_w: palette[8 + ((int64(floor(px * 2.0)) + int64(floor(py * 2.0))) & 1)], px = x + dx * floor_d,
+               py = y + dy * floor_d
+      wall     t_w finite: palette[_mix32(b_w, 0, 31) % 8] (b_w counts inside the camera's own world); then, in this order,
+               an odd panel: ch -= ch >> 3; a y-face: ch -= ch >> 2; rr >= r_sk: ch >>= 1
+      void     palette[10], as it is
+    and on the first three the depth cue g = int(depth * 128.0f) (f32, truncated: 0..128), ch = (ch * (256 - g)) >> 8.
+    Every multiply and add is rounded once; everything after the geometry is integer arithmetic.  The colour plane never shows
+    an object the id plane does not: both clamp beyond ``hi``, where an object is not STRICTLY nearer than its background.
+    Whole-array f64 NumPy."""
+    depth, ids = render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6, boxes)
+    boxes6 = np.asarray(boxes6, np.float64).reshape(-1, 6)
+    colours = np.asarray(colours, np.int64).reshape(-1)
+    palette = np.asarray(palette, np.int64).reshape(-1)
+    if len(colours) != len(boxes6) or len(palette) != 12:
+        raise ValueError("render_rgb_numpy: one colour per object slot and a palette of 12")
+    g = _rgb_geometry(x, y, c, s, height, fx, H, W, boxes6, boxes)
+    rr = (np.arange(H) - H // 2)[:, None]
+    wall_base = palette[np.array([_mix32(int(b), 0, 31) % 8 for b in g["b_w"]], np.int64)]
+    ch = _channels(wall_base)[None].repeat(H, axis=0)                                              # [H,W,3]: the wall
+    ch = np.where(g["panel"][None, :, None] == 1, ch - (ch >> 3), ch)
+    ch = np.where(g["wall_y"][None, :, None], ch - (ch >> 2), ch)
+    ch = np.where((rr >= g["r_sk"][None, :])[:, :, None], ch >> 1, ch)
+    ch = np.where(g["on_floor"][:, :, None], _channels(palette[8 + g["check"]]), ch)
+    if len(boxes6):
+        k = np.maximum(ids.astype(np.int64) - 1, 0)
+        oc = _channels(colours[k])
+        oc = np.where(g["obj_y"][np.arange(W)[None, :], k][:, :, None], oc - (oc >> 2), oc)
+        ch = np.where((ids > 0)[:, :, None], oc, ch)
+    cue = (depth * np.float32(128.0)).astype(np.int64)[:, :, None]
+    ch = (ch * (256 - cue)) >> 8
+    void = (ids == 0) & ~g["on_floor"] & ~np.isfinite(g["t_w"])[None, :]
+    ch = np.where(void[:, :, None], _channels(palette[10])[None, None, :], ch)
+    return depth, ids, ch.astype(np.uint8)
+
+
+def _rgb_geometry(x, y, c, s, height, fx, H, W, boxes6, boxes=None):
+    """The geometry `render_rgb_numpy` colours by: per column b_w, t_w, wall_y (a y-face), panel, r_sk and obj_y [W,K]; per
+    pixel on_floor (floor_d < t_w) and check (the floor's checker bit)."""
+    walls = _walls_of(boxes)
+    m = -(np.arange(W, dtype=np.float64) - W // 2) / fx
+    dx, dy = c - s * m, s + c * m
+    dx = np.where(np.abs(dx) < 1e-12, 1e-12, dx)
+    dy = np.where(np.abs(dy) < 1e-12, 1e-12, dy)
+
+    def slab(b):       # ([W,B] tmin, inf where the column misses the box; [W,B] bool: a y-face)
+        tx0, tx1 = (b[None, :, 0] - x) / dx[:, None], (b[None, :, 2] - x) / dx[:, None]
+        ty0, ty1 = (b[None, :, 1] - y) / dy[:, None], (b[None, :, 3] - y) / dy[:, None]
+        ex, ey = np.minimum(tx0, tx1), np.minimum(ty0, ty1)
+        tmin = np.maximum(ex, ey)
+        tmax = np.minimum(np.maximum(tx0, tx1), np.maximum(ty0, ty1))
+        return np.where((tmax >= np.maximum(tmin, 0.0)) & (tmin > 0.0), tmin, np.inf), ey > ex
+
+    def odd(v):        # int64(floor(v)) & 1, 0 where v is not finite
+        return np.floor(np.where(np.isfinite(v), v, 0.0)).astype(np.int64) & 1
+
+    cols = np.arange(W)
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        if len(walls):
+            t, yface = slab(walls)
+            b_w = t.argmin(axis=1)                                      # (argmin: the first, i.e. lowest, index among equals)
+            t_w = t[cols, b_w].astype(np.float32).astype(np.float64)
+            wall_y = yface[cols, b_w]
+        else:
+            b_w, t_w, wall_y = np.zeros(W, np.int64), np.full(W, np.inf), np.zeros(W, bool)
+        q = np.where(wall_y, x + dx * t_w, y + dy * t_w)
+        r_sk = np.ceil(((height - SKIRTING_HEIGHT) * fx) / t_w)
+        r_sk = np.where(np.isnan(r_sk), 32767.0, np.clip(r_sk, -32768.0, 32767.0))
+        rr = (np.arange(H) - H // 2)[:, None]
+        floor_d = np.where(rr > 0, (height * fx) / np.maximum(rr, 1), np.inf)                       # [H,1]
+        on_floor = floor_d < t_w[None, :]                                                            # [H,W]
+        fd = np.where(on_floor, floor_d, 0.0)
+        px, py = x + dx[None, :] * fd, y + dy[None, :] * fd
+        check = (odd(px * 2.0) + odd(py * 2.0)) & 1
+        obj_y = slab(np.asarray(boxes6, np.float64).reshape(-1, 6)[:, :4])[1]                       # [W,K]
+    return {"b_w": b_w, "t_w": t_w, "wall_y": wall_y, "panel": odd(q * 2.0), "r_sk": r_sk, "on_floor": on_floor,
+            "check": check, "obj_y": obj_y}
+
+
+def rgb_kinds_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6, boxes=None):
+    """What `render_rgb_numpy` shows where, for tests and probes: u8 [H,W] kind (0 void, 1 wall, 2 floor, 3 object) and bool
+    [H,W] planes "skirting" (wall pixels at half brightness), "odd panel" and "y-face" (of the wall or object shown; False on
+    floor and void)."""
+    ids = render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6, boxes)[1]
+    g = _rgb_geometry(x, y, c, s, height, fx, H, W, boxes6, boxes)
+    obj = ids > 0
+    floor = ~obj & g["on_floor"]
+    wall = ~obj & ~floor & np.isfinite(g["t_w"])[None, :]
+    kind = np.where(obj, 3, np.where(floor, 2, np.where(wall, 1, 0))).astype(np.uint8)
+    rr = (np.arange(H) - H // 2)[:, None]
+    yface = wall & g["wall_y"][None, :]
+    if obj.any():
+        yface |= obj & g["obj_y"][np.arange(W)[None, :], np.maximum(ids.astype(np.int64) - 1, 0)]
+    return kind, wall & (rr >= g["r_sk"][None, :]), wall & (g["panel"][None, :] == 1), yface
+
+
 # ---------------------------------------------------------------------------------------------- ObjectNav metrics
 # The length of the shortest collision-free path to an episode's goal, which SPL, SoftSPL and Habitat's distance_to_goal are
 # made of (the reference reads them off Habitat's navmesh).  This section is the HOST STATEMENT of the rule; the device
