@@ -843,44 +843,74 @@ int vlfm_jpeg_decode_batched(const uint8_t* d_files, size_t files_bytes, const i
                              void* d_scratch, size_t scratch_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Rooms world renderer (ABI 15): the depth frames n cameras see in a world of axis-aligned boxes, ray-cast per image column
- * in ONE launch (csrc/world_render.hip), bit for bit what vlfm_amd.harness.RoomsRenderer.render_cameras computes with torch
- * f64 operations and, for the tabulated headings, what synthetic.depth_from_profile(synthetic.wall_profile(...)) computes
- * in NumPy.  Test-world infrastructure of the batched harness (the reference observes through Habitat): it lets a closed-loop
- * episode render from wherever the robot's own actions took it.
+ * Synthetic worlds (ABI 24, csrc/world_render.hip): what n cameras see in worlds of axis-aligned boxes, ray-cast per image
+ * column in ONE launch.  Test-world infrastructure of the batched harness (the reference observes through Habitat): it lets a
+ * closed-loop episode render from wherever the robot's own actions took it.
+ *
+ * The world table: every camera (and every geodesic field, below) stands in one row of a table of floor plans
+ * (vlfm_amd.harness.WorldTable keeps it, synthetic.ProceduralWorlds generates plans).  The fixed rooms world (synthetic.BOXES) is
+ * a table of one row with max_boxes = its box count.
+ *   d_world_boxes  [n_worlds][max_boxes][4] doubles: x0, y0, x1, y1
+ *   d_box_counts   [n_worlds] int32: the boxes of each world, clamped to [0, max_boxes] by the kernels; rows beyond a world's
+ *                  count are never read as boxes, whatever they hold
+ *   d_world_of     [n] int32: the world (row of the table) of each camera / field.  An index outside [0, n_worlds) is an EMPTY
+ *                  world; the kernels never read out of bounds for it (the Python wrappers refuse it before any launch).
+ * A workgroup stages the `count` boxes of its camera's world; max_boxes sizes the LDS layout and the output strides.
+ *
+ * vlfm_worlds_raycast, on `stream`:
  *   d_cameras  n records of 8 doubles (64 bytes): x, y, cos(yaw), sin(yaw), camera height, fx (pixels), min_depth, max_depth
  *              (max_depth > min_depth: the frame is normalised to that range and clamped to [1e-3, 1])
- *   d_boxes    [n_boxes][4] doubles: x0, y0, x1, y1
- *   d_out      [n][H][W] float
- * The boxes, one image row and one band of rows must fit 64 KB of LDS (VLFM_ERR_INVALID otherwise). */
-int vlfm_rooms_raycast(const double* d_cameras, int n, const double* d_boxes, int n_boxes, int H, int W, float* d_out,
-                       void* stream);
-
-/* Rooms world with objects (ABI 16): vlfm_rooms_raycast's frames with up to 8 objects per environment -- axis-aligned boxes
- * with a vertical extent -- standing in front of the walls, rendered with occlusion in ONE launch (plus a fill of d_stats),
- * bit for bit what vlfm_amd.synthetic.render_objects_numpy / object_stats_numpy compute.
+ *   d_depth    [n][H][W] float
+ * d_objects == NULL: walls only.  Bit for bit what RoomsRenderer.render_cameras computes with torch f64 operations in the rooms
+ * world and, for the tabulated headings, synthetic.depth_from_profile(synthetic.wall_profile(..., boxes = the world's boxes)) in
+ * NumPy.  d_env_of, n_envs, d_ids, d_stats and the colour arguments are ignored; d_rgb must be NULL.  max_boxes, one image row
+ * and one band of rows must fit 64 KB of LDS.
+ *
+ * d_objects set: up to 8 objects per environment -- axis-aligned boxes with a vertical extent -- stand in front of the walls,
+ * rendered with occlusion (plus a fill of d_stats), bit for bit synthetic.render_objects_numpy(..., boxes = the world's boxes) /
+ * object_stats_numpy.
  *   d_objects  [n_envs][8][8] doubles: x0, y0, x1, y1, z0, z1, valid (0 = no object in this slot), pad
  *   d_env_of   [n] the environment (row of d_objects) each camera looks at, in [0, n_envs) (checked by the caller: the
  *              kernel treats anything else as "no objects")
- *   d_depth    [n][H][W] float; d_ids [n][H][W] uint8: 0 = wall / floor, k + 1 = object slot k
+ *   d_ids      [n][H][W] uint8: 0 = wall / floor, k + 1 = object slot k
  *   d_stats    [n][8][5] int32 per object slot: visible pixels, first / last column, first / last row;
  *              (0, W, -1, H, -1) for an object without a pixel
  * Per column u an object is hit by the walls' slab test at t = f64(f32(tmin)) and covers the rows r with
  * ceil((height - z1) fx / t) <= r - H/2 <= floor((height - z0) fx / t); a pixel takes the f32 minimum of wall, floor and
  * the covering objects, and the id of the nearest covering object (lowest slot among equals) where that is STRICTLY nearer
- * than wall and floor.  The boxes, 69 bytes per image column and one band of rows must fit 64 KB of LDS, and H <= 32768
- * (VLFM_ERR_INVALID otherwise, nothing written). */
-int vlfm_rooms_raycast_objects(const double* d_cameras, int n, const double* d_boxes, int n_boxes, const double* d_objects,
-                               const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids,
-                               int32_t* d_stats, void* stream);
+ * than wall and floor.  max_boxes, 69 bytes per image column and one band of rows must fit 64 KB of LDS; n_envs >= 1, H <= 32768.
+ *
+ * d_objects and d_rgb set: the camera's RGB view of the same world as well, from the same launch, every byte what
+ * synthetic.render_rgb_numpy computes; d_depth, d_ids and d_stats are bit for bit those without d_rgb.  d_rgb without d_objects
+ * is refused; a world without objects is an object row of zeros.  Colours are packed 0x00RRGGBB (the top byte is ignored).
+ *   d_object_colours  [n_envs][8] int32: the colour of each object slot of d_objects (required with d_rgb)
+ *   d_palette         [12] int32: 8 wall colours, 2 floor colours, the void, one spare entry (required with d_rgb)
+ *   d_rgb             [n][H][W][3] uint8: R, G, B
+ * Per column: the wall is the box b_w with the least tmin among the hit boxes (lowest index among equals, counted inside the
+ * camera's own world) at t_w = f64(f32(tmin)); it shows a y-face iff min(ty0, ty1) > min(tx0, tx1); q = x + dx t_w on a y-face,
+ * y + dy t_w on an x-face; panel = floor(2 q) & 1; r_sk = ceil(((height - 0.12) fx) / t_w) clamped to int16.  Per pixel, with
+ * rr = r - H/2, the first that holds:
+ *   object  id > 0: the slot's colour; its footprint shows a y-face: ch -= ch >> 2
+ *   floor   floor_d < t_w (f64): palette[8 + ((floor(2 px) + floor(2 py)) & 1)], (px, py) = (x, y) + (dx, dy) floor_d
+ *   wall    t_w finite: palette[mix32(b_w, 0, 31) % 8]; an odd panel: ch -= ch >> 3; a y-face: ch -= ch >> 2; rr >= r_sk: ch >>= 1
+ *   void    palette[10], as it is
+ * and on the first three the depth cue g = int(depth * 128.0f), ch = (ch * (256 - g)) >> 8.  One rounding per f64 operation.
+ * max_boxes, 95 bytes per image column and one band of at most 128 rows (12 bytes each) must fit 64 KB of LDS.
+ *
+ * n <= 65535; anything refused above is VLFM_ERR_INVALID, nothing launched, nothing written; n == 0 returns VLFM_OK. */
+int vlfm_worlds_raycast(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts, int n_worlds,
+                        int max_boxes, const int32_t* d_world_of, const double* d_objects, const int32_t* d_env_of, int n_envs,
+                        int H, int W, float* d_depth, uint8_t* d_ids, int32_t* d_stats, const int32_t* d_object_colours,
+                        const int32_t* d_palette, uint8_t* d_rgb, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Geodesic distances in the rooms world (ABI 19, csrc/geodesic.hip): the length of the shortest collision-free path from a
- * point to an ObjectNav goal, which SPL, SoftSPL and distance_to_goal are made of (the reference reads them off Habitat's
+ * Geodesic distances in the synthetic worlds (ABI 19; the fields read the world table since ABI 24; csrc/geodesic.hip): the
+ * length of the shortest collision-free path from a point to an ObjectNav goal, which SPL, SoftSPL and distance_to_goal are made of (the reference reads them off Habitat's
  * navmesh).  Bit for bit vlfm_amd.synthetic.geodesic_field_numpy / geodesic_query_numpy: f64, one rounding per operation,
  * no fused multiply-add, the expressions as written here.
- *   rectangles  the n_boxes shared wall boxes (x0, y0, x1, y1), then the environment's object slots with valid != 0 in slot
- *               order, each inflated to (x0 - margin, y0 - margin, x1 + margin, y1 + margin).  OPEN sets.
+ *   rectangles  the `count` wall boxes (x0, y0, x1, y1) of the field's world, then the environment's object slots with
+ *               valid != 0 in slot order -- synthetic.inflated_rects(objects, margin, boxes) --, each inflated to
+ *               (x0 - margin, y0 - margin, x1 + margin, y1 + margin).  OPEN sets.
  *   blocked     the segment p -> q is blocked by a rectangle iff some t in (0, 1) puts p + t (q - p) strictly inside it:
  *               per axis, with d = q - p:  d == 0: the interval is (-inf, inf) if lo < p < hi, else empty;  otherwise
  *               t0 = (lo - p) / d, t1 = (hi - p) / d, interval (min(t0, t1), max(t0, t1));
@@ -897,75 +927,29 @@ int vlfm_rooms_raycast_objects(const double* d_cameras, int n, const double* d_b
  * Two rectangles that exactly abut leave a slit of zero width that a path may use: d can only come out shorter for it.
  *
  * vlfm_geodesic_fields: the fields of n environments, ONE launch (one workgroup per environment) on `stream`.
- *   d_boxes         [n_boxes][4] doubles, shared;  margin: the inflation
- *   d_objects       [n][8][8] doubles: vlfm_rooms_raycast_objects' records (x0 y0 x1 y1 z0 z1 valid pad)
+ *   d_world_boxes, d_box_counts, n_worlds, max_boxes, d_world_of [n]: the world table above and the world of each field
+ *   margin          the inflation
+ *   d_objects       [n][8][8] doubles: vlfm_worlds_raycast's records (x0 y0 x1 y1 z0 z1 valid pad)
  *   d_sources       [n][max_sources][2] doubles, d_source_counts [n] int32 (clamped to [0, max_sources]; 0: every dist is inf)
- *   d_rects         [n][R][4] doubles out, R = n_boxes + 8;  d_nodes [n][4R][2] doubles out;  d_dist [n][4R] doubles out;
- *                   d_counts [n][2] int32 out: rectangles, nodes.  Table tails are zeros at infinite distance.
+ *   d_rects         [n][R][4] doubles out, R = max_boxes + 8 whatever the counts;  d_nodes [n][4R][2] doubles out;
+ *                   d_dist [n][4R] doubles out;  d_counts [n][2] int32 out: rectangles, nodes.  Table tails are zeros at
+ *                   infinite distance.
  * The tables of 4R candidate nodes and their 4R x 4R visibility bitmap must fit 64 KB of LDS (VLFM_ERR_INVALID otherwise,
  * nothing launched): R <= 141.
  *
  * vlfm_geodesic_query: d of m points, ONE launch (one workgroup per point) on `stream`.
  *   d_points        [m][2] doubles;  d_field_of [m] int32: the field of each point; outside [0, n_fields): the answer is NaN
- *   d_rects, d_nodes, d_dist, d_counts, d_sources, d_source_counts, max_sources, n_boxes: the n_fields fields as built above
+ *   d_rects, d_nodes, d_dist, d_counts, d_sources, d_source_counts, max_sources: the n_fields fields as built above;
+ *                   n_boxes = the max_boxes they were built with
  *   d_out           [m] doubles
  * n == 0 and m == 0 return VLFM_OK without a launch. */
-int vlfm_geodesic_fields(const double* d_boxes, int n_boxes, double margin, const double* d_objects, const double* d_sources,
+int vlfm_geodesic_fields(const double* d_world_boxes, const int32_t* d_box_counts, int n_worlds, int max_boxes,
+                         const int32_t* d_world_of, double margin, const double* d_objects, const double* d_sources,
                          const int32_t* d_source_counts, int n, int max_sources, double* d_rects, double* d_nodes,
                          double* d_dist, int32_t* d_counts, void* stream);
 int vlfm_geodesic_query(const double* d_points, const int32_t* d_field_of, int m, int n_fields, int n_boxes,
                         const double* d_rects, const double* d_nodes, const double* d_dist, const int32_t* d_counts,
                         const double* d_sources, const int32_t* d_source_counts, int max_sources, double* d_out, void* stream);
-
-/* ---------------------------------------------------------------------------------------------
- * Procedural worlds (ABI 22): a world per camera / per field instead of one shared box table (vlfm_amd.synthetic.
- * ProceduralWorlds generates the floor plans; harness.WorldTable keeps the table).
- *   d_world_boxes  [n_worlds][max_boxes][4] doubles: x0, y0, x1, y1
- *   d_box_counts   [n_worlds] int32: the boxes of each world, clamped to [0, max_boxes] by the kernels; rows beyond a world's
- *                  count are never read as boxes, whatever they hold
- *   d_world_of     [n] int32: the world (row of the table) of each camera / field.  An index outside [0, n_worlds) is an EMPTY
- *                  world; the kernels never read out of bounds for it (the Python wrappers refuse it before any launch).
- *
- * vlfm_worlds_raycast: vlfm_rooms_raycast_objects with the walls of each camera's own world, ONE launch plus the fill of d_stats,
- * bit for bit synthetic.render_objects_numpy(..., boxes = that world's boxes) / object_stats_numpy.  d_objects == NULL: walls
- * only -- d_env_of, n_envs, d_ids and d_stats are ignored and the frames are vlfm_rooms_raycast's, i.e.
- * depth_from_profile(wall_profile(..., boxes = ...)).  Grid, row bands, LDS layout and store paths are those of the shared-table
- * entries; a workgroup stages the `count` boxes of its camera's world.  The LDS budget is that of the shared-table entries with
- * n_boxes = max_boxes (VLFM_ERR_INVALID otherwise, nothing launched, nothing written); n <= 65535, and H <= 32768 with objects.
- *
- * vlfm_geodesic_fields_worlds: vlfm_geodesic_fields with the rectangles of field i = the `count` boxes of world d_world_of[i], then
- * the valid objects of d_objects[i] -- synthetic.inflated_rects(objects, margin, boxes) -- ONE launch, one workgroup per field,
- * bit for bit synthetic.geodesic_field_numpy.  The outputs are strided by R = max_boxes + 8 whatever the counts, so
- * vlfm_geodesic_query reads them unchanged when called with n_boxes = max_boxes.  R <= 141 (VLFM_ERR_INVALID otherwise). */
-int vlfm_worlds_raycast(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts, int n_worlds,
-                        int max_boxes, const int32_t* d_world_of, const double* d_objects, const int32_t* d_env_of, int n_envs,
-                        int H, int W, float* d_depth, uint8_t* d_ids, int32_t* d_stats, void* stream);
-int vlfm_geodesic_fields_worlds(const double* d_world_boxes, const int32_t* d_box_counts, int n_worlds, int max_boxes,
-                                const int32_t* d_world_of, double margin, const double* d_objects, const double* d_sources,
-                                const int32_t* d_source_counts, int n, int max_sources, double* d_rects, double* d_nodes,
-                                double* d_dist, int32_t* d_counts, void* stream);
-
-/* World colours (ABI 23): vlfm_worlds_raycast with objects, and the camera's RGB view of the same world, ONE launch plus the
- * fill of d_stats (csrc/world_render.hip), every byte what vlfm_amd.synthetic.render_rgb_numpy computes.  d_depth, d_ids and
- * d_stats are always written and are bit for bit vlfm_worlds_raycast's.  Colours are packed 0x00RRGGBB (the top byte is ignored).
- *   d_object_colours  [n_envs][8] int32: the colour of each object slot of d_objects
- *   d_palette         [12] int32: 8 wall colours, 2 floor colours, the void, one spare entry
- *   d_rgb             [n][H][W][3] uint8: R, G, B
- * Per column: the wall is the box b_w with the least tmin among the hit boxes (lowest index among equals, counted inside the
- * camera's own world) at t_w = f64(f32(tmin)); it shows a y-face iff min(ty0, ty1) > min(tx0, tx1); q = x + dx t_w on a y-face,
- * y + dy t_w on an x-face; panel = floor(2 q) & 1; r_sk = ceil(((height - 0.12) fx) / t_w) clamped to int16.  Per pixel, with
- * rr = r - H/2, the first that holds:
- *   object  id > 0: the slot's colour; its footprint shows a y-face: ch -= ch >> 2
- *   floor   floor_d < t_w (f64): palette[8 + ((floor(2 px) + floor(2 py)) & 1)], (px, py) = (x, y) + (dx, dy) floor_d
- *   wall    t_w finite: palette[mix32(b_w, 0, 31) % 8]; an odd panel: ch -= ch >> 3; a y-face: ch -= ch >> 2; rr >= r_sk: ch >>= 1
- *   void    palette[10], as it is
- * and on the first three the depth cue g = int(depth * 128.0f), ch = (ch * (256 - g)) >> 8.  One rounding per f64 operation.
- * The world table's max_boxes, 95 bytes per image column and one band of at most 128 rows (12 bytes each) must fit 64 KB of LDS;
- * n <= 65535, n_envs >= 1, H <= 32768; every pointer is required (VLFM_ERR_INVALID otherwise, nothing launched). */
-int vlfm_worlds_raycast_rgb(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts, int n_worlds,
-                            int max_boxes, const int32_t* d_world_of, const double* d_objects, const int32_t* d_env_of, int n_envs,
-                            int H, int W, float* d_depth, uint8_t* d_ids, int32_t* d_stats, const int32_t* d_object_colours,
-                            const int32_t* d_palette, uint8_t* d_rgb, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Map planner (ABI 21, csrc/map_planner.hip): shortest paths over the navigable planes of the obstacle maps (the reference's

@@ -29,7 +29,8 @@ def _records(boxes_per_env, slots_per_env=None) -> np.ndarray:
 
 
 def _fields(device, walls, margin, records, sources_per_env, max_sources=MAX_SRC):
-    """Raw call of vlfm_geodesic_fields -> dict of device tensors (the strides of include/vlfm_amd.h)."""
+    """Raw call of vlfm_geodesic_fields, the shared ``walls`` as a table of one world that every field stands in -> dict of
+    device tensors (the strides of include/vlfm_amd.h)."""
     import torch
 
     L = _lib()
@@ -45,8 +46,10 @@ def _fields(device, walls, margin, records, sources_per_env, max_sources=MAX_SRC
          "sources": torch.tensor(src, **f64), "source_counts": torch.tensor(cnt, dtype=torch.int32, device=device),
          "rects": torch.full((n, R, 4), -7.0, **f64), "nodes": torch.full((n, 4 * R, 2), -7.0, **f64),
          "dist": torch.full((n, 4 * R), -7.0, **f64), "counts": torch.full((n, 2), -7, dtype=torch.int32, device=device),
-         "n": n, "B": B, "max_sources": max_sources}
-    rc = L.lib().vlfm_geodesic_fields(t["walls"].data_ptr() if B else None, B, float(margin), t["records"].data_ptr(),
+         "box_counts": torch.tensor([B], dtype=torch.int32, device=device),
+         "world_of": torch.zeros(n, dtype=torch.int32, device=device), "n": n, "B": B, "max_sources": max_sources}
+    rc = L.lib().vlfm_geodesic_fields(t["walls"].data_ptr() if B else None, t["box_counts"].data_ptr(), 1, B,
+                                      t["world_of"].data_ptr(), float(margin), t["records"].data_ptr(),
                                       t["sources"].data_ptr(), t["source_counts"].data_ptr(), n, max_sources,
                                       t["rects"].data_ptr(), t["nodes"].data_ptr(), t["dist"].data_ptr(), t["counts"].data_ptr(),
                                       torch.cuda.current_stream().cuda_stream)
@@ -227,9 +230,10 @@ def test_empty_calls_and_refusals(gpu_device):
 
     L = _lib()
     lib = L.lib()
-    assert lib.vlfm_abi_version() >= 19
+    assert lib.vlfm_abi_version() >= 24
     st = torch.cuda.current_stream().cuda_stream
-    assert lib.vlfm_geodesic_fields(None, 0, 0.2, None, None, None, 0, 8, None, None, None, None, st) == L.VLFM_OK     # n == 0
+    assert lib.vlfm_geodesic_fields(None, None, 0, 0, None, 0.2, None, None, None, 0, 8, None, None, None, None,
+                                    st) == L.VLFM_OK                                                                   # n == 0
     assert lib.vlfm_geodesic_query(None, None, 0, 0, 0, None, None, None, None, None, None, 8, None, st) == L.VLFM_OK  # m == 0
     # tables that do not fit 64 KB of LDS are refused by status, before any launch: 134 walls + 8 slots = 142 rectangles
     B = 134
@@ -239,17 +243,18 @@ def test_empty_calls_and_refusals(gpu_device):
     bufs = dict(walls=torch.tensor(walls, **f64), rec=torch.zeros((1, 8, 8), **f64), src=torch.zeros((1, 8, 2), **f64),
                 cnt=torch.zeros(1, dtype=torch.int32, device=gpu_device), rects=torch.full((1, R, 4), -7.0, **f64),
                 nodes=torch.full((1, 4 * R, 2), -7.0, **f64), dist=torch.full((1, 4 * R), -7.0, **f64),
-                counts=torch.full((1, 2), -7, dtype=torch.int32, device=gpu_device))
+                counts=torch.full((1, 2), -7, dtype=torch.int32, device=gpu_device),
+                nb=torch.tensor([B], dtype=torch.int32, device=gpu_device), wof=torch.zeros(1, dtype=torch.int32, device=gpu_device))
     p = {k: v.data_ptr() for k, v in bufs.items()}
-    rc = lib.vlfm_geodesic_fields(p["walls"], B, 0.2, p["rec"], p["src"], p["cnt"], 1, 8, p["rects"], p["nodes"], p["dist"],
-                                  p["counts"], st)
+    rc = lib.vlfm_geodesic_fields(p["walls"], p["nb"], 1, B, p["wof"], 0.2, p["rec"], p["src"], p["cnt"], 1, 8, p["rects"],
+                                  p["nodes"], p["dist"], p["counts"], st)
     assert rc == L.VLFM_ERR_INVALID and "LDS" in L.last_error()
     torch.cuda.synchronize()
     assert bool((bufs["dist"] == -7.0).all()) and bool((bufs["counts"] == -7).all())                 # nothing written
-    assert lib.vlfm_geodesic_fields(p["walls"], -1, 0.2, p["rec"], p["src"], p["cnt"], 1, 8, p["rects"], p["nodes"], p["dist"],
-                                    p["counts"], st) == L.VLFM_ERR_INVALID
-    assert lib.vlfm_geodesic_fields(p["walls"], 4, float("nan"), p["rec"], p["src"], p["cnt"], 1, 8, p["rects"], p["nodes"],
-                                    p["dist"], p["counts"], st) == L.VLFM_ERR_INVALID
+    assert lib.vlfm_geodesic_fields(p["walls"], p["nb"], 1, -1, p["wof"], 0.2, p["rec"], p["src"], p["cnt"], 1, 8, p["rects"],
+                                    p["nodes"], p["dist"], p["counts"], st) == L.VLFM_ERR_INVALID
+    assert lib.vlfm_geodesic_fields(p["walls"], p["nb"], 1, 4, p["wof"], float("nan"), p["rec"], p["src"], p["cnt"], 1, 8,
+                                    p["rects"], p["nodes"], p["dist"], p["counts"], st) == L.VLFM_ERR_INVALID
     assert lib.vlfm_geodesic_query(None, None, 3, 1, 4, p["rects"], p["nodes"], p["dist"], p["counts"], p["src"], p["cnt"], 8,
                                    None, st) == L.VLFM_ERR_INVALID
     # the largest wall count that fits does run (133 walls: 141 rectangles, 564 candidate nodes over 256 lanes)

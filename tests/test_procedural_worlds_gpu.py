@@ -1,4 +1,4 @@
-"""-m gpu: a world per camera / per field (vlfm_worlds_raycast, vlfm_geodesic_fields_worlds through RoomsRenderer.cast_worlds /
+"""-m gpu: a world per camera / per field (vlfm_worlds_raycast, vlfm_geodesic_fields through RoomsRenderer.cast_worlds /
 geodesic_fields_worlds and WorldTable) against the host statements, bit for bit, and BatchedEpisodes(worlds=...)."""
 import functools
 
@@ -152,15 +152,24 @@ def test_walls_only_on_lattice_poses(gpu_device):
 
 @pytest.mark.parametrize("H,W", [(48, 64), (9, 18)], ids=["64x48", "18x9"])
 def test_a_row_of_BOXES_is_the_existing_entries(gpu_device, H, W):
+    """The rooms-world methods and a table row that holds BOXES are one path now: both are held against the host statements
+    of the rooms world (render_objects_numpy / object_stats_numpy with boxes=None; render_cameras, torch f64, for walls only)."""
     tf, hfov, lo, hi = _cameras()
     r = _renderer(H, W, gpu_device)
     table = _table(gpu_device, [_worlds()[0][1], S.BOXES])
-    objs = objects_array(_objects())
-    old = r.cast_cameras_objects(tf, objs, ENV_OF, hfov, lo, hi)
-    new = r.cast_worlds(tf, table, [1] * 7, objs, ENV_OF, hfov, lo, hi)
+    objs = _objects()
+    ref = [S.render_objects_numpy(t[0, 3], t[1, 3], t[0, 0], t[1, 0], t[2, 3], W / (2 * np.tan(f / 2)), a, b, H, W, objs[e],
+                                  boxes=None) for t, f, a, b, e in zip(tf, hfov, lo, hi, ENV_OF)]
+    want = (np.stack([x[0] for x in ref]), np.stack([x[1] for x in ref]), np.stack([S.object_stats_numpy(x[1]) for x in ref]))
+    assert (want[1] > 0).any()
+    old = r.cast_cameras_objects(tf, objects_array(objs), ENV_OF, hfov, lo, hi)
+    new = r.cast_worlds(tf, table, [1] * 7, objects_array(objs), ENV_OF, hfov, lo, hi)
+    _assert_equal(old, want)
+    _assert_equal(new, want)
     assert np.array_equal(_bits(new[0]), _bits(old[0])) and (new[1] == old[1]).all() and (new[2] == old[2]).all()
-    assert np.array_equal(_bits(r.cast_worlds(tf, table, [1] * 7, hfov=hfov, min_depth=lo, max_depth=hi)),
-                          _bits(r.cast_cameras(tf, hfov, lo, hi)))
+    walls = _bits(r.render_cameras(tf, hfov, lo, hi))
+    assert np.array_equal(_bits(r.cast_worlds(tf, table, [1] * 7, hfov=hfov, min_depth=lo, max_depth=hi)), walls)
+    assert np.array_equal(_bits(r.cast_cameras(tf, hfov, lo, hi)), walls)
 
 
 def test_lds_refusal_out_and_shapes(gpu_device):
@@ -192,6 +201,37 @@ def test_lds_refusal_out_and_shapes(gpu_device):
             r.cast_worlds(tf, big, WORLD_OF, objs, ENV_OF, out=bad)
     with pytest.raises(ValueError):
         r.cast_worlds(tf, big, WORLD_OF, objs, [0, 1, 2, 3, 0, 0, 0])
+
+
+def test_the_one_entry_refuses_colour_without_objects(gpu_device):
+    """Raw calls of vlfm_worlds_raycast, one camera of 18x9 in a table of one world (BOXES): d_rgb without d_objects is refused
+    by status with nothing written; the same call without d_rgb is the walls-only frame; n == 0 needs no pointer."""
+    import torch
+
+    from vlfm_amd import _lib as L
+
+    lib, H, W = L.lib(), 9, 18
+    st = torch.cuda.current_stream().cuda_stream
+    f64 = dict(dtype=torch.float64, device=gpu_device)
+    cam = torch.tensor([[0.0, 0.0, 1.0, 0.0, S.CAMERA_HEIGHT, S.camera_intrinsics(W)[0], S.MIN_DEPTH, S.MAX_DEPTH]], **f64)
+    boxes = torch.tensor(np.asarray(S.BOXES, np.float64), **f64)
+    counts = torch.tensor([len(S.BOXES)], dtype=torch.int32, device=gpu_device)
+    world_of = torch.zeros(1, dtype=torch.int32, device=gpu_device)
+    depth = torch.full((1, H, W), -1.0, dtype=torch.float32, device=gpu_device)
+    rgb = torch.full((1, H, W, 3), 7, dtype=torch.uint8, device=gpu_device)
+
+    def call(d_rgb):
+        return lib.vlfm_worlds_raycast(cam.data_ptr(), 1, boxes.data_ptr(), counts.data_ptr(), 1, len(S.BOXES), world_of.data_ptr(),
+                                       None, None, 0, H, W, depth.data_ptr(), None, None, None, None, d_rgb, st)
+
+    assert call(rgb.data_ptr()) == L.VLFM_ERR_INVALID
+    torch.cuda.synchronize()
+    assert bool((depth == -1.0).all()) and bool((rgb == 7).all())
+    assert lib.vlfm_worlds_raycast(None, 0, None, None, 0, 0, None, None, None, 0, H, W, None, None, None, None, None, None,
+                                   st) == L.VLFM_OK
+    assert call(None) == L.VLFM_OK, L.last_error()
+    want = S.depth_from_profile(S.wall_profile(0.0, 0.0, 0, W), H)
+    assert np.array_equal(_bits(depth[0]), want.view(np.int32)) and bool((rgb == 7).all())
 
 
 def test_launch_is_ordered_on_the_current_stream(gpu_device):

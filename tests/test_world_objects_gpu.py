@@ -1,4 +1,4 @@
-"""-m gpu: RoomsRenderer.cast_cameras_objects (csrc/world_render.hip: vlfm_rooms_raycast_objects, one launch) against the NumPy
+"""-m gpu: RoomsRenderer.cast_cameras_objects (csrc/world_render.hip: vlfm_worlds_raycast with objects, one launch) against the NumPy
 statement of its contract (synthetic.render_objects_numpy / object_stats_numpy): depth as bits, ids and stats all equal."""
 import functools
 

@@ -1,4 +1,4 @@
-"""-m gpu: the camera's RGB view of the synthetic worlds (vlfm_worlds_raycast_rgb through RoomsRenderer.cast_worlds_rgb /
+"""-m gpu: the camera's RGB view of the synthetic worlds (vlfm_worlds_raycast with d_rgb through RoomsRenderer.cast_worlds_rgb /
 cast_cameras_rgb) against the host statement synthetic.render_rgb_numpy, byte for byte, and BatchedEpisodes(render_rgb=True)."""
 import numpy as np
 import pytest

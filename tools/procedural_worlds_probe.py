@@ -1,13 +1,13 @@
 """What a floor plan per environment (synthetic.ProceduralWorlds, harness.WorldTable, vlfm_worlds_raycast,
-vlfm_geodesic_fields_worlds) costs and what it shows, measured in one place.
+vlfm_geodesic_fields) costs and what it shows, measured in one place.
 
   (a) kernel time of the ray caster from `rocprofv3 --kernel-trace --stats`, in a run of its own (a fresh child process), at 8 and
-      256 cameras of 640x480 with objects: the shared-table entry (vlfm_rooms_raycast_objects on BOXES), the per-world entry with
-      every camera on a table row that holds BOXES (same cameras, same objects: the staging is the only difference), and the
-      per-world entry on generated worlds (cameras at the worlds' start poses, box counts vary).  The three legs alternate over
+      256 cameras of 640x480 with objects: the rooms world (the renderer's own table of one row, max_boxes = 37), every camera on
+      its own row of a 64-box table that holds BOXES (same cameras, same objects: the table is the only difference), and
+      generated worlds (cameras at the worlds' start poses, box counts vary).  The three legs alternate over
       --windows windows of TRACE_LAUNCHES launches each; reported per leg: the median over all launches, their min-max, and the
-      min-max of the per-window medians.  From the same trace: geodesic_fields_kernel for 256 fields, shared walls and generated
-      worlds.
+      min-max of the per-window medians.  From the same trace: geodesic_fields_kernel for 256 fields, the rooms world and
+      generated worlds.
   (b) closed-loop ObjectNav at 256 environments without a model (stub cosines): env-steps/s, success rate, SPL, SoftSPL for
       BangBangController and MapPlannerController, in the fixed rooms world and in procedural worlds, the four harnesses
       alternating over the same windows in one process (the windows of tools/map_planner_probe.py: 45 steps in, 3 x --steps).
@@ -26,7 +26,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
 CAMERAS = (8, 256)
-LEGS = ("shared BOXES", "table rows of BOXES", "generated worlds")
+LEGS = ("rooms world (table of one)", "table rows of BOXES", "generated worlds")
 TRACE_LAUNCHES, TRACE_WARMUP = 20, 3
 H, W = 480, 640
 
@@ -82,7 +82,7 @@ def cast(rooms, scene, out):
 
 def trace_child(windows: int) -> None:
     """Per camera count: `windows` windows; in each, per leg in the order of LEGS, TRACE_WARMUP + TRACE_LAUNCHES launches.  Then
-    the geodesic fields of 256 environments, shared walls and generated worlds alternating, the same counts."""
+    the geodesic fields of 256 environments, the rooms world and generated worlds alternating, the same counts."""
     import numpy as np
     import torch
 
@@ -131,11 +131,8 @@ def probe_trace(lines, workdir: str, windows: int) -> None:
         for g, group in enumerate(groups):
             for k, leg in enumerate(legs):
                 us = np.array([[t for t, _ in ours[((g * windows + w) * len(legs) + k) * per:][TRACE_WARMUP:per]] for w in range(windows)])
-                names = {name for w in range(windows) for _, name in ours[((g * windows + w) * len(legs) + k) * per:][:per]}
-                want = "WorldBoxes" if leg != LEGS[0] else "SharedBoxes"
-                assert all(want in name for name in names), (leg, names)
                 med = np.median(us, axis=1)
-                lines.append("kernel %s  %-20s %-30s %9.1f us (%.1f-%.1f over %d launches; per-window medians %.1f-%.1f, %d windows)"
+                lines.append("kernel %s  %-27s %-30s %9.1f us (%.1f-%.1f over %d launches; per-window medians %.1f-%.1f, %d windows)"
                              % (label(group), leg, kernel, *stats(us.reshape(-1)), us.size, med.min(), med.max(), windows))
                 print(lines[-1], flush=True)
 

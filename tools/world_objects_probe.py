@@ -1,4 +1,4 @@
-"""What objects in the rooms world cost (csrc/world_render.hip: vlfm_rooms_raycast_objects), measured in one place.
+"""What objects in the rooms world cost (csrc/world_render.hip: vlfm_worlds_raycast with objects), measured in one place.
 
   (a) kernel time of rooms_raycast_objects_kernel from `rocprofv3 --kernel-trace --stats`, in a run of its own (a fresh child
       process, started before this process touches the device): 256 and 8 frames of 640x480, each environment with the two

@@ -1,8 +1,8 @@
-"""What the camera's RGB view of the world costs (csrc/world_render.hip: vlfm_worlds_raycast_rgb), measured in one place, with HIP
+"""What the camera's RGB view of the world costs (csrc/world_render.hip: vlfm_worlds_raycast + d_rgb), measured in one place, with HIP
 events, in one session, on the same inputs.
 
   (a) per launch at 256 cameras of 640x480 in 256 generated worlds with their objects: vlfm_worlds_raycast (depth, ids, stats:
-      5 bytes per pixel) next to vlfm_worlds_raycast_rgb (the same and the colour plane: 8 bytes per pixel).  Two clocks: the
+      5 bytes per pixel) next to vlfm_worlds_raycast + d_rgb (the same and the colour plane: 8 bytes per pixel).  Two clocks: the
       events the library attaches to the dispatch itself (vlfm_profile_enable: the kernel alone) and a pair of events around a
       window of calls (the small host-to-device copy, the fill of the stats and the kernel).  The two entries alternate over
       --windows windows of LAUNCHES launches after WARMUP warm-up launches each.
@@ -19,7 +19,7 @@ sys.path.insert(0, ROOT)
 
 N, H, W = 256, 480, 640
 LAUNCHES, WARMUP = 20, 3
-KERNELS = {"vlfm_worlds_raycast": "worlds_raycast_objects_kernel", "vlfm_worlds_raycast_rgb": "worlds_raycast_rgb_kernel"}
+KERNELS = {"vlfm_worlds_raycast": "worlds_raycast_objects_kernel", "vlfm_worlds_raycast + d_rgb": "worlds_raycast_rgb_kernel"}
 
 
 def stats(xs):
@@ -52,9 +52,9 @@ def probe_launch(windows: int, lines) -> None:
     depth = torch.empty((N, H, W), dtype=torch.float32, device=dev)
     rgb = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
     calls = {"vlfm_worlds_raycast": lambda: rooms.cast_worlds(tf, table, idx, objects, idx, out=depth),
-             "vlfm_worlds_raycast_rgb": lambda: rooms.cast_worlds_rgb(tf, table, idx, objects, idx, colours, out=depth, rgb_out=rgb)}
+             "vlfm_worlds_raycast + d_rgb": lambda: rooms.cast_worlds_rgb(tf, table, idx, objects, idx, colours, out=depth, rgb_out=rgb)}
     a = calls["vlfm_worlds_raycast"]()
-    b = calls["vlfm_worlds_raycast_rgb"]()
+    b = calls["vlfm_worlds_raycast + d_rgb"]()
     torch.cuda.synchronize()
     assert torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
     pixels = int((b[1] > 0).sum())
@@ -77,7 +77,7 @@ def probe_launch(windows: int, lines) -> None:
             assert n == LAUNCHES, (name, n)
             kernel[name].append(ms * 1e3)
             call[name].append(start.elapsed_time(stop) * 1e3 / LAUNCHES)
-    written = {"vlfm_worlds_raycast": 5, "vlfm_worlds_raycast_rgb": 8}
+    written = {"vlfm_worlds_raycast": 5, "vlfm_worlds_raycast + d_rgb": 8}
     for name in calls:
         k = stats(kernel[name])
         lines.append("launch n=%d %dx%d  %-24s kernel %7.1f us (%.1f-%.1f)   whole call %7.1f us (%.1f-%.1f)   %d B/pixel: %.0f MB, "
@@ -87,8 +87,8 @@ def probe_launch(windows: int, lines) -> None:
         print(lines[-1], flush=True)
     lines.append("ratio rgb / plain: kernel %.2fx, whole call %.2fx (the bytes written: 1.60x); object pixels %d of %d; boxes per "
                  "world %d-%d"
-                 % (stats(kernel["vlfm_worlds_raycast_rgb"])[0] / stats(kernel["vlfm_worlds_raycast"])[0],
-                    stats(call["vlfm_worlds_raycast_rgb"])[0] / stats(call["vlfm_worlds_raycast"])[0], pixels, N * H * W,
+                 % (stats(kernel["vlfm_worlds_raycast + d_rgb"])[0] / stats(kernel["vlfm_worlds_raycast"])[0],
+                    stats(call["vlfm_worlds_raycast + d_rgb"])[0] / stats(call["vlfm_worlds_raycast"])[0], pixels, N * H * W,
                     min(len(w.boxes) for w in made), max(len(w.boxes) for w in made)))
     print(lines[-1], flush=True)
 

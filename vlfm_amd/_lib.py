@@ -243,13 +243,9 @@ def lib() -> ctypes.CDLL:
         L.vlfm_jpeg_decode_scratch_bytes.restype = ctypes.c_size_t
         L.vlfm_jpeg_decode_batched.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ci, ci, ci, vp, vp, ci, vp, ci, ci,
                                                ctypes.c_size_t, ci, vp, vp, vp, ctypes.c_size_t, vp]
-        L.vlfm_rooms_raycast.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp]
-        L.vlfm_rooms_raycast_objects.argtypes = [vp, ci, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp]
-        L.vlfm_geodesic_fields.argtypes = [vp, ci, cd, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
+        L.vlfm_worlds_raycast.argtypes = [vp, ci, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        L.vlfm_geodesic_fields.argtypes = [vp, vp, ci, ci, vp, cd, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
         L.vlfm_geodesic_query.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp]
-        L.vlfm_worlds_raycast.argtypes = [vp, ci, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]
-        L.vlfm_worlds_raycast_rgb.argtypes = [vp, ci, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
-        L.vlfm_geodesic_fields_worlds.argtypes = [vp, vp, ci, ci, vp, cd, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
         L.vlfm_plan_scratch_bytes.argtypes = [ci, ci]
         L.vlfm_plan_scratch_bytes.restype = ctypes.c_size_t
         L.vlfm_plan_paths.argtypes = [vp, ci, ci, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.c_size_t, vp]

@@ -3,7 +3,7 @@
 // bit vlfm_amd.synthetic.geodesic_field_numpy / geodesic_query_numpy (f64, one rounding per operation: the library is built with
 // -ffp-contract=off and the expressions below go through __dadd_rn / __dsub_rn / __dmul_rn / __dsqrt_rn and true divisions).
 //
-//   rectangles  the shared wall boxes, then the environment's valid object footprints in slot order, each inflated to
+//   rectangles  the wall boxes of the field's world, then the environment's valid object footprints in slot order, each inflated to
 //               (x0 - m, y0 - m, x1 + m, y1 + m); OPEN sets
 //   blocked     p -> q is blocked by a rectangle iff max(enter_x, enter_y, 0) < min(exit_x, exit_y, 1), where per axis, with
 //               d = q - p:  d == 0: (-inf, inf) if lo < p < hi, else empty;  otherwise t0 = (lo - p) / d, t1 = (hi - p) / d and
@@ -89,11 +89,10 @@ __host__ __device__ inline size_t field_lds_bytes(int max_rects) {
     return (size_t)max_rects * 32 + nn * 16 + 2 * nn * 8 + nn * 4 + nn * wpr * 4;
 }
 
-// A template over where a field finds its wall boxes (world_table.h): SharedBoxes for vlfm_geodesic_fields, WorldBoxes for
-// vlfm_geodesic_fields_worlds.  walls.capacity() + 8 is R, the stride of the outputs; the field's own count varies below it.
-template <class Walls>
+// A field finds its wall boxes in the row of its world in the table (world_table.h).  walls.capacity() + 8 is R, the stride of
+// the outputs; the field's own count varies below it.
 __global__ __launch_bounds__(FIELD_THREADS) void geodesic_fields_kernel(
-    const Walls walls, double margin, const double* __restrict__ objects,
+    const WorldBoxes walls, double margin, const double* __restrict__ objects,
     const double* __restrict__ sources, const int32_t* __restrict__ source_counts, int max_sources, double* __restrict__ out_rects,
     double* __restrict__ out_nodes, double* __restrict__ out_dist, int32_t* __restrict__ out_counts) {
     extern __shared__ double smem[];
@@ -260,43 +259,25 @@ __global__ __launch_bounds__(THREADS) void geodesic_query_kernel(
 using namespace vlfm;
 using namespace vlfm::geodesic;
 
-extern "C" int vlfm_geodesic_fields(const double* d_boxes, int n_boxes, double margin, const double* d_objects,
-                                    const double* d_sources, const int32_t* d_source_counts, int n, int max_sources,
-                                    double* d_rects, double* d_nodes, double* d_dist, int32_t* d_counts, void* stream) {
-    if (n < 0 || n_boxes < 0 || n_boxes > 16384 || max_sources < 0 || !(margin == margin) || (n_boxes > 0 && !d_boxes) ||
-        (n > 0 && (!d_objects || !d_source_counts || !d_rects || !d_nodes || !d_dist || !d_counts)) ||
-        (n > 0 && max_sources > 0 && !d_sources))
-        return fail(VLFM_ERR_INVALID, "geodesic_fields: bad argument");
-    if (n == 0) return VLFM_OK;
-    const size_t lds = field_lds_bytes(n_boxes + MAX_OBJECTS);
-    if (lds > 64 * 1024)
-        return fail(VLFM_ERR_INVALID, "geodesic_fields: rectangles, nodes and the visibility bitmap exceed 64 KB of LDS");
-    hipStream_t st = (hipStream_t)stream;
-    VLFM_TIMED("geodesic_fields_kernel", st);
-    VLFM_KLAUNCH(geodesic_fields_kernel<SharedBoxes>, dim3(n), dim3(FIELD_THREADS), lds, st, SharedBoxes{d_boxes, n_boxes}, margin,
-                 d_objects, d_sources, d_source_counts, max_sources, d_rects, d_nodes, d_dist, d_counts);
-    return check_launch("geodesic_fields_kernel");
-}
-
-extern "C" int vlfm_geodesic_fields_worlds(const double* d_world_boxes, const int32_t* d_box_counts, int n_worlds, int max_boxes,
-                                           const int32_t* d_world_of, double margin, const double* d_objects,
-                                           const double* d_sources, const int32_t* d_source_counts, int n, int max_sources,
-                                           double* d_rects, double* d_nodes, double* d_dist, int32_t* d_counts, void* stream) {
+extern "C" int vlfm_geodesic_fields(const double* d_world_boxes, const int32_t* d_box_counts, int n_worlds, int max_boxes,
+                                    const int32_t* d_world_of, double margin, const double* d_objects, const double* d_sources,
+                                    const int32_t* d_source_counts, int n, int max_sources, double* d_rects, double* d_nodes,
+                                    double* d_dist, int32_t* d_counts, void* stream) {
     if (n < 0 || n_worlds < 0 || max_boxes < 0 || max_boxes > 16384 || max_sources < 0 || !(margin == margin) ||
         (n_worlds > 0 && (!d_box_counts || (max_boxes > 0 && !d_world_boxes))) ||
         (n > 0 && (!d_world_of || !d_objects || !d_source_counts || !d_rects || !d_nodes || !d_dist || !d_counts)) ||
         (n > 0 && max_sources > 0 && !d_sources))
-        return fail(VLFM_ERR_INVALID, "geodesic_fields_worlds: bad argument");
+        return fail(VLFM_ERR_INVALID, "geodesic_fields: bad argument");
     if (n == 0) return VLFM_OK;
     const size_t lds = field_lds_bytes(max_boxes + MAX_OBJECTS);
     if (lds > 64 * 1024)
-        return fail(VLFM_ERR_INVALID, "geodesic_fields_worlds: rectangles, nodes and the visibility bitmap exceed 64 KB of LDS");
+        return fail(VLFM_ERR_INVALID, "geodesic_fields: rectangles, nodes and the visibility bitmap exceed 64 KB of LDS");
     hipStream_t st = (hipStream_t)stream;
-    VLFM_TIMED("geodesic_fields_worlds_kernel", st);
-    VLFM_KLAUNCH(geodesic_fields_kernel<WorldBoxes>, dim3(n), dim3(FIELD_THREADS), lds, st,
+    VLFM_TIMED("geodesic_fields_kernel", st);
+    VLFM_KLAUNCH(geodesic_fields_kernel, dim3(n), dim3(FIELD_THREADS), lds, st,
                  WorldBoxes{d_world_boxes, d_box_counts, d_world_of, n_worlds, max_boxes}, margin, d_objects, d_sources,
                  d_source_counts, max_sources, d_rects, d_nodes, d_dist, d_counts);
-    return check_launch("geodesic_fields_worlds_kernel");
+    return check_launch("geodesic_fields_kernel");
 }
 
 extern "C" int vlfm_geodesic_query(const double* d_points, const int32_t* d_field_of, int m, int n_fields, int n_boxes,

@@ -17,9 +17,9 @@
 // normalised floor values of its band of rows in LDS; the column profile is recomputed per band (W * B * 4 divisions) so that a
 // handful of cameras still spreads over the chip.  With W a multiple of 4 and a 16-byte aligned output every lane owns 4
 // adjacent columns and a band leaves as consecutive 16-byte stores; any other W takes the scalar store loop.
-// The kernels are templates over where a workgroup finds its boxes: one shared table (vlfm_rooms_raycast, vlfm_rooms_raycast_objects)
-// or the row of its camera's world in a table of worlds (vlfm_worlds_raycast, at the end of the file).  The objects kernel is also
-// a template over "with colour": vlfm_worlds_raycast_rgb, the last entry, adds the camera's RGB view from the same geometry.
+// A workgroup finds its boxes in the row of its camera's world in a table of worlds (world_table.h; the fixed rooms world is a
+// table of one row).  Three kernels -- walls only, with objects, with objects and colour (the objects kernel is a template over
+// "with colour") -- behind ONE entry, vlfm_worlds_raycast, at the end of the file.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -45,9 +45,8 @@ __device__ __forceinline__ float normalise(double d, double lo, double span) {
     return (float)v;
 }
 
-template <class Table>
-__global__ __launch_bounds__(THREADS) void rooms_raycast_kernel(const CameraRec* __restrict__ cameras, const Table table, int H,
-                                                                int W, int band, int vec4, float* __restrict__ out) {
+__global__ __launch_bounds__(THREADS) void rooms_raycast_kernel(const CameraRec* __restrict__ cameras, const WorldBoxes table,
+                                                                int H, int W, int band, int vec4, float* __restrict__ out) {
     extern __shared__ double smem[];
     const int r0 = blockIdx.x * band;
     if (r0 >= H) return;                                   // (uniform for the workgroup: before any barrier)
@@ -120,37 +119,8 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_kernel(const CameraRec*
     }
 }
 
-}  // namespace world
-}  // namespace vlfm
-
-using namespace vlfm;
-using namespace vlfm::world;
-
-extern "C" int vlfm_rooms_raycast(const double* d_cameras, int n, const double* d_boxes, int n_boxes, int H, int W,
-                                  float* d_out, void* stream) {
-    static_assert(sizeof(CameraRec) == 64, "camera record layout");
-    if (n < 0 || n > 65535 || n_boxes < 0 || H <= 0 || W <= 0 || (n > 0 && (!d_cameras || !d_out)) || (n_boxes > 0 && !d_boxes))
-        return fail(VLFM_ERR_INVALID, "rooms_raycast: bad argument");
-    if (n == 0) return VLFM_OK;
-    // row bands: enough workgroups for four per compute unit, never fewer than MIN_BAND_ROWS rows each
-    const long long want = 4LL * device_cu_count();
-    long long bands = (want + n - 1) / n;
-    const long long most = (H + MIN_BAND_ROWS - 1) / MIN_BAND_ROWS;
-    bands = bands < 1 ? 1 : (bands > most ? most : bands);
-    const int band = (int)((H + bands - 1) / bands);
-    const int grid_x = (H + band - 1) / band;
-    const size_t lds = (size_t)n_boxes * 32 + (size_t)((W + 3) & ~3) * 4 + (size_t)band * 4;
-    if (lds > 64 * 1024) return fail(VLFM_ERR_INVALID, "rooms_raycast: boxes + one image row + one row band exceed 64 KB of LDS");
-    const int vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_out) % 16 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    VLFM_TIMED("rooms_raycast_kernel", st);
-    VLFM_KLAUNCH(rooms_raycast_kernel<SharedBoxes>, dim3(grid_x, n), dim3(THREADS), lds, st,
-                 reinterpret_cast<const CameraRec*>(d_cameras), SharedBoxes{d_boxes, n_boxes}, H, W, band, vec4, d_out);
-    return check_launch("rooms_raycast_kernel");
-}
-
 // ------------------------------------------------------------------------------------------------------------ world objects
-// vlfm_rooms_raycast_objects: the same frames with up to 8 objects per environment standing in front of the walls -- axis-aligned
+// With objects: the same frames with up to 8 objects per environment standing in front of the walls -- axis-aligned
 // boxes with a vertical extent (x0 y0 x1 y1 z0 z1) -- rendered with occlusion, plus an instance-id plane and per (camera, object)
 // the visible pixel count and bounding box.  Arithmetic (synthetic.render_objects_numpy is the host statement of it):
 //
@@ -168,9 +138,6 @@ extern "C" int vlfm_rooms_raycast(const double* d_cameras, int n, const double* 
 // Stats: every lane keeps the running (count, bounding box) of the object it saw last in registers and flushes it into the
 // workgroup's LDS table with integer atomics when the object changes and at the end; then ONE global integer atomic per
 // (workgroup, object, field) that saw a pixel.  Integer add / min / max commute: the result does not depend on the order.
-namespace vlfm {
-namespace world {
-
 constexpr int MAX_OBJECTS = 8;                // vlfm_amd.h: objects per environment
 constexpr int OBJ_REC = 8;                    // doubles per object record: x0 y0 x1 y1 z0 z1 valid pad
 
@@ -222,7 +189,7 @@ __device__ __forceinline__ float shade(float bg, unsigned mask, const ObjCol* __
     return fminf(bg, best);
 }
 
-// ---- world colours (vlfm_worlds_raycast_rgb; the rule is stated with the entry point at the end of the file) ----------------
+// ---- world colours (the rule is stated with the entry point at the end of the file) ----------------
 // Colours are packed 0x00RRGGBB; the per-channel steps of the rule run on all three channels of a packed colour at once (the
 // subtrahend of a channel never exceeds the channel: no borrow crosses into the next one).
 constexpr int RGB_COL_BYTES = 26;             // per image column: dx, dy (f64), the wall (f32), wall colour | face bits, r_sk (int16)
@@ -295,11 +262,11 @@ __device__ __forceinline__ uint32_t finish(Paint p, float depth) {
     return __builtin_bswap32(c) >> 8;
 }
 
-// RGB = false: vlfm_rooms_raycast_objects / vlfm_worlds_raycast as they always were (`object_colours`, `palette`, `rgb` unused);
-// RGB = true: the colour plane as well, from the same per-column geometry (vlfm_worlds_raycast_rgb).
-template <class Table, bool RGB>
+// RGB = false: depth, ids and stats (`object_colours`, `palette`, `rgb` unused);
+// RGB = true: the colour plane as well, from the same per-column geometry.
+template <bool RGB>
 __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
-    const CameraRec* __restrict__ cameras, const Table table, const double* __restrict__ objects,
+    const CameraRec* __restrict__ cameras, const WorldBoxes table, const double* __restrict__ objects,
     const int32_t* __restrict__ env_of, int n_envs, int H, int W, int band, int vec4, float* __restrict__ out,
     uint8_t* __restrict__ ids, int32_t* __restrict__ stats, const int32_t* __restrict__ object_colours,
     const int32_t* __restrict__ palette, uint8_t* __restrict__ rgb) {
@@ -551,94 +518,44 @@ __global__ void rooms_stats_init_kernel(int32_t* __restrict__ stats, int total, 
     stats[i] = f == 0 ? 0 : (f == 1 ? W : (f == 3 ? H : -1));
 }
 
+// ---- launch geometry (host) -------------------------------------------------------------------------------------------------
+struct Bands {
+    int band, grid_x;                         // rows per workgroup, workgroups per camera
+};
+
+// row bands: enough workgroups for four per compute unit, never fewer than MIN_BAND_ROWS rows each and never more than `max_rows`
+static Bands plan_bands(int n, int H, int max_rows) {
+    const long long want = 4LL * device_cu_count();
+    long long bands = (want + n - 1) / n;
+    const long long most = (H + MIN_BAND_ROWS - 1) / MIN_BAND_ROWS, least = ((long long)H + max_rows - 1) / max_rows;
+    bands = bands < least ? least : (bands > most ? most : bands);
+    const int band = (int)((H + bands - 1) / bands);
+    return Bands{band, (H + band - 1) / band};
+}
+
+// LDS of the three kernels for `wp` padded columns and a band of `band` rows: each adds its tables to the one before
+static size_t walls_lds(int max_boxes, size_t wp, int band) { return (size_t)max_boxes * 32 + wp * 4 + (size_t)band * 4; }
+static size_t objects_lds(int max_boxes, size_t wp, int band) {
+    return walls_lds(max_boxes, wp, band) + MAX_OBJECTS * OBJ_REC * 8 + wp * MAX_OBJECTS * sizeof(ObjCol) + 5 * MAX_OBJECTS * 4 + wp;
+}
+static size_t rgb_lds(int max_boxes, size_t wp, int band) {
+    return objects_lds(max_boxes, wp, band) + wp * RGB_COL_BYTES + (size_t)band * RGB_ROW_BYTES + RGB_FIXED_BYTES;
+}
+
 }  // namespace world
 }  // namespace vlfm
 
-extern "C" int vlfm_rooms_raycast_objects(const double* d_cameras, int n, const double* d_boxes, int n_boxes,
-                                          const double* d_objects, const int32_t* d_env_of, int n_envs, int H, int W,
-                                          float* d_depth, uint8_t* d_ids, int32_t* d_stats, void* stream) {
-    static_assert(sizeof(ObjCol) == 8, "object column entry layout");
-    if (n < 0 || n > 65535 || n_boxes < 0 || n_envs <= 0 || H <= 0 || W <= 0 || H > 32768 ||
-        (n > 0 && (!d_cameras || !d_objects || !d_env_of || !d_depth || !d_ids || !d_stats)) || (n_boxes > 0 && !d_boxes))
-        return fail(VLFM_ERR_INVALID, "rooms_raycast_objects: bad argument");
-    if (n == 0) return VLFM_OK;
-    const long long want = 4LL * device_cu_count();         // row bands: as in vlfm_rooms_raycast
-    long long bands = (want + n - 1) / n;
-    const long long most = (H + MIN_BAND_ROWS - 1) / MIN_BAND_ROWS;
-    bands = bands < 1 ? 1 : (bands > most ? most : bands);
-    const int band = (int)((H + bands - 1) / bands);
-    const int grid_x = (H + band - 1) / band;
-    const size_t wp = (size_t)((W + 3) & ~3);
-    const size_t lds = (size_t)n_boxes * 32 + MAX_OBJECTS * OBJ_REC * 8 + wp * MAX_OBJECTS * sizeof(ObjCol) + wp * 4 +
-                       (size_t)band * 4 + 5 * MAX_OBJECTS * 4 + wp;
-    if (lds > 64 * 1024)
-        return fail(VLFM_ERR_INVALID, "rooms_raycast_objects: boxes + 69 bytes per image column + one row band exceed 64 KB of LDS");
-    const int vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_depth) % 16 == 0) && (reinterpret_cast<uintptr_t>(d_ids) % 4 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    const int total = n * 5 * MAX_OBJECTS;
-    VLFM_KLAUNCH(rooms_stats_init_kernel, dim3((total + THREADS - 1) / THREADS), dim3(THREADS), 0, st, d_stats, total, H, W);
-    int rc = check_launch("rooms_stats_init_kernel");
-    if (rc != VLFM_OK) return rc;
-    VLFM_TIMED("rooms_raycast_objects_kernel", st);
-    constexpr auto kernel = rooms_raycast_objects_kernel<SharedBoxes, false>;
-    VLFM_KLAUNCH(kernel, dim3(grid_x, n), dim3(THREADS), lds, st, reinterpret_cast<const CameraRec*>(d_cameras),
-                 SharedBoxes{d_boxes, n_boxes}, d_objects, d_env_of, n_envs, H, W, band, vec4, d_depth, d_ids, d_stats,
-                 (const int32_t*)nullptr, (const int32_t*)nullptr, (uint8_t*)nullptr);
-    return check_launch("rooms_raycast_objects_kernel");
-}
+using namespace vlfm;
+using namespace vlfm::world;
 
-// ------------------------------------------------------------------------------------------------------------ a world per camera
-// vlfm_worlds_raycast: the two kernels above with the boxes looked up per camera in a table of worlds (WorldBoxes): a workgroup
-// stages the `count` boxes of ITS camera's world.  Grid, bands, LDS layout (sized by max_boxes) and store paths are those of the
-// shared-table entries; d_objects == NULL renders walls only.
-extern "C" int vlfm_worlds_raycast(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts,
-                                   int n_worlds, int max_boxes, const int32_t* d_world_of, const double* d_objects,
-                                   const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids,
-                                   int32_t* d_stats, void* stream) {
-    const bool with_objects = d_objects != nullptr;
-    if (n < 0 || n > 65535 || n_worlds < 0 || max_boxes < 0 || H <= 0 || W <= 0 || (n > 0 && (!d_cameras || !d_world_of || !d_depth)) ||
-        (n_worlds > 0 && (!d_box_counts || (max_boxes > 0 && !d_world_boxes))) ||
-        (with_objects && (n_envs <= 0 || H > 32768 || (n > 0 && (!d_env_of || !d_ids || !d_stats)))))
-        return fail(VLFM_ERR_INVALID, "worlds_raycast: bad argument");
-    if (n == 0) return VLFM_OK;
-    const long long want = 4LL * device_cu_count();         // row bands: as in vlfm_rooms_raycast
-    long long bands = (want + n - 1) / n;
-    const long long most = (H + MIN_BAND_ROWS - 1) / MIN_BAND_ROWS;
-    bands = bands < 1 ? 1 : (bands > most ? most : bands);
-    const int band = (int)((H + bands - 1) / bands);
-    const int grid_x = (H + band - 1) / band;
-    const size_t wp = (size_t)((W + 3) & ~3);
-    const WorldBoxes table{d_world_boxes, d_box_counts, d_world_of, n_worlds, max_boxes};
-    hipStream_t st = (hipStream_t)stream;
-    if (!with_objects) {
-        const size_t lds = (size_t)max_boxes * 32 + wp * 4 + (size_t)band * 4;
-        if (lds > 64 * 1024) return fail(VLFM_ERR_INVALID, "worlds_raycast: max_boxes + one image row + one row band exceed 64 KB of LDS");
-        const int vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_depth) % 16 == 0);
-        VLFM_TIMED("worlds_raycast_kernel", st);
-        VLFM_KLAUNCH(rooms_raycast_kernel<WorldBoxes>, dim3(grid_x, n), dim3(THREADS), lds, st,
-                     reinterpret_cast<const CameraRec*>(d_cameras), table, H, W, band, vec4, d_depth);
-        return check_launch("worlds_raycast_kernel");
-    }
-    const size_t lds = (size_t)max_boxes * 32 + MAX_OBJECTS * OBJ_REC * 8 + wp * MAX_OBJECTS * sizeof(ObjCol) + wp * 4 +
-                       (size_t)band * 4 + 5 * MAX_OBJECTS * 4 + wp;
-    if (lds > 64 * 1024)
-        return fail(VLFM_ERR_INVALID, "worlds_raycast: max_boxes + 69 bytes per image column + one row band exceed 64 KB of LDS");
-    const int vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_depth) % 16 == 0) && (reinterpret_cast<uintptr_t>(d_ids) % 4 == 0);
-    const int total = n * 5 * MAX_OBJECTS;
-    VLFM_KLAUNCH(rooms_stats_init_kernel, dim3((total + THREADS - 1) / THREADS), dim3(THREADS), 0, st, d_stats, total, H, W);
-    int rc = check_launch("rooms_stats_init_kernel");
-    if (rc != VLFM_OK) return rc;
-    VLFM_TIMED("worlds_raycast_objects_kernel", st);
-    constexpr auto kernel = rooms_raycast_objects_kernel<WorldBoxes, false>;
-    VLFM_KLAUNCH(kernel, dim3(grid_x, n), dim3(THREADS), lds, st, reinterpret_cast<const CameraRec*>(d_cameras), table, d_objects,
-                 d_env_of, n_envs, H, W, band, vec4, d_depth, d_ids, d_stats, (const int32_t*)nullptr, (const int32_t*)nullptr,
-                 (uint8_t*)nullptr);
-    return check_launch("worlds_raycast_objects_kernel");
-}
-
-// ------------------------------------------------------------------------------------------------------------ world colours
-// vlfm_worlds_raycast_rgb: vlfm_worlds_raycast with objects, and the camera's RGB view of the same world from the same launch
-// (synthetic.render_rgb_numpy is the host statement; every byte agrees).  Colours are packed 0x00RRGGBB and arrive as arguments.
+// ------------------------------------------------------------------------------------------------------------ the entry
+// vlfm_worlds_raycast: the frames of n cameras, camera i in world d_world_of[i] of the table, in ONE launch.
+//   d_objects == NULL            walls only: rooms_raycast_kernel writes d_depth; d_env_of, n_envs, d_ids, d_stats and the colour
+//                                arguments are ignored, d_rgb must be NULL
+//   d_objects, d_rgb == NULL     rooms_raycast_objects_kernel<false>: d_depth, d_ids, d_stats
+//   d_objects and d_rgb          rooms_raycast_objects_kernel<true>: the camera's RGB view of the same world as well
+//                                (synthetic.render_rgb_numpy is the host statement; every byte agrees).  Colours are packed
+//                                0x00RRGGBB and arrive as arguments.
 //
 //   column u:  b_w = the box the wall's tmin came from (lowest index among equals), t_w = f64(f32(tmin))
 //              y-face iff min(ty0, ty1) > min(tx0, tx1) at b_w;  q = x + dx*t_w (y-face) | y + dy*t_w;  panel = floor(2q) & 1
@@ -650,47 +567,55 @@ extern "C" int vlfm_worlds_raycast(const double* d_cameras, int n, const double*
 //              void: palette[10], as it is
 //              depth cue on the first three: g = int(depth * 128.0f), ch = (ch * (256 - g)) >> 8
 //
-// Layout: the kernel above with RGB = true.  A column costs 26 more bytes of LDS (dx, dy, the f32 wall, one dword with the wall's
-// colour AFTER panel and face in bits 0-23 and the objects' face bits above them, r_sk) and a row of the band 8 (floor_d): box
-// index, face and panel parity are only ever used for that colour, so the column pass resolves them once and a wall pixel costs
-// one LDS dword, one compare and the depth cue.  The pixel pass is selects, not branches (a first version that branched per
-// pixel on object / floor / wall / void took 317 us for 256 frames of 640x480 against 220 us for this one): per group of four
-// pixels one branch around the floor's f64 checker ("is any of the four floor") and one around the objects' colours.  Bands
-// are capped at RGB_MAX_BAND_ROWS rows so that the LDS need does not grow with the camera count.  Stores: with W % 4 == 0 and
-// aligned outputs a lane's 4 pixels leave as three dwords (one 12-byte store); else bytes.
-extern "C" int vlfm_worlds_raycast_rgb(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts,
-                                       int n_worlds, int max_boxes, const int32_t* d_world_of, const double* d_objects,
-                                       const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids,
-                                       int32_t* d_stats, const int32_t* d_object_colours, const int32_t* d_palette, uint8_t* d_rgb,
-                                       void* stream) {
-    if (n < 0 || n > 65535 || n_worlds < 0 || max_boxes < 0 || n_envs <= 0 || H <= 0 || W <= 0 || H > 32768 ||
-        (n > 0 && (!d_cameras || !d_world_of || !d_objects || !d_env_of || !d_depth || !d_ids || !d_stats || !d_object_colours ||
-                   !d_palette || !d_rgb)) ||
-        (n_worlds > 0 && (!d_box_counts || (max_boxes > 0 && !d_world_boxes))))
-        return fail(VLFM_ERR_INVALID, "worlds_raycast_rgb: bad argument");
+// Layout with colour: a column costs 26 more bytes of LDS (dx, dy, the f32 wall, one dword with the wall's colour AFTER panel and
+// face in bits 0-23 and the objects' face bits above them, r_sk) and a row of the band 8 (floor_d): box index, face and panel
+// parity are only ever used for that colour, so the column pass resolves them once and a wall pixel costs one LDS dword, one
+// compare and the depth cue.  The pixel pass is selects, not branches (a first version that branched per pixel on object / floor
+// / wall / void took 317 us for 256 frames of 640x480 against 220 us for this one): per group of four pixels one branch around
+// the floor's f64 checker ("is any of the four floor") and one around the objects' colours.  Bands are capped at
+// RGB_MAX_BAND_ROWS rows so that the LDS need does not grow with the camera count.  Stores: with W % 4 == 0 and aligned outputs a
+// lane's 4 pixels leave as three dwords (one 12-byte store); else bytes.
+extern "C" int vlfm_worlds_raycast(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts,
+                                   int n_worlds, int max_boxes, const int32_t* d_world_of, const double* d_objects,
+                                   const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids,
+                                   int32_t* d_stats, const int32_t* d_object_colours, const int32_t* d_palette, uint8_t* d_rgb,
+                                   void* stream) {
+    static_assert(sizeof(CameraRec) == 64, "camera record layout");
+    static_assert(sizeof(ObjCol) == 8, "object column entry layout");
+    const bool with_objects = d_objects != nullptr, with_rgb = d_rgb != nullptr;
+    if (n < 0 || n > 65535 || n_worlds < 0 || max_boxes < 0 || H <= 0 || W <= 0 || (n > 0 && (!d_cameras || !d_world_of || !d_depth)) ||
+        (n_worlds > 0 && (!d_box_counts || (max_boxes > 0 && !d_world_boxes))) ||
+        (with_objects && (n_envs <= 0 || H > 32768 || (n > 0 && (!d_env_of || !d_ids || !d_stats)))) ||
+        (with_rgb && (!with_objects || !d_object_colours || !d_palette)))
+        return fail(VLFM_ERR_INVALID, "worlds_raycast: bad argument");
     if (n == 0) return VLFM_OK;
-    const long long want = 4LL * device_cu_count();         // row bands: as in vlfm_rooms_raycast, and no taller than the cap
-    long long bands = (want + n - 1) / n;
-    const long long most = (H + MIN_BAND_ROWS - 1) / MIN_BAND_ROWS, least = (H + RGB_MAX_BAND_ROWS - 1) / RGB_MAX_BAND_ROWS;
-    bands = bands < least ? least : (bands > most ? most : bands);
-    const int band = (int)((H + bands - 1) / bands);
-    const int grid_x = (H + band - 1) / band;
+    const Bands b = plan_bands(n, H, with_rgb ? RGB_MAX_BAND_ROWS : H);
     const size_t wp = (size_t)((W + 3) & ~3);
     const WorldBoxes table{d_world_boxes, d_box_counts, d_world_of, n_worlds, max_boxes};
-    const size_t lds = (size_t)max_boxes * 32 + MAX_OBJECTS * OBJ_REC * 8 + wp * MAX_OBJECTS * sizeof(ObjCol) + wp * 4 +
-                       (size_t)band * 4 + 5 * MAX_OBJECTS * 4 + wp + wp * RGB_COL_BYTES + (size_t)band * RGB_ROW_BYTES + RGB_FIXED_BYTES;
-    if (lds > 64 * 1024)
-        return fail(VLFM_ERR_INVALID, "worlds_raycast_rgb: max_boxes + 95 bytes per image column + one row band exceed 64 KB of LDS");
-    const int vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_depth) % 16 == 0) && (reinterpret_cast<uintptr_t>(d_ids) % 4 == 0) &&
-                     (reinterpret_cast<uintptr_t>(d_rgb) % 4 == 0);
+    const CameraRec* cameras = reinterpret_cast<const CameraRec*>(d_cameras);
+    const dim3 grid(b.grid_x, n);
     hipStream_t st = (hipStream_t)stream;
+    int vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(d_depth) % 16 == 0);
+    if (!with_objects) {
+        const size_t lds = walls_lds(max_boxes, wp, b.band);
+        if (lds > 64 * 1024) return fail(VLFM_ERR_INVALID, "worlds_raycast: max_boxes + one image row + one row band exceed 64 KB of LDS");
+        VLFM_TIMED("worlds_raycast_kernel", st);
+        VLFM_KLAUNCH(rooms_raycast_kernel, grid, dim3(THREADS), lds, st, cameras, table, H, W, b.band, vec4, d_depth);
+        return check_launch("worlds_raycast_kernel");
+    }
+    const size_t lds = with_rgb ? rgb_lds(max_boxes, wp, b.band) : objects_lds(max_boxes, wp, b.band);
+    if (lds > 64 * 1024)
+        return fail(VLFM_ERR_INVALID, with_rgb ? "worlds_raycast: max_boxes + 95 bytes per image column + one row band exceed 64 KB of LDS"
+                                               : "worlds_raycast: max_boxes + 69 bytes per image column + one row band exceed 64 KB of LDS");
+    vec4 = vec4 && (reinterpret_cast<uintptr_t>(d_ids) % 4 == 0) && (!with_rgb || reinterpret_cast<uintptr_t>(d_rgb) % 4 == 0);
     const int total = n * 5 * MAX_OBJECTS;
     VLFM_KLAUNCH(rooms_stats_init_kernel, dim3((total + THREADS - 1) / THREADS), dim3(THREADS), 0, st, d_stats, total, H, W);
     int rc = check_launch("rooms_stats_init_kernel");
     if (rc != VLFM_OK) return rc;
-    VLFM_TIMED("worlds_raycast_rgb_kernel", st);
-    constexpr auto kernel = rooms_raycast_objects_kernel<WorldBoxes, true>;
-    VLFM_KLAUNCH(kernel, dim3(grid_x, n), dim3(THREADS), lds, st, reinterpret_cast<const CameraRec*>(d_cameras), table, d_objects,
-                 d_env_of, n_envs, H, W, band, vec4, d_depth, d_ids, d_stats, d_object_colours, d_palette, d_rgb);
-    return check_launch("worlds_raycast_rgb_kernel");
+    const char* label = with_rgb ? "worlds_raycast_rgb_kernel" : "worlds_raycast_objects_kernel";
+    VLFM_TIMED(label, st);
+    const auto kernel = with_rgb ? rooms_raycast_objects_kernel<true> : rooms_raycast_objects_kernel<false>;
+    VLFM_KLAUNCH(kernel, grid, dim3(THREADS), lds, st, cameras, table, d_objects, d_env_of, n_envs, H, W, b.band, vec4, d_depth,
+                 d_ids, d_stats, d_object_colours, d_palette, d_rgb);
+    return check_launch(label);
 }

@@ -1,8 +1,7 @@
-// world_table.h -- where a workgroup finds the wall boxes of ITS camera (world_render.hip) or field (geodesic.hip).
-//   SharedBoxes  one table [n_boxes][4] for everybody: vlfm_rooms_raycast, vlfm_rooms_raycast_objects, vlfm_geodesic_fields
-//   WorldBoxes   a table of worlds [n_worlds][max_boxes][4] with a count per world and, per camera or field, the world it stands
-//                in: vlfm_worlds_raycast, vlfm_geodesic_fields_worlds.  A world outside [0, n_worlds) is EMPTY and is never
-//                dereferenced; a count is clamped to [0, max_boxes]; rows beyond a world's count are never read.
+// world_table.h -- where a workgroup finds the wall boxes of ITS camera (world_render.hip) or field (geodesic.hip): a table of
+// worlds [n_worlds][max_boxes][4] with a count per world and, per camera or field, the world it stands in.  The fixed rooms
+// world is a table of one row.  A world outside [0, n_worlds) is EMPTY and is never dereferenced; a count is clamped to
+// [0, max_boxes]; rows beyond a world's count are never read.
 // `capacity()` is what a kernel's LDS layout and output strides reserve for the boxes -- the same for every workgroup of a
 // launch --, `find(i, count)` the boxes of camera / field i and how many of them there are.
 #pragma once
@@ -12,16 +11,6 @@
 #include <hip/hip_runtime.h>
 
 namespace vlfm {
-
-struct SharedBoxes {
-    const double* boxes;
-    int n_boxes;
-    __device__ __forceinline__ int capacity() const { return n_boxes; }
-    __device__ __forceinline__ const double* find(int, int& count) const {
-        count = n_boxes;
-        return boxes;
-    }
-};
 
 struct WorldBoxes {
     const double* boxes;

@@ -332,7 +332,8 @@ class RoomsRenderer:
         self.window = None
         self.window_t0 = 0
         self.painter = None      # optional (t, frames [E,H,W]) -> frames: scripted objects in front of the walls
-        self._rooms_table = None  # cast_cameras_rgb: BOXES as the one row of a world table
+        self.table = WorldTable(1, self.boxes.device, len(BOXES))     # the rooms world for the kernels: a world table of one row
+        self.table.assign([0], [BOXES])
 
     @torch.no_grad()
     def render(self, t: int) -> torch.Tensor:
@@ -385,272 +386,151 @@ class RoomsRenderer:
         return ((d - lo) / (hi - lo)).clamp(1e-3, 1.0).float()
 
     @torch.no_grad()
-    def cast_cameras(self, tf: np.ndarray, hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None,
-                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``render_cameras`` -- same arguments, the same frames bit for bit -- in ONE kernel launch on the current stream
-        (csrc/world_render.hip) instead of a chain of torch f64 operations over [n,W,B] and [n,H,W] temporaries: what a
-        closed-loop step, which cannot pre-render, pays per step.  The camera records (x, y, cos, sin, height, fx, lo, hi) are
-        built on the host and cross in one small copy.  ``out``: a contiguous f32 [n,H,W] device tensor to render into."""
-        tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
-        n = len(tf)
-        rec = np.empty((n, 8), np.float64)
-        rec[:, 0:2], rec[:, 2:4], rec[:, 4] = tf[:, :2, 3], tf[:, :2, 0], tf[:, 2, 3]
-        rec[:, 5] = camera_intrinsics(self.W)[0] if hfov is None else self.W / (2 * np.tan(np.asarray(hfov, np.float64) / 2))
-        rec[:, 6] = MIN_DEPTH if min_depth is None else np.asarray(min_depth, np.float64)
-        rec[:, 7] = MAX_DEPTH if max_depth is None else np.asarray(max_depth, np.float64)
-        if not np.all(rec[:, 7] > rec[:, 6]):
-            raise ValueError("cast_cameras: every camera needs max_depth > min_depth")
-        if out is None:
-            out = torch.empty((n, self.H, self.W), dtype=torch.float32, device=self.device)
-        elif out.shape != (n, self.H, self.W) or out.dtype != torch.float32 or not out.is_contiguous() \
-                or out.device != self.boxes.device:
-            raise ValueError(f"cast_cameras: out must be a contiguous f32 [{n},{self.H},{self.W}] tensor on {self.boxes.device}")
-        if n == 0:
-            return out
-        with torch.cuda.device(self.boxes.device):
-            d_rec = torch.from_numpy(rec).to(self.boxes.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().vlfm_rooms_raycast(d_rec.data_ptr(), n, self.boxes.data_ptr(), len(self.boxes), self.H, self.W,
-                                                     out.data_ptr(), stream), "rooms_raycast")
-        return out
-
-    @torch.no_grad()
-    def cast_cameras_objects(self, tf: np.ndarray, objects: np.ndarray, env_of, hfov: Optional[np.ndarray] = None,
-                             min_depth=None, max_depth=None, out: Optional[torch.Tensor] = None):
-        """``cast_cameras`` with the objects of the cameras' environments standing in the world (vlfm_rooms_raycast_objects, one
-        launch on the current stream): ``objects`` [n_envs,8,8] f64 on the host -- x0, y0, x1, y1, z0, z1, valid, pad per slot;
-        it crosses in one small copy -- and ``env_of`` [n], the row of ``objects`` each camera looks at.  Returns (depth f32
-        [n,H,W], ids u8 [n,H,W]: 0 = wall / floor, k + 1 = object slot k, stats int32 [n,8,5]: visible pixels, first / last
-        column, first / last row of each slot; (0, W, -1, H, -1) for none), all on the device, bit for bit
-        synthetic.render_objects_numpy / object_stats_numpy.  ``out``: the depth buffer, as in ``cast_cameras``."""
-        from .synthetic import WORLD_MAX_OBJECTS
-
-        tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
-        n = len(tf)
-        objects = np.ascontiguousarray(objects, np.float64)
-        if objects.ndim != 3 or objects.shape[0] < 1 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
-            raise ValueError(f"cast_cameras_objects: objects must be [n_envs >= 1, {WORLD_MAX_OBJECTS}, 8]")
-        env_of = np.ascontiguousarray(np.asarray(env_of).reshape(-1), np.int32)
-        if len(env_of) != n or np.any((env_of < 0) | (env_of >= len(objects))):
-            raise ValueError("cast_cameras_objects: env_of must name one row of objects per camera")
-        rec = np.empty((n, 8), np.float64)
-        rec[:, 0:2], rec[:, 2:4], rec[:, 4] = tf[:, :2, 3], tf[:, :2, 0], tf[:, 2, 3]
-        rec[:, 5] = camera_intrinsics(self.W)[0] if hfov is None else self.W / (2 * np.tan(np.asarray(hfov, np.float64) / 2))
-        rec[:, 6] = MIN_DEPTH if min_depth is None else np.asarray(min_depth, np.float64)
-        rec[:, 7] = MAX_DEPTH if max_depth is None else np.asarray(max_depth, np.float64)
-        if not np.all(rec[:, 7] > rec[:, 6]):
-            raise ValueError("cast_cameras_objects: every camera needs max_depth > min_depth")
-        dev = self.boxes.device
-        if out is None:
-            out = torch.empty((n, self.H, self.W), dtype=torch.float32, device=dev)
-        elif out.shape != (n, self.H, self.W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"cast_cameras_objects: out must be a contiguous f32 [{n},{self.H},{self.W}] tensor on {dev}")
-        ids = torch.empty((n, self.H, self.W), dtype=torch.uint8, device=dev)
-        stats = torch.empty((n, WORLD_MAX_OBJECTS, 5), dtype=torch.int32, device=dev)
-        if n == 0:
-            return out, ids, stats
-        with torch.cuda.device(dev):
-            # camera records, object records and env_of in ONE host buffer and one copy (all 8-byte aligned pieces)
-            blob = np.concatenate([rec.reshape(-1), objects.reshape(-1), np.zeros((n + 1) // 2, np.float64)])
-            blob[rec.size + objects.size:].view(np.int32)[:n] = env_of
-            d_blob = torch.from_numpy(blob).to(dev)
-            p = d_blob.data_ptr()
-            stream = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().vlfm_rooms_raycast_objects(p, n, self.boxes.data_ptr(), len(self.boxes), p + 8 * rec.size,
-                                                             p + 8 * (rec.size + objects.size), len(objects), self.H, self.W,
-                                                             out.data_ptr(), ids.data_ptr(), stats.data_ptr(), stream),
-                       "rooms_raycast_objects")
-        return out, ids, stats
-
-    @torch.no_grad()
-    def geodesic_fields(self, objects: np.ndarray, targets_boxes, success_distance: float,
-                        max_sources: int = GEODESIC_MAX_SOURCES) -> GeodesicFields:
-        """The geodesic fields of n environments in ONE launch on the current stream (vlfm_geodesic_fields, bit for bit
-        synthetic.geodesic_field_numpy): ``objects`` [n,8,8] f64 on the host, the ray caster's records -- walls and valid
-        footprints, inflated by STEP_MARGIN, are the obstacles; ``targets_boxes`` [n,>=4] the footprint each environment has to
-        reach within ``success_distance`` (a NaN row: no target, every distance in that field is inf).  The view points
-        (synthetic.goal_viewpoints) are worked out on the host; they, their counts and the records cross in one small copy each."""
-        objects = np.ascontiguousarray(objects, np.float64)
-        if objects.ndim != 3 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
-            raise ValueError(f"geodesic_fields: objects must be [n, {WORLD_MAX_OBJECTS}, 8]")
-        n = len(objects)
-        boxes = np.asarray(targets_boxes, np.float64).reshape(n, -1)[:, :4] if n else np.zeros((0, 4))
-        src = np.zeros((n, max_sources, 2))
-        cnt = np.zeros(n, np.int32)
-        has = np.zeros(n, bool)
-        for e in range(n):
-            if np.all(np.isfinite(boxes[e])):
-                pts = goal_viewpoints(boxes[e], inflated_rects(objects[e]), success_distance, max_sources)
-                src[e, :len(pts)], cnt[e], has[e] = pts, len(pts), True
-        dev = self.boxes.device
-        R = len(self.boxes) + WORLD_MAX_OBJECTS
-        f64 = dict(dtype=torch.float64, device=dev)
-        h = GeodesicFields(n, max_sources, torch.empty((n, R, 4), **f64), torch.empty((n, 4 * R, 2), **f64),
-                           torch.empty((n, 4 * R), **f64), torch.empty((n, 2), dtype=torch.int32, device=dev),
-                           torch.empty((n, max_sources, 2), **f64), torch.empty((n,), dtype=torch.int32, device=dev), has)
-        if n == 0:
-            return h
-        with torch.cuda.device(dev):
-            d_obj = torch.from_numpy(objects).to(dev)
-            h.sources.copy_(torch.from_numpy(src))
-            h.source_counts.copy_(torch.from_numpy(cnt))
-            stream = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().vlfm_geodesic_fields(self.boxes.data_ptr(), len(self.boxes), STEP_MARGIN, d_obj.data_ptr(),
-                                                       h.sources.data_ptr(), h.source_counts.data_ptr(), n, max_sources,
-                                                       h.rects.data_ptr(), h.nodes.data_ptr(), h.dist.data_ptr(),
-                                                       h.counts.data_ptr(), stream), "geodesic_fields")
-        return h
-
-    @torch.no_grad()
-    def cast_worlds(self, tf: np.ndarray, table: WorldTable, world_of, objects: Optional[np.ndarray] = None, env_of=None,
-                    hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None, out: Optional[torch.Tensor] = None):
-        """``cast_cameras_objects`` with a floor plan per camera (vlfm_worlds_raycast, one launch on the current stream): camera i
-        stands in world ``world_of[i]`` of ``table`` and sees the objects ``objects[env_of[i]]``.  Returns (depth, ids, stats) as
-        ``cast_cameras_objects`` does, bit for bit synthetic.render_objects_numpy(..., boxes=table.world(world_of[i])); with
-        ``objects=None`` the walls-only frames, as ``cast_cameras`` returns them.  Camera records, object records and both index
-        lists cross in one small copy."""
+    def _raycast(self, who: str, tf: np.ndarray, table: WorldTable, world_of, objects=None, env_of=None, hfov=None,
+                 min_depth=None, max_depth=None, out=None, rgb: bool = False, colours=None, palette=None, rgb_out=None):
+        """What every ``cast_*`` method does (vlfm_worlds_raycast, one launch on the current stream): camera i stands in world
+        ``world_of[i]`` of ``table``.  ``objects=None``: walls only; ``rgb``: the colour plane as well.  Returns (depth, ids,
+        stats, rgb), None for what was not asked for.  The camera records (x, y, cos, sin, height, fx, lo, hi) are built on the
+        host; they, the object records and the int32 lists (world_of, env_of, colours, palette) cross in ONE host buffer and one
+        copy (all 8-byte aligned pieces).  ``who`` names the caller in error messages."""
         tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
         n = len(tf)
         dev = self.boxes.device
         if table.device != dev:
-            raise ValueError(f"cast_worlds: the world table must live on {dev}")
+            raise ValueError(f"{who}: the world table must live on {dev}")
         world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
         if len(world_of) != n or np.any((world_of < 0) | (world_of >= table.n_worlds)):
-            raise ValueError("cast_worlds: world_of must name one world of the table per camera")
+            raise ValueError(f"{who}: world_of must name one world of the table per camera")
+        ints = [world_of]
+        if objects is None and rgb:                 # a world without objects: one row of empty slots, ids of zeros
+            if env_of is not None or colours is not None:
+                raise ValueError(f"{who}: env_of and colours belong to objects")
+            objects, env_of = np.zeros((1, WORLD_MAX_OBJECTS, 8)), np.zeros(n, np.int32)
         if objects is None:
-            objects, env_of = np.zeros((0, WORLD_MAX_OBJECTS, 8)), np.zeros(n, np.int32)
+            objects = np.zeros((0, WORLD_MAX_OBJECTS, 8))
         else:
             objects = np.ascontiguousarray(objects, np.float64)
             if objects.ndim != 3 or objects.shape[0] < 1 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
-                raise ValueError(f"cast_worlds: objects must be [n_envs >= 1, {WORLD_MAX_OBJECTS}, 8]")
+                raise ValueError(f"{who}: objects must be [n_envs >= 1, {WORLD_MAX_OBJECTS}, 8]")
             env_of = np.ascontiguousarray(np.asarray(env_of).reshape(-1), np.int32)
             if len(env_of) != n or np.any((env_of < 0) | (env_of >= len(objects))):
-                raise ValueError("cast_worlds: env_of must name one row of objects per camera")
+                raise ValueError(f"{who}: env_of must name one row of objects per camera")
+            ints.append(env_of)
         with_objects = len(objects) > 0
+        if rgb:
+            colours = np.zeros((len(objects), WORLD_MAX_OBJECTS), np.int32) if colours is None else np.asarray(colours)
+            if colours.shape != (len(objects), WORLD_MAX_OBJECTS) or colours.dtype.kind not in "iu":
+                raise ValueError(f"{who}: colours must be integers [{len(objects)}, {WORLD_MAX_OBJECTS}], one per object slot")
+            palette = np.asarray(WORLD_PALETTE if palette is None else palette)
+            if palette.shape != (12,) or palette.dtype.kind not in "iu":
+                raise ValueError(f"{who}: palette must be 12 integers")
+            ints += [(colours.astype(np.int64) & 0xFFFFFF).astype(np.int32).reshape(-1),
+                     (palette.astype(np.int64) & 0xFFFFFF).astype(np.int32)]
         rec = np.empty((n, 8), np.float64)
         rec[:, 0:2], rec[:, 2:4], rec[:, 4] = tf[:, :2, 3], tf[:, :2, 0], tf[:, 2, 3]
         rec[:, 5] = camera_intrinsics(self.W)[0] if hfov is None else self.W / (2 * np.tan(np.asarray(hfov, np.float64) / 2))
         rec[:, 6] = MIN_DEPTH if min_depth is None else np.asarray(min_depth, np.float64)
         rec[:, 7] = MAX_DEPTH if max_depth is None else np.asarray(max_depth, np.float64)
         if not np.all(rec[:, 7] > rec[:, 6]):
-            raise ValueError("cast_worlds: every camera needs max_depth > min_depth")
-        if out is None:
-            out = torch.empty((n, self.H, self.W), dtype=torch.float32, device=dev)
-        elif out.shape != (n, self.H, self.W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"cast_worlds: out must be a contiguous f32 [{n},{self.H},{self.W}] tensor on {dev}")
+            raise ValueError(f"{who}: every camera needs max_depth > min_depth")
+
+        def plane(given, name, shape, dtype):
+            if given is None:
+                return torch.empty(shape, dtype=dtype, device=dev)
+            if given.shape != shape or given.dtype != dtype or not given.is_contiguous() or given.device != dev:
+                kind = "f32" if dtype == torch.float32 else "u8"
+                raise ValueError(f"{who}: {name} must be a contiguous {kind} [{','.join(map(str, shape))}] tensor on {dev}")
+            return given
+
+        out = plane(out, "out", (n, self.H, self.W), torch.float32)
+        rgb_out = plane(rgb_out, "rgb_out", (n, self.H, self.W, 3), torch.uint8) if rgb else None
         ids = stats = None
         if with_objects:
             ids = torch.empty((n, self.H, self.W), dtype=torch.uint8, device=dev)
             stats = torch.empty((n, WORLD_MAX_OBJECTS, 5), dtype=torch.int32, device=dev)
         if n > 0:
             with torch.cuda.device(dev):
-                # camera records, object records, world_of and env_of in ONE host buffer and one copy (all 8-byte aligned pieces)
-                pad = (n + 1) // 2
-                blob = np.concatenate([rec.reshape(-1), objects.reshape(-1), np.zeros(2 * pad, np.float64)])
-                blob[rec.size + objects.size:].view(np.int32)[:n] = world_of
-                blob[rec.size + objects.size + pad:].view(np.int32)[:n] = env_of
-                d_blob = torch.from_numpy(blob).to(dev)
-                p = d_blob.data_ptr()
-                p_world_of = p + 8 * (rec.size + objects.size)
-                stream = torch.cuda.current_stream().cuda_stream
-                _lib.check(_lib.lib().vlfm_worlds_raycast(
-                    p, n, table.d_boxes.data_ptr(), table.d_counts.data_ptr(), table.n_worlds, table.max_boxes, p_world_of,
-                    p + 8 * rec.size if with_objects else None, p_world_of + 8 * pad, len(objects), self.H, self.W,
-                    out.data_ptr(), ids.data_ptr() if with_objects else None, stats.data_ptr() if with_objects else None,
-                    stream), "worlds_raycast")
-        return (out, ids, stats) if with_objects else out
-
-    @torch.no_grad()
-    def cast_worlds_rgb(self, tf: np.ndarray, table: WorldTable, world_of, objects: Optional[np.ndarray] = None, env_of=None,
-                        colours=None, palette=None, hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None,
-                        out: Optional[torch.Tensor] = None, rgb_out: Optional[torch.Tensor] = None):
-        """``cast_worlds`` and the cameras' RGB view of the same worlds from the same launch (vlfm_worlds_raycast_rgb, on the
-        current stream).  Returns (depth, ids, stats, rgb u8 [n,H,W,3]) -- always all four; ``objects=None`` is a world without
-        objects: ids of zeros -- with (depth, ids, stats) bit for bit ``cast_worlds``' and rgb every byte
-        synthetic.render_rgb_numpy's.  ``colours`` int [n_envs,8]: packed 0x00RRGGBB of each slot of ``objects`` (None: zeros);
-        ``palette`` int [12] (None: synthetic.WORLD_PALETTE).  ``rgb_out``: a contiguous u8 [n,H,W,3] device tensor to render
-        into.  Camera records, object records, index lists, colours and palette cross in one small copy."""
-        tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
-        n = len(tf)
-        dev = self.boxes.device
-        if table.device != dev:
-            raise ValueError(f"cast_worlds_rgb: the world table must live on {dev}")
-        world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
-        if len(world_of) != n or np.any((world_of < 0) | (world_of >= table.n_worlds)):
-            raise ValueError("cast_worlds_rgb: world_of must name one world of the table per camera")
-        if objects is None:
-            if env_of is not None or colours is not None:
-                raise ValueError("cast_worlds_rgb: env_of and colours belong to objects")
-            objects, env_of = np.zeros((1, WORLD_MAX_OBJECTS, 8)), np.zeros(n, np.int32)
-        else:
-            objects = np.ascontiguousarray(objects, np.float64)
-            if objects.ndim != 3 or objects.shape[0] < 1 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
-                raise ValueError(f"cast_worlds_rgb: objects must be [n_envs >= 1, {WORLD_MAX_OBJECTS}, 8]")
-            env_of = np.ascontiguousarray(np.asarray(env_of).reshape(-1), np.int32)
-            if len(env_of) != n or np.any((env_of < 0) | (env_of >= len(objects))):
-                raise ValueError("cast_worlds_rgb: env_of must name one row of objects per camera")
-        colours = np.zeros((len(objects), WORLD_MAX_OBJECTS), np.int32) if colours is None else np.asarray(colours)
-        if colours.shape != (len(objects), WORLD_MAX_OBJECTS) or colours.dtype.kind not in "iu":
-            raise ValueError(f"cast_worlds_rgb: colours must be integers [{len(objects)}, {WORLD_MAX_OBJECTS}], one per object slot")
-        palette = np.asarray(WORLD_PALETTE if palette is None else palette)
-        if palette.shape != (12,) or palette.dtype.kind not in "iu":
-            raise ValueError("cast_worlds_rgb: palette must be 12 integers")
-        rec = np.empty((n, 8), np.float64)
-        rec[:, 0:2], rec[:, 2:4], rec[:, 4] = tf[:, :2, 3], tf[:, :2, 0], tf[:, 2, 3]
-        rec[:, 5] = camera_intrinsics(self.W)[0] if hfov is None else self.W / (2 * np.tan(np.asarray(hfov, np.float64) / 2))
-        rec[:, 6] = MIN_DEPTH if min_depth is None else np.asarray(min_depth, np.float64)
-        rec[:, 7] = MAX_DEPTH if max_depth is None else np.asarray(max_depth, np.float64)
-        if not np.all(rec[:, 7] > rec[:, 6]):
-            raise ValueError("cast_worlds_rgb: every camera needs max_depth > min_depth")
-        if out is None:
-            out = torch.empty((n, self.H, self.W), dtype=torch.float32, device=dev)
-        elif out.shape != (n, self.H, self.W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"cast_worlds_rgb: out must be a contiguous f32 [{n},{self.H},{self.W}] tensor on {dev}")
-        if rgb_out is None:
-            rgb_out = torch.empty((n, self.H, self.W, 3), dtype=torch.uint8, device=dev)
-        elif rgb_out.shape != (n, self.H, self.W, 3) or rgb_out.dtype != torch.uint8 or not rgb_out.is_contiguous() \
-                or rgb_out.device != dev:
-            raise ValueError(f"cast_worlds_rgb: rgb_out must be a contiguous u8 [{n},{self.H},{self.W},3] tensor on {dev}")
-        ids = torch.empty((n, self.H, self.W), dtype=torch.uint8, device=dev)
-        stats = torch.empty((n, WORLD_MAX_OBJECTS, 5), dtype=torch.int32, device=dev)
-        if n > 0:
-            with torch.cuda.device(dev):
-                # camera and object records, then the int32 lists (world_of, env_of, colours, palette), in ONE host buffer
-                ints = np.concatenate([world_of, env_of, (colours.astype(np.int64) & 0xFFFFFF).astype(np.int32).reshape(-1),
-                                       (palette.astype(np.int64) & 0xFFFFFF).astype(np.int32)])
+                ints = np.concatenate(ints)
                 blob = np.concatenate([rec.reshape(-1), objects.reshape(-1), np.zeros((len(ints) + 1) // 2, np.float64)])
                 blob[rec.size + objects.size:].view(np.int32)[:len(ints)] = ints
                 d_blob = torch.from_numpy(blob).to(dev)
                 p = d_blob.data_ptr()
-                p_ints = p + 8 * (rec.size + objects.size)
-                stream = torch.cuda.current_stream().cuda_stream
-                _lib.check(_lib.lib().vlfm_worlds_raycast_rgb(
+                p_ints = p + 8 * (rec.size + objects.size)          # world_of [n], env_of [n], colours, palette
+                _lib.check(_lib.lib().vlfm_worlds_raycast(
                     p, n, table.d_boxes.data_ptr(), table.d_counts.data_ptr(), table.n_worlds, table.max_boxes, p_ints,
-                    p + 8 * rec.size, p_ints + 4 * n, len(objects), self.H, self.W, out.data_ptr(), ids.data_ptr(),
-                    stats.data_ptr(), p_ints + 8 * n, p_ints + 8 * n + 4 * colours.size, rgb_out.data_ptr(), stream),
-                    "worlds_raycast_rgb")
+                    p + 8 * rec.size if with_objects else None, p_ints + 4 * n if with_objects else None, len(objects),
+                    self.H, self.W, out.data_ptr(), ids.data_ptr() if with_objects else None, stats.data_ptr() if with_objects else None,
+                    p_ints + 8 * n if rgb else None, p_ints + 8 * n + 4 * WORLD_MAX_OBJECTS * len(objects) if rgb else None,
+                    rgb_out.data_ptr() if rgb else None, torch.cuda.current_stream().cuda_stream), "worlds_raycast")
         return out, ids, stats, rgb_out
 
-    @torch.no_grad()
+    def _rooms_world_of(self, tf) -> np.ndarray:
+        """The rooms world: every camera of ``tf`` stands in row 0 of the renderer's own table."""
+        return np.zeros(np.size(tf) // 16, np.int32)
+
+    def cast_cameras(self, tf: np.ndarray, hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``render_cameras`` -- same arguments, the same frames bit for bit -- in ONE kernel launch on the current stream
+        (csrc/world_render.hip) instead of a chain of torch f64 operations over [n,W,B] and [n,H,W] temporaries: what a
+        closed-loop step, which cannot pre-render, pays per step.  ``out``: a contiguous f32 [n,H,W] device tensor to render
+        into."""
+        return self._raycast("cast_cameras", tf, self.table, self._rooms_world_of(tf), None, None, hfov, min_depth, max_depth,
+                             out)[0]
+
+    def cast_cameras_objects(self, tf: np.ndarray, objects: np.ndarray, env_of, hfov: Optional[np.ndarray] = None,
+                             min_depth=None, max_depth=None, out: Optional[torch.Tensor] = None):
+        """``cast_cameras`` with the objects of the cameras' environments standing in the world: ``objects`` [n_envs,8,8] f64 on
+        the host -- x0, y0, x1, y1, z0, z1, valid, pad per slot -- and ``env_of`` [n], the row of ``objects`` each camera looks
+        at.  Returns (depth f32 [n,H,W], ids u8 [n,H,W]: 0 = wall / floor, k + 1 = object slot k, stats int32 [n,8,5]: visible
+        pixels, first / last column, first / last row of each slot; (0, W, -1, H, -1) for none), all on the device, bit for bit
+        synthetic.render_objects_numpy / object_stats_numpy.  ``out``: the depth buffer, as in ``cast_cameras``."""
+        return self._raycast("cast_cameras_objects", tf, self.table, self._rooms_world_of(tf), np.asarray(objects, np.float64),
+                             env_of, hfov, min_depth, max_depth, out)[:3]
+
+    def cast_worlds(self, tf: np.ndarray, table: WorldTable, world_of, objects: Optional[np.ndarray] = None, env_of=None,
+                    hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None, out: Optional[torch.Tensor] = None):
+        """``cast_cameras_objects`` with a floor plan per camera: camera i stands in world ``world_of[i]`` of ``table`` and sees
+        the objects ``objects[env_of[i]]``.  Returns (depth, ids, stats) as ``cast_cameras_objects`` does, bit for bit
+        synthetic.render_objects_numpy(..., boxes=table.world(world_of[i])); with ``objects=None`` the walls-only frames, as
+        ``cast_cameras`` returns them."""
+        res = self._raycast("cast_worlds", tf, table, world_of, objects, env_of, hfov, min_depth, max_depth, out)
+        return res[0] if objects is None else res[:3]
+
+    def cast_worlds_rgb(self, tf: np.ndarray, table: WorldTable, world_of, objects: Optional[np.ndarray] = None, env_of=None,
+                        colours=None, palette=None, hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None,
+                        out: Optional[torch.Tensor] = None, rgb_out: Optional[torch.Tensor] = None):
+        """``cast_worlds`` and the cameras' RGB view of the same worlds from the same launch.  Returns (depth, ids, stats, rgb u8
+        [n,H,W,3]) -- always all four; ``objects=None`` is a world without objects: ids of zeros -- with (depth, ids, stats) bit
+        for bit ``cast_worlds``' and rgb every byte synthetic.render_rgb_numpy's.  ``colours`` int [n_envs,8]: packed 0x00RRGGBB
+        of each slot of ``objects`` (None: zeros); ``palette`` int [12] (None: synthetic.WORLD_PALETTE).  ``rgb_out``: a
+        contiguous u8 [n,H,W,3] device tensor to render into."""
+        return self._raycast("cast_worlds_rgb", tf, table, world_of, objects, env_of, hfov, min_depth, max_depth, out, True,
+                             colours, palette, rgb_out)
+
     def cast_cameras_rgb(self, tf: np.ndarray, objects: Optional[np.ndarray] = None, env_of=None, colours=None, palette=None,
                          hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None, out: Optional[torch.Tensor] = None,
                          rgb_out: Optional[torch.Tensor] = None):
-        """``cast_worlds_rgb`` for the rooms world: every camera stands in the one row of a world table the renderer keeps (BOXES).
-        (depth, ids, stats) are bit for bit ``cast_cameras_objects``'."""
-        if self._rooms_table is None:
-            self._rooms_table = WorldTable(1, self.boxes.device, len(BOXES))
-            self._rooms_table.assign([0], [BOXES])
-        n = len(np.asarray(tf, np.float64).reshape(-1, 4, 4))
-        return self.cast_worlds_rgb(tf, self._rooms_table, np.zeros(n, np.int32), objects, env_of, colours, palette, hfov,
-                                    min_depth, max_depth, out, rgb_out)
+        """``cast_worlds_rgb`` for the rooms world.  (depth, ids, stats) are bit for bit ``cast_cameras_objects``'."""
+        return self._raycast("cast_cameras_rgb", tf, self.table, self._rooms_world_of(tf), objects, env_of, hfov, min_depth,
+                             max_depth, out, True, colours, palette, rgb_out)
+
+    def geodesic_fields(self, objects: np.ndarray, targets_boxes, success_distance: float,
+                        max_sources: int = GEODESIC_MAX_SOURCES) -> GeodesicFields:
+        """``geodesic_fields_worlds`` for the rooms world: every field stands in the renderer's own table."""
+        return self.geodesic_fields_worlds(self.table, np.zeros(len(objects), np.int32), objects, targets_boxes, success_distance,
+                                           max_sources)
 
     @torch.no_grad()
     def geodesic_fields_worlds(self, table: WorldTable, world_of, objects: np.ndarray, targets_boxes, success_distance: float,
                                max_sources: int = GEODESIC_MAX_SOURCES) -> GeodesicFields:
-        """``geodesic_fields`` with a floor plan per field (vlfm_geodesic_fields_worlds, ONE launch on the current stream): the
-        obstacles of field i are the walls of world ``world_of[i]`` of ``table`` and the valid footprints of ``objects[i]``,
-        i.e. synthetic.inflated_rects(objects[i], STEP_MARGIN, table.world(world_of[i])).  The handle is strided by
-        R = table.max_boxes + 8; ``geodesic_distances`` and ``GeodesicFields.assign`` take it as they take any other."""
+        """The geodesic fields of n environments in ONE launch on the current stream (vlfm_geodesic_fields, bit for bit
+        synthetic.geodesic_field_numpy): ``objects`` [n,8,8] f64 on the host, the ray caster's records; the obstacles of field
+        i are the walls of world ``world_of[i]`` of ``table`` and the valid footprints of ``objects[i]``, inflated by
+        STEP_MARGIN, i.e. synthetic.inflated_rects(objects[i], STEP_MARGIN, table.world(world_of[i])).  ``targets_boxes``
+        [n,>=4]: the footprint each environment has to reach within ``success_distance`` (a NaN row: no target, every distance
+        in that field is inf).  The view points (synthetic.goal_viewpoints) are worked out on the host; they, their counts and
+        world_of cross in one small copy, the records in another.  The handle is strided by R = table.max_boxes + 8;
+        ``geodesic_distances`` and ``GeodesicFields.assign`` take it as they take any other."""
         objects = np.ascontiguousarray(objects, np.float64)
         if objects.ndim != 3 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
             raise ValueError(f"geodesic_fields_worlds: objects must be [n, {WORLD_MAX_OBJECTS}, 8]")
@@ -687,11 +567,11 @@ class RoomsRenderer:
             h.sources.copy_(d_blob[:n * max_sources * 2].view(n, max_sources, 2))
             h.source_counts.copy_(d_blob[n * max_sources * 2:].view(torch.int32)[:n])
             stream = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().vlfm_geodesic_fields_worlds(
+            _lib.check(_lib.lib().vlfm_geodesic_fields(
                 table.d_boxes.data_ptr(), table.d_counts.data_ptr(), table.n_worlds, table.max_boxes,
                 d_blob.data_ptr() + 8 * (n * max_sources * 2 + pad), STEP_MARGIN, d_obj.data_ptr(), h.sources.data_ptr(),
                 h.source_counts.data_ptr(), n, max_sources, h.rects.data_ptr(), h.nodes.data_ptr(), h.dist.data_ptr(),
-                h.counts.data_ptr(), stream), "geodesic_fields_worlds")
+                h.counts.data_ptr(), stream), "geodesic_fields")
         return h
 
     @torch.no_grad()
@@ -893,8 +773,10 @@ class BatchedEpisodes:
                 self.world_xy, self.world_k = self._start_xy.copy(), self._start_k.copy()
                 self._collided = np.zeros(n_envs, bool)
                 self._live_frames = None
+                # where each robot's walls are: a row per environment with ``worlds``, else the renderer's one row for everybody
+                self.world_table, self.world_of = self.rooms.table, np.zeros(n_envs, np.int32)
                 if worlds is not None:
-                    self.world_table = WorldTable(n_envs, self.device)
+                    self.world_table, self.world_of = WorldTable(n_envs, self.device), np.arange(n_envs, dtype=np.int32)
                     self.world_episode = np.full(n_envs, -1, np.int64)      # the episode whose world each environment is in
                     if world_objects is None:
                         self._enter_worlds(range(n_envs), np.zeros(n_envs, np.int64))
@@ -1285,11 +1167,8 @@ class BatchedEpisodes:
             return
         slots = self._target_slot[envs]
         boxes = np.where((slots >= 0)[:, None], self._objects[envs, np.maximum(slots, 0), :4], np.nan)
-        if self.worlds is not None:
-            fresh = self.rooms.geodesic_fields_worlds(self.world_table, envs, self._objects[envs], boxes,
-                                                      self.world_objects.success_distance)
-        else:
-            fresh = self.rooms.geodesic_fields(self._objects[envs], boxes, self.world_objects.success_distance)
+        fresh = self.rooms.geodesic_fields_worlds(self.world_table, self.world_of[envs], self._objects[envs], boxes,
+                                                  self.world_objects.success_distance)
         if self._geodesic is None:              # (the first call starts every environment's episode)
             assert len(envs) == self.E and np.array_equal(envs, np.arange(self.E))
             self._geodesic = fresh
@@ -1641,19 +1520,13 @@ class BatchedEpisodes:
             self._live_frames = torch.empty((self.E, self.H, self.W), dtype=torch.float32, device=self.device)
         if self.render_rgb and not fresh:
             return self._live_depth_rgb(t_ep, tf)
-        if self.worlds is not None and self.world_objects is None:
-            return self.rooms.cast_worlds(tf, self.world_table, np.arange(self.E), out=None if fresh else self._live_frames)
+        out = None if fresh else self._live_frames
         if self.world_objects is not None:
-            if self.worlds is not None:
-                d, ids, stats = self.rooms.cast_worlds(tf, self.world_table, np.arange(self.E), self._objects, np.arange(self.E),
-                                                       out=None if fresh else self._live_frames)
-            else:
-                d, ids, stats = self.rooms.cast_cameras_objects(tf, self._objects, np.arange(self.E),
-                                                                out=None if fresh else self._live_frames)
+            d, ids, stats = self.rooms.cast_worlds(tf, self.world_table, self.world_of, self._objects, np.arange(self.E), out=out)
             if not fresh:
                 self._note_sightings(ids, stats)
             return d
-        d = self.rooms.cast_cameras(tf, out=None if fresh else self._live_frames)
+        d = self.rooms.cast_worlds(tf, self.world_table, self.world_of, out=out)
         return self.rooms.painter(t_ep, d) if self.rooms.painter is not None else d
 
     def _note_sightings(self, ids: torch.Tensor, stats: torch.Tensor) -> None:
@@ -1677,11 +1550,8 @@ class BatchedEpisodes:
             colours = np.zeros((self.E, WORLD_MAX_OBJECTS), np.int32)
             for e, classes in enumerate(self._object_classes):
                 colours[e, :len(classes)] = [OBJECT_COLOURS.get(c, 0x808080) for c in classes]
-        if self.worlds is not None:
-            d, ids, stats, _ = self.rooms.cast_worlds_rgb(tf, self.world_table, np.arange(self.E), objects, env_of, colours,
-                                                          out=self._live_frames, rgb_out=self.last_rgb)
-        else:
-            d, ids, stats, _ = self.rooms.cast_cameras_rgb(tf, objects, env_of, colours, out=self._live_frames, rgb_out=self.last_rgb)
+        d, ids, stats, _ = self.rooms.cast_worlds_rgb(tf, self.world_table, self.world_of, objects, env_of, colours,
+                                                      out=self._live_frames, rgb_out=self.last_rgb)
         if self.world_objects is not None:
             self._note_sightings(ids, stats)
             return d

@@ -359,7 +359,7 @@ class ReplayController:
 # ---------------------------------------------------------------------------------------------- world objects
 # Target and distractor objects standing IN the rooms world: an object is an axis-aligned box with a vertical extent,
 # (x0, y0, x1, y1, z0, z1) in metres, plus a class name.  The ray caster renders them with occlusion (csrc/world_render.hip:
-# vlfm_rooms_raycast_objects; `render_objects_numpy` below is the host statement of the same arithmetic), `step_poses` refuses
+# vlfm_worlds_raycast with objects; `render_objects_numpy` below is the host statement of the same arithmetic), `step_poses` refuses
 # moves into them, and the batched harness reports as detections what is actually in view (BatchedEpisodes(world_objects=...)).
 WORLD_MAX_OBJECTS = 8
 # free-standing centres, hand-placed over the hall and the ring rooms: `object_layout` asserts that each keeps 0.65 m to every
@@ -469,7 +469,7 @@ def object_stats_numpy(ids, K: int = WORLD_MAX_OBJECTS) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------------- world colours
-# What the camera's RGB frame shows of the same world (csrc/world_render.hip: vlfm_worlds_raycast_rgb; `render_rgb_numpy` is the
+# What the camera's RGB frame shows of the same world (csrc/world_render.hip: vlfm_worlds_raycast with d_rgb; `render_rgb_numpy` is the
 # host statement).  Colours are packed 0x00RRGGBB integers and reach the kernel as arguments: it holds no colour constants.
 WORLD_PALETTE = np.array([0xC8B7A6, 0xB5C4B1, 0xA9B8C8, 0xD6C58F, 0xC49A8A, 0x9FB7AD, 0xBFAFCB, 0xD9D4C7,      # 8 wall colours
                           0x8A6F4E, 0x6F5B41,                                                                  # 2 floor colours
