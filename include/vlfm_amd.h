@@ -903,6 +903,30 @@ int vlfm_worlds_raycast(const double* d_cameras, int n, const double* d_world_bo
                         int H, int W, float* d_depth, uint8_t* d_ids, int32_t* d_stats, const int32_t* d_object_colours,
                         const int32_t* d_palette, uint8_t* d_rgb, void* stream);
 
+/* Grid worlds (ABI 25): a world of the table may also hold an OCCUPANCY GRID -- a top-down map of up to 1024 x 1024 cells whose
+ * occupied cells are full-height walls (vlfm_amd.synthetic.GridPlan).  A grid world IS the box world of its occupied cells:
+ * cell (i, j) is the box (xs[i], ys[j], xs[i+1], ys[j+1]), and depth, ids and stats are bit for bit what the box statements give
+ * for those boxes (closed slabs, tmin > 0: a cell around the camera is transparent, |dx| < 1e-12 -> 1e-12).  A world with boxes
+ * AND a grid: the wall of a column is the f64 minimum of the two, rounded to f32 after.  The kernels do not loop over cells:
+ * per column a grid walk over the slab test's own crossing times (csrc/world_render.hip: grid_walk; the host statement is
+ * synthetic.grid_profile_numpy) gives the same bits in at most nx + ny + 2 steps.
+ *   d_grid_bits   [n_worlds][max_ny][ceil(max_nx / 32)] uint32: bit i % 32 of word i / 32 of row j: cell (i, j) is a wall
+ *   d_grid_edges  [n_worlds][max_nx + 1 + max_ny + 1] doubles: xs (nx + 1 of them, strictly increasing), then, from index
+ *                 max_nx + 1, ys (ny + 1)
+ *   d_grid_dims   [n_worlds][2] int32: ny, nx, clamped to [0, max_ny] and [0, max_nx] by the kernels; a zero: the world has no
+ *                 grid.  Cells and edges beyond a world's dims are never read, whatever the table holds there.
+ * vlfm_worlds_raycast_grids is vlfm_worlds_raycast with these arrays -- all three, or all three NULL, which IS
+ * vlfm_worlds_raycast (max_nx, max_ny ignored).  With grids: max_nx and max_ny in [1, VLFM_GRID_MAX_CELLS], and d_rgb must be
+ * NULL (wall colours are defined by box and face); anything else is VLFM_ERR_INVALID, nothing launched, nothing written.  Bits
+ * and edges are read from global memory; the LDS needs are those above. */
+#define VLFM_GRID_MAX_CELLS 1024
+int vlfm_worlds_raycast_grids(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts,
+                              int n_worlds, int max_boxes, const int32_t* d_world_of, const double* d_objects,
+                              const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids, int32_t* d_stats,
+                              const int32_t* d_object_colours, const int32_t* d_palette, uint8_t* d_rgb,
+                              const uint32_t* d_grid_bits, const double* d_grid_edges, const int32_t* d_grid_dims, int max_nx,
+                              int max_ny, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Geodesic distances in the synthetic worlds (ABI 19; the fields read the world table since ABI 24; csrc/geodesic.hip): the
  * length of the shortest collision-free path from a point to an ObjectNav goal, which SPL, SoftSPL and distance_to_goal are made of (the reference reads them off Habitat's

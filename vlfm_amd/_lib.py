@@ -244,6 +244,7 @@ def lib() -> ctypes.CDLL:
         L.vlfm_jpeg_decode_batched.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ci, ci, ci, vp, vp, ci, vp, ci, ci,
                                                ctypes.c_size_t, ci, vp, vp, vp, ctypes.c_size_t, vp]
         L.vlfm_worlds_raycast.argtypes = [vp, ci, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        L.vlfm_worlds_raycast_grids.argtypes = L.vlfm_worlds_raycast.argtypes[:-1] + [vp, vp, vp, ci, ci, vp]
         L.vlfm_geodesic_fields.argtypes = [vp, vp, ci, ci, vp, cd, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
         L.vlfm_geodesic_query.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp]
         L.vlfm_plan_scratch_bytes.argtypes = [ci, ci]

@@ -19,7 +19,8 @@
 // adjacent columns and a band leaves as consecutive 16-byte stores; any other W takes the scalar store loop.
 // A workgroup finds its boxes in the row of its camera's world in a table of worlds (world_table.h; the fixed rooms world is a
 // table of one row).  Three kernels -- walls only, with objects, with objects and colour (the objects kernel is a template over
-// "with colour") -- behind ONE entry, vlfm_worlds_raycast, at the end of the file.
+// "with colour") -- behind ONE entry, vlfm_worlds_raycast, at the end of the file.  A world may also hold an occupancy grid whose
+// occupied cells are walls (grid_walk below): walls-only and objects kernels are templates over "has grids".
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -45,8 +46,84 @@ __device__ __forceinline__ float normalise(double d, double lo, double span) {
     return (float)v;
 }
 
+// ---- grid worlds: the occupied cells of an occupancy grid are walls as well (synthetic.GridPlan) ---------------------------------
+// A grid world IS the box world of its occupied cells; grid_walk returns, bit for bit, the minimum the box loop would find over
+// those cells (synthetic.grid_profile_numpy is the host statement).  With T(e) = (edge[e] - p) / d, the slab test's own crossing
+// times (true divisions, nothing accumulated; monotone in e because a rounded subtraction and a rounded division are):
+//   first_slab   the slab of one axis at t = 0+: the i with T(i) <= 0 < T(i+1) for d > 0, T(i+1) <= 0 < T(i) for d < 0; -1 or n
+//                outside.  {T <= 0} (d > 0) and {T > 0} (d < 0) are prefixes of the edges: a binary search counts them.
+//   walk         the smaller of the next x and the next y crossing is taken and the cell behind it entered; occupied: that
+//                crossing time is the answer.  Equal crossing times: the answer is that time if any of (i+sx, j), (i, j+sy),
+//                (i+sx, j+sy) is occupied (all three have that tmin under the closed-slab rule), else a diagonal step.
+// The walk ends once an index is past the far side of its axis; every step advances an index, so nx + ny + 2 steps bound it and
+// the loop carries that bound as a counter.  Bits and edges are read from global memory through the cache: at 1024 x 1024 they
+// (128 KB + 16 KB) do not fit the 64 KB of LDS beside the column tables.
+__device__ __forceinline__ int first_slab(const double* __restrict__ edge, int n, double p, double d) {
+    int lo = 0, hi = n + 1;                                // the count of edges "behind" lies in [lo, hi]
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;                    // 0 <= mid <= n
+        const double t = (edge[mid] - p) / d;
+        if (d > 0.0 ? t <= 0.0 : t > 0.0) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo - 1;
+}
+
+__device__ __forceinline__ double grid_walk(const GridView& g, double x, double y, double dx, double dy) {
+    const double inf = __builtin_inf();
+    if (g.nx == 0) return inf;
+    const int sx = dx > 0.0 ? 1 : -1, sy = dy > 0.0 ? 1 : -1;
+    const int ox = dx > 0.0 ? 1 : 0, oy = dy > 0.0 ? 1 : 0;           // the next edge of slab i is edge i + ox
+    int i = first_slab(g.xs, g.nx, x, dx), j = first_slab(g.ys, g.ny, y, dy);
+    if (i + ox < 0 || i + ox > g.nx || j + oy < 0 || j + oy > g.ny) return inf;
+    double tx = (g.xs[i + ox] - x) / dx, ty = (g.ys[j + oy] - y) / dy;
+    // A step is a chain of dependent work: the edge, its division, the cell's bit.  Two things take the loads off that chain
+    // without touching the arithmetic: the edge BEHIND the next crossing of each axis is loaded a step early (index clamped into
+    // the array; the value is used only after the range check passed), and the word of bits a cell was found in stays in a
+    // register until the walk leaves its 32 columns or its row.
+    double ex_next = g.xs[min(max(i + ox + sx, 0), g.nx)], ey_next = g.ys[min(max(j + oy + sy, 0), g.ny)];
+    int wrow = -1, wcol = -1;
+    uint32_t word = 0;
+    auto wall = [&](int ci, int cj) -> bool {              // cells outside the grid are free
+        if (ci < 0 || ci >= g.nx || cj < 0 || cj >= g.ny) return false;
+        if (cj != wrow || (ci >> 5) != wcol) {
+            wrow = cj;
+            wcol = ci >> 5;
+            word = g.bits[(size_t)cj * g.words + wcol];
+        }
+        return (word >> (ci & 31)) & 1u;
+    };
+    for (int step = g.nx + g.ny + 2; step > 0; --step) {
+        if (tx < ty) {
+            i += sx;
+            if (wall(i, j)) return tx;
+            if (i + ox < 0 || i + ox > g.nx) return inf;
+            tx = (ex_next - x) / dx;
+            ex_next = g.xs[min(max(i + ox + sx, 0), g.nx)];
+        } else if (ty < tx) {
+            j += sy;
+            if (wall(i, j)) return ty;
+            if (j + oy < 0 || j + oy > g.ny) return inf;
+            ty = (ey_next - y) / dy;
+            ey_next = g.ys[min(max(j + oy + sy, 0), g.ny)];
+        } else {                                           // a corner (or a NaN pose: the counter and the range checks end it)
+            if (wall(i + sx, j) || wall(i, j + sy) || wall(i + sx, j + sy)) return tx;
+            i += sx;
+            j += sy;
+            if (i + ox < 0 || i + ox > g.nx || j + oy < 0 || j + oy > g.ny) return inf;
+            tx = (ex_next - x) / dx;
+            ty = (ey_next - y) / dy;
+            ex_next = g.xs[min(max(i + ox + sx, 0), g.nx)];
+            ey_next = g.ys[min(max(j + oy + sy, 0), g.ny)];
+        }
+    }
+    return inf;
+}
+
+template <bool GRID>
 __global__ __launch_bounds__(THREADS) void rooms_raycast_kernel(const CameraRec* __restrict__ cameras, const WorldBoxes table,
-                                                                int H, int W, int band, int vec4, float* __restrict__ out) {
+                                                                const WorldGrids grids, int H, int W, int band, int vec4,
+                                                                float* __restrict__ out) {
     extern __shared__ double smem[];
     const int r0 = blockIdx.x * band;
     if (r0 >= H) return;                                   // (uniform for the workgroup: before any barrier)
@@ -58,6 +135,8 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_kernel(const CameraRec*
     float* ncol = reinterpret_cast<float*>(smem + 4 * table.capacity());   // [W rounded up to 4]: 16-byte aligned (32 * capacity bytes in)
     float* nrow = ncol + ((W + 3) & ~3);                   // [band]
     const CameraRec cam = cameras[blockIdx.y];
+    GridView gview{};
+    if constexpr (GRID) gview = grids.find(table, blockIdx.y);
     for (int i = tid; i < 4 * n_boxes; i += THREADS) sbox[i] = boxes[i];
     const double span = cam.hi - cam.lo;
     const double inf = __builtin_inf();
@@ -81,6 +160,7 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_kernel(const CameraRec*
             const double tmax = fmin(fmax(tx0, tx1), fmax(ty0, ty1));
             if (tmax >= fmax(tmin, 0.0) && tmin > 0.0) best = fmin(best, tmin);
         }
+        if constexpr (GRID) best = fmin(best, grid_walk(gview, cam.x, cam.y, dx, dy));
         const float wall = (float)best;                    // the host path keeps the profile in f32
         ncol[u] = normalise((double)wall, cam.lo, span);
     }
@@ -264,9 +344,11 @@ __device__ __forceinline__ uint32_t finish(Paint p, float depth) {
 
 // RGB = false: depth, ids and stats (`object_colours`, `palette`, `rgb` unused);
 // RGB = true: the colour plane as well, from the same per-column geometry.
-template <bool RGB>
+// GRID: the column's wall is the minimum of the boxes and the camera's grid (never with RGB: wall colours are defined by box and
+// face).  A template parameter, so that the box-only kernels are the code they were.
+template <bool RGB, bool GRID>
 __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
-    const CameraRec* __restrict__ cameras, const WorldBoxes table, const double* __restrict__ objects,
+    const CameraRec* __restrict__ cameras, const WorldBoxes table, const WorldGrids grids, const double* __restrict__ objects,
     const int32_t* __restrict__ env_of, int n_envs, int H, int W, int band, int vec4, float* __restrict__ out,
     uint8_t* __restrict__ ids, int32_t* __restrict__ stats, const int32_t* __restrict__ object_colours,
     const int32_t* __restrict__ palette, uint8_t* __restrict__ rgb) {
@@ -288,6 +370,8 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
     const CameraRec cam = cameras[blockIdx.y];
     const int env = env_of[blockIdx.y];
     const bool has_env = env >= 0 && env < n_envs;         // (the host wrapper refuses anything else; never read out of bounds)
+    GridView gview{};
+    if constexpr (GRID) gview = grids.find(table, blockIdx.y);
     RgbLds L{};
     if constexpr (RGB) {                                   // behind cmask, from the next 16-byte boundary (wp is a multiple of 4)
         const uintptr_t end = reinterpret_cast<uintptr_t>(cmask + wp), base0 = reinterpret_cast<uintptr_t>(smem);
@@ -349,6 +433,7 @@ __global__ __launch_bounds__(THREADS) void rooms_raycast_objects_kernel(
                 }
             }
         }
+        if constexpr (GRID && !RGB) best = fmin(best, grid_walk(gview, cam.x, cam.y, dx, dy));
         const float wall = (float)best;                    // the host path keeps the profile in f32
         const float nwall = normalise((double)wall, cam.lo, span);
         ncol[u] = nwall;
@@ -575,14 +660,23 @@ using namespace vlfm::world;
 // the floor's f64 checker ("is any of the four floor") and one around the objects' colours.  Bands are capped at
 // RGB_MAX_BAND_ROWS rows so that the LDS need does not grow with the camera count.  Stores: with W % 4 == 0 and aligned outputs a
 // lane's 4 pixels leave as three dwords (one 12-byte store); else bytes.
-extern "C" int vlfm_worlds_raycast(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts,
-                                   int n_worlds, int max_boxes, const int32_t* d_world_of, const double* d_objects,
-                                   const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids,
-                                   int32_t* d_stats, const int32_t* d_object_colours, const int32_t* d_palette, uint8_t* d_rgb,
-                                   void* stream) {
+//
+// vlfm_worlds_raycast_grids: the same call with the worlds' occupancy grids (world_table.h: d_grid_bits, d_grid_edges,
+// d_grid_dims, all three or none).  A column's wall is the f64 minimum of the box loop and grid_walk; everything behind that
+// number is the code above.  The kernels are templates over "has grids": a launch without grids runs the box-only instantiation.
+extern "C" int vlfm_worlds_raycast_grids(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts,
+                                         int n_worlds, int max_boxes, const int32_t* d_world_of, const double* d_objects,
+                                         const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids,
+                                         int32_t* d_stats, const int32_t* d_object_colours, const int32_t* d_palette,
+                                         uint8_t* d_rgb, const uint32_t* d_grid_bits, const double* d_grid_edges,
+                                         const int32_t* d_grid_dims, int max_nx, int max_ny, void* stream) {
     static_assert(sizeof(CameraRec) == 64, "camera record layout");
     static_assert(sizeof(ObjCol) == 8, "object column entry layout");
     const bool with_objects = d_objects != nullptr, with_rgb = d_rgb != nullptr;
+    const bool with_grids = d_grid_bits || d_grid_edges || d_grid_dims;
+    if (with_grids && (!d_grid_bits || !d_grid_edges || !d_grid_dims || with_rgb || max_nx < 1 || max_nx > VLFM_GRID_MAX_CELLS ||
+                       max_ny < 1 || max_ny > VLFM_GRID_MAX_CELLS))
+        return fail(VLFM_ERR_INVALID, "worlds_raycast: grids need all three arrays, max_nx and max_ny in [1, 1024], and no d_rgb");
     if (n < 0 || n > 65535 || n_worlds < 0 || max_boxes < 0 || H <= 0 || W <= 0 || (n > 0 && (!d_cameras || !d_world_of || !d_depth)) ||
         (n_worlds > 0 && (!d_box_counts || (max_boxes > 0 && !d_world_boxes))) ||
         (with_objects && (n_envs <= 0 || H > 32768 || (n > 0 && (!d_env_of || !d_ids || !d_stats)))) ||
@@ -592,6 +686,7 @@ extern "C" int vlfm_worlds_raycast(const double* d_cameras, int n, const double*
     const Bands b = plan_bands(n, H, with_rgb ? RGB_MAX_BAND_ROWS : H);
     const size_t wp = (size_t)((W + 3) & ~3);
     const WorldBoxes table{d_world_boxes, d_box_counts, d_world_of, n_worlds, max_boxes};
+    const WorldGrids grids{with_grids ? d_grid_bits : nullptr, d_grid_edges, d_grid_dims, with_grids ? max_nx : 0, with_grids ? max_ny : 0};
     const CameraRec* cameras = reinterpret_cast<const CameraRec*>(d_cameras);
     const dim3 grid(b.grid_x, n);
     hipStream_t st = (hipStream_t)stream;
@@ -600,7 +695,8 @@ extern "C" int vlfm_worlds_raycast(const double* d_cameras, int n, const double*
         const size_t lds = walls_lds(max_boxes, wp, b.band);
         if (lds > 64 * 1024) return fail(VLFM_ERR_INVALID, "worlds_raycast: max_boxes + one image row + one row band exceed 64 KB of LDS");
         VLFM_TIMED("worlds_raycast_kernel", st);
-        VLFM_KLAUNCH(rooms_raycast_kernel, grid, dim3(THREADS), lds, st, cameras, table, H, W, b.band, vec4, d_depth);
+        const auto kernel = with_grids ? rooms_raycast_kernel<true> : rooms_raycast_kernel<false>;
+        VLFM_KLAUNCH(kernel, grid, dim3(THREADS), lds, st, cameras, table, grids, H, W, b.band, vec4, d_depth);
         return check_launch("worlds_raycast_kernel");
     }
     const size_t lds = with_rgb ? rgb_lds(max_boxes, wp, b.band) : objects_lds(max_boxes, wp, b.band);
@@ -614,8 +710,19 @@ extern "C" int vlfm_worlds_raycast(const double* d_cameras, int n, const double*
     if (rc != VLFM_OK) return rc;
     const char* label = with_rgb ? "worlds_raycast_rgb_kernel" : "worlds_raycast_objects_kernel";
     VLFM_TIMED(label, st);
-    const auto kernel = with_rgb ? rooms_raycast_objects_kernel<true> : rooms_raycast_objects_kernel<false>;
-    VLFM_KLAUNCH(kernel, grid, dim3(THREADS), lds, st, cameras, table, d_objects, d_env_of, n_envs, H, W, b.band, vec4, d_depth,
-                 d_ids, d_stats, d_object_colours, d_palette, d_rgb);
+    const auto kernel = with_rgb ? rooms_raycast_objects_kernel<true, false>
+                                 : (with_grids ? rooms_raycast_objects_kernel<false, true> : rooms_raycast_objects_kernel<false, false>);
+    VLFM_KLAUNCH(kernel, grid, dim3(THREADS), lds, st, cameras, table, grids, d_objects, d_env_of, n_envs, H, W, b.band, vec4,
+                 d_depth, d_ids, d_stats, d_object_colours, d_palette, d_rgb);
     return check_launch(label);
+}
+
+extern "C" int vlfm_worlds_raycast(const double* d_cameras, int n, const double* d_world_boxes, const int32_t* d_box_counts,
+                                   int n_worlds, int max_boxes, const int32_t* d_world_of, const double* d_objects,
+                                   const int32_t* d_env_of, int n_envs, int H, int W, float* d_depth, uint8_t* d_ids,
+                                   int32_t* d_stats, const int32_t* d_object_colours, const int32_t* d_palette, uint8_t* d_rgb,
+                                   void* stream) {
+    return vlfm_worlds_raycast_grids(d_cameras, n, d_world_boxes, d_box_counts, n_worlds, max_boxes, d_world_of, d_objects, d_env_of,
+                                     n_envs, H, W, d_depth, d_ids, d_stats, d_object_colours, d_palette, d_rgb, nullptr, nullptr,
+                                     nullptr, 0, 0, stream);
 }

@@ -24,7 +24,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -36,7 +36,7 @@ from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TUR
     MAX_DEPTH, MIN_DEPTH, YAWS, BangBangController, ReplayController, Trajectory, camera_intrinsics, depth_frame, integrate, \
     GEODESIC_MAX_SOURCES, STEP_MARGIN, WORLD_MAX_BOXES, WORLD_MAX_OBJECTS, ProceduralWorlds, goal_viewpoints, inflated_rects, object_layout, plan_actions, \
     pose_to_tf, rect_distance, rgb_frame, soft_spl, spl, step_poses, tf_of, PLAN_INVALID, PLAN_OK, PLAN_TOO_LONG, \
-    PLAN_UNREACHABLE, OBJECT_COLOURS, WORLD_PALETTE
+    PLAN_UNREACHABLE, OBJECT_COLOURS, WORLD_PALETTE, GRID_MAX_CELLS, GridPlan, GridWorlds
 
 PROMPT = "Seems like there is a target_object ahead."  # vlfm/policy/base_objectnav_policy.py:377
 TARGETS = ["chair", "bed", "potted plant", "toilet", "tv", "couch"]  # HM3D ObjectNav categories
@@ -261,12 +261,26 @@ class WorldTable:
     """A table of ``n_worlds`` floor plans for the per-world entries (RoomsRenderer.cast_worlds / geodesic_fields_worlds): the
     host mirror -- ``boxes`` [n_worlds,max_boxes,4] f64, NaN beyond each world's ``counts`` [n_worlds] int32 (what
     synthetic.step_poses takes as ``boxes``) -- and its copy on ``device`` (``d_boxes``, ``d_counts``).  Every world starts
-    empty."""
+    empty.  ``max_grid`` = (ny, nx): every world may also hold an occupancy grid of up to that many cells (synthetic.GridPlan)
+    whose occupied cells are walls as well: ``grids`` [n_worlds] on the host (a plan or None: what step_poses takes as
+    ``grids``) and on the device bit-packed rows ``d_grid_bits`` int32 [n_worlds, ny, ceil(nx / 32)], edges ``d_grid_edges`` f64
+    [n_worlds, nx + 1 + ny + 1] (xs, then ys from index nx + 1) and ``d_grid_dims`` int32 [n_worlds, 2] = (ny, nx) of each
+    world, (0, 0) for none (include/vlfm_amd.h: grid worlds)."""
 
-    def __init__(self, n_worlds: int, device, max_boxes: int = WORLD_MAX_BOXES) -> None:
+    def __init__(self, n_worlds: int, device, max_boxes: int = WORLD_MAX_BOXES, max_grid=None) -> None:
         if n_worlds < 0 or max_boxes < 0:
             raise ValueError("WorldTable: n_worlds and max_boxes must not be negative")
         self.n_worlds, self.max_boxes, self.device = int(n_worlds), int(max_boxes), torch.device(device)
+        self.max_grid = None
+        self.grids: List[Optional[GridPlan]] = [None] * self.n_worlds
+        if max_grid is not None:
+            ny, nx = (int(v) for v in max_grid)
+            if not (1 <= ny <= GRID_MAX_CELLS and 1 <= nx <= GRID_MAX_CELLS):
+                raise ValueError(f"WorldTable: max_grid = (ny, nx), each in [1, {GRID_MAX_CELLS}]")
+            self.max_grid, self.grid_words = (ny, nx), (nx + 31) // 32
+            self.d_grid_bits = torch.zeros((self.n_worlds, ny, self.grid_words), dtype=torch.int32, device=self.device)
+            self.d_grid_edges = torch.zeros((self.n_worlds, nx + ny + 2), dtype=torch.float64, device=self.device)
+            self.d_grid_dims = torch.zeros((self.n_worlds, 2), dtype=torch.int32, device=self.device)
         self.boxes = np.full((self.n_worlds, self.max_boxes, 4), np.nan)
         self.counts = np.zeros(self.n_worlds, np.int32)
         self.d_boxes = torch.full((self.n_worlds, self.max_boxes, 4), float("nan"), dtype=torch.float64, device=self.device)
@@ -276,14 +290,25 @@ class WorldTable:
         """[count,4] f64: the boxes of world ``row`` (a copy of the host mirror's)."""
         return self.boxes[row, :self.counts[row]].copy()
 
-    def assign(self, rows, list_of_boxes) -> None:
-        """World ``rows[i]`` becomes the boxes ``list_of_boxes[i]`` [B_i,4] (finite, B_i <= max_boxes).  Only these rows cross,
-        in ONE host-to-device copy (boxes, counts and row indices in one buffer), and are scattered into the table on the
-        device, on the current stream."""
+    def assign(self, rows, list_of_boxes, grids=None) -> None:
+        """World ``rows[i]`` becomes the boxes ``list_of_boxes[i]`` [B_i,4] (finite, B_i <= max_boxes) and, in a table with
+        ``max_grid``, the grid ``grids[i]`` (a GridPlan within max_grid, or None; ``grids=None``: none of these rows has one).
+        Only these rows cross, in ONE host-to-device copy (boxes, counts, row indices, grid dims, edges and bits in one buffer),
+        and are scattered into the table on the device, on the current stream."""
         rows = np.asarray(rows, np.int64).reshape(-1)
         worlds = [np.asarray(b, np.float64).reshape(-1, 4) for b in list_of_boxes]
         if len(rows) != len(worlds):
             raise ValueError("WorldTable.assign: one list of boxes per row")
+        grids = [None] * len(rows) if grids is None else list(grids)
+        if len(grids) != len(rows):
+            raise ValueError("WorldTable.assign: one grid (or None) per row")
+        for g in grids:
+            if g is None:
+                continue
+            if not isinstance(g, GridPlan):
+                raise ValueError("WorldTable.assign: a grid must be a synthetic.GridPlan")
+            if self.max_grid is None or g.ny > self.max_grid[0] or g.nx > self.max_grid[1]:
+                raise ValueError(f"WorldTable.assign: a grid of {g.ny} x {g.nx} cells, the table holds max_grid = {self.max_grid}")
         if np.any((rows < 0) | (rows >= self.n_worlds)) or len(np.unique(rows)) != len(rows):
             raise ValueError("WorldTable.assign: rows must be distinct rows of the table")
         for b in worlds:
@@ -293,16 +318,34 @@ class WorldTable:
                 raise ValueError("WorldTable.assign: boxes must be finite")
         if not len(rows):
             return
-        blob = np.full((len(rows), 4 * self.max_boxes + 2), np.nan)
-        for i, b in enumerate(worlds):
+        nb = 4 * self.max_boxes
+        ne = nw = 0                                  # doubles of a row's grid edges / of its bit rows (two words each)
+        if self.max_grid is not None:
+            ny, nx = self.max_grid
+            ne, nw = nx + ny + 2, (ny * self.grid_words + 1) // 2
+        blob = np.full((len(rows), nb + 4 + ne + nw), np.nan)
+        blob[:, nb + 2:] = 0.0
+        for i, (b, g) in enumerate(zip(worlds, grids)):
             blob[i, :4 * len(b)] = b.reshape(-1)
-            blob[i, -2:] = len(b), rows[i]
-        self.boxes[rows] = blob[:, :-2].reshape(len(rows), self.max_boxes, 4)
+            blob[i, nb:nb + 2] = len(b), rows[i]
+            if g is not None:
+                blob[i, nb + 2:nb + 4] = g.ny, g.nx
+                blob[i, nb + 4:nb + 4 + g.nx + 1] = g.xs
+                blob[i, nb + 4 + nx + 1:nb + 4 + nx + 1 + g.ny + 1] = g.ys
+                words = blob[i, nb + 4 + ne:].view(np.uint32)[:ny * self.grid_words].reshape(ny, self.grid_words)
+                words[:g.ny] = g.packed_rows(self.grid_words)
+            self.grids[rows[i]] = g
+        self.boxes[rows] = blob[:, :nb].reshape(len(rows), self.max_boxes, 4)
         self.counts[rows] = [len(b) for b in worlds]
         d_blob = torch.from_numpy(blob).to(self.device)
-        idx = d_blob[:, -1].long()
-        self.d_boxes.index_copy_(0, idx, d_blob[:, :-2].reshape(len(rows), self.max_boxes, 4))
-        self.d_counts.index_copy_(0, idx, d_blob[:, -2].to(torch.int32))
+        idx = d_blob[:, nb + 1].long()
+        self.d_boxes.index_copy_(0, idx, d_blob[:, :nb].reshape(len(rows), self.max_boxes, 4))
+        self.d_counts.index_copy_(0, idx, d_blob[:, nb].to(torch.int32))
+        if self.max_grid is not None:
+            self.d_grid_dims.index_copy_(0, idx, d_blob[:, nb + 2:nb + 4].to(torch.int32))
+            self.d_grid_edges.index_copy_(0, idx, d_blob[:, nb + 4:nb + 4 + ne])
+            bits = d_blob[:, nb + 4 + ne:].contiguous().view(torch.int32)[:, :ny * self.grid_words]
+            self.d_grid_bits.index_copy_(0, idx, bits.reshape(len(rows), ny, self.grid_words))
 
 
 class RoomsRenderer:
@@ -390,7 +433,8 @@ class RoomsRenderer:
                  min_depth=None, max_depth=None, out=None, rgb: bool = False, colours=None, palette=None, rgb_out=None):
         """What every ``cast_*`` method does (vlfm_worlds_raycast, one launch on the current stream): camera i stands in world
         ``world_of[i]`` of ``table``.  ``objects=None``: walls only; ``rgb``: the colour plane as well.  Returns (depth, ids,
-        stats, rgb), None for what was not asked for.  The camera records (x, y, cos, sin, height, fx, lo, hi) are built on the
+        stats, rgb), None for what was not asked for.  A table with ``max_grid`` brings its grid arrays (vlfm_worlds_raycast_grids:
+        the occupied cells of a world's grid are walls as well); with ``rgb`` that is refused.  The camera records (x, y, cos, sin, height, fx, lo, hi) are built on the
         host; they, the object records and the int32 lists (world_of, env_of, colours, palette) cross in ONE host buffer and one
         copy (all 8-byte aligned pieces).  ``who`` names the caller in error messages."""
         tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
@@ -402,6 +446,9 @@ class RoomsRenderer:
         if len(world_of) != n or np.any((world_of < 0) | (world_of >= table.n_worlds)):
             raise ValueError(f"{who}: world_of must name one world of the table per camera")
         ints = [world_of]
+        with_grids = table.max_grid is not None
+        if with_grids and rgb:
+            raise ValueError(f"{who}: a table with grids has no colour view (wall colours are defined by box and face)")
         if objects is None and rgb:                 # a world without objects: one row of empty slots, ids of zeros
             if env_of is not None or colours is not None:
                 raise ValueError(f"{who}: env_of and colours belong to objects")
@@ -456,12 +503,17 @@ class RoomsRenderer:
                 d_blob = torch.from_numpy(blob).to(dev)
                 p = d_blob.data_ptr()
                 p_ints = p + 8 * (rec.size + objects.size)          # world_of [n], env_of [n], colours, palette
-                _lib.check(_lib.lib().vlfm_worlds_raycast(
+                g_bits, g_edges, g_dims, g_ny, g_nx = None, None, None, 0, 0
+                if with_grids:
+                    g_bits, g_edges, g_dims = table.d_grid_bits.data_ptr(), table.d_grid_edges.data_ptr(), table.d_grid_dims.data_ptr()
+                    g_ny, g_nx = table.max_grid
+                _lib.check(_lib.lib().vlfm_worlds_raycast_grids(
                     p, n, table.d_boxes.data_ptr(), table.d_counts.data_ptr(), table.n_worlds, table.max_boxes, p_ints,
                     p + 8 * rec.size if with_objects else None, p_ints + 4 * n if with_objects else None, len(objects),
                     self.H, self.W, out.data_ptr(), ids.data_ptr() if with_objects else None, stats.data_ptr() if with_objects else None,
                     p_ints + 8 * n if rgb else None, p_ints + 8 * n + 4 * WORLD_MAX_OBJECTS * len(objects) if rgb else None,
-                    rgb_out.data_ptr() if rgb else None, torch.cuda.current_stream().cuda_stream), "worlds_raycast")
+                    rgb_out.data_ptr() if rgb else None, g_bits, g_edges, g_dims, g_nx, g_ny,
+                    torch.cuda.current_stream().cuda_stream), "worlds_raycast")
         return out, ids, stats, rgb_out
 
     def _rooms_world_of(self, tf) -> np.ndarray:
@@ -635,7 +687,7 @@ class BatchedEpisodes:
                  text_prompt: str = PROMPT, exploration_thresh: Optional[float] = None, closed_loop: bool = False,
                  controller=None, world_objects: Optional[WorldObjects] = None, batch_object_maps: bool = True,
                  device_object_clouds: bool = True, objectnav_metrics: bool = False,
-                 worlds: Optional[ProceduralWorlds] = None, render_rgb: bool = False) -> None:
+                 worlds: Optional[Union[ProceduralWorlds, GridWorlds]] = None, render_rgb: bool = False) -> None:
         # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
         # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -688,7 +740,9 @@ class BatchedEpisodes:
         # worlds: environment e lives in its OWN floor plan, worlds.world(env_ids[e], episode) -- its robot starts at that world's
         # start pose, its depth is ray-cast against that world's walls (RoomsRenderer.cast_worlds, still one launch per step), its
         # moves are refused by them, and with world_objects every episode end draws the NEXT world (layouts from the world's own
-        # spots, geodesics over its own walls); without world_objects it stays in episode 0's.  None: the one rooms world
+        # spots, geodesics over its own walls); without world_objects it stays in episode 0's.  None: the one rooms world.
+        # synthetic.GridWorlds: the worlds are occupancy grids (a top-down map someone already has) -- the same code, the world
+        # table carries the grids beside the boxes
         self.worlds = worlds
         if worlds is not None:
             if not self.closed_loop:
@@ -697,6 +751,13 @@ class BatchedEpisodes:
                 raise ValueError("worlds renders the robot's own camera: it cannot be combined with a camera rig")
             if sightings is not None:
                 raise ValueError("worlds cannot be combined with the scripted sightings, which are painted along the rooms tour")
+            # grid worlds (synthetic.GridWorlds: ``worlds.max_grid``): floor plans as occupancy grids, through the same code
+            if getattr(worlds, "max_grid", None) is not None:
+                if render_rgb:
+                    raise ValueError("grid worlds cannot be combined with render_rgb: wall colours are defined by box and face")
+                if objectnav_metrics:
+                    raise ValueError("grid worlds cannot be combined with objectnav_metrics: the geodesic fields hold at most "
+                                     "141 rectangles")
         # render_rgb: the step's RGB frames are the camera's view of the world the depth frame shows (RoomsRenderer.cast_worlds_rgb /
         # cast_cameras_rgb: depth, ids, stats and colours from ONE launch) instead of the pool's noise -- what the transport hop,
         # BLIP-2, the detector and the segmenter then see; they stay readable as ``last_rgb``.  Off: every step is the step it was
@@ -776,7 +837,8 @@ class BatchedEpisodes:
                 # where each robot's walls are: a row per environment with ``worlds``, else the renderer's one row for everybody
                 self.world_table, self.world_of = self.rooms.table, np.zeros(n_envs, np.int32)
                 if worlds is not None:
-                    self.world_table, self.world_of = WorldTable(n_envs, self.device), np.arange(n_envs, dtype=np.int32)
+                    self.world_table = WorldTable(n_envs, self.device, max_grid=getattr(worlds, "max_grid", None))
+                    self.world_of = np.arange(n_envs, dtype=np.int32)
                     self.world_episode = np.full(n_envs, -1, np.int64)      # the episode whose world each environment is in
                     if world_objects is None:
                         self._enter_worlds(range(n_envs), np.zeros(n_envs, np.int64))
@@ -1153,7 +1215,7 @@ class BatchedEpisodes:
         their robots stand at those worlds' start poses, nothing refused yet."""
         envs = list(envs)
         made = [self.worlds.world(self.env_ids[e], int(k)) for e, k in zip(envs, episodes)]
-        self.world_table.assign(envs, [w.boxes for w in made])
+        self.world_table.assign(envs, [w.boxes for w in made], [w.grid for w in made])
         for e, k, w in zip(envs, episodes, made):
             self._start_xy[e], self._start_k[e] = w.start_xy, w.start_k
             self.world_xy[e], self.world_k[e] = w.start_xy, w.start_k
@@ -1585,8 +1647,10 @@ class BatchedEpisodes:
         if self.world_objects is not None:
             acts = np.where(self.last_episode_end, ACTION_STOP, acts)     # an episode that ended: the robot stays where it is
             extra = np.where(self._objects[:, :, 6:7] != 0.0, self._objects[:, :, :4], np.nan)
+        grid_worlds = self.worlds is not None and self.world_table.max_grid is not None
         self.world_xy, self.world_k, self._collided = step_poses(self.world_xy, self.world_k, acts, extra,
-                                                                 None if self.worlds is None else self.world_table.boxes)
+                                                                 None if self.worlds is None else self.world_table.boxes,
+                                                                 self.world_table.grids if grid_worlds else None)
         st = self.closed_loop_stats
         fwd = acts == ACTION_FORWARD
         st["forward_steps"] += fwd

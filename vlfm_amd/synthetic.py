@@ -141,9 +141,10 @@ def _walls_of(boxes) -> np.ndarray:
     return BOXES if boxes is None else np.asarray(boxes, np.float64).reshape(-1, 4)
 
 
-def wall_profile(x: float, y: float, k: int, width: int = ROOMS_W, boxes=None) -> np.ndarray:
+def wall_profile(x: float, y: float, k: int, width: int = ROOMS_W, boxes=None, grid=None) -> np.ndarray:
     """(width,) f32 depth along the optical axis of the nearest box face per image column (inf where nothing is hit).
-    ``boxes`` [B,4]: the walls of the world (None: BOXES)."""
+    ``boxes`` [B,4]: the walls of the world (None: BOXES).  ``grid``: a GridPlan whose occupied cells are walls as well (the
+    f64 minimum of the two, then rounded; grid worlds section below)."""
     b = _walls_of(boxes)
     fx = camera_intrinsics(width)[0]
     c, s = HEADINGS[k]
@@ -157,7 +158,10 @@ def wall_profile(x: float, y: float, k: int, width: int = ROOMS_W, boxes=None) -
     tmin = np.maximum(np.minimum(tx0, tx1), np.minimum(ty0, ty1))
     tmax = np.minimum(np.maximum(tx0, tx1), np.maximum(ty0, ty1))
     hit = (tmax >= np.maximum(tmin, 0.0)) & (tmin > 0.0)
-    return np.where(hit, tmin, np.inf).min(axis=1, initial=np.inf).astype(np.float32)      # (initial: a world without boxes)
+    best = np.where(hit, tmin, np.inf).min(axis=1, initial=np.inf)                          # (initial: a world without boxes)
+    if grid is not None:
+        best = np.minimum(best, grid_profile_numpy(x, y, c, s, fx, width, grid))
+    return best.astype(np.float32)
 
 
 def depth_from_profile(wall: np.ndarray, height: int = ROOMS_H) -> np.ndarray:
@@ -174,9 +178,10 @@ def tf_of(x: float, y: float, k: int) -> np.ndarray:
     return np.array([[c, -s, 0.0, x], [s, c, 0.0, y], [0.0, 0.0, 1.0, CAMERA_HEIGHT], [0.0, 0.0, 0.0, 1.0]])
 
 
-def _blocked(x: float, y: float, margin: float = 0.3, boxes=None) -> bool:
+def _blocked(x: float, y: float, margin: float = 0.3, boxes=None, grid=None) -> bool:
     b = _walls_of(boxes)
-    return bool(np.any((b[:, 0] - margin <= x) & (x <= b[:, 2] + margin) & (b[:, 1] - margin <= y) & (y <= b[:, 3] + margin)))
+    hit = bool(np.any((b[:, 0] - margin <= x) & (x <= b[:, 2] + margin) & (b[:, 1] - margin <= y) & (y <= b[:, 3] + margin)))
+    return hit or (grid is not None and grid_blocked(grid, x, y, margin))
 
 
 def integrate(actions):
@@ -238,14 +243,15 @@ ACTION_STOP, ACTION_FORWARD, ACTION_TURN_LEFT, ACTION_TURN_RIGHT = 0, 1, 2, 3
 STEP_MARGIN = 0.2          # the clearance plan_actions asserts for every pose of the tour
 
 
-def step_poses(xy, k, actions, extra_boxes=None, boxes=None):
+def step_poses(xy, k, actions, extra_boxes=None, boxes=None, grids=None):
     """Apply one action per robot: ``xy`` [E,2] f64 positions, ``k`` [E] heading indices (multiples of 30 degrees),
     ``actions`` [E] action ids -> (xy, k, collided [E] bool), new arrays.  A turn changes k by +-1 mod 12; FORWARD adds
     0.25 * HEADINGS[k] (the expression of `integrate`) unless the new position lies within STEP_MARGIN of a box, in which case
     the move is refused (pose unchanged, ``collided`` set: no sliding along walls); STOP changes nothing.  ``extra_boxes``
     [E,K,4] f64: per robot up to K more boxes (x0, y0, x1, y1; a NaN row is "none") that refuse its moves like the walls do:
     the objects of its own environment (world objects section below).  ``boxes`` [E,B,4] f64: per robot the walls of ITS world
-    instead of the shared BOXES (a NaN row blocks nothing: the padding of a world table)."""
+    instead of the shared BOXES (a NaN row blocks nothing: the padding of a world table).  ``grids``: per robot a GridPlan or
+    None; its occupied cells refuse moves as boxes do (`grid_blocked`: only the cells near the new position are looked at)."""
     xy = np.array(xy, np.float64).reshape(-1, 2)
     k = np.array(k, np.int64).reshape(-1)
     a = np.asarray(actions).reshape(-1).astype(np.int64)
@@ -272,6 +278,12 @@ def step_poses(xy, k, actions, extra_boxes=None, boxes=None):
         # (every comparison with a NaN row is False: such a row blocks nothing)
         blocked = blocked | np.any((x[:, :, 0] - m <= new[:, None, 0]) & (new[:, None, 0] <= x[:, :, 2] + m) &
                                    (x[:, :, 1] - m <= new[:, None, 1]) & (new[:, None, 1] <= x[:, :, 3] + m), axis=1)
+    if grids is not None:
+        if len(grids) != len(xy):
+            raise ValueError("step_poses: grids must hold one plan or None per robot")
+        for e, g in enumerate(grids):
+            if g is not None and not blocked[e]:
+                blocked[e] = grid_blocked(g, new[e, 0], new[e, 1], m)
     forward = a == ACTION_FORWARD
     collided = forward & blocked
     xy[forward & ~blocked] = new[forward & ~blocked]
@@ -420,13 +432,14 @@ def _normalise(d, lo, hi):
     return np.clip((d - lo) / (hi - lo), 1e-3, 1.0).astype(np.float32)
 
 
-def render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6, boxes=None):
+def render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6, boxes=None, grid=None):
     """(depth f32 [H,W], ids u8 [H,W]) seen by ONE camera at (x, y), heading (c, s) = (cos, sin), ``height`` above the floor,
     focal length ``fx`` pixels, range [lo, hi]: the walls and the floor of `wall_profile` / `depth_from_profile`, and the
     objects ``boxes6`` [K,6] in front of them.  Per column u an object is hit at t = f64(f32(tmin)) of the walls' slab test
     and covers the rows rr = r - H//2 with ceil((height - z1) fx / t) <= rr <= floor((height - z0) fx / t); the pixel's depth
     is the f32 minimum of the normalised wall, floor and covering objects, its id is k + 1 of the nearest covering object
     (lowest k among equals) where that is STRICTLY nearer than wall and floor, else 0.  ``boxes`` [B,4]: the walls (None: BOXES).
+    ``grid``: a GridPlan whose occupied cells are walls as well (the f64 minimum of the two, then rounded to f32).
     Whole-array f64 NumPy."""
     boxes6 = np.asarray(boxes6, np.float64).reshape(-1, 6)
     m = -(np.arange(W, dtype=np.float64) - W // 2) / fx
@@ -442,7 +455,10 @@ def render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6, boxes=Non
         return np.where((tmax >= np.maximum(tmin, 0.0)) & (tmin > 0.0), tmin, np.inf)
 
     with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
-        wall = slab(_walls_of(boxes)).min(axis=1, initial=np.inf).astype(np.float32).astype(np.float64)
+        wall = slab(_walls_of(boxes)).min(axis=1, initial=np.inf)
+        if grid is not None:
+            wall = np.minimum(wall, grid_profile_numpy(x, y, c, s, fx, W, grid))
+        wall = wall.astype(np.float32).astype(np.float64)
         rr = (np.arange(H) - H // 2)[:, None]
         floor = np.where(rr > 0, (height * fx) / np.maximum(rr, 1), np.inf)
         bg = np.minimum(_normalise(wall, lo, hi)[None, :], _normalise(floor, lo, hi))              # [H,W] f32
@@ -802,6 +818,7 @@ class World(NamedTuple):
     start_k: int             # heading index into HEADINGS
     spots: np.ndarray        # [S,2] f64 object centres
     doors: np.ndarray        # [D,2] f64 doorway centres
+    grid: object = None      # a GridPlan whose occupied cells are walls as well (grid worlds section below), or None
 
 
 def rects_abut(a, b) -> np.ndarray:
@@ -920,17 +937,293 @@ class ProceduralWorlds:
     def layout(self, env_id: int, episode: int, robot_xy):
         """`object_layout` over the spots of ``world(env_id, episode)``: the target (class ``env_id mod 6``) and one distractor,
         both farther than OBJECT_START_CLEARANCE from the robot and more than 1.5 m apart."""
-        spots = [tuple(p) for p in self.world(env_id, episode).spots.tolist()]
-        classes = list(OBJECT_SIZES)
-        target = classes[env_id % len(classes)]
-        rx, ry = float(robot_xy[0]), float(robot_xy[1])
-        free = [p for p in spots if (p[0] - rx) ** 2 + (p[1] - ry) ** 2 > OBJECT_START_CLEARANCE ** 2]
-        a = free[_mix32(env_id, episode, 21) % len(free)]
-        apart = [p for p in free if (p[0] - a[0]) ** 2 + (p[1] - a[1]) ** 2 > 1.5 ** 2]
-        b = apart[_mix32(env_id, episode, 22) % len(apart)]
-        other = [c for c in classes if c != target]
-        distractor = other[_mix32(env_id, episode, 23) % len(other)]
-        return [(target, object_box(target, *a)), (distractor, object_box(distractor, *b))]
+        return _layout_over_spots(self.world(env_id, episode).spots, env_id, episode, robot_xy)
+
+
+def _layout_over_spots(spots, env_id: int, episode: int, robot_xy):
+    """The layout rule of the generated worlds (ProceduralWorlds.layout, GridWorlds.layout) over the object spots ``spots``."""
+    spots = [tuple(p) for p in np.asarray(spots, np.float64).reshape(-1, 2).tolist()]
+    classes = list(OBJECT_SIZES)
+    target = classes[env_id % len(classes)]
+    rx, ry = float(robot_xy[0]), float(robot_xy[1])
+    free = [p for p in spots if (p[0] - rx) ** 2 + (p[1] - ry) ** 2 > OBJECT_START_CLEARANCE ** 2]
+    a = free[_mix32(env_id, episode, 21) % len(free)]
+    apart = [p for p in free if (p[0] - a[0]) ** 2 + (p[1] - a[1]) ** 2 > 1.5 ** 2]
+    b = apart[_mix32(env_id, episode, 22) % len(apart)]
+    other = [c for c in classes if c != target]
+    distractor = other[_mix32(env_id, episode, 23) % len(other)]
+    return [(target, object_box(target, *a)), (distractor, object_box(distractor, *b))]
+
+
+# ---------------------------------------------------------------------------------------------- grid worlds
+# A floor plan as an occupancy grid: a top-down map someone already has (a scanned scene's occupancy export, an obstacle map
+# recorded by this package, a drawn PNG with diagonal walls and round pillars) instead of at most WORLD_MAX_BOXES boxes.
+#
+#   plan        occ bool [ny, nx], xs f64 [nx + 1], ys f64 [ny + 1] strictly increasing.  Cell (i, j) is the box
+#               (xs[i], ys[j], xs[i+1], ys[j+1]) and a full-height wall iff occ[j, i].
+#   definition  a grid world IS the box world of its occupied cells: depth, ids, stats and refused moves are what the box
+#               statements (`wall_profile`, `render_objects_numpy`, `step_poses`) give for boxes = grid_boxes(plan), with their
+#               rules: closed slabs, tmin > 0 (a cell around the camera is transparent), |dx| < 1e-12 -> 1e-12, STEP_MARGIN with
+#               closed comparisons.  With boxes AND a grid a column's wall is the f64 minimum of the two, rounded to f32 after.
+#   algorithm   `grid_profile_numpy`, and csrc/world_render.hip's grid_walk with the same bits: per column, with the slab test's
+#               own crossing times TX[e] = (xs[e] - x) / dx, TY[e] = (ys[e] - y) / dy (true divisions, nothing accumulated):
+#               the x slab at t = 0+ is the i with TX[i] <= 0 < TX[i+1] (dx > 0; mirrored for dx < 0; -1 or nx: the camera is
+#               outside), likewise in y; then repeatedly the smaller of the next x and the next y crossing is taken and the cell
+#               behind it entered -- occupied: the answer is that crossing time.  Equal crossing times: the answer is that time
+#               if any of (i+sx, j), (i, j+sy), (i+sx, j+sy) is occupied (all three have that tmin under the closed-slab rule),
+#               else the walk steps diagonally.  Cells outside the grid are free; the walk ends once an index is past the far
+#               side of its axis, after nx + ny + 2 steps at the most.
+# TX and TY are monotone in e (a rounded subtraction and a rounded division are monotone), which is all the walk relies on.
+GRID_MAX_CELLS = 1024
+GRID_MIN_SPACING = 1e-3
+GRID_MAX_EDGE = 1e4
+
+
+class GridPlan:
+    """An occupancy-grid floor plan: ``occ`` bool [ny,nx], ``xs`` f64 [nx+1], ``ys`` f64 [ny+1] (the rule above).  Refuses
+    nx or ny outside [1, GRID_MAX_CELLS], edges that do not increase strictly, a spacing below GRID_MIN_SPACING metres and
+    |edge| > GRID_MAX_EDGE.  The arrays are copies and read-only."""
+
+    def __init__(self, occ, xs, ys) -> None:
+        occ = np.array(occ)
+        if occ.ndim != 2 or occ.dtype.kind not in "biu":
+            raise ValueError("GridPlan: occ must be a [ny,nx] array of truth values")
+        occ = occ.astype(bool)
+        xs, ys = np.array(xs, np.float64).reshape(-1), np.array(ys, np.float64).reshape(-1)
+        ny, nx = occ.shape
+        if not (1 <= nx <= GRID_MAX_CELLS and 1 <= ny <= GRID_MAX_CELLS):
+            raise ValueError(f"GridPlan: nx and ny must lie in [1, {GRID_MAX_CELLS}]")
+        if len(xs) != nx + 1 or len(ys) != ny + 1:
+            raise ValueError("GridPlan: xs must hold nx + 1 edges and ys ny + 1")
+        for e in (xs, ys):
+            if not np.all(np.isfinite(e)) or np.any(np.abs(e) > GRID_MAX_EDGE):
+                raise ValueError(f"GridPlan: edges must be finite and within +-{GRID_MAX_EDGE:g} m")
+            if not np.all(np.diff(e) > 0.0):
+                raise ValueError("GridPlan: edges must increase strictly")
+            if np.any(np.diff(e) < GRID_MIN_SPACING):
+                raise ValueError(f"GridPlan: cells must be at least {GRID_MIN_SPACING:g} m wide")
+        for a in (occ, xs, ys):
+            a.setflags(write=False)
+        self.occ, self.xs, self.ys = occ, xs, ys
+
+    @property
+    def nx(self) -> int:
+        return self.occ.shape[1]
+
+    @property
+    def ny(self) -> int:
+        return self.occ.shape[0]
+
+    def packed_rows(self, words: int = None) -> np.ndarray:
+        """uint32 [ny, words]: bit i % 32 of word i // 32 of row j is occ[j, i] (words >= ceil(nx / 32), the rest zero)."""
+        need = (self.nx + 31) // 32
+        words = need if words is None else int(words)
+        if words < need:
+            raise ValueError("GridPlan.packed_rows: too few words for a row")
+        bits = np.zeros((self.ny, words * 32), np.uint8)
+        bits[:, :self.nx] = self.occ
+        return np.packbits(bits, axis=1, bitorder="little").view("<u4").astype(np.uint32).reshape(self.ny, words)
+
+    @classmethod
+    def uniform(cls, occ, cells_per_metre: int, i0: int, j0: int) -> "GridPlan":
+        """Square cells on the lattice of 1 / ``cells_per_metre`` m: edge e of x is (i0 + e) / cells_per_metre -- ONE division,
+        the procedural generator's own values -- and likewise (j0 + e) / cells_per_metre in y."""
+        occ = np.asarray(occ)
+        n = int(cells_per_metre)
+        if n != cells_per_metre or n < 1 or int(i0) != i0 or int(j0) != j0 or occ.ndim != 2:
+            raise ValueError("GridPlan.uniform: cells_per_metre >= 1, i0 and j0 must be integers, occ [ny,nx]")
+        ny, nx = occ.shape
+        return cls(occ, (int(i0) + np.arange(nx + 1, dtype=np.float64)) / float(n),
+                   (int(j0) + np.arange(ny + 1, dtype=np.float64)) / float(n))
+
+    @classmethod
+    def from_boxes(cls, boxes, cells_per_metre: int = 20) -> "GridPlan":
+        """The boxes ``boxes`` [B,4] rasterised on the lattice of 1 / ``cells_per_metre`` m over their bounding box.  Refuses
+        boxes whose edges are not lattice values (k / cells_per_metre, the same double)."""
+        b = np.asarray(boxes, np.float64).reshape(-1, 4)
+        n = int(cells_per_metre)
+        if n != cells_per_metre or n < 1 or not len(b) or not np.all(np.isfinite(b)):
+            raise ValueError("GridPlan.from_boxes: cells_per_metre >= 1 and at least one finite box")
+        k = np.rint(b * n)
+        if not np.array_equal(k / float(n), b) or np.any(k[:, 2] <= k[:, 0]) or np.any(k[:, 3] <= k[:, 1]):
+            raise ValueError(f"GridPlan.from_boxes: every box edge must be a multiple of 1/{n} m and x0 < x1, y0 < y1")
+        k = k.astype(np.int64)
+        i0, j0, i1, j1 = k[:, 0].min(), k[:, 1].min(), k[:, 2].max(), k[:, 3].max()
+        if i1 - i0 > GRID_MAX_CELLS or j1 - j0 > GRID_MAX_CELLS:
+            raise ValueError(f"GridPlan.from_boxes: the boxes span more than {GRID_MAX_CELLS} cells")
+        occ = np.zeros((j1 - j0, i1 - i0), bool)
+        for (a0, c0, a1, c1) in k.tolist():
+            occ[c0 - j0:c1 - j0, a0 - i0:a1 - i0] = True
+        return cls.uniform(occ, n, int(i0), int(j0))
+
+    @classmethod
+    def from_image(cls, array_or_path, cells_per_metre: int, i0: int, j0: int, occupied_below: int = 128) -> "GridPlan":
+        """A greyscale picture of the plan seen from above: a uint8 [rows, columns] array, or a file Pillow opens (converted to
+        greyscale).  A pixel darker than ``occupied_below`` is a wall; image row 0 is the HIGHEST y."""
+        if isinstance(array_or_path, np.ndarray):
+            img = array_or_path
+        else:
+            from PIL import Image
+
+            with Image.open(array_or_path) as im:
+                img = np.array(im.convert("L"))
+        if img.ndim != 2 or img.dtype != np.uint8:
+            raise ValueError("GridPlan.from_image: a uint8 [rows, columns] array or an image file")
+        return cls.uniform(img[::-1] < int(occupied_below), cells_per_metre, i0, j0)
+
+
+def grid_boxes(plan: GridPlan) -> np.ndarray:
+    """[K,4] f64: the boxes (xs[i], ys[j], xs[i+1], ys[j+1]) of the occupied cells, rows first -- the definition of a grid world."""
+    j, i = np.nonzero(plan.occ)
+    return np.stack([plan.xs[i], plan.ys[j], plan.xs[i + 1], plan.ys[j + 1]], axis=1).reshape(-1, 4)
+
+
+def _grid_first_slab(edges, p, d) -> np.ndarray:
+    """int64 [W]: per column the slab of one axis at t = 0+: the i with T[i] <= 0 < T[i+1] for d > 0 (T[i+1] <= 0 < T[i] for
+    d < 0), T[e] = (edges[e] - p) / d; -1 or len(edges) - 1 outside."""
+    T = (edges[None, :] - p) / d[:, None]
+    return np.where(d > 0.0, (T <= 0.0).sum(axis=1), (T > 0.0).sum(axis=1)) - 1
+
+
+def grid_profile_numpy(x, y, c, s, fx, W: int, plan: GridPlan, return_steps: bool = False):
+    """f64 [W]: per image column the ray parameter at which the ray of `wall_profile` enters the first occupied cell of
+    ``plan`` (inf: none) -- the grid walk of the rule above, vectorised over columns; bit for bit
+    min over grid_boxes(plan) of the slab test's tmin BEFORE the rounding to f32.  ``return_steps``: also int64 [W], the cells
+    each column's walk entered."""
+    m = -(np.arange(W, dtype=np.float64) - W // 2) / fx
+    dx, dy = c - s * m, s + c * m
+    dx = np.where(np.abs(dx) < 1e-12, 1e-12, dx)
+    dy = np.where(np.abs(dy) < 1e-12, 1e-12, dy)
+    nx, ny, xs, ys = plan.nx, plan.ny, plan.xs, plan.ys
+    occ = np.zeros((ny + 2, nx + 2), bool)              # a free ring around the grid: cell (i, j) is occ[j + 1, i + 1]
+    occ[1:-1, 1:-1] = plan.occ
+    sx, sy = np.where(dx > 0.0, 1, -1), np.where(dy > 0.0, 1, -1)
+    i, j = _grid_first_slab(xs, x, dx), _grid_first_slab(ys, y, dy)
+    out = np.full(W, np.inf)
+    steps = np.zeros(W, np.int64)
+    live = np.ones(W, bool)
+
+    def at(ii, jj):         # occupancy of the cells (ii, jj), free outside [-1, nx] x [-1, ny]
+        inside = (ii >= -1) & (ii <= nx) & (jj >= -1) & (jj <= ny)
+        return inside & occ[np.clip(jj, -1, ny) + 1, np.clip(ii, -1, nx) + 1]
+
+    for _ in range(nx + ny + 2):
+        ex, ey = i + (sx > 0), j + (sy > 0)              # the next edge of each axis
+        live &= (ex >= 0) & (ex <= nx) & (ey >= 0) & (ey <= ny)      # past the far side of an axis: nothing more to enter
+        if not live.any():
+            break
+        tx = (xs[np.clip(ex, 0, nx)] - x) / dx
+        ty = (ys[np.clip(ey, 0, ny)] - y) / dy
+        gx, gy = live & (tx <= ty), live & (ty <= tx)    # which axes cross next; both: a corner
+        tie = gx & gy
+        i2, j2 = np.where(gx, i + sx, i), np.where(gy, j + sy, j)
+        hit = live & (at(i2, j2) | (tie & (at(i + sx, j) | at(i, j + sy))))
+        out[hit] = np.where(gx, tx, ty)[hit]
+        steps += live
+        live &= ~hit
+        i, j = i2, j2
+    return (out, steps) if return_steps else out
+
+
+def grid_blocked(plan: GridPlan, x: float, y: float, margin: float = STEP_MARGIN) -> bool:
+    """`_blocked` / `step_poses`' test against the occupied cells of ``plan``: is there an occupied cell (i, j) with
+    xs[i] - m <= x <= xs[i+1] + m and ys[j] - m <= y <= ys[j+1] + m (the box rule's own comparisons on the cell's edges).  Only
+    the cells near (x, y) are looked at: edge - m and edge + m are monotone in the edge, so the cells that pass each comparison
+    are a run of indices."""
+    m = float(margin)
+    i0, i1 = np.searchsorted(plan.xs[1:] + m, x, side="left"), np.searchsorted(plan.xs[:-1] - m, x, side="right")
+    j0, j1 = np.searchsorted(plan.ys[1:] + m, y, side="left"), np.searchsorted(plan.ys[:-1] - m, y, side="right")
+    return bool(i0 < i1 and j0 < j1 and plan.occ[j0:j1, i0:i1].any())
+
+
+def grid_spots(plan: GridPlan, clearance: float = 0.65, step: float = 0.25, start=None) -> np.ndarray:
+    """[S,2] f64: the lattice points (step * a, step * b) inside the plan's extent that keep ``clearance`` to every occupied
+    cell (`rect_distance` >= clearance), ordered by (a, b), restricted to those a 4-connected flood fill over the lattice points
+    that the STEP_MARGIN-inflated grid does not block (`grid_blocked`) reaches from ``start`` (a lattice point; None: the first
+    clear point in that order)."""
+    a = np.arange(int(np.ceil(plan.xs[0] / step)), int(np.floor(plan.xs[-1] / step)) + 1)
+    b = np.arange(int(np.ceil(plan.ys[0] / step)), int(np.floor(plan.ys[-1] / step)) + 1)
+    free = np.zeros((len(a), len(b)), bool)
+    clear = np.zeros((len(a), len(b)), bool)
+    boxes = grid_boxes(plan)
+    for p, ia in enumerate(a):
+        px = step * float(ia)
+        for q, ib in enumerate(b):
+            py = step * float(ib)
+            free[p, q] = not grid_blocked(plan, px, py, STEP_MARGIN)
+            if free[p, q] and not grid_blocked(plan, px, py, clearance):     # (no cell within the square: the disc is inside it)
+                clear[p, q] = True
+            elif free[p, q] and len(boxes):
+                i0, i1 = np.searchsorted(plan.xs[1:] + clearance, px, side="left"), np.searchsorted(plan.xs[:-1] - clearance, px, side="right")
+                j0, j1 = np.searchsorted(plan.ys[1:] + clearance, py, side="left"), np.searchsorted(plan.ys[:-1] - clearance, py, side="right")
+                jj, ii = np.nonzero(plan.occ[j0:j1, i0:i1])
+                ddx = np.maximum(np.maximum(plan.xs[i0 + ii] - px, 0.0), px - plan.xs[i0 + ii + 1])
+                ddy = np.maximum(np.maximum(plan.ys[j0 + jj] - py, 0.0), py - plan.ys[j0 + jj + 1])
+                clear[p, q] = bool(np.all(ddx * ddx + ddy * ddy >= clearance * clearance))
+    if not clear.any():
+        return np.zeros((0, 2))
+    if start is None:
+        p0, q0 = (int(v) for v in np.argwhere(clear)[0])
+    else:
+        p0, q0 = int(round(float(start[0]) / step)) - int(a[0]), int(round(float(start[1]) / step)) - int(b[0])
+        if not (0 <= p0 < len(a) and 0 <= q0 < len(b)) or step * float(a[p0]) != float(start[0]) or step * float(b[q0]) != float(start[1]):
+            raise ValueError("grid_spots: start must be a lattice point inside the plan")
+    seen = np.zeros_like(free)
+    if free[p0, q0]:
+        seen[p0, q0] = True
+        todo = [(p0, q0)]
+        while todo:
+            p, q = todo.pop()
+            for (u, v) in ((p + 1, q), (p - 1, q), (p, q + 1), (p, q - 1)):
+                if 0 <= u < len(a) and 0 <= v < len(b) and free[u, v] and not seen[u, v]:
+                    seen[u, v] = True
+                    todo.append((u, v))
+    pq = np.argwhere(clear & seen)
+    return np.stack([step * a[pq[:, 0]].astype(np.float64), step * b[pq[:, 1]].astype(np.float64)], axis=1).reshape(-1, 2)
+
+
+class GridWorlds:
+    """``worlds.world(env_id, episode)`` over a list of GridPlans: a pure function of (seed, env_id, episode) through `_mix32` --
+    the plan, and a hashed start among the plan's spots with a hashed heading unless ``starts`` gives one (x, y, k) per plan.
+    ``spots``: per plan the object spots [S,2] (None: `grid_spots(plan)`).  The World has no boxes; its ``grid`` is the plan.
+    ``layout`` is ProceduralWorlds.layout's rule over the plan's spots.  ``max_grid`` = (ny, nx): what a WorldTable must hold."""
+
+    def __init__(self, plans, starts=None, spots=None, seed: int = 0) -> None:
+        self.plans = list(plans)
+        if not self.plans or not all(isinstance(p, GridPlan) for p in self.plans):
+            raise ValueError("GridWorlds: a non-empty list of GridPlans")
+        if (starts is not None and len(starts) != len(self.plans)) or (spots is not None and len(spots) != len(self.plans)):
+            raise ValueError("GridWorlds: one start and one list of spots per plan")
+        self.seed = int(seed)
+        self.starts = None if starts is None else [(float(x), float(y), int(k) % 12) for (x, y, k) in starts]
+        self._spots = [None] * len(self.plans) if spots is None else [np.array(s, np.float64).reshape(-1, 2) for s in spots]
+        self.max_grid = (max(p.ny for p in self.plans), max(p.nx for p in self.plans))
+
+    def spots(self, n: int) -> np.ndarray:
+        if self._spots[n] is None:
+            self._spots[n] = grid_spots(self.plans[n])
+        self._spots[n].setflags(write=False)
+        return self._spots[n]
+
+    def plan_of(self, env_id: int, episode: int) -> int:
+        return _mix32(_mix32(self.seed, int(env_id), 111), int(episode), 112) % len(self.plans)
+
+    def world(self, env_id: int, episode: int) -> World:
+        n = self.plan_of(env_id, episode)
+        base = _mix32(_mix32(self.seed, int(env_id), 113), int(episode), 114)
+        spots = self.spots(n)
+        if self.starts is not None:
+            x, y, k = self.starts[n]
+        else:
+            if not len(spots):
+                raise ValueError("GridWorlds: a plan without a spot needs a start")
+            (x, y), k = spots[_mix32(base, 0, 115) % len(spots)], _mix32(base, 1, 115) % 12
+        start = np.array([x, y], np.float64)
+        start.setflags(write=False)
+        return World(np.zeros((0, 4)), start, int(k), spots, np.zeros((0, 2)), self.plans[n])
+
+    def layout(self, env_id: int, episode: int, robot_xy):
+        return _layout_over_spots(self.world(env_id, episode).spots, env_id, episode, robot_xy)
 
 
 # ---------------------------------------------------------------------------------------------- map planner
