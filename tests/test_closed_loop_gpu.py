@@ -52,14 +52,14 @@ def test_replay_of_the_plan_equals_the_open_loop_step(gpu_device):
         opened.step()
         torch.cuda.synchronize()
         assert np.array_equal(closed.last_poses, opened.pose_table[t]), t           # x, y, yaw with ==
-        assert _equal(closed._live_frames, opened.rooms.frame(t)), t
+        assert _equal(closed.live.frames, opened.rooms.frame(t)), t
         fc, fo = closed.obstacles.frontiers_px(), opened.obstacles.frontiers_px()
         assert len(fc) == len(fo) and all(np.array_equal(x, y) for x, y in zip(fc, fo)), t
         assert np.array_equal(closed.last_goals, opened.last_goals, equal_nan=True) and closed.last_modes == opened.last_modes, t
         assert np.array_equal(closed.last_rho_theta, opened.last_rho_theta, equal_nan=True), t
     _maps_equal(closed, opened)
     closed.check()
-    st = closed.closed_loop_stats
+    st = closed.live.stats
     assert not st["collisions"].any() and (st["forward_steps"] + st["turn_steps"] + st["stops"] == steps).all()
 
 
@@ -96,7 +96,7 @@ def _bang_bang_run(device, steps=60, E=4):
         actions.append(sim.last_world_actions.copy())
         if t in (0, 25, steps - 1):
             torch.cuda.synchronize()
-            frames[t] = sim._live_frames[0].cpu().numpy()
+            frames[t] = sim.live.frames[0].cpu().numpy()
     torch.cuda.synchronize()
     sim.check()
     return sim, np.stack(poses), np.stack(actions), frames
@@ -121,12 +121,12 @@ def test_bang_bang_run_is_consistent(bang_bang):
         heading[t] = int(k[0])
         xy, k, hit = S.step_poses(xy, k, actions[t])
         refused += hit
-    assert np.array_equal(sim.world_xy, xy) and np.array_equal(sim.world_k, k)
+    assert np.array_equal(sim.live.xy, xy) and np.array_equal(sim.live.k, k)
     # what environment 0 saw at three steps is the NumPy renderer's frame at its recorded pose
     for t, got in frames.items():
         want = S.depth_from_profile(S.wall_profile(poses[t, 0, 0], poses[t, 0, 1], heading[t], sim.W), sim.H)
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), t
-    st = sim.closed_loop_stats
+    st = sim.live.stats
     forward = (actions == ACTION_FORWARD).sum(axis=0)
     turns = ((actions == ACTION_TURN_LEFT) | (actions == ACTION_TURN_RIGHT)).sum(axis=0)
     assert np.array_equal(st["forward_steps"], forward) and np.array_equal(st["turn_steps"], turns)
@@ -153,7 +153,7 @@ def test_episode_wrap_returns_to_the_start_pose(gpu_device):
     start = sim.pose_table[0].copy()
     for _ in range(L):
         sim.step()
-    assert (sim.closed_loop_stats["turn_steps"] >= 12).all()
+    assert (sim.live.stats["turn_steps"] >= 12).all()
     sim.step()                                                       # step 20: the wrap
     fresh.step()
     torch.cuda.synchronize()
@@ -164,5 +164,5 @@ def test_episode_wrap_returns_to_the_start_pose(gpu_device):
     for name in ("obstacle_bits", "navigable_bits", "explored_bits"):
         assert _equal(getattr(sim.obstacles, name), getattr(fresh.obstacles, name)), name
     assert _equal(sim.values.conf, fresh.values.conf)
-    assert (sim.closed_loop_stats["forward_steps"] + sim.closed_loop_stats["turn_steps"] + sim.closed_loop_stats["stops"]
+    assert (sim.live.stats["forward_steps"] + sim.live.stats["turn_steps"] + sim.live.stats["stops"]
             == L + 1).all()                                          # the statistics run on across episodes

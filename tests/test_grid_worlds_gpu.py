@@ -306,8 +306,8 @@ def _harness(device, **kw):
 
 
 def _clear(h, e):
-    x, y = h.world_xy[e]
-    plan = h.world_table.grids[e]
+    x, y = h.live.xy[e]
+    plan = h.live.table.grids[e]
     return plan is not None and not S.grid_blocked(plan, x, y, S.STEP_MARGIN) and \
         not S._blocked(x, y, S.STEP_MARGIN, boxes=S.grid_boxes(plan))
 
@@ -318,41 +318,41 @@ def test_harness_in_grid_worlds(gpu_device):
     a, b = _harness(gpu_device), _harness(gpu_device)
     worlds = S.GridWorlds(_two_plans(), seed=3)
     fx = S.camera_intrinsics(a.W)[0]
-    assert a.world_episode.tolist() == [0] * E and a.world_table.max_grid == (100, 120)
+    assert a.live.world_episode.tolist() == [0] * E and a.live.table.max_grid == (100, 120)
     for e in range(E):
         w = worlds.world(a.env_ids[e], 0)
-        assert a.world_table.grids[e] is not None and np.array_equal(a.world_table.grids[e].occ, w.grid.occ)
-        assert len(a.world_table.world(e)) == 0 and np.array_equal(a.world_xy[e], w.start_xy) and a.world_k[e] == w.start_k
+        assert a.live.table.grids[e] is not None and np.array_equal(a.live.table.grids[e].occ, w.grid.occ)
+        assert len(a.live.table.world(e)) == 0 and np.array_equal(a.live.xy[e], w.start_xy) and a.live.k[e] == w.start_k
     moved, lived_in = 0, set()
     for t in range(STEPS):
-        before = [(a.world_xy[e].copy(), int(a.world_k[e]), a.world_table.grids[e], a._objects[e].copy(), int(a.world_episode[e]))
+        before = [(a.live.xy[e].copy(), int(a.live.k[e]), a.live.table.grids[e], a.live.objects[e].copy(), int(a.live.world_episode[e]))
                   for e in range(E)]
         lived_in |= {_two_plans().index(x[2]) for x in before}
         a.step()
         b.step()
         assert np.array_equal(a.last_poses, b.last_poses) and np.array_equal(a.last_world_actions, b.last_world_actions)
-        assert np.array_equal(a.world_xy, b.world_xy) and np.array_equal(a.world_k, b.world_k)
+        assert np.array_equal(a.live.xy, b.live.xy) and np.array_equal(a.live.k, b.live.k)
         if t in (0, 7, 29):
             torch.cuda.synchronize()
-            assert np.array_equal(_bits(a._live_frames), _bits(b._live_frames))
+            assert np.array_equal(_bits(a.live.frames), _bits(b.live.frames))
             for e in (0, 3):
                 (x, y), k, plan, objs, _ = before[e]
                 c, s = S.HEADINGS[k]
                 want = S.render_objects_numpy(x, y, c, s, S.CAMERA_HEIGHT, fx, S.MIN_DEPTH, S.MAX_DEPTH, a.H, a.W,
                                               objs[objs[:, 6] != 0.0, :6], boxes=NONE, grid=plan)
-                assert np.array_equal(_bits(a._live_frames[e]), want[0].view(np.int32)), (t, e)
-                assert np.array_equal(a._live_ids[e].cpu().numpy(), want[1]), (t, e)
+                assert np.array_equal(_bits(a.live.frames[e]), want[0].view(np.int32)), (t, e)
+                assert np.array_equal(a.live.ids[e].cpu().numpy(), want[1]), (t, e)
         for e in range(E):
             assert _clear(a, e), (t, e)
-            if a.world_episode[e] != before[e][4]:              # the episode ended: the NEXT world, from its start
+            if a.live.world_episode[e] != before[e][4]:              # the episode ended: the NEXT world, from its start
                 moved += 1
                 w = worlds.world(a.env_ids[e], before[e][4] + 1)
-                assert a.world_episode[e] == before[e][4] + 1 == a._ep_index[e] and a.last_episode_end[e]
-                assert a.world_table.grids[e] is w.grid or np.array_equal(a.world_table.grids[e].occ, w.grid.occ)
-                assert np.array_equal(a.world_xy[e], w.start_xy) and a.world_k[e] == w.start_k and not a._collided[e]
+                assert a.live.world_episode[e] == before[e][4] + 1 == a.live.ep_index[e] and a.last_episode_end[e]
+                assert a.live.table.grids[e] is w.grid or np.array_equal(a.live.table.grids[e].occ, w.grid.occ)
+                assert np.array_equal(a.live.xy[e], w.start_xy) and a.live.k[e] == w.start_k and not a.live.collided[e]
     assert moved >= 2 * E and lived_in == {0, 1}                # 30 steps, episodes of 12 at the most; both plans
-    np.testing.assert_equal(a.closed_loop_stats, b.closed_loop_stats)
-    np.testing.assert_equal(a.objectnav_stats, b.objectnav_stats)
+    np.testing.assert_equal(a.live.stats, b.live.stats)
+    np.testing.assert_equal(a.live.objectnav_stats, b.live.objectnav_stats)
 
 
 def test_harness_with_the_map_planner(gpu_device):
@@ -363,4 +363,4 @@ def test_harness_with_the_map_planner(gpu_device):
             assert _clear(h, e), (t, e)
     ps = h.planner_stats
     assert np.array_equal(ps["plans"], ps["ok"] + ps["unreachable"] + ps["too_long"] + ps["invalid"])
-    assert len(h.objectnav_stats["episode_outcome"]) >= 2 * E
+    assert len(h.live.objectnav_stats["episode_outcome"]) >= 2 * E

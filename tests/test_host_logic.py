@@ -105,6 +105,7 @@ def test_harness_decide_and_navigate_are_the_scalar_rules_vectorised():
     h = H()
     h.E, h.targets, h.device, h.stop_radius = 4, ["chair", "bed", "tv", "couch"], torch.device("cpu"), 0.9
     h.sightings = None                                     # no episode script: every environment is on the harness clock
+    h.live, h.closed_loop, h.exploration_thresh, h.device_object_clouds = None, False, None, False   # open loop, single prompt
     h._episode_steps = lambda t_ep: BatchedEpisodes._episode_steps(h, t_ep)
     h.selectors = [FrontierSelector() for _ in range(4)]
     h.object_maps = [FakeObjectMap(None), FakeObjectMap(None), FakeObjectMap(None), FakeObjectMap([4.5, 4.0, 0.3])]

@@ -420,7 +420,7 @@ def test_harness_with_the_map_planner(gpu_device):
     assert np.array_equal(ps["plans"], (status >= 0).sum(axis=0)) and ps["plans"].sum() > 0
     assert np.array_equal(ps["ok"], (status == PLAN_OK).sum(axis=0)) and ps["ok"].sum() > 0
     assert np.array_equal(ps["plans"], ps["ok"] + ps["unreachable"] + ps["too_long"] + ps["invalid"])
-    assert set(sim.closed_loop_stats) == {"path_length", "collisions", "forward_steps", "turn_steps", "stops"}
+    assert set(sim.live.stats) == {"path_length", "collisions", "forward_steps", "turn_steps", "stops"}
     # every plan, recomputed on the host from the bits of its step.  The full search for the last call; for the
     # others the search is bounded by the reported cost, which leaves a PLAN_OK result as it is (and turns a cost that is too
     # small into PLAN_TOO_LONG)

@@ -266,6 +266,7 @@ def test_episode_log_applies_the_rule_per_environment(tmp_path, monkeypatch):
 
     h = H()
     h.E, h.C, h.exploration_thresh, h.obstacles = 3, 2, 0.4, None
+    h.live, h.closed_loop, h.device_object_clouds = None, False, True
     h.env_ids, h.targets, h.episodes_done, h.episode_len, h.t = [0, 1, 2], ["chair", "bed", "tv"], 0, 5, 5
     h.pose_table = np.zeros((5, 3, 3))
     h.last_frontier_values = np.array([[0.30, 0.20], [0.35, 0.10], [0.50, 0.90], [0.10, 0.95]])

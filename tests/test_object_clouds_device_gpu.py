@@ -503,6 +503,6 @@ def test_harness_device_clouds_equal_host_clouds(gpu_device):
     assert a.object_stats.keys() == b.object_stats.keys()
     for key in a.object_stats:
         assert np.array_equal(np.asarray(a.object_stats[key]), np.asarray(b.object_stats[key])), key
-    assert a.objectnav_stats.keys() == b.objectnav_stats.keys()
-    for key in a.objectnav_stats:
-        assert np.array_equal(np.asarray(a.objectnav_stats[key]), np.asarray(b.objectnav_stats[key])), key
+    assert a.live.objectnav_stats.keys() == b.live.objectnav_stats.keys()
+    for key in a.live.objectnav_stats:
+        assert np.array_equal(np.asarray(a.live.objectnav_stats[key]), np.asarray(b.live.objectnav_stats[key])), key

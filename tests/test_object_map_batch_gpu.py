@@ -313,14 +313,14 @@ def test_harness_batched_equals_one_by_one(gpu_device):
     torch.cuda.synchronize()
     a, b = sims
     assert together >= 1                                          # a step with detections in two or more environments
-    assert int(a.objectnav_stats["episodes"].sum()) >= 1          # an episode ended
+    assert int(a.live.objectnav_stats["episodes"].sum()) >= 1          # an episode ended
     assert a.object_stats["cloud_updates"] > 0
     assert a.object_stats.keys() == b.object_stats.keys()
     for key in a.object_stats:
         assert np.array_equal(np.asarray(a.object_stats[key]), np.asarray(b.object_stats[key])), key
-    assert a.objectnav_stats.keys() == b.objectnav_stats.keys()
-    for key in a.objectnav_stats:
-        assert np.array_equal(np.asarray(a.objectnav_stats[key]), np.asarray(b.objectnav_stats[key])), key
+    assert a.live.objectnav_stats.keys() == b.live.objectnav_stats.keys()
+    for key in a.live.objectnav_stats:
+        assert np.array_equal(np.asarray(a.live.objectnav_stats[key]), np.asarray(b.live.objectnav_stats[key])), key
 
 
 # ---------------------------------------------------------------------------------------------- 5. launches and read-backs

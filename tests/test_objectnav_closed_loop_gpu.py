@@ -52,19 +52,19 @@ def test_without_objects_it_is_the_closed_loop_step(gpu_device):
         with_objects.step()
         plain.step()
         torch.cuda.synchronize()
-        assert _equal(with_objects._live_frames, plain._live_frames), t
-        assert not bool(with_objects._live_ids.any()), t
+        assert _equal(with_objects.live.frames, plain.live.frames), t
+        assert not bool(with_objects.live.ids.any()), t
         fa, fb = with_objects.obstacles.frontiers_px(), plain.obstacles.frontiers_px()
         assert len(fa) == len(fb) and all(np.array_equal(x, y) for x, y in zip(fa, fb)), t
         assert np.array_equal(with_objects.last_goals, plain.last_goals, equal_nan=True), t
         assert with_objects.last_modes == plain.last_modes, t
         assert np.array_equal(with_objects.last_poses, plain.last_poses), t
         assert np.array_equal(with_objects.last_world_actions, plain.last_world_actions), t
-    assert np.array_equal(with_objects.world_xy, plain.world_xy) and np.array_equal(with_objects.world_k, plain.world_k)
+    assert np.array_equal(with_objects.live.xy, plain.live.xy) and np.array_equal(with_objects.live.k, plain.live.k)
     for name in ("obstacle_bits", "navigable_bits", "explored_bits"):
         assert _equal(getattr(with_objects.obstacles, name), getattr(plain.obstacles, name)), name
     assert _equal(with_objects.values.conf, plain.values.conf) and _equal(with_objects.values.value, plain.values.value)
-    assert not with_objects.objectnav_stats["episodes"].any() and (with_objects._ep_clock == 30).all()
+    assert not with_objects.live.objectnav_stats["episodes"].any() and (with_objects.live.ep_clock == 30).all()
 
 
 def test_target_in_line_of_sight_is_found_and_reached(gpu_device):
@@ -75,9 +75,9 @@ def test_target_in_line_of_sight_is_found_and_reached(gpu_device):
 
     E, cap = 2, 100
     sim = _sim(gpu_device, E, layout=_first_episode({0: [("chair", A)]}), wo=dict(max_episode_steps=cap), object_maps=True)
-    assert sim.targets[0] == "chair" and sim.world_xy[0].tolist() == [0.0, 0.0] and sim.world_k[0] == 0
+    assert sim.targets[0] == "chair" and sim.live.xy[0].tolist() == [0.0, 0.0] and sim.live.k[0] == 0
     modes, goals = [], []
-    st = sim.objectnav_stats
+    st = sim.live.objectnav_stats
     while st["episodes"][0] == 0 and len(modes) < cap + 1:
         sim.step()
         modes.append(sim.last_modes[0])
@@ -86,24 +86,24 @@ def test_target_in_line_of_sight_is_found_and_reached(gpu_device):
             assert sim.object_maps[0].has_object("chair")
     torch.cuda.synchronize()
     print("steps of the episode:", st["episode_steps"], "outcome:", st["episode_outcome"], "first sighting:",
-          st["episode_first_sighting"], "robot:", sim.world_xy[0], "goal at step 12:", goals[12] if len(goals) > 12 else None)
+          st["episode_first_sighting"], "robot:", sim.live.xy[0], "goal at step 12:", goals[12] if len(goals) > 12 else None)
     assert modes[:12] == ["initialize"] * 12 and modes[12] == "navigate"
     assert S.rect_distance(goals[12], A) <= 0.1
     assert st["episodes"][0] == 1 and st["successes"][0] == 1 and st["episode_outcome"][0] == "success"
     assert st["episode_env"][0] == 0 and st["episode_steps"][0] == len(modes) <= cap
     assert 0 <= st["episode_first_sighting"][0] < 12
-    assert st["episode_path_length"][0] == sim.closed_loop_stats["path_length"][0] > 0
+    assert st["episode_path_length"][0] == sim.live.stats["path_length"][0] > 0
     assert sim.last_stops[0] and sim.last_episode_end[0] and not sim.last_episode_end[1]
-    assert S.rect_distance(sim.world_xy[0], A) <= 1.0
+    assert S.rect_distance(sim.live.xy[0], A) <= 1.0
     # the environment starts its next episode in place: maps, object map and clock are fresh, the neighbour's are not
-    assert sim._ep_index[0] == 1 and sim._ep_clock[0] == 0
+    assert sim.live.ep_index[0] == 1 and sim.live.ep_clock[0] == 0
     assert not sim.object_maps[0].has_object("chair")
     assert not bool(sim.values.conf[0].any()) and bool(sim.values.conf[1].any())
     assert not bool(sim.obstacles.explored_bits[0].any()) and bool(sim.obstacles.explored_bits[1].any())
-    assert not sim._objects[0].any()                                   # the second episode's layout: nothing
-    where = sim.world_xy[0].copy()
+    assert not sim.live.objects[0].any()                                   # the second episode's layout: nothing
+    where = sim.live.xy[0].copy()
     sim.step()                                                         # (the stop did not move the robot; a new episode initialises)
-    assert np.array_equal(sim.last_poses[0, :2], where) and sim.last_modes[0] == "initialize" and sim._ep_clock[0] == 1
+    assert np.array_equal(sim.last_poses[0, :2], where) and sim.last_modes[0] == "initialize" and sim.live.ep_clock[0] == 1
 
 
 def test_a_distractor_in_view_is_not_a_detection(gpu_device):
@@ -111,7 +111,7 @@ def test_a_distractor_in_view_is_not_a_detection(gpu_device):
     seen = set()
     for t in range(14):
         sim.step()
-        seen |= {(s[1], s[2]) for s in sim._live_sightings if s[0] == 0}
+        seen |= {(s[1], s[2]) for s in sim.live.sightings if s[0] == 0}
         if t == 12:
             assert sim.last_modes[0] == "explore"
     assert seen == {("tv", 0.9)}                                       # the distractor was in view, the target never
@@ -128,10 +128,10 @@ def test_objects_block_the_robot(gpu_device):
     xs = []
     for _ in range(steps):
         sim.step()
-        xs.append(sim.world_xy[0].copy())
+        xs.append(sim.live.xy[0].copy())
     # 0.25 m steps towards the face at x = 2.25: x = 2.0 keeps the 0.2 m margin, x = 2.25 would not
     assert [float(p[0]) for p in xs] == [0.25 * i for i in range(1, 9)] + [2.0] * 3 and all(p[1] == 0.0 for p in xs)
-    assert sim.closed_loop_stats["collisions"][0] == 3 and sim.closed_loop_stats["path_length"][0] == 2.0
+    assert sim.live.stats["collisions"][0] == 3 and sim.live.stats["path_length"][0] == 2.0
     # without the object nothing stops the robot there
     assert not S.step_poses([[2.0, 0.0]], [0], [ACTION_FORWARD])[2][0]
 
@@ -146,8 +146,8 @@ def test_the_mask_is_the_instance(gpu_device):
     want_depth, want_ids = render((0.0, 0.0, 0), [(3.2, 0.6, 3.6, 1.0, 0.0, 1.3), A], 480, 640)
     assert envs == [0] and masks.dtype == torch.bool and masks.shape == (1, 480, 640)
     assert np.array_equal(masks[0].cpu().numpy(), want_ids == 2) and int(masks.sum()) == 13485      # the chair is slot 1
-    assert torch.equal(masks[0], sim._live_ids[0] == 2)
-    assert np.array_equal(sim._live_frames[0].cpu().numpy().view(np.int32), want_depth.view(np.int32))
+    assert torch.equal(masks[0], sim.live.ids[0] == 2)
+    assert np.array_equal(sim.live.frames[0].cpu().numpy().view(np.int32), want_depth.view(np.int32))
     assert sim.object_stats["detections"] == 1 and sim.object_stats["masks"] == 1
 
 
@@ -168,25 +168,25 @@ def test_runs_are_reproducible_and_the_counts_add_up(gpu_device):
     a, pa = _run(gpu_device)
     b, pb = _run(gpu_device)
     assert np.array_equal(pa, pb)
-    sa, sb = a.objectnav_stats, b.objectnav_stats
+    sa, sb = a.live.objectnav_stats, b.live.objectnav_stats
     assert sa.keys() == sb.keys()
     for key in sa:
         assert np.array_equal(np.asarray(sa[key]), np.asarray(sb[key])), key
     for name in ("obstacle_bits", "navigable_bits", "explored_bits"):
         assert _equal(getattr(a.obstacles, name), getattr(b.obstacles, name)), name
     assert _equal(a.values.conf, b.values.conf) and _equal(a.values.value, b.values.value)
-    assert np.array_equal(a._objects, b._objects)
+    assert np.array_equal(a.live.objects, b.live.objects)
     total = sa["successes"] + sa["wrong_stops"] + sa["no_frontier_stops"] + sa["timeouts"]
     assert np.array_equal(sa["episodes"], total) and (sa["episodes"] >= 2).all()          # 60 steps, at most 25 per episode
     assert len(sa["episode_steps"]) == len(sa["episode_outcome"]) == len(sa["episode_path_length"]) == int(sa["episodes"].sum())
     assert all(1 <= n <= 25 for n in sa["episode_steps"])
     for e in range(3):
         mine = [n for n, env in zip(sa["episode_steps"], sa["episode_env"]) if env == e]
-        assert sum(mine) + a._ep_clock[e] == 60
-        assert np.array_equal(a._ep_index, sa["episodes"])
+        assert sum(mine) + a.live.ep_clock[e] == 60
+        assert np.array_equal(a.live.ep_index, sa["episodes"])
     # every episode drew the default layout: the environment's target and one distractor, away from the robot
     for e in range(3):
-        assert a._object_classes[e][0] == a.targets[e] and len(a._object_classes[e]) == 2 and a._target_slot[e] == 0
+        assert a.live.object_classes[e][0] == a.targets[e] and len(a.live.object_classes[e]) == 2 and a.live.target_slot[e] == 0
 
 
 def test_the_real_detector_head_reports_the_visible_boxes(gpu_device):
@@ -219,4 +219,4 @@ def test_the_real_detector_head_reports_the_visible_boxes(gpu_device):
                 seen += 1
     assert sim.object_stats.get("head_mismatch", 0) == 0 and seen >= 4
     # step 0 of environment 0: the visible bounding box of A (columns 277-363, rows 237-391)
-    assert sim.objectnav_stats["episodes"].sum() == 0
+    assert sim.live.objectnav_stats["episodes"].sum() == 0

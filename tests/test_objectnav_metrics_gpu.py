@@ -63,20 +63,20 @@ def test_target_in_line_of_sight_scores_spl(gpu_device):
     E, cap = 2, 100
     sim = _sim(gpu_device, E, layout=_first_episode({0: [("chair", A)]}), wo=dict(max_episode_steps=cap), object_maps=True,
                objectnav_metrics=True)
-    st = sim.objectnav_stats
+    st = sim.live.objectnav_stats
     assert set(st) == PARENT_KEYS | METRIC_KEYS
     l_host = float(_host_distance(A, [(0.0, 0.0)])[0])
-    assert sim._ep_geodesic[0] == l_host and np.isnan(sim._ep_geodesic[1])
-    assert sim.distance_to_goal[0] == l_host and np.isnan(sim.distance_to_goal[1])
+    assert sim.live.ep_geodesic[0] == l_host and np.isnan(sim.live.ep_geodesic[1])
+    assert sim.live.distance_to_goal[0] == l_host and np.isnan(sim.live.distance_to_goal[1])
     dists, acts, poses = [], [], []
     while st["episodes"][0] == 0 and len(dists) < cap + 1:
-        where = sim.world_xy[0].copy()
+        where = sim.live.xy[0].copy()
         sim.step()
         poses.append(where)
         acts.append(int(sim.last_world_actions[0]))
         if st["episodes"][0] == 0:
-            dists.append(float(sim.distance_to_goal[0]))
-            assert np.isnan(sim.distance_to_goal[1])
+            dists.append(float(sim.live.distance_to_goal[0]))
+            assert np.isnan(sim.live.distance_to_goal[1])
     torch.cuda.synchronize()
     assert st["episode_outcome"][0] == "success" and st["episode_env"][0] == 0
     l, p, d_end = st["episode_geodesic"][0], st["episode_path_length"][0], st["episode_distance_to_goal"][0]
@@ -85,7 +85,7 @@ def test_target_in_line_of_sight_scores_spl(gpu_device):
     assert l == l_host and 1.0 < l < 1.5                   # 2.25 m to the face, success within 1 m of it
     assert st["episode_spl"][0] == S.spl(True, l, p) and 0.0 < st["episode_spl"][0] <= 1.0
     final = poses[-1]                                      # the pose the last step judged: the STOP did not move the robot
-    assert np.array_equal(final, sim.world_xy[0])
+    assert np.array_equal(final, sim.live.xy[0])
     assert d_end == float(_host_distance(A, [final])[0]) and d_end == 0.0 and S.rect_distance(final, A) <= 1.0
     assert st["episode_soft_spl"][0] == S.soft_spl(d_end, l, p) == st["episode_spl"][0]
     # every step's distance is the host's at the pose the step judged; it never grows on the way in
@@ -95,8 +95,8 @@ def test_target_in_line_of_sight_scores_spl(gpu_device):
     moved = [i for i in range(1, len(dists)) if acts[i - 1] == ACTION_FORWARD]
     assert len(moved) >= 3 and all(dists[i] < dists[i - 1] for i in moved if dists[i - 1] > 0.0)
     # the next episode has no target: nan, and it is in no mean
-    assert np.isnan(sim.distance_to_goal[0]) and np.isnan(sim._ep_geodesic[0])
-    summary = sim.objectnav_summary()
+    assert np.isnan(sim.live.distance_to_goal[0]) and np.isnan(sim.live.ep_geodesic[0])
+    summary = sim.live.objectnav_summary()
     assert summary["episodes"] == 1 and summary["scored"] == 1 and summary["success_rate"] == 1.0
     assert summary["spl"] == st["episode_spl"][0] and summary["soft_spl"] == st["episode_soft_spl"][0]
     assert summary["distance_to_goal"] == 0.0 and summary["excluded_no_target"] == 0 and summary["excluded_unreachable"] == 0
@@ -108,10 +108,10 @@ def test_a_timeout_scores_zero_spl_and_soft_spl_as_defined(gpu_device):
     E, cap = 2, 30
     sim = _sim(gpu_device, E, layout=_first_episode({0: [("chair", HIDDEN)]}), wo=dict(max_episode_steps=cap),
                objectnav_metrics=True)
-    st = sim.objectnav_stats
+    st = sim.live.objectnav_stats
     last = None
     while st["episodes"][0] == 0:
-        last = sim.world_xy[0].copy()
+        last = sim.live.xy[0].copy()
         sim.step()
     torch.cuda.synchronize()
     i0, i1 = st["episode_env"].index(0), st["episode_env"].index(1)
@@ -125,7 +125,7 @@ def test_a_timeout_scores_zero_spl_and_soft_spl_as_defined(gpu_device):
     # environment 1 had no target: recorded as nan, scored 0, excluded from the means
     assert st["episode_outcome"][i1] == "timeout" and np.isnan(st["episode_geodesic"][i1])
     assert np.isnan(st["episode_distance_to_goal"][i1]) and st["episode_spl"][i1] == 0.0 and st["episode_soft_spl"][i1] == 0.0
-    summary = sim.objectnav_summary()
+    summary = sim.live.objectnav_summary()
     assert summary["episodes"] == 2 and summary["scored"] == 1 and summary["excluded_no_target"] == 1
     assert summary["success_rate"] == 0.0 and summary["spl"] == 0.0 and summary["soft_spl"] == st["episode_soft_spl"][i0]
     assert summary["distance_to_goal"] == d_end
@@ -139,29 +139,29 @@ def test_the_metrics_change_nothing(gpu_device):
     E = 3
     kw = dict(wo=dict(max_episode_steps=25), object_maps=True)
     on, off = _sim(gpu_device, E, objectnav_metrics=True, **kw), _sim(gpu_device, E, **kw)
-    assert set(off.objectnav_stats) == PARENT_KEYS and not hasattr(off, "distance_to_goal")
+    assert set(off.live.objectnav_stats) == PARENT_KEYS and off.live.distance_to_goal is None
     for t in range(30):
         on.step()
         off.step()
         torch.cuda.synchronize()
-        assert _equal(on._live_frames, off._live_frames) and _equal(on._live_ids, off._live_ids), t
+        assert _equal(on.live.frames, off.live.frames) and _equal(on.live.ids, off.live.ids), t
         assert on.last_modes == off.last_modes, t
         assert np.array_equal(on.last_goals, off.last_goals, equal_nan=True), t
         assert np.array_equal(on.last_world_actions, off.last_world_actions), t
         assert np.array_equal(on.last_poses, off.last_poses), t
         assert np.array_equal(on.last_episode_end, off.last_episode_end), t
-        assert on.distance_to_goal.shape == (E,) and not np.isnan(on.distance_to_goal).any(), t
-    assert np.array_equal(on.world_xy, off.world_xy) and np.array_equal(on.world_k, off.world_k)
-    assert np.array_equal(on._objects, off._objects)
+        assert on.live.distance_to_goal.shape == (E,) and not np.isnan(on.live.distance_to_goal).any(), t
+    assert np.array_equal(on.live.xy, off.live.xy) and np.array_equal(on.live.k, off.live.k)
+    assert np.array_equal(on.live.objects, off.live.objects)
     for name in ("obstacle_bits", "navigable_bits", "explored_bits"):
         assert _equal(getattr(on.obstacles, name), getattr(off.obstacles, name)), name
     assert _equal(on.values.conf, off.values.conf) and _equal(on.values.value, off.values.value)
-    assert set(off.objectnav_stats) == PARENT_KEYS
+    assert set(off.live.objectnav_stats) == PARENT_KEYS
     for key in PARENT_KEYS:
-        assert np.array_equal(np.asarray(on.objectnav_stats[key]), np.asarray(off.objectnav_stats[key])), key
-    n = len(on.objectnav_stats["episode_outcome"])
-    assert n >= E and all(len(on.objectnav_stats[k]) == n for k in METRIC_KEYS)               # 30 steps, 25 per episode
+        assert np.array_equal(np.asarray(on.live.objectnav_stats[key]), np.asarray(off.live.objectnav_stats[key])), key
+    n = len(on.live.objectnav_stats["episode_outcome"])
+    assert n >= E and all(len(on.live.objectnav_stats[k]) == n for k in METRIC_KEYS)               # 30 steps, 25 per episode
     # the default layouts from the environments' start poses: every episode has a reachable target
-    assert np.isfinite(on.objectnav_stats["episode_geodesic"]).all()
-    assert set(off.objectnav_summary()) == {"episodes", "success_rate"}
-    print("summary after 30 steps:", on.objectnav_summary())
+    assert np.isfinite(on.live.objectnav_stats["episode_geodesic"]).all()
+    assert set(off.live.objectnav_summary()) == {"episodes", "success_rate"}
+    print("summary after 30 steps:", on.live.objectnav_summary())

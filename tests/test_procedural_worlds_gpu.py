@@ -335,11 +335,11 @@ def _harness(device, **kw):
 
 
 def _host_geodesic(h, e):
-    rects = S.inflated_rects(h._objects[e], S.STEP_MARGIN, h.world_table.world(e))
-    box = h._objects[e, h._target_slot[e], :4]
+    rects = S.inflated_rects(h.live.objects[e], S.STEP_MARGIN, h.live.table.world(e))
+    box = h.live.objects[e, h.live.target_slot[e], :4]
     src = S.goal_viewpoints(box, rects, h.world_objects.success_distance)
     nodes, dist = S.geodesic_field_numpy(rects, src)
-    return S.geodesic_query_numpy(rects, src, nodes, dist, [h.world_xy[e]])[0]
+    return S.geodesic_query_numpy(rects, src, nodes, dist, [h.live.xy[e]])[0]
 
 
 def test_harness_in_procedural_worlds(gpu_device):
@@ -348,19 +348,19 @@ def test_harness_in_procedural_worlds(gpu_device):
     a, b = _harness(gpu_device), _harness(gpu_device)
     worlds = S.ProceduralWorlds(3)
     fx = S.camera_intrinsics(a.W)[0]
-    assert a.world_episode.tolist() == [0] * E and len({a.world_table.world(e).tobytes() for e in range(E)}) == E
+    assert a.live.world_episode.tolist() == [0] * E and len({a.live.table.world(e).tobytes() for e in range(E)}) == E
     for e in range(E):
         w = worlds.world(a.env_ids[e], 0)
-        assert np.array_equal(a.world_table.world(e), w.boxes) and np.array_equal(a.world_xy[e], w.start_xy) and a.world_k[e] == w.start_k
-        assert (a._target_slot >= 0).all() and a._ep_geodesic[e] == _host_geodesic(a, e) and np.isfinite(a._ep_geodesic[e])
+        assert np.array_equal(a.live.table.world(e), w.boxes) and np.array_equal(a.live.xy[e], w.start_xy) and a.live.k[e] == w.start_k
+        assert (a.live.target_slot >= 0).all() and a.live.ep_geodesic[e] == _host_geodesic(a, e) and np.isfinite(a.live.ep_geodesic[e])
     moved = 0
     for t in range(STEPS):
-        before = [(a.world_xy[e].copy(), int(a.world_k[e]), a.world_table.world(e), a._objects[e].copy(), int(a.world_episode[e]))
+        before = [(a.live.xy[e].copy(), int(a.live.k[e]), a.live.table.world(e), a.live.objects[e].copy(), int(a.live.world_episode[e]))
                   for e in range(E)]
         a.step()
         b.step()
         assert np.array_equal(a.last_poses, b.last_poses) and np.array_equal(a.last_world_actions, b.last_world_actions)
-        assert np.array_equal(a.world_xy, b.world_xy) and np.array_equal(a.world_k, b.world_k)
+        assert np.array_equal(a.live.xy, b.live.xy) and np.array_equal(a.live.k, b.live.k)
         if t in (0, 7, 29):
             torch.cuda.synchronize()
             for e in (0, 3):
@@ -368,24 +368,24 @@ def test_harness_in_procedural_worlds(gpu_device):
                 c, s = S.HEADINGS[k]
                 want = S.render_objects_numpy(x, y, c, s, S.CAMERA_HEIGHT, fx, S.MIN_DEPTH, S.MAX_DEPTH, a.H, a.W,
                                               objs[objs[:, 6] != 0.0, :6], boxes=boxes)
-                assert np.array_equal(_bits(a._live_frames[e]), want[0].view(np.int32)), (t, e)
-                assert np.array_equal(a._live_ids[e].cpu().numpy(), want[1]), (t, e)
+                assert np.array_equal(_bits(a.live.frames[e]), want[0].view(np.int32)), (t, e)
+                assert np.array_equal(a.live.ids[e].cpu().numpy(), want[1]), (t, e)
         for e in range(E):
-            x, y = a.world_xy[e]
-            assert not S._blocked(x, y, S.STEP_MARGIN, boxes=a.world_table.world(e)), (t, e)
-            if a.world_episode[e] != before[e][4]:              # the episode ended: the NEXT world, from its start
+            x, y = a.live.xy[e]
+            assert not S._blocked(x, y, S.STEP_MARGIN, boxes=a.live.table.world(e)), (t, e)
+            if a.live.world_episode[e] != before[e][4]:              # the episode ended: the NEXT world, from its start
                 moved += 1
                 w = worlds.world(a.env_ids[e], before[e][4] + 1)
-                assert a.world_episode[e] == before[e][4] + 1 == a._ep_index[e] and a.last_episode_end[e]
-                assert not np.array_equal(w.boxes, before[e][2]) and np.array_equal(a.world_table.world(e), w.boxes)
-                assert np.array_equal(a.world_xy[e], w.start_xy) and a.world_k[e] == w.start_k and not a._collided[e]
+                assert a.live.world_episode[e] == before[e][4] + 1 == a.live.ep_index[e] and a.last_episode_end[e]
+                assert not np.array_equal(w.boxes, before[e][2]) and np.array_equal(a.live.table.world(e), w.boxes)
+                assert np.array_equal(a.live.xy[e], w.start_xy) and a.live.k[e] == w.start_k and not a.live.collided[e]
                 if before[e][4] == 0:
-                    assert a._ep_geodesic[e] == _host_geodesic(a, e) and a.distance_to_goal[e] == a._ep_geodesic[e]
+                    assert a.live.ep_geodesic[e] == _host_geodesic(a, e) and a.live.distance_to_goal[e] == a.live.ep_geodesic[e]
     assert moved >= 2 * E                                       # 30 steps, episodes of 12 at the most
-    np.testing.assert_equal(a.closed_loop_stats, b.closed_loop_stats)
-    np.testing.assert_equal(a.objectnav_stats, b.objectnav_stats)
-    np.testing.assert_equal(a.objectnav_summary(), b.objectnav_summary())
-    assert a.objectnav_summary()["episodes"] >= 2 * E
+    np.testing.assert_equal(a.live.stats, b.live.stats)
+    np.testing.assert_equal(a.live.objectnav_stats, b.live.objectnav_stats)
+    np.testing.assert_equal(a.live.objectnav_summary(), b.live.objectnav_summary())
+    assert a.live.objectnav_summary()["episodes"] >= 2 * E
 
 
 def test_harness_with_the_map_planner(gpu_device):
@@ -393,10 +393,10 @@ def test_harness_with_the_map_planner(gpu_device):
     for _ in range(STEPS):
         h.step()
         for e in range(E):
-            assert not S._blocked(h.world_xy[e][0], h.world_xy[e][1], S.STEP_MARGIN, boxes=h.world_table.world(e))
+            assert not S._blocked(h.live.xy[e][0], h.live.xy[e][1], S.STEP_MARGIN, boxes=h.live.table.world(e))
     ps = h.planner_stats
     assert np.array_equal(ps["plans"], ps["ok"] + ps["unreachable"] + ps["too_long"] + ps["invalid"])
-    assert len(h.objectnav_stats["episode_outcome"]) >= 2 * E
+    assert len(h.live.objectnav_stats["episode_outcome"]) >= 2 * E
 
 
 @pytest.mark.parametrize("planner", [False, True], ids=["bang_bang", "planner"])
@@ -407,18 +407,18 @@ def test_worlds_without_objects_stay_in_episode_zero(gpu_device, planner):
     h = BatchedEpisodes(2, device=gpu_device, use_blip2=False, select_frontiers=True, closed_loop=True, worlds=S.ProceduralWorlds(3),
                         controller=S.MapPlannerController() if planner else None)
     made = [S.ProceduralWorlds(3).world(e, 0) for e in range(2)]
-    assert all(np.array_equal(h.world_xy[e], made[e].start_xy) for e in range(2))
+    assert all(np.array_equal(h.live.xy[e], made[e].start_xy) for e in range(2))
     for t in range(40):
-        xy, k = h.world_xy.copy(), h.world_k.copy()
+        xy, k = h.live.xy.copy(), h.live.k.copy()
         h.step()
         if t % 13 == 0:
             want = np.stack([S.depth_from_profile(S.wall_profile(xy[e][0], xy[e][1], int(k[e]), h.W, boxes=made[e].boxes), h.H)
                              for e in range(2)])
-            assert np.array_equal(_bits(h._live_frames), want.view(np.int32)), t
+            assert np.array_equal(_bits(h.live.frames), want.view(np.int32)), t
         for e in range(2):
-            assert not S._blocked(h.world_xy[e][0], h.world_xy[e][1], S.STEP_MARGIN, boxes=made[e].boxes), (t, e)
-    assert h.world_episode.tolist() == [0, 0] and all(np.array_equal(h.world_table.world(e), made[e].boxes) for e in range(2))
-    assert h.closed_loop_stats["forward_steps"].sum() > 0 and h.closed_loop_stats["path_length"].sum() > 0
+            assert not S._blocked(h.live.xy[e][0], h.live.xy[e][1], S.STEP_MARGIN, boxes=made[e].boxes), (t, e)
+    assert h.live.world_episode.tolist() == [0, 0] and all(np.array_equal(h.live.table.world(e), made[e].boxes) for e in range(2))
+    assert h.live.stats["forward_steps"].sum() > 0 and h.live.stats["path_length"].sum() > 0
     if planner:
         ps = h.planner_stats
         assert ps["plans"].sum() > 0 and np.array_equal(ps["plans"], ps["ok"] + ps["unreachable"] + ps["too_long"] + ps["invalid"])

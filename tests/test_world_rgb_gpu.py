@@ -184,40 +184,40 @@ def _statement(h, e, x, y, k, boxes, objs, classes):
 
 
 def test_harness_renders_what_the_robot_sees(gpu_device):
-    """Every step's last_rgb is the statement at that step's poses, layouts and worlds; and nothing else changes: with stub
+    """Every step's live.rgb is the statement at that step's poses, layouts and worlds; and nothing else changes: with stub
     cosines and without a detector nothing downstream reads the colours."""
     import torch
 
     a, b = _harness(gpu_device, render_rgb=True), _harness(gpu_device)
-    assert b.last_rgb is None and not b.render_rgb
+    assert b.live.rgb is None and not b.render_rgb
     objects_seen = episodes = 0
     for t in range(STEPS):
-        before = [(a.world_xy[e].copy(), int(a.world_k[e]), a.world_table.world(e), a._objects[e].copy(), list(a._object_classes[e]))
+        before = [(a.live.xy[e].copy(), int(a.live.k[e]), a.live.table.world(e), a.live.objects[e].copy(), list(a.live.object_classes[e]))
                   for e in range(E)]
         a.step()
         b.step()
         torch.cuda.synchronize()
-        rgb = a.last_rgb.cpu().numpy()
+        rgb = a.live.rgb.cpu().numpy()
         assert rgb.shape == (E, HH, WW, 3)
         for e in range(E):
             (x, y), k, boxes, objs, classes = before[e]
             want = _statement(a, e, x, y, k, boxes, objs, classes)
             assert np.array_equal(rgb[e], want[2]), (t, e)
-            assert np.array_equal(_bits(a._live_frames[e]), want[0].view(np.int32)) and np.array_equal(a._live_ids[e].cpu().numpy(), want[1])
+            assert np.array_equal(_bits(a.live.frames[e]), want[0].view(np.int32)) and np.array_equal(a.live.ids[e].cpu().numpy(), want[1])
             objects_seen += int((want[1] > 0).sum())
         episodes += int(a.last_episode_end.sum())
         assert np.array_equal(a.last_poses, b.last_poses) and np.array_equal(a.last_world_actions, b.last_world_actions)
-        assert np.array_equal(a.world_xy, b.world_xy) and np.array_equal(a.world_k, b.world_k)
-        assert np.array_equal(_bits(a._live_frames), _bits(b._live_frames)) and bool((a._live_ids == b._live_ids).all())
-        assert np.array_equal(a._live_stats, b._live_stats)
+        assert np.array_equal(a.live.xy, b.live.xy) and np.array_equal(a.live.k, b.live.k)
+        assert np.array_equal(_bits(a.live.frames), _bits(b.live.frames)) and bool((a.live.ids == b.live.ids).all())
+        assert np.array_equal(a.live.seen_stats, b.live.seen_stats)
     assert objects_seen > 0 and episodes >= E                          # objects were in view; every world was left for the next
     for name in ("obstacle_bits", "navigable_bits", "explored_bits"):
         assert torch.equal(getattr(a.obstacles, name), getattr(b.obstacles, name)), name
     assert torch.equal(a.values.conf.view(torch.int32), b.values.conf.view(torch.int32))
     assert torch.equal(a.values.value.view(torch.int64), b.values.value.view(torch.int64))
-    np.testing.assert_equal(a.closed_loop_stats, b.closed_loop_stats)
-    np.testing.assert_equal(a.objectnav_stats, b.objectnav_stats)
-    assert a.objectnav_stats["episodes"].sum() >= E
+    np.testing.assert_equal(a.live.stats, b.live.stats)
+    np.testing.assert_equal(a.live.objectnav_stats, b.live.objectnav_stats)
+    assert a.live.objectnav_stats["episodes"].sum() >= E
 
 
 @pytest.mark.parametrize("mode", ["rooms", "rooms_objects", "worlds"])
@@ -231,20 +231,20 @@ def test_harness_other_worlds(gpu_device, mode):
     h = BatchedEpisodes(2, device=gpu_device, height=HH, width=WW, use_blip2=False, select_frontiers=True, closed_loop=True,
                         render_rgb=True, **kw)
     for t in range(2):
-        xy, k = h.world_xy.copy(), h.world_k.copy()
+        xy, k = h.live.xy.copy(), h.live.k.copy()
         h.step()
         torch.cuda.synchronize()
         for e in range(2):
-            boxes = h.world_table.world(e) if mode == "worlds" else None
-            objs = h._objects[e] if mode == "rooms_objects" else np.zeros((8, 8))
-            classes = h._object_classes[e] if mode == "rooms_objects" else []
+            boxes = h.live.table.world(e) if mode == "worlds" else None
+            objs = h.live.objects[e] if mode == "rooms_objects" else np.zeros((8, 8))
+            classes = h.live.object_classes[e] if mode == "rooms_objects" else []
             want = _statement(h, e, xy[e][0], xy[e][1], int(k[e]), boxes, objs, classes)
-            assert np.array_equal(h.last_rgb[e].cpu().numpy(), want[2]), (t, e)
-            assert np.array_equal(_bits(h._live_frames[e]), want[0].view(np.int32)), (t, e)
+            assert np.array_equal(h.live.rgb[e].cpu().numpy(), want[2]), (t, e)
+            assert np.array_equal(_bits(h.live.frames[e]), want[0].view(np.int32)), (t, e)
 
 
 def test_transport_hop_sees_the_rendered_frames(gpu_device):
-    """emulate_jpeg=True: the transported frames are Pillow's q90 round trip of last_rgb.  jpeg_roundtrip_batch takes any frame
+    """emulate_jpeg=True: the transported frames are Pillow's q90 round trip of live.rgb.  jpeg_roundtrip_batch takes any frame
     size; 16 x 16 -- one MCU of the 4:2:0 coder, a width the depth ingest takes -- is the smallest the harness can step."""
     import torch
 
@@ -257,7 +257,7 @@ def test_transport_hop_sees_the_rendered_frames(gpu_device):
     for _ in range(2):
         h.step()
         torch.cuda.synchronize()
-        rgb, sent = h.last_rgb.cpu().numpy(), h.jpeg_frames.cpu().numpy()
+        rgb, sent = h.live.rgb.cpu().numpy(), h.jpeg_frames.cpu().numpy()
         for e in range(E):
             assert np.array_equal(sent[e], jpeg_roundtrip(rgb[e], 90)), e
             frames.add(rgb[e].tobytes())

@@ -225,7 +225,7 @@ def probe_steps(steps: int, lines) -> None:
     E = 256
     sims = {"procedural box worlds": mid_episode(E, ProceduralWorlds(0)), "their rasterised twins": mid_episode(E, RasterisedWorlds(0))}
     a, b = sims.values()
-    same = np.array_equal(a.world_xy, b.world_xy) and np.array_equal(a.world_k, b.world_k)
+    same = np.array_equal(a.live.xy, b.live.xy) and np.array_equal(a.live.k, b.live.k)
     rate = {k: [] for k in sims}
     for _ in range(3):                 # alternating windows
         for key, s in sims.items():
@@ -237,14 +237,14 @@ def probe_steps(steps: int, lines) -> None:
             rate[key].append(E * steps / (time.perf_counter() - t0))
     for name, s in sims.items():
         s.check()
-        st = s.closed_loop_stats
+        st = s.live.stats
         lines.append("steps  E=%3d  ObjectNav  %-23s %8.1f env-steps/s (%.1f-%.1f over 3 windows of %d steps)   per environment: "
                      "%.2f refused moves, %.1f forward steps, path %.2f m; episodes per environment up to %d"
                      % (E, name, *stats(rate[name]), steps, float(st["collisions"].mean()), float(st["forward_steps"].mean()),
-                        float(st["path_length"].mean()), int(s.world_episode.max()) + 1))
+                        float(st["path_length"].mean()), int(s.live.world_episode.max()) + 1))
         print(lines[-1], flush=True)
     lines.append("steps  the two harnesses stood at the same poses after 45 steps: %s; after the windows: %s"
-                 % (same, np.array_equal(a.world_xy, b.world_xy) and np.array_equal(a.world_k, b.world_k)))
+                 % (same, np.array_equal(a.live.xy, b.live.xy) and np.array_equal(a.live.k, b.live.k)))
     print(lines[-1], flush=True)
 
 

@@ -161,7 +161,7 @@ def probe_calls(reps: int, lines) -> None:
     # the depth pass and the obstacle pipeline of one step of the same harness, on the frames and poses of its next step
     t_ep = sim.t % sim.episode_len
     poses, tf = sim._poses_tf(t_ep)
-    depth = sim._live_depth(t_ep, tf)
+    depth = sim.live.observe(sim.rooms.painter, t_ep, tf=tf)
     torch.cuda.synchronize()
     ti, tu = [], []
     for r in range(reps + 5):
@@ -201,7 +201,7 @@ def probe_steps(steps: int, lines) -> None:
                 rate[name].append(E * steps / (time.perf_counter() - t0))
         for name, s in sims.items():
             s.check()
-            st, ps = s.closed_loop_stats, s.planner_stats
+            st, ps = s.live.stats, s.planner_stats
             lines.append("steps  E=%3d  %-20s %-21s %8.1f env-steps/s (%.1f-%.1f over 3 windows of %d steps)   per environment: "
                          "%.2f refused moves, %.1f forward steps, path %.2f m;  plans %d (ok %d, unreachable %d, too long %d, invalid %d)"
                          % (E, label, name, *stats(rate[name]), steps, float(st["collisions"].mean()),
@@ -210,7 +210,7 @@ def probe_steps(steps: int, lines) -> None:
             print(lines[-1], flush=True)
             if objectnav:
                 lines.append("summary E=%3d  %-21s %s" % (E, name, "  ".join(
-                    "%s %s" % (k, ("%.4f" % v) if isinstance(v, float) else v) for k, v in s.objectnav_summary().items())))
+                    "%s %s" % (k, ("%.4f" % v) if isinstance(v, float) else v) for k, v in s.live.objectnav_summary().items())))
                 print(lines[-1], flush=True)
         del sims
         torch.cuda.empty_cache()

@@ -177,26 +177,26 @@ def probe_steps(steps: int, lines) -> None:
             rate[key].append(E * steps / (time.perf_counter() - t0))
     for (world, name), s in sims.items():
         s.check()
-        st, ps = s.closed_loop_stats, s.planner_stats
+        st, ps = s.live.stats, s.planner_stats
         lines.append("steps  E=%3d  ObjectNav  %-12s %-21s %8.1f env-steps/s (%.1f-%.1f over 3 windows of %d steps)   per environment: "
                      "%.2f refused moves, %.1f forward steps, path %.2f m;  plans %d (ok %d, unreachable %d, too long %d, invalid %d)"
                      % (E, world, name, *stats(rate[(world, name)]), steps, float(st["collisions"].mean()),
                         float(st["forward_steps"].mean()), float(st["path_length"].mean()), int(ps["plans"].sum()),
                         int(ps["ok"].sum()), int(ps["unreachable"].sum()), int(ps["too_long"].sum()), int(ps["invalid"].sum())))
         print(lines[-1], flush=True)
-        out = s.objectnav_stats["episode_outcome"]
-        l = np.asarray(s.objectnav_stats["episode_geodesic"], np.float64)
+        out = s.live.objectnav_stats["episode_outcome"]
+        l = np.asarray(s.live.objectnav_stats["episode_geodesic"], np.float64)
         fin = l[np.isfinite(l)]
         lines.append("summary E=%3d  %-12s %-21s %s;  outcomes %s;  start-to-goal geodesic %.2f-%.2f m (median %.2f)"
                      % (E, world, name, "  ".join("%s %s" % (k, ("%.4f" % v) if isinstance(v, float) else v)
-                                                  for k, v in s.objectnav_summary().items()),
+                                                  for k, v in s.live.objectnav_summary().items()),
                         ", ".join("%s %d" % (o, out.count(o)) for o in sorted(set(out))),
                         fin.min(initial=np.inf), fin.max(initial=-np.inf), float(np.median(fin)) if len(fin) else float("nan")))
         print(lines[-1], flush=True)
         if world == "procedural":
-            counts = s.world_table.counts
+            counts = s.live.table.counts
             lines.append("worlds E=%3d  %-21s boxes per world %d-%d (median %d); episodes per environment up to %d"
-                         % (E, name, counts.min(), counts.max(), int(np.median(counts)), int(s.world_episode.max()) + 1))
+                         % (E, name, counts.min(), counts.max(), int(np.median(counts)), int(s.live.world_episode.max()) + 1))
             print(lines[-1], flush=True)
 
 

@@ -2,7 +2,7 @@
 environment and map, every frame encoded on the device (BatchedEpisodes.render_jpeg).  Play one with
 `ffplay -f mjpeg out/env0_value_map.mjpeg`.  `--first-person` steps a closed-loop harness that renders the robots' RGB view of the
 world (BatchedEpisodes(closed_loop=True, render_rgb=True)) and writes one more file per environment, env<e>_first_person.mjpeg:
-what the robot saw (last_rgb), through the same encoder.
+what the robot saw (live.rgb), through the same encoder.
 Usage: python tools/record_episodes.py [--envs 4] [--steps 50] [--every 1] [--quality 90] [--out recordings] [--first-person]"""
 import argparse
 import os
@@ -38,7 +38,7 @@ def main():
                 continue
             frames = sim.render_jpeg(quality=args.quality)
             if args.first_person:
-                frames["first_person"] = jpeg_encode_batch_bytes(sim.last_rgb, args.quality, "rgb")
+                frames["first_person"] = jpeg_encode_batch_bytes(sim.live.rgb, args.quality, "rgb")
             for name, files in frames.items():
                 for e, data in enumerate(files):
                     key = (e, name)

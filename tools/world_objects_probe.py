@@ -406,7 +406,7 @@ def probe_steps(steps: int, lines, batch: str = "on", clouds: str = "on", metric
             s.check()
             extra = ""
             if s.world_objects is not None:
-                st = s.objectnav_stats
+                st = s.live.objectnav_stats
                 extra = ("   %d detections, %d cloud updates; episodes ended: %d (%d successes, %d wrong stops, %d no frontier); "
                          "object-map stage per step: %.1f kernel launches, %.1f host read-backs; cloud queries per step: %.1f "
                          "launches, %.0f bytes uploaded, %.2f band points") % (
@@ -419,7 +419,7 @@ def probe_steps(steps: int, lines, batch: str = "on", clouds: str = "on", metric
             print(lines[-1], flush=True)
             if getattr(s, "objectnav_metrics", False):
                 lines.append("summary E=%3d  %s" % (E, "  ".join("%s %s" % (k, ("%.4f" % v) if isinstance(v, float) else v)
-                                                                  for k, v in s.objectnav_summary().items())))
+                                                                  for k, v in s.live.objectnav_summary().items())))
                 print(lines[-1], flush=True)
         del sims
         torch.cuda.empty_cache()

@@ -117,7 +117,7 @@ def probe_steps(steps: int, lines) -> None:
             s.check()
             extra = ""
             if s.closed_loop:
-                st = s.closed_loop_stats
+                st = s.live.stats
                 extra = "   path %.1f m mean, %d refused moves, %d stops" % (float(st["path_length"].mean()),
                                                                            int(st["collisions"].sum()), int(st["stops"].sum()))
             lines.append("steps  E=%3d  %-31s %8.1f env-steps/s (%.1f-%.1f over 3 windows of %d steps)%s"
