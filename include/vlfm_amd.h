@@ -861,9 +861,9 @@ int vlfm_jpeg_decode_batched(const uint8_t* d_files, size_t files_bytes, const i
  *   d_cameras  n records of 8 doubles (64 bytes): x, y, cos(yaw), sin(yaw), camera height, fx (pixels), min_depth, max_depth
  *              (max_depth > min_depth: the frame is normalised to that range and clamped to [1e-3, 1])
  *   d_depth    [n][H][W] float
- * d_objects == NULL: walls only.  Bit for bit what RoomsRenderer.render_cameras computes with torch f64 operations in the rooms
- * world and, for the tabulated headings, synthetic.depth_from_profile(synthetic.wall_profile(..., boxes = the world's boxes)) in
- * NumPy.  d_env_of, n_envs, d_ids, d_stats and the colour arguments are ignored; d_rgb must be NULL.  max_boxes, one image row
+ * d_objects == NULL: walls only.  Bit for bit synthetic.render_objects_numpy(..., boxes6 = [], boxes = the world's boxes)[0] in
+ * NumPy and, for the tabulated headings, synthetic.depth_from_profile(synthetic.wall_profile(..., boxes = the world's boxes)).
+ * d_env_of, n_envs, d_ids, d_stats and the colour arguments are ignored; d_rgb must be NULL.  max_boxes, one image row
  * and one band of rows must fit 64 KB of LDS.
  *
  * d_objects set: up to 8 objects per environment -- axis-aligned boxes with a vertical extent -- stand in front of the walls,

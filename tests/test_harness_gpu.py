@@ -27,7 +27,7 @@ KW = dict(min_height=0.61, max_height=0.88, agent_radius=0.18, area_thresh=1.5)
 
 
 def test_device_renderer_equals_host_renderer_bit_for_bit(gpu_device):
-    """RoomsRenderer.render(t) (torch f64 on the device) == synthetic.depth_from_profile(wall_profile(...)) (NumPy f64 on
+    """RoomsRenderer.render(t) (the ray-cast kernel, f64 on the device) == synthetic.depth_from_profile(wall_profile(...)) (NumPy f64 on
     the host), for every environment of a batch at steps spread over the tour."""
     from vlfm_amd.harness import RoomsRenderer
 

@@ -153,7 +153,7 @@ def test_walls_only_on_lattice_poses(gpu_device):
 @pytest.mark.parametrize("H,W", [(48, 64), (9, 18)], ids=["64x48", "18x9"])
 def test_a_row_of_BOXES_is_the_existing_entries(gpu_device, H, W):
     """The rooms-world methods and a table row that holds BOXES are one path now: both are held against the host statements
-    of the rooms world (render_objects_numpy / object_stats_numpy with boxes=None; render_cameras, torch f64, for walls only)."""
+    of the rooms world (render_objects_numpy / object_stats_numpy with boxes=None; walls only: render_objects_numpy without objects)."""
     tf, hfov, lo, hi = _cameras()
     r = _renderer(H, W, gpu_device)
     table = _table(gpu_device, [_worlds()[0][1], S.BOXES])
@@ -167,7 +167,8 @@ def test_a_row_of_BOXES_is_the_existing_entries(gpu_device, H, W):
     _assert_equal(old, want)
     _assert_equal(new, want)
     assert np.array_equal(_bits(new[0]), _bits(old[0])) and (new[1] == old[1]).all() and (new[2] == old[2]).all()
-    walls = _bits(r.render_cameras(tf, hfov, lo, hi))
+    walls = np.stack([S.render_objects_numpy(t[0, 3], t[1, 3], t[0, 0], t[1, 0], t[2, 3], W / (2 * np.tan(f / 2)), a, b, H, W, [])[0]
+                      for t, f, a, b in zip(tf, hfov, lo, hi)]).view(np.int32)
     assert np.array_equal(_bits(r.cast_worlds(tf, table, [1] * 7, hfov=hfov, min_depth=lo, max_depth=hi)), walls)
     assert np.array_equal(_bits(r.cast_cameras(tf, hfov, lo, hi)), walls)
 

@@ -1,5 +1,5 @@
-"""-m gpu: RoomsRenderer.cast_cameras (csrc/world_render.hip, one launch) against the NumPy renderer of vlfm_amd/synthetic.py and
-against the torch f64 chain of RoomsRenderer.render_cameras, bit for bit."""
+"""-m gpu: RoomsRenderer.cast_cameras (csrc/world_render.hip, one launch) against the NumPy renderers of vlfm_amd/synthetic.py
+(wall_profile / depth_from_profile on the tour, render_objects_numpy for arbitrary cameras), bit for bit."""
 import functools
 
 import numpy as np
@@ -90,15 +90,29 @@ def _rig_like_cameras():
     return tf, np.array([m[0] for m in models])[cam], np.array([m[1] for m in models])[cam], np.array([m[2] for m in models])[cam]
 
 
+def _numpy_cameras(H, W, tf, hfov=None, lo=None, hi=None):
+    """[n,H,W] f32: render_objects_numpy without objects from each transform; None: the documented defaults (the renderer's
+    own optics, 0.5 / 5 m)."""
+    n = len(tf)
+    fx = np.full(n, S.camera_intrinsics(W)[0]) if hfov is None else W / (2 * np.tan(np.asarray(hfov, np.float64) / 2))
+    lo = np.full(n, S.MIN_DEPTH) if lo is None else lo
+    hi = np.full(n, S.MAX_DEPTH) if hi is None else hi
+    return np.stack([S.render_objects_numpy(t[0, 3], t[1, 3], t[0, 0], t[1, 0], t[2, 3], f, a, b, H, W, [])[0]
+                     for t, f, a, b in zip(tf, fx, lo, hi)])
+
+
 @pytest.mark.parametrize("H,W", [(480, 640), (50, 70)], ids=["640x480", "70x50"])
-def test_equals_render_cameras_for_arbitrary_cameras(gpu_device, H, W):
+def test_equals_render_objects_numpy_for_arbitrary_cameras(gpu_device, H, W):
+    import torch
+
     tf, hfov, lo, hi = _rig_like_cameras()
     r = _renderer(H, W)
-    assert _same_bits(r.cast_cameras(tf, hfov, lo, hi), r.render_cameras(tf, hfov, lo, hi))
+    want = lambda *a: torch.from_numpy(_numpy_cameras(H, W, tf, *a)).to(gpu_device)   # noqa: E731
+    assert _same_bits(r.cast_cameras(tf, hfov, lo, hi), want(hfov, lo, hi))
     # defaults: None means the renderer's own optics and the 0.5 / 5 m range, for each argument on its own
-    assert _same_bits(r.cast_cameras(tf), r.render_cameras(tf))
-    assert _same_bits(r.cast_cameras(tf, hfov), r.render_cameras(tf, hfov))
-    assert _same_bits(r.cast_cameras(tf, None, lo, hi), r.render_cameras(tf, None, lo, hi))
+    assert _same_bits(r.cast_cameras(tf), want())
+    assert _same_bits(r.cast_cameras(tf, hfov), want(hfov))
+    assert _same_bits(r.cast_cameras(tf, None, lo, hi), want(None, lo, hi))
 
 
 def test_camera_inside_a_box_sees_through_it(gpu_device):

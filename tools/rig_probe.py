@@ -5,7 +5,10 @@ for K = 3 and 6 cameras at 1, 16 and 256 slots of 640x480 frames of the rooms wo
 device events around the Python call(s) -- launch chain and host prologue included, which is what a step pays -- median / min /
 max of --reps calls after warm-up.  The sequential calls are the unchanged single-camera entry points, so they are the baseline
 in the same binary.
-    python tools/rig_probe.py [--reps 30] [--out profiles/rig_probe.txt]"""
+--harness E [E ...]: instead, env-steps/s of an open-loop BatchedEpisodes with a three-camera rig (stub cosines) at E environments:
+the whole step, in which the 3 E frames are ray-cast on the fly -- --windows windows of --steps steps after warm-up.
+    python tools/rig_probe.py [--reps 30] [--out profiles/rig_probe.txt]
+    python tools/rig_probe.py --harness 8 256 [--steps 20] [--windows 3]"""
 import argparse
 import os
 import sys
@@ -49,7 +52,7 @@ def probe(E: int, K: int, reps: int, lines) -> None:
     steps = [150, 151, 152, 153]
     tfs = [rig.camera_tfs(rr.tf_table[t]).reshape(E * K, 4, 4) for t in steps]
     robot = [rr.tf_table[t] for t in steps]
-    frames = [rr.render_cameras(tf) for tf in tfs]                                  # [E*K,H,W], environment-major
+    frames = [rr.cast_cameras(tf) for tf in tfs]                                      # [E*K,H,W], environment-major
     by_cam = [[f.reshape(E, K, H, W)[:, k].contiguous() for k in range(K)] for f in frames]
     rng = np.random.default_rng(0)
     vals = rng.uniform(0.15, 0.45, (E * K, 1))
@@ -145,22 +148,59 @@ def probe(E: int, K: int, reps: int, lines) -> None:
     torch.cuda.empty_cache()
 
 
+def probe_harness(E: int, steps: int, windows: int, lines) -> None:
+    import time
+
+    import numpy as np
+    import torch
+
+    from vlfm_amd.harness import BatchedEpisodes, Camera, CameraRig
+
+    rig = CameraRig([Camera(yaw=0.5, max_depth=3.5), Camera(yaw=-0.5, forward=0.1, hfov=float(np.deg2rad(60.0))),
+                     Camera(yaw=np.pi, left=0.1, value=False, max_depth=2.5)])
+    sim = BatchedEpisodes(E, device=torch.device("cuda:0"), use_blip2=False, rig=rig, episode_len=500)
+    for _ in range(5):
+        sim.step()
+    rate = []
+    for _ in range(windows):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            sim.step()
+        torch.cuda.synchronize()
+        rate.append(E * steps / (time.perf_counter() - t0))
+    sim.check()
+    lines.append("harness  E=%3d K=3  open loop, rig frames ray-cast on the fly: %s env-steps/s per window of %d steps, median %.1f"
+                 % (E, " ".join("%.1f" % r for r in rate), steps, stats(rate)[0]))
+    del sim
+    torch.cuda.empty_cache()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default=None)
     ap.add_argument("--slots", type=int, nargs="*", default=[1, 16, 256])
     ap.add_argument("--cameras", type=int, nargs="*", default=[3, 6])
+    ap.add_argument("--harness", type=int, nargs="+", default=None, help="environments: time whole open-loop rig steps instead")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--windows", type=int, default=3)
     a = ap.parse_args()
     import torch
 
     assert torch.cuda.is_available(), "rig_probe measures on the GPU; there is no CPU path"
-    lines = ["rig_probe: median (min-max) of %d calls after 5 warm-up calls, device events around the Python call(s), 640x480, "
-             "device %s" % (a.reps, torch.cuda.get_device_name(0))]
-    for E in a.slots:
-        for K in a.cameras:
-            probe(E, K, a.reps, lines)
-            print("\n".join(lines[-3:]), flush=True)
+    if a.harness:
+        lines = ["rig_probe --harness: device %s" % torch.cuda.get_device_name(0)]
+        for E in a.harness:
+            probe_harness(E, a.steps, a.windows, lines)
+            print(lines[-1], flush=True)
+    else:
+        lines = ["rig_probe: median (min-max) of %d calls after 5 warm-up calls, device events around the Python call(s), 640x480, "
+                 "device %s" % (a.reps, torch.cuda.get_device_name(0))]
+        for E in a.slots:
+            for K in a.cameras:
+                probe(E, K, a.reps, lines)
+                print("\n".join(lines[-3:]), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

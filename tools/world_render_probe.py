@@ -1,9 +1,9 @@
 """What closing the loop costs and what the ray-cast kernel (csrc/world_render.hip) buys, measured in one place.
 
-  (a) RoomsRenderer.cast_cameras (one launch) against RoomsRenderer.render_cameras (the torch f64 chain it reproduces) on the
-      same cameras, one process, the two alternating: device events around the Python call -- host prologue, the record's H2D
-      copy and the launch chain included, which is what a step pays -- median (min-max) of --reps calls each after warm-up, at
-      256 / 128 / 8 frames of 640x480 and 16 frames of 1280x720; the frames are compared bit for bit on the way.
+  (a) RoomsRenderer.cast_cameras (one launch): device events around the Python call -- host prologue, the record's H2D copy
+      and the launch chain included, which is what a step pays -- median (min-max) of --reps calls after warm-up, at
+      256 / 128 / 8 frames of 640x480 and 16 frames of 1280x720.  (profiles/world_render_probe.txt also holds the column of the
+      chain of torch f64 operations the kernel replaced, and the bit comparison with it, from before that chain was removed.)
   (b) env-steps/s of a closed-loop harness next to an open-loop harness that renders on the fly (no prepare()), at 256 and 8
       environments, both with the BLIP-2 forward (random-init weights) and the frontier decision.
   (c) kernel time of rooms_raycast_kernel from `rocprofv3 --kernel-trace --stats`, in a run of its own (a fresh child
@@ -70,18 +70,9 @@ def probe_calls(reps: int, lines) -> None:
     for n, H, W in SIZES:
         rr, tf, hfov, lo, hi = cameras(n, H, W, dev)
         out = torch.empty((n, H, W), dtype=torch.float32, device=dev)
-        same = bool(torch.equal(rr.cast_cameras(tf, hfov, lo, hi, out=out).view(torch.int32),
-                                rr.render_cameras(tf, hfov, lo, hi).view(torch.int32)))
-        t_k, t_t = [], []
-        for r in range(reps + 10):
-            a = timed(lambda: rr.cast_cameras(tf, hfov, lo, hi, out=out))
-            b = timed(lambda: rr.render_cameras(tf, hfov, lo, hi))
-            if r >= 10:
-                t_k.append(a)
-                t_t.append(b)
+        t_k = [timed(lambda: rr.cast_cameras(tf, hfov, lo, hi, out=out)) for _ in range(reps + 10)][10:]
         torch.cuda.synchronize()
-        lines.append("calls  n=%3d %4dx%-4d  cast_cameras %9.1f us (%.1f-%.1f)   render_cameras %9.1f us (%.1f-%.1f)   ratio %6.2f   "
-                     "frames bit-equal: %s" % (n, W, H, *stats(t_k), *stats(t_t), stats(t_t)[0] / stats(t_k)[0], same))
+        lines.append("calls  n=%3d %4dx%-4d  cast_cameras %9.1f us (%.1f-%.1f)" % (n, W, H, *stats(t_k)))
         print(lines[-1], flush=True)
         del rr, out
         torch.cuda.empty_cache()
@@ -185,8 +176,8 @@ def main() -> None:
     assert torch.cuda.is_available(), "world_render_probe measures on the GPU; there is no CPU path"
     if a.trace_child:
         return trace_child()
-    lines = ["world_render_probe: device %s; (a) device events around the Python call, median (min-max) of %d calls each after 10 "
-             "warm-up calls, the two alternating" % (torch.cuda.get_device_name(0), a.reps)]
+    lines = ["world_render_probe: device %s; (a) device events around the Python call, median (min-max) of %d calls after 10 "
+             "warm-up calls" % (torch.cuda.get_device_name(0), a.reps)]
     if not a.skip_trace:
         probe_trace(lines, a.workdir)      # first, while this process has nothing queued on the device
     probe_calls(a.reps, lines)

@@ -1,6 +1,6 @@
 // world_render.hip -- depth frames of the rooms-and-pillars world (vlfm_amd/synthetic.py) ray-cast for n cameras at arbitrary
-// poses in ONE launch: the arithmetic of synthetic.wall_profile / depth_from_profile and of harness.RoomsRenderer._cast, bit for
-// bit (f64, true divisions, no contraction: the library is built with -ffp-contract=off and the two-rounding expressions below
+// poses in ONE launch: the arithmetic of synthetic.wall_profile / depth_from_profile and of synthetic.render_objects_numpy, bit
+// for bit (f64, true divisions, no contraction: the library is built with -ffp-contract=off and the two-rounding expressions below
 // go through __dmul_rn / __dadd_rn / __dsub_rn, which are never fused).
 //
 //   column u:  m = -(u - W/2) / fx;  dx = c - s*m;  dy = s + c*m;  |dx| < 1e-12 -> 1e-12 (same for dy)

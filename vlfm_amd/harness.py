@@ -33,7 +33,7 @@ from . import _lib
 from .mapping.base_map import require_gpu
 from .mapping.value_map import ValueMapBatch
 from .synthetic import MAX_DEPTH, MIN_DEPTH, BangBangController, ReplayController, Trajectory, camera_intrinsics, depth_frame, \
-    ProceduralWorlds, pose_to_tf, rgb_frame, PLAN_INVALID, PLAN_OK, PLAN_TOO_LONG, PLAN_UNREACHABLE, GridWorlds  # noqa: F401
+    ProceduralWorlds, pose_to_tf, rgb_frame, PLAN_INVALID, PLAN_OK, PLAN_TOO_LONG, PLAN_UNREACHABLE, GridWorlds, _mix32  # noqa: F401
 from .worlds import GeodesicFields, LiveWorld, RoomsRenderer, WorldObjects, WorldTable, objectnav_outcome, \
     sightings_from_stats  # noqa: F401  (the worlds' names stay importable from here)
 
@@ -60,21 +60,12 @@ class ScriptedSightings:
         self.search_min, self.search_span, self.nav_steps = search_min, search_span, nav_steps
         self.H, self.W, self.desync = height, width, desync
 
-    @staticmethod
-    def _mix(a: int, b: int, salt: int) -> int:
-        h = (a * 2654435761 + b * 40503 + salt * 97 + 0x9E3779B9) & 0xFFFFFFFF
-        h ^= h >> 16
-        h = (h * 0x85EBCA6B) & 0xFFFFFFFF
-        h ^= h >> 13
-        h = (h * 0xC2B2AE35) & 0xFFFFFFFF
-        return h ^ (h >> 16)
-
     def episode_length(self, env_id: int, k: int) -> int:
-        return 12 + self.search_min + self._mix(env_id, k, 3) % max(self.search_span, 1) + self.nav_steps
+        return 12 + self.search_min + _mix32(env_id, k, 3) % max(self.search_span, 1) + self.nav_steps
 
     def locate(self, env_id: int, step: int):
         """(episode index, step inside the episode, episode length) of environment ``env_id`` at harness step ``step``."""
-        g = step + (self._mix(env_id, 0, 9) % self.episode_length(env_id, 0) if self.desync else 0)
+        g = step + (_mix32(env_id, 0, 9) % self.episode_length(env_id, 0) if self.desync else 0)
         k = 0
         while g >= self.episode_length(env_id, k):
             g -= self.episode_length(env_id, k)
@@ -94,10 +85,10 @@ class ScriptedSightings:
         if s_ < 12:
             return []
         in_view = s_ >= n - self.nav_steps
-        u = self._mix(env_id, step, 1) / 2.0 ** 32
+        u = _mix32(env_id, step, 1) / 2.0 ** 32
         if u >= (self.in_view_rate if in_view else self.distractor_rate):
             return []
-        g = self._mix(env_id, step, 2)
+        g = _mix32(env_id, step, 2)
         cx = int(self.W * (0.2 + 0.6 * ((g & 0xFF) / 255.0)))
         cy = int(self.H * (0.45 + 0.15 * (((g >> 8) & 0xFF) / 255.0)))
         ax, ay = 40 + ((g >> 16) & 0x1F), 50 + ((g >> 21) & 0x1F)
@@ -901,7 +892,7 @@ class BatchedEpisodes:
         cam = np.tile(np.arange(K), self.E)
         hf = np.array([self.fov if c.hfov is None else c.hfov for c in self.rig.cameras])[cam]
         lo, hi = (np.array([getattr(c, a) for c in self.rig.cameras], np.float64)[cam] for a in ("min_depth", "max_depth"))
-        frames = self.rooms.cast_cameras(tf, hf, lo, hi) if self.closed_loop else self.rooms.render_cameras(tf, hf, lo, hi)
+        frames = self.rooms.cast_cameras(tf, hf, lo, hi)
         if self.rooms.painter is not None:     # scripted objects: in front of the DESIGNATED camera (the detector stage's frame)
             d_idx = torch.from_numpy(np.arange(self.E) * K + self.rig.designated).to(self.device)
             frames[d_idx] = self.rooms.painter(t_ep, frames[d_idx])

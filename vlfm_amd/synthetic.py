@@ -21,14 +21,8 @@ def camera_intrinsics(width: int, hfov_deg: float = HFOV_DEG):
 
 def depth_frame(rng: np.random.Generator, height: int = 480, width: int = 640, holes: bool = False) -> np.ndarray:
     """Piecewise-smooth wall profile + floor plane, normalised to (0,1] (no exact zeros unless holes=True)."""
-    fx, fy, _ = camera_intrinsics(width)
     wall = rng.uniform(1.0, 5.0, size=width + 30)
-    wall = np.convolve(wall, np.ones(31) / 31.0, mode="valid")[:width]
-    rows = np.arange(height)[:, None] - height // 2
-    with np.errstate(divide="ignore"):
-        floor = np.where(rows > 0, CAMERA_HEIGHT * fy / np.maximum(rows, 1e-9), np.inf)
-    d = np.minimum(wall[None, :], floor)
-    d = np.clip((d - MIN_DEPTH) / (MAX_DEPTH - MIN_DEPTH), 1e-3, 1.0).astype(np.float32)
+    d = depth_from_profile(np.convolve(wall, np.ones(31) / 31.0, mode="valid")[:width], height)
     if holes:
         for _ in range(5):
             r0, c0 = rng.integers(0, height - 40), rng.integers(0, width - 40)
@@ -141,35 +135,59 @@ def _walls_of(boxes) -> np.ndarray:
     return BOXES if boxes is None else np.asarray(boxes, np.float64).reshape(-1, 4)
 
 
+def _column_rays(c, s, fx, W: int):
+    """(dx, dy) f64 [W]: the world direction of the ray through each image column u of a camera heading (c, s) = (cos, sin)
+    with the focal length ``fx`` pixels -- (1, m) in the camera frame, m = -(u - W//2) / fx (geometry_utils.py:216-236: y_cam =
+    -(u - W//2) z / fx), so the ray parameter t == z -- with a component of |d| < 1e-12 replaced by 1e-12."""
+    m = -(np.arange(W, dtype=np.float64) - W // 2) / fx
+    dx, dy = c - s * m, s + c * m
+    return np.where(np.abs(dx) < 1e-12, 1e-12, dx), np.where(np.abs(dy) < 1e-12, 1e-12, dy)
+
+
+def _slab(b, x, y, dx, dy):
+    """The slab test of the rays (dx, dy) [W] out of (x, y) against the boxes ``b`` [B,>=4]: ([W,B] f64 tmin, the ray parameter
+    at which the column enters the box, inf where it misses it or starts inside; [W,B] bool: it enters through a y-face, i.e.
+    min(ty0, ty1) > min(tx0, tx1) -- ties: an x-face)."""
+    dx, dy = dx[:, None], dy[:, None]
+    tx0, tx1 = (b[None, :, 0] - x) / dx, (b[None, :, 2] - x) / dx
+    ty0, ty1 = (b[None, :, 1] - y) / dy, (b[None, :, 3] - y) / dy
+    ex, ey = np.minimum(tx0, tx1), np.minimum(ty0, ty1)
+    tmin = np.maximum(ex, ey)
+    tmax = np.minimum(np.maximum(tx0, tx1), np.maximum(ty0, ty1))
+    return np.where((tmax >= np.maximum(tmin, 0.0)) & (tmin > 0.0), tmin, np.inf), ey > ex
+
+
+def _within(px, py, boxes, m) -> np.ndarray:
+    """bool [...]: does the point (px, py) [...] lie within ``m`` of one of ITS boxes ``boxes`` [...,B,4] (or [B,4]: the same for
+    every point) -- the CLOSED test x0 - m <= x <= x1 + m, y0 - m <= y <= y1 + m.  Every comparison with a NaN row is False:
+    such a row blocks nothing."""
+    px, py = np.asarray(px, np.float64)[..., None], np.asarray(py, np.float64)[..., None]
+    return np.any((boxes[..., 0] - m <= px) & (px <= boxes[..., 2] + m) & (boxes[..., 1] - m <= py) & (py <= boxes[..., 3] + m),
+                  axis=-1)
+
+
 def wall_profile(x: float, y: float, k: int, width: int = ROOMS_W, boxes=None, grid=None) -> np.ndarray:
     """(width,) f32 depth along the optical axis of the nearest box face per image column (inf where nothing is hit).
     ``boxes`` [B,4]: the walls of the world (None: BOXES).  ``grid``: a GridPlan whose occupied cells are walls as well (the
     f64 minimum of the two, then rounded; grid worlds section below)."""
-    b = _walls_of(boxes)
     fx = camera_intrinsics(width)[0]
     c, s = HEADINGS[k]
-    m = -(np.arange(width, dtype=np.float64) - width // 2) / fx        # geometry_utils.py:216-236: y_cam = -(u - W//2) z / fx
-    dx, dy = (c - s * m)[:, None], (s + c * m)[:, None]        # world direction of (1, m): parameter t == z
-    tiny = 1e-12
-    dx = np.where(np.abs(dx) < tiny, tiny, dx)
-    dy = np.where(np.abs(dy) < tiny, tiny, dy)
-    tx0, tx1 = (b[None, :, 0] - x) / dx, (b[None, :, 2] - x) / dx
-    ty0, ty1 = (b[None, :, 1] - y) / dy, (b[None, :, 3] - y) / dy
-    tmin = np.maximum(np.minimum(tx0, tx1), np.minimum(ty0, ty1))
-    tmax = np.minimum(np.maximum(tx0, tx1), np.maximum(ty0, ty1))
-    hit = (tmax >= np.maximum(tmin, 0.0)) & (tmin > 0.0)
-    best = np.where(hit, tmin, np.inf).min(axis=1, initial=np.inf)                          # (initial: a world without boxes)
+    dx, dy = _column_rays(c, s, fx, width)
+    best = _slab(_walls_of(boxes), x, y, dx, dy)[0].min(axis=1, initial=np.inf)            # (initial: a world without boxes)
     if grid is not None:
         best = np.minimum(best, grid_profile_numpy(x, y, c, s, fx, width, grid))
     return best.astype(np.float32)
+
+
+def _normalise(d, lo, hi):
+    return np.clip((d - lo) / (hi - lo), 1e-3, 1.0).astype(np.float32)
 
 
 def depth_from_profile(wall: np.ndarray, height: int = ROOMS_H) -> np.ndarray:
     fy = camera_intrinsics(len(wall))[1]
     rows = np.arange(height)[:, None] - height // 2
     floor = np.where(rows > 0, CAMERA_HEIGHT * fy / np.maximum(rows, 1e-9), np.inf)
-    d = np.minimum(wall.astype(np.float64)[None, :], floor)
-    return np.clip((d - MIN_DEPTH) / (MAX_DEPTH - MIN_DEPTH), 1e-3, 1.0).astype(np.float32)
+    return _normalise(np.minimum(wall.astype(np.float64)[None, :], floor), MIN_DEPTH, MAX_DEPTH)
 
 
 def tf_of(x: float, y: float, k: int) -> np.ndarray:
@@ -179,9 +197,7 @@ def tf_of(x: float, y: float, k: int) -> np.ndarray:
 
 
 def _blocked(x: float, y: float, margin: float = 0.3, boxes=None, grid=None) -> bool:
-    b = _walls_of(boxes)
-    hit = bool(np.any((b[:, 0] - margin <= x) & (x <= b[:, 2] + margin) & (b[:, 1] - margin <= y) & (y <= b[:, 3] + margin)))
-    return hit or (grid is not None and grid_blocked(grid, x, y, margin))
+    return bool(_within(x, y, _walls_of(boxes), margin)) or (grid is not None and grid_blocked(grid, x, y, margin))
 
 
 def integrate(actions):
@@ -269,15 +285,12 @@ def step_poses(xy, k, actions, extra_boxes=None, boxes=None, grids=None):
         w = np.asarray(boxes, np.float64)
         if w.ndim != 3 or w.shape[0] != len(xy) or w.shape[2] != 4:
             raise ValueError("step_poses: boxes must be [E,B,4]")
-    blocked = np.any((w[:, :, 0] - m <= new[:, None, 0]) & (new[:, None, 0] <= w[:, :, 2] + m) &
-                     (w[:, :, 1] - m <= new[:, None, 1]) & (new[:, None, 1] <= w[:, :, 3] + m), axis=1)
+    blocked = _within(new[:, 0], new[:, 1], w, m)
     if extra_boxes is not None:
         x = np.asarray(extra_boxes, np.float64)
         if x.ndim != 3 or x.shape[0] != len(xy) or x.shape[2] != 4:
             raise ValueError("step_poses: extra_boxes must be [E,K,4]")
-        # (every comparison with a NaN row is False: such a row blocks nothing)
-        blocked = blocked | np.any((x[:, :, 0] - m <= new[:, None, 0]) & (new[:, None, 0] <= x[:, :, 2] + m) &
-                                   (x[:, :, 1] - m <= new[:, None, 1]) & (new[:, None, 1] <= x[:, :, 3] + m), axis=1)
+        blocked = blocked | _within(new[:, 0], new[:, 1], x, m)
     if grids is not None:
         if len(grids) != len(xy):
             raise ValueError("step_poses: grids must hold one plan or None per robot")
@@ -387,7 +400,8 @@ OBJECT_START_CLEARANCE = 1.5   # no object on a spot nearer than this to the rob
 
 
 def _mix32(a: int, b: int, salt: int) -> int:
-    """The 32-bit mixer of harness.ScriptedSightings._mix (a murmur3-style finaliser): a pure function, no global RNG."""
+    """The package's 32-bit mixer (a murmur3-style finaliser; harness.ScriptedSightings scripts its episodes with it): a pure
+    function, no global RNG."""
     h = (a * 2654435761 + b * 40503 + salt * 97 + 0x9E3779B9) & 0xFFFFFFFF
     h ^= h >> 16
     h = (h * 0x85EBCA6B) & 0xFFFFFFFF
@@ -428,10 +442,6 @@ def rect_distance(xy, box) -> float:
     return float(np.hypot(dx, dy))
 
 
-def _normalise(d, lo, hi):
-    return np.clip((d - lo) / (hi - lo), 1e-3, 1.0).astype(np.float32)
-
-
 def render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6, boxes=None, grid=None):
     """(depth f32 [H,W], ids u8 [H,W]) seen by ONE camera at (x, y), heading (c, s) = (cos, sin), ``height`` above the floor,
     focal length ``fx`` pixels, range [lo, hi]: the walls and the floor of `wall_profile` / `depth_from_profile`, and the
@@ -442,20 +452,9 @@ def render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6, boxes=Non
     ``grid``: a GridPlan whose occupied cells are walls as well (the f64 minimum of the two, then rounded to f32).
     Whole-array f64 NumPy."""
     boxes6 = np.asarray(boxes6, np.float64).reshape(-1, 6)
-    m = -(np.arange(W, dtype=np.float64) - W // 2) / fx
-    dx, dy = c - s * m, s + c * m
-    dx = np.where(np.abs(dx) < 1e-12, 1e-12, dx)[:, None]
-    dy = np.where(np.abs(dy) < 1e-12, 1e-12, dy)[:, None]
-
-    def slab(b):       # [W,B] distance along the optical axis to each box, inf where the column misses it
-        tx0, tx1 = (b[None, :, 0] - x) / dx, (b[None, :, 2] - x) / dx
-        ty0, ty1 = (b[None, :, 1] - y) / dy, (b[None, :, 3] - y) / dy
-        tmin = np.maximum(np.minimum(tx0, tx1), np.minimum(ty0, ty1))
-        tmax = np.minimum(np.maximum(tx0, tx1), np.maximum(ty0, ty1))
-        return np.where((tmax >= np.maximum(tmin, 0.0)) & (tmin > 0.0), tmin, np.inf)
-
+    dx, dy = _column_rays(c, s, fx, W)
     with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
-        wall = slab(_walls_of(boxes)).min(axis=1, initial=np.inf)
+        wall = _slab(_walls_of(boxes), x, y, dx, dy)[0].min(axis=1, initial=np.inf)
         if grid is not None:
             wall = np.minimum(wall, grid_profile_numpy(x, y, c, s, fx, W, grid))
         wall = wall.astype(np.float32).astype(np.float64)
@@ -464,7 +463,7 @@ def render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, boxes6, boxes=Non
         bg = np.minimum(_normalise(wall, lo, hi)[None, :], _normalise(floor, lo, hi))              # [H,W] f32
         if not len(boxes6):
             return bg, np.zeros((H, W), np.uint8)
-        t = slab(boxes6).astype(np.float32).astype(np.float64)                                      # [W,K]
+        t = _slab(boxes6, x, y, dx, dy)[0].astype(np.float32).astype(np.float64)                    # [W,K]
         rlo = np.ceil(((height - boxes6[None, :, 5]) * fx) / t)
         rhi = np.floor(((height - boxes6[None, :, 4]) * fx) / t)
         cover = np.isfinite(t)[None] & (rlo[None] <= rr[:, :, None]) & (rr[:, :, None] <= rhi[None])   # [H,W,K]
@@ -553,18 +552,7 @@ def _rgb_geometry(x, y, c, s, height, fx, H, W, boxes6, boxes=None):
     """The geometry `render_rgb_numpy` colours by: per column b_w, t_w, wall_y (a y-face), panel, r_sk and obj_y [W,K]; per
     pixel on_floor (floor_d < t_w) and check (the floor's checker bit)."""
     walls = _walls_of(boxes)
-    m = -(np.arange(W, dtype=np.float64) - W // 2) / fx
-    dx, dy = c - s * m, s + c * m
-    dx = np.where(np.abs(dx) < 1e-12, 1e-12, dx)
-    dy = np.where(np.abs(dy) < 1e-12, 1e-12, dy)
-
-    def slab(b):       # ([W,B] tmin, inf where the column misses the box; [W,B] bool: a y-face)
-        tx0, tx1 = (b[None, :, 0] - x) / dx[:, None], (b[None, :, 2] - x) / dx[:, None]
-        ty0, ty1 = (b[None, :, 1] - y) / dy[:, None], (b[None, :, 3] - y) / dy[:, None]
-        ex, ey = np.minimum(tx0, tx1), np.minimum(ty0, ty1)
-        tmin = np.maximum(ex, ey)
-        tmax = np.minimum(np.maximum(tx0, tx1), np.maximum(ty0, ty1))
-        return np.where((tmax >= np.maximum(tmin, 0.0)) & (tmin > 0.0), tmin, np.inf), ey > ex
+    dx, dy = _column_rays(c, s, fx, W)
 
     def odd(v):        # int64(floor(v)) & 1, 0 where v is not finite
         return np.floor(np.where(np.isfinite(v), v, 0.0)).astype(np.int64) & 1
@@ -572,7 +560,7 @@ def _rgb_geometry(x, y, c, s, height, fx, H, W, boxes6, boxes=None):
     cols = np.arange(W)
     with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
         if len(walls):
-            t, yface = slab(walls)
+            t, yface = _slab(walls, x, y, dx, dy)
             b_w = t.argmin(axis=1)                                      # (argmin: the first, i.e. lowest, index among equals)
             t_w = t[cols, b_w].astype(np.float32).astype(np.float64)
             wall_y = yface[cols, b_w]
@@ -587,7 +575,7 @@ def _rgb_geometry(x, y, c, s, height, fx, H, W, boxes6, boxes=None):
         fd = np.where(on_floor, floor_d, 0.0)
         px, py = x + dx[None, :] * fd, y + dy[None, :] * fd
         check = (odd(px * 2.0) + odd(py * 2.0)) & 1
-        obj_y = slab(np.asarray(boxes6, np.float64).reshape(-1, 6)[:, :4])[1]                       # [W,K]
+        obj_y = _slab(np.asarray(boxes6, np.float64).reshape(-1, 6), x, y, dx, dy)[1]               # [W,K]
     return {"b_w": b_w, "t_w": t_w, "wall_y": wall_y, "panel": odd(q * 2.0), "r_sk": r_sk, "on_floor": on_floor,
             "check": check, "obj_y": obj_y}
 
@@ -645,7 +633,7 @@ def inflated_rects(objects=None, margin: float = STEP_MARGIN, boxes=None) -> np.
     """[R,4] f64 (x0 - m, y0 - m, x1 + m, y1 + m): the walls ``boxes`` (default BOXES), then the objects in slot order.
     ``objects``: [K,8] ray-caster records (a slot counts iff its ``valid`` field, column 6, is non-zero) or [K,4] / [K,6]
     boxes (all count)."""
-    b = np.asarray(BOXES if boxes is None else boxes, np.float64).reshape(-1, 4)
+    b = _walls_of(boxes)
     if objects is not None and len(objects):
         o = np.asarray(objects, np.float64)
         o = o.reshape(-1, o.shape[-1])
@@ -701,9 +689,7 @@ def goal_viewpoints(target_box, rects, success_distance: float, max_points: int 
     dx = np.maximum(np.maximum(x0 - px, 0.0), px - x1)
     dy = np.maximum(np.maximum(y0 - py, 0.0), py - y1)
     keep = dx * dx + dy * dy <= r * r
-    b = np.asarray(rects, np.float64).reshape(-1, 4)
-    keep &= ~np.any((b[None, :, 0] <= px[:, None]) & (px[:, None] <= b[None, :, 2]) &
-                    (b[None, :, 1] <= py[:, None]) & (py[:, None] <= b[None, :, 3]), axis=1)
+    keep &= ~_within(px, py, np.asarray(rects, np.float64).reshape(-1, 4), 0.0)     # (inflated already: e - 0.0 is e)
     pts = np.stack([px[keep], py[keep]], axis=1)
     if len(pts) > max_points:
         raise ValueError(f"goal_viewpoints: {len(pts)} view points, at most {max_points} fit a geodesic field")
@@ -1090,10 +1076,7 @@ def grid_profile_numpy(x, y, c, s, fx, W: int, plan: GridPlan, return_steps: boo
     ``plan`` (inf: none) -- the grid walk of the rule above, vectorised over columns; bit for bit
     min over grid_boxes(plan) of the slab test's tmin BEFORE the rounding to f32.  ``return_steps``: also int64 [W], the cells
     each column's walk entered."""
-    m = -(np.arange(W, dtype=np.float64) - W // 2) / fx
-    dx, dy = c - s * m, s + c * m
-    dx = np.where(np.abs(dx) < 1e-12, 1e-12, dx)
-    dy = np.where(np.abs(dy) < 1e-12, 1e-12, dy)
+    dx, dy = _column_rays(c, s, fx, W)
     nx, ny, xs, ys = plan.nx, plan.ny, plan.xs, plan.ys
     occ = np.zeros((ny + 2, nx + 2), bool)              # a free ring around the grid: cell (i, j) is occ[j + 1, i + 1]
     occ[1:-1, 1:-1] = plan.occ

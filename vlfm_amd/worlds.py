@@ -10,10 +10,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TURN_RIGHT, BOXES, CAMERA_HEIGHT, HEADINGS, \
-    MAX_DEPTH, MIN_DEPTH, YAWS, camera_intrinsics, integrate, GEODESIC_MAX_SOURCES, STEP_MARGIN, WORLD_MAX_BOXES, \
-    WORLD_MAX_OBJECTS, goal_viewpoints, inflated_rects, object_layout, plan_actions, rect_distance, soft_spl, spl, step_poses, \
-    tf_of, OBJECT_COLOURS, WORLD_PALETTE, GRID_MAX_CELLS, GridPlan
+from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TURN_RIGHT, BOXES, MAX_DEPTH, MIN_DEPTH, YAWS, \
+    camera_intrinsics, integrate, GEODESIC_MAX_SOURCES, STEP_MARGIN, WORLD_MAX_BOXES, WORLD_MAX_OBJECTS, goal_viewpoints, \
+    inflated_rects, object_layout, plan_actions, rect_distance, soft_spl, spl, step_poses, tf_of, OBJECT_COLOURS, WORLD_PALETTE, \
+    GRID_MAX_CELLS, GridPlan
 
 
 @dataclass(frozen=True)
@@ -186,83 +186,32 @@ class WorldTable:
 
 class RoomsRenderer:
     """Depth frames of the consistent rooms-and-pillars world (vlfm_amd/synthetic.py) for E environments at once, ray-cast ON
-    THE DEVICE (f64, the arithmetic of synthetic.wall_profile / depth_from_profile batched over environments): environment
-    e walks the planned tour starting ``37 * env_id mod L`` steps in, so the batch sees rooms, doorways, pillars and a dozen
-    or more simultaneous frontiers instead of the per-frame random walls of depth_frame().  ``prepare(t0, n)`` renders a
-    window of steps ahead of a timed region (inputs resident in HBM before the clock starts); other steps render on the fly."""
+    THE DEVICE by one kernel (csrc/world_render.hip; f64, bit for bit synthetic.render_objects_numpy, and for the table's
+    headings depth_from_profile(wall_profile(...))): environment e walks the planned tour starting ``37 * env_id mod L`` steps
+    in, so the batch sees rooms, doorways, pillars and a dozen or more simultaneous frontiers instead of the per-frame random
+    walls of depth_frame().  ``prepare(t0, n)`` renders a window of steps ahead of a timed region (inputs resident in HBM
+    before the clock starts); other steps render on the fly."""
 
     def __init__(self, env_ids, episode_len: int, height: int, width: int, device) -> None:
-        self.L, self.H, self.W, self.device = episode_len, height, width, device
+        self.L, self.H, self.W = episode_len, height, width
+        self.device = torch.empty(0, device=device).device           # with its index, as a tensor on it reports it
         poses = integrate(plan_actions(2 * episode_len))            # two laps of the tour: no wrap inside an episode
         offs = [(37 * int(i)) % episode_len for i in env_ids]
         at = [[poses[o + t] for o in offs] for t in range(episode_len)]
         self.pose_table = np.array([[(x, y, YAWS[k]) for (x, y, k) in row] for row in at])       # [L,E,3]
         self.tf_table = np.stack([np.stack([tf_of(x, y, k) for (x, y, k) in row]) for row in at])  # [L,E,4,4]
         self.k_table = np.array([[k for (_, _, k) in row] for row in at], np.int64)               # [L,E] heading indices
-        f64 = dict(dtype=torch.float64, device=device)
-        self.xy = torch.tensor([[(x, y) for (x, y, _) in row] for row in at], **f64)             # [L,E,2]
-        self.cs = torch.tensor([[HEADINGS[k] for (_, _, k) in row] for row in at], **f64)        # [L,E,2] exact (cos, sin)
-        fx, fy, _ = camera_intrinsics(width)
-        self.m = (-(torch.arange(width, **f64) - width // 2) / fx)[None, :, None]               # [1,W,1]
-        rows = torch.arange(height, **f64) - height // 2
-        self.floor = torch.where(rows > 0, CAMERA_HEIGHT * fy / rows.clamp(min=1e-9),
-                                 torch.full_like(rows, float("inf")))[None, :, None]            # [1,H,1]
-        self.boxes = torch.tensor(BOXES, **f64)                                                  # [B,4]
         self.window = None
         self.window_t0 = 0
         self.painter = None      # optional (t, frames [E,H,W]) -> frames: scripted objects in front of the walls
-        self.table = WorldTable(1, self.boxes.device, len(BOXES))     # the rooms world for the kernels: a world table of one row
+        self.table = WorldTable(1, self.device, len(BOXES))     # the rooms world for the kernels: a world table of one row
         self.table.assign([0], [BOXES])
 
     @torch.no_grad()
     def render(self, t: int) -> torch.Tensor:
         """[E,H,W] f32 normalised depth of episode step t."""
-        d = self._render_walls(t)
+        d = self.cast_cameras(self.tf_table[t])
         return self.painter(t, d) if self.painter is not None else d
-
-    def _render_walls(self, t: int) -> torch.Tensor:
-        return self._cast(self.xy[t], self.cs[t], self.m, self.floor)
-
-    @torch.no_grad()
-    def render_cameras(self, tf: np.ndarray, hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None) -> torch.Tensor:
-        """[n,H,W] f32 normalised depth seen from n camera -> episodic transforms [n,4,4] (yaw about z; a camera is just another
-        pose for the ray caster): position tf[:, :2, 3], heading (cos, sin) = tf[:, :2, 0], height tf[:, 2, 3]; ``hfov`` [n]
-        per camera (None = the renderer's); ``min_depth`` / ``max_depth`` [n]: each camera's own range, which its frame is
-        normalised to (None = 0.5 / 5 m), so that a short-range camera sees a far wall as "beyond range", not nearer.  Walls only: the painter of scripted objects belongs to the robot's own frame."""
-        tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        xy, cs = torch.tensor(tf[:, :2, 3], **f64), torch.tensor(tf[:, :2, 0], **f64)
-        fx = np.full(len(tf), camera_intrinsics(self.W)[0]) if hfov is None else \
-            self.W / (2 * np.tan(np.asarray(hfov, np.float64) / 2))
-        m = -(torch.arange(self.W, **f64)[None, :] - self.W // 2) / torch.tensor(fx, **f64)[:, None]      # [n,W]
-        rows = (torch.arange(self.H, **f64) - self.H // 2)[None, :]
-        height = torch.tensor(tf[:, 2, 3], **f64)[:, None]
-        floor = torch.where(rows > 0, height * torch.tensor(fx, **f64)[:, None] / rows.clamp(min=1e-9),
-                            torch.full_like(rows, float("inf")).expand(len(tf), -1))                      # [n,H]
-        lo = None if min_depth is None else torch.tensor(np.asarray(min_depth, np.float64), **f64)[:, None, None]
-        hi = None if max_depth is None else torch.tensor(np.asarray(max_depth, np.float64), **f64)[:, None, None]
-        return self._cast(xy, cs, m[:, :, None], floor[:, :, None], lo, hi)
-
-    def _cast(self, xy: torch.Tensor, cs: torch.Tensor, m: torch.Tensor, floor: torch.Tensor, lo=None, hi=None) -> torch.Tensor:
-        x, y = xy[:, 0][:, None, None], xy[:, 1][:, None, None]
-        c, s = cs[:, 0][:, None, None], cs[:, 1][:, None, None]
-        dx, dy = c - s * m, s + c * m                                                            # [E,W,1]
-        tiny = 1e-12
-        dx = torch.where(dx.abs() < tiny, torch.full_like(dx, tiny), dx)
-        dy = torch.where(dy.abs() < tiny, torch.full_like(dy, tiny), dy)
-        b = self.boxes
-        tx0, tx1 = (b[:, 0] - x) / dx, (b[:, 2] - x) / dx                                        # [E,W,B]
-        ty0, ty1 = (b[:, 1] - y) / dy, (b[:, 3] - y) / dy
-        tmin = torch.maximum(torch.minimum(tx0, tx1), torch.minimum(ty0, ty1))
-        tmax = torch.minimum(torch.maximum(tx0, tx1), torch.maximum(ty0, ty1))
-        hit = (tmax >= tmin.clamp(min=0.0)) & (tmin > 0.0)
-        wall = torch.where(hit, tmin, torch.full_like(tmin, float("inf"))).amin(dim=2).float().double()   # f32 like the host path
-        d = torch.minimum(wall[:, None, :], floor)                                               # [E,H,W]
-        if lo is None and hi is None:
-            return ((d - MIN_DEPTH) / (MAX_DEPTH - MIN_DEPTH)).clamp(1e-3, 1.0).float()
-        lo = MIN_DEPTH if lo is None else lo
-        hi = MAX_DEPTH if hi is None else hi
-        return ((d - lo) / (hi - lo)).clamp(1e-3, 1.0).float()
 
     @torch.no_grad()
     def _raycast(self, who: str, tf: np.ndarray, table: WorldTable, world_of, objects=None, env_of=None, hfov=None,
@@ -275,7 +224,7 @@ class RoomsRenderer:
         copy (all 8-byte aligned pieces).  ``who`` names the caller in error messages."""
         tf = np.asarray(tf, np.float64).reshape(-1, 4, 4)
         n = len(tf)
-        dev = self.boxes.device
+        dev = self.device
         if table.device != dev:
             raise ValueError(f"{who}: the world table must live on {dev}")
         world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
@@ -358,10 +307,13 @@ class RoomsRenderer:
 
     def cast_cameras(self, tf: np.ndarray, hfov: Optional[np.ndarray] = None, min_depth=None, max_depth=None,
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``render_cameras`` -- same arguments, the same frames bit for bit -- in ONE kernel launch on the current stream
-        (csrc/world_render.hip) instead of a chain of torch f64 operations over [n,W,B] and [n,H,W] temporaries: what a
-        closed-loop step, which cannot pre-render, pays per step.  ``out``: a contiguous f32 [n,H,W] device tensor to render
-        into."""
+        """[n,H,W] f32 normalised depth seen from n camera -> episodic transforms [n,4,4] (yaw about z; a camera is just another
+        pose for the ray caster), ONE kernel launch on the current stream: position tf[:, :2, 3], heading (cos, sin) =
+        tf[:, :2, 0], height tf[:, 2, 3]; ``hfov`` [n] per camera (None = the renderer's); ``min_depth`` / ``max_depth`` [n]: each
+        camera's own range, which its frame is normalised to (None = 0.5 / 5 m), so that a short-range camera sees a far wall as
+        "beyond range", not nearer.  Walls only (the painter of scripted objects belongs to ``render``), bit for bit
+        synthetic.render_objects_numpy(x, y, c, s, height, fx, lo, hi, H, W, [])[0].  ``out``: a contiguous f32 [n,H,W] device
+        tensor to render into."""
         return self._raycast("cast_cameras", tf, self.table, self._rooms_world_of(tf), None, None, hfov, min_depth, max_depth,
                              out)[0]
 
@@ -423,7 +375,7 @@ class RoomsRenderer:
         if objects.ndim != 3 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
             raise ValueError(f"geodesic_fields_worlds: objects must be [n, {WORLD_MAX_OBJECTS}, 8]")
         n = len(objects)
-        dev = self.boxes.device
+        dev = self.device
         if table.device != dev:
             raise ValueError(f"geodesic_fields_worlds: the world table must live on {dev}")
         world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
@@ -472,7 +424,7 @@ class RoomsRenderer:
         field_of = np.ascontiguousarray(np.asarray(field_of).reshape(-1), np.int32)
         if len(field_of) != m or np.any((field_of < -1) | (field_of >= handle.n)):
             raise ValueError("geodesic_distances: field_of must name one field of the handle (or -1) per point")
-        dev = self.boxes.device
+        dev = self.device
         out = torch.empty((m,), dtype=torch.float64, device=dev)
         if m == 0:
             return out
