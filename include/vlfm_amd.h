@@ -1042,6 +1042,57 @@ int vlfm_plan_paths(const int32_t* d_navigable, int n_envs, int size, const Vlfm
                     int max_cost, uint16_t* d_fields, int field_h, int field_w, VlfmPlanResult* d_results, void* d_scratch,
                     size_t scratch_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Lattice geodesic (ABI 26, csrc/lattice_geodesic.hip): the ObjectNav metrics' geodesic for worlds the visibility graph above
+ * cannot hold -- grid worlds, box worlds beyond 141 rectangles -- on a metric lattice with integer costs.  Bit for bit
+ * vlfm_amd.synthetic.lattice_free_numpy / lattice_field_numpy / lattice_query_numpy; integers everywhere except the free test
+ * and the query (f64, one rounding per operation, no fused multiply-add).
+ *   lattice     n = cells_per_metre, a multiple of 4.  Node (a, b), global integers, sits at (a / n, b / n), true divisions.
+ *               Field f covers a0 .. a0 + na - 1 by b0 .. b0 + nb - 1: d_dims [n][4] int32 = a0, b0, na, nb, with na and nb
+ *               clamped to [0, max_na] and [0, max_nb] by the kernels (a zero: the field has no nodes).  Nodes outside do not
+ *               exist.  max_nb and max_na, in [1, VLFM_LATTICE_MAX_NODES], are the strides of every plane of a call.
+ *   free        node (x, y) is blocked iff some obstacle has x0 - m < x < x1 + m and y0 - m < y < y1 + m (OPEN sets, the
+ *               expressions of the geodesic above): the `count` boxes of the field's world, the occupied cells of its grid, the
+ *               object slots with valid != 0.  Grid cells are not looped over: edge - m and edge + m are monotone in the edge,
+ *               two strict binary searches per axis give the block of cells that pass, and the node is blocked iff a bit of
+ *               that block is set.  Free planes: uint32 [n][max_nb][ceil(max_na / 32)], bit a % 32 of word a / 32 of row b
+ *               (local indices); vlfm_lattice_free writes zeros beyond a field's dims.
+ *   moves       16-connected: cost 5 straight, 7 diagonal, 11 for a knight move (+-2, +-1) / (+-1, +-2).  Both ends free, and
+ *               the intermediate nodes: a diagonal needs the two nodes that share an edge with both ends; a knight move (2s, t)
+ *               from (a, b) needs (a + s, b) and (a + s, b + t); (s, 2t) needs (a, b + t) and (a + s, b + t).  Symmetric.
+ *   sources     d_sources [n][max_sources][2] int32 global nodes (a, b), d_source_counts [n] (clamped to [0, max_sources]);
+ *               a source outside its lattice or on a blocked node is ignored.
+ *   field       d_dist uint16 [n][max_nb][max_na]: the least cost over move sequences from a source; 0xFFFF: none, above
+ *               max_cost (in [0, 65534]), or beyond the field's dims.
+ *   query       p = (x, y) in field f: fa = floor(x * n), fb = floor(y * n); over the four nodes (fa | fa + 1, fb | fb + 1)
+ *               that lie in the lattice and hold a cost, d = min fl(sqrt(dx*dx + dy*dy) + cost / (5.0 * n)) with
+ *               dx = x - a / n, dy = y - b / n; inf if none qualifies; a field outside [0, n_fields): NaN.
+ * cost / (5 n) is the path length in metres; in free space it lies within [0.98387, 1.01980] of the Euclidean length.
+ *
+ * vlfm_lattice_free: the free planes of n fields (n <= 65535), ONE launch on `stream`.  World table, grids (all three arrays
+ * or all three NULL), d_world_of, margin and d_objects (NULL: no objects) as in vlfm_worlds_raycast_grids / vlfm_geodesic_fields.
+ * vlfm_lattice_fields: a memset that presets d_dist, then ONE kernel, one workgroup per field.  It reads free planes, never
+ * worlds; whatever the planes hold beyond a field's dims is ignored.  Returns VLFM_LATTICE_IN_LDS (0) when the fourteen bit
+ * planes of a max_nb x max_na lattice fit 160 KB of LDS (e.g. 256 x 256); else VLFM_LATTICE_IN_SCRATCH (1): `free` and `open`
+ * stay in LDS and the twelve level planes live in d_scratch (while two planes fit: up to about 780 x 780); else
+ * VLFM_LATTICE_ALL_IN_SCRATCH (2).  d_scratch: at least vlfm_lattice_scratch_bytes(n, max_nb, max_na) bytes (0 when LDS holds
+ * everything; VLFM_ERR_CAPACITY if the scratch is smaller).  Same results in all three.
+ * vlfm_lattice_query: d of m points, ONE launch.
+ * A bound outside [1, 1024], cells_per_metre not a positive multiple of 4, negative counts, max_cost outside [0, 65534] or a
+ * missing array: VLFM_ERR_INVALID, nothing launched, nothing written.  n == 0 and m == 0 return VLFM_OK without a launch. */
+#define VLFM_LATTICE_MAX_NODES 1024
+enum { VLFM_LATTICE_IN_LDS = 0, VLFM_LATTICE_IN_SCRATCH = 1, VLFM_LATTICE_ALL_IN_SCRATCH = 2 };
+int vlfm_lattice_free(const double* d_world_boxes, const int32_t* d_box_counts, int n_worlds, int max_boxes,
+                      const uint32_t* d_grid_bits, const double* d_grid_edges, const int32_t* d_grid_dims, int max_nx, int max_ny,
+                      const int32_t* d_world_of, double margin, const double* d_objects, const int32_t* d_dims, int n,
+                      int cells_per_metre, int max_nb, int max_na, uint32_t* d_free, void* stream);
+size_t vlfm_lattice_scratch_bytes(int n, int max_nb, int max_na);
+int vlfm_lattice_fields(const uint32_t* d_free, const int32_t* d_dims, int n, int max_nb, int max_na, const int32_t* d_sources,
+                        const int32_t* d_source_counts, int max_sources, int max_cost, uint16_t* d_dist, void* d_scratch,
+                        size_t scratch_bytes, void* stream);
+int vlfm_lattice_query(const double* d_points, const int32_t* d_field_of, int m, int n_fields, const uint16_t* d_dist,
+                       const int32_t* d_dims, int max_nb, int max_na, int cells_per_metre, double* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

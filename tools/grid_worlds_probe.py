@@ -12,8 +12,17 @@ vlfm_worlds_raycast_grids) cost, measured in one place.
   (b) closed-loop ObjectNav at 256 environments without a model (stub cosines): env-steps/s in procedural box worlds and in
       their rasterised twins, the two harnesses alternating over 3 windows of --steps steps in one process, 45 steps in.
 
+  (c) --geodesic lattice: what scoring SPL on the metric lattice costs (RoomsRenderer.lattice_fields_worlds / lattice_distances):
+      kernel times of lattice_free_kernel, lattice_fields_kernel and lattice_query_kernel from a rocprofv3 kernel trace in a child
+      process of its own, for 8 and 256 fields of the rooms world and of the 400 x 400 plans of (a); the host statement's time for
+      one field of each; and closed-loop env-steps/s at 256 environments in the rooms world with the metrics off, with
+      geodesic="graph" and with geodesic="lattice", three harnesses alternating over 3 windows whose leg order rotates.  It
+      runs INSTEAD of (a) and (b).
+
     python tools/grid_worlds_probe.py [--windows 5] [--steps 20] [--parent-lib PATH] [--skip-steps] [--skip-trace] [--out profiles/grid_worlds_probe.txt]
-    python tools/grid_worlds_probe.py --trace-child        # the process (a) points rocprofv3 at"""
+    python tools/grid_worlds_probe.py --geodesic lattice [--steps 20] [--skip-steps] [--skip-trace] [--out profiles/lattice_geodesic_probe.txt]
+    python tools/grid_worlds_probe.py --trace-child        # the process (a) points rocprofv3 at
+    python tools/grid_worlds_probe.py --lattice-child      # the process (c) points rocprofv3 at"""
 import argparse
 import ctypes
 import glob
@@ -248,6 +257,148 @@ def probe_steps(steps: int, lines) -> None:
     print(lines[-1], flush=True)
 
 
+# ------------------------------------------------------------------------------------------------ (c) the lattice geodesic
+LATTICE_FIELDS = (8, 256)
+LATTICE_KINDS = ("rooms world", "400x400 plan")
+LATTICE_LAUNCHES, LATTICE_WARMUP = 6, 2
+LATTICE_KERNELS = ("lattice_free_kernel", "lattice_fields_kernel", "lattice_query_kernel")
+
+
+def lattice_scene(n: int, kind: str):
+    """(renderer, table, world_of [n], objects [n,8,8], target boxes [n,4], query points [n,2]) of ``n`` fields."""
+    import numpy as np
+    import torch
+
+    from vlfm_amd import synthetic as S
+    from vlfm_amd.harness import RoomsRenderer, WorldTable
+
+    dev = torch.device("cuda:0")
+    rooms = RoomsRenderer(list(range(n)), 500, 48, 64, dev)
+    obj = np.zeros((n, S.WORLD_MAX_OBJECTS, 8))
+    if kind == LATTICE_KINDS[0]:
+        table, world_of, xy = rooms.table, np.zeros(n, np.int32), rooms.pose_table[0][:, :2].copy()
+        lays = [S.object_layout(e, 0, xy[e]) for e in range(n)]
+    else:
+        worlds = RasterisedWorlds(0)
+        made = [worlds.world(e, 0) for e in range(n)]
+        table = WorldTable(n, dev, max_grid=worlds.max_grid)
+        table.assign(np.arange(n), [w.boxes for w in made], [w.grid for w in made])
+        world_of, xy = np.arange(n, dtype=np.int32), np.stack([w.start_xy for w in made])
+        lays = [worlds.layout(e, 0, xy[e]) for e in range(n)]
+    for e, lay in enumerate(lays):
+        for k, (_, box) in enumerate(lay):
+            obj[e, k, :6], obj[e, k, 6] = box, 1.0
+    targets = np.array([obj[e, 0, :4] if len(lays[e]) else [np.nan] * 4 for e in range(n)])
+    return rooms, table, world_of, obj, targets, xy
+
+
+def lattice_child() -> None:
+    """Per field count and kind of world: LATTICE_WARMUP + LATTICE_LAUNCHES times the two field launches, then as many queries."""
+    import numpy as np
+    import torch
+
+    for n in LATTICE_FIELDS:
+        for kind in LATTICE_KINDS:
+            rooms, table, world_of, obj, targets, xy = lattice_scene(n, kind)
+            for _ in range(LATTICE_WARMUP + LATTICE_LAUNCHES):
+                h = rooms.lattice_fields_worlds(table, world_of, obj, targets, 1.0)
+                torch.cuda.synchronize()
+            for _ in range(LATTICE_WARMUP + LATTICE_LAUNCHES):
+                rooms.lattice_distances(h, np.arange(n), xy)
+            torch.cuda.synchronize()
+
+
+def probe_lattice_trace(lines, workdir: str) -> None:
+    import time
+
+    import numpy as np
+
+    from vlfm_amd import synthetic as S
+
+    if shutil.which("rocprofv3") is None:
+        raise RuntimeError("rocprofv3 not found: the kernel-time leg needs it (--skip-trace leaves the leg out)")
+    shutil.rmtree(workdir, ignore_errors=True)
+    os.makedirs(workdir)
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", workdir, "-o", "lattice", "--", sys.executable, os.path.abspath(__file__),
+           "--lattice-child"]
+    with open(os.path.join(workdir, "child.log"), "w") as log:
+        subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, timeout=500)
+    dbs = glob.glob(os.path.join(workdir, "**", "*_results.db"), recursive=True)
+    if not dbs:
+        raise RuntimeError(f"no rocprofv3 database under {workdir}")
+    rows = sqlite3.connect(dbs[0]).execute("select name, start, end from kernels order by start").fetchall()
+    per = LATTICE_WARMUP + LATTICE_LAUNCHES
+    groups = [(n, kind) for n in LATTICE_FIELDS for kind in LATTICE_KINDS]
+    for kernel in LATTICE_KERNELS:
+        us = [(e - s) * 1e-3 for (name, s, e) in rows if kernel in name]
+        if len(us) != per * len(groups):
+            raise RuntimeError(f"expected {per * len(groups)} dispatches of {kernel}, found {len(us)}")
+        for g, (n, kind) in enumerate(groups):
+            lines.append("kernel fields=%3d  %-13s %-22s %10.1f us (%.1f-%.1f over %d launches after %d)"
+                         % (n, kind, kernel, *stats(us[g * per + LATTICE_WARMUP:(g + 1) * per]), LATTICE_LAUNCHES, LATTICE_WARMUP))
+            print(lines[-1], flush=True)
+    for kind in LATTICE_KINDS:          # the host statement, one field
+        if kind == LATTICE_KINDS[0]:
+            boxes, grid, lay = None, None, S.object_layout(0, 0, np.zeros(2))
+        else:
+            w = RasterisedWorlds(0).world(0, 0)
+            boxes, grid, lay = w.boxes, w.grid, RasterisedWorlds(0).layout(0, 0, w.start_xy)
+        obj = np.zeros((S.WORLD_MAX_OBJECTS, 8))
+        for k, (_, box) in enumerate(lay):
+            obj[k, :6], obj[k, 6] = box, 1.0
+        t0 = time.perf_counter()
+        ext = S.lattice_extent(boxes, grid, obj)
+        free = S.lattice_free_numpy(ext, boxes, grid, obj)
+        t1 = time.perf_counter()
+        pts = S.goal_viewpoints(obj[0, :4], S.inflated_rects(obj, S.STEP_MARGIN, boxes), 1.0, grid=grid)
+        t2 = time.perf_counter()
+        field = S.lattice_field_numpy(free, S.lattice_sources(pts), ext[:2])
+        t3 = time.perf_counter()
+        lines.append("host   one field     %-13s %d x %d nodes: free mask %.1f ms, view points %.1f ms, field %.1f ms (largest cost %d)"
+                     % (kind, ext[2], ext[3], 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2), int(field[field != S.LATTICE_NONE].max())))
+        print(lines[-1], flush=True)
+
+
+def probe_lattice_steps(steps: int, lines) -> None:
+    import time
+
+    import numpy as np
+    import torch
+
+    from vlfm_amd.harness import BatchedEpisodes, WorldObjects
+
+    E = 256
+    legs = {"metrics off": {}, 'geodesic="graph"': dict(objectnav_metrics=True, geodesic="graph"),
+            'geodesic="lattice"': dict(objectnav_metrics=True, geodesic="lattice")}
+    sims = {}
+    for name, kw in legs.items():
+        sims[name] = BatchedEpisodes(E, device=torch.device("cuda:0"), use_blip2=False, select_frontiers=True, episode_len=500,
+                                     closed_loop=True, object_maps=True, world_objects=WorldObjects(), **kw)
+        for _ in range(45):
+            sims[name].step()
+    names = list(sims)
+    rate = {k: [] for k in sims}
+    for w in range(3):                  # alternating windows, the order rotated by one per window
+        for name in names[w % 3:] + names[:w % 3]:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                sims[name].step()
+            torch.cuda.synchronize()
+            rate[name].append(E * steps / (time.perf_counter() - t0))
+    ref = sims[names[0]]
+    for name, s in sims.items():
+        s.check()
+        same = np.array_equal(s.live.xy, ref.live.xy) and np.array_equal(s.live.k, ref.live.k)
+        lines.append("steps  E=%3d  ObjectNav, rooms world  %-19s %8.1f env-steps/s (%.1f-%.1f over 3 windows of %d steps); episodes "
+                     "scored %d; poses equal to the first leg's: %s" % (E, name, *stats(rate[name]), steps,
+                                                                       len(s.live.objectnav_stats["episode_outcome"]), same))
+        print(lines[-1], flush=True)
+    for name in names[1:]:
+        lines.append("steps  summary %-19s %s" % (name, sims[name].live.objectnav_summary()))
+        print(lines[-1], flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=5)
@@ -259,12 +410,29 @@ def main() -> None:
     ap.add_argument("--workdir", default=os.path.join(ROOT, "scratch", "grid_worlds_trace"),
                     help="where the kernel trace of leg (a) is written (removed and rewritten by every run)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--geodesic", choices=("none", "lattice"), default="none", help="lattice: leg (c), the lattice geodesic")
+    ap.add_argument("--lattice-child", action="store_true")
     a = ap.parse_args()
     import torch
 
     assert torch.cuda.is_available(), "grid_worlds_probe measures on the GPU; there is no CPU path"
     if a.trace_child:
         return trace_child(a.windows, a.parent_lib)
+    if a.lattice_child:
+        return lattice_child()
+    if a.geodesic == "lattice":
+        lines = ["grid_worlds_probe --geodesic lattice: device %s; rocprofv3 kernel trace of lattice_fields_worlds / lattice_distances "
+                 "at 20 nodes per metre, pad 1 m; closed loop without a model, stub cosines, object maps on"
+                 % torch.cuda.get_device_name(0)]
+        if not a.skip_trace:
+            probe_lattice_trace(lines, a.workdir + "_lattice")
+        if not a.skip_steps:
+            probe_lattice_steps(a.steps, lines)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     lines = ["grid_worlds_probe: device %s; (a) rocprofv3 kernel trace of %dx%d frames with objects, legs alternating over windows of %d "
              "launches after %d warm-up launches each; worlds: ProceduralWorlds(0).world(e, 0) as boxes and rasterised at %d cells per "
              "metre; (b) no model, stub cosines, object maps on" % (torch.cuda.get_device_name(0), W, H, TRACE_LAUNCHES, TRACE_WARMUP,

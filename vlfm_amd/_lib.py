@@ -13,7 +13,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlfm_amd.so")
-SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "qformer_attention.hip", "detect_ops.hip", "object_cloud.hip", "cloud_query.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "world_render.hip", "geodesic.hip", "map_planner.hip", "host.cpp"]
+SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "qformer_attention.hip", "detect_ops.hip", "object_cloud.hip", "cloud_query.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "world_render.hip", "geodesic.hip", "map_planner.hip", "lattice_geodesic.hip", "host.cpp"]
 
 VLFM_OK = 0
 VLFM_ERR_INVALID = -1
@@ -76,6 +76,7 @@ class PlanResult(ctypes.Structure):       # VlfmPlanResult
 
 PLAN_OK, PLAN_UNREACHABLE, PLAN_TOO_LONG, PLAN_INVALID = 0, 1, 2, 3
 PLAN_IN_LDS, PLAN_IN_SCRATCH = 0, 1
+LATTICE_IN_LDS, LATTICE_IN_SCRATCH, LATTICE_ALL_IN_SCRATCH = 0, 1, 2
 
 assert ctypes.sizeof(PlanJob) == 48 and ctypes.sizeof(PlanResult) == 32
 assert ctypes.sizeof(CloudQuery) == 80
@@ -250,6 +251,11 @@ def lib() -> ctypes.CDLL:
         L.vlfm_plan_scratch_bytes.argtypes = [ci, ci]
         L.vlfm_plan_scratch_bytes.restype = ctypes.c_size_t
         L.vlfm_plan_paths.argtypes = [vp, ci, ci, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.c_size_t, vp]
+        L.vlfm_lattice_free.argtypes = [vp, vp, ci, ci, vp, vp, vp, ci, ci, vp, cd, vp, vp, ci, ci, ci, ci, vp, vp]
+        L.vlfm_lattice_scratch_bytes.argtypes = [ci, ci, ci]
+        L.vlfm_lattice_scratch_bytes.restype = ctypes.c_size_t
+        L.vlfm_lattice_fields.argtypes = [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp, vp, ctypes.c_size_t, vp]
+        L.vlfm_lattice_query.argtypes = [vp, vp, ci, ci, vp, vp, ci, ci, ci, vp, vp]
         _lib = L
     return _lib
 

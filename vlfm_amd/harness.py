@@ -34,8 +34,8 @@ from .mapping.base_map import require_gpu
 from .mapping.value_map import ValueMapBatch
 from .synthetic import MAX_DEPTH, MIN_DEPTH, BangBangController, ReplayController, Trajectory, camera_intrinsics, depth_frame, \
     ProceduralWorlds, pose_to_tf, rgb_frame, PLAN_INVALID, PLAN_OK, PLAN_TOO_LONG, PLAN_UNREACHABLE, GridWorlds, _mix32  # noqa: F401
-from .worlds import GeodesicFields, LiveWorld, RoomsRenderer, WorldObjects, WorldTable, objectnav_outcome, \
-    sightings_from_stats  # noqa: F401  (the worlds' names stay importable from here)
+from .worlds import GeodesicFields, LatticeFields, LiveWorld, RoomsRenderer, WorldObjects, WorldTable, check_geodesic_backend, \
+    objectnav_outcome, sightings_from_stats  # noqa: F401  (the worlds' names stay importable from here)
 
 PROMPT = "Seems like there is a target_object ahead."  # vlfm/policy/base_objectnav_policy.py:377
 TARGETS = ["chair", "bed", "potted plant", "toilet", "tv", "couch"]  # HM3D ObjectNav categories
@@ -194,7 +194,8 @@ class BatchedEpisodes:
                  text_prompt: str = PROMPT, exploration_thresh: Optional[float] = None, closed_loop: bool = False,
                  controller=None, world_objects: Optional[WorldObjects] = None, batch_object_maps: bool = True,
                  device_object_clouds: bool = True, objectnav_metrics: bool = False,
-                 worlds: Optional[Union[ProceduralWorlds, GridWorlds]] = None, render_rgb: bool = False) -> None:
+                 worlds: Optional[Union[ProceduralWorlds, GridWorlds]] = None, render_rgb: bool = False,
+                 geodesic: str = "graph") -> None:
         # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
         # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -262,9 +263,11 @@ class BatchedEpisodes:
             if getattr(worlds, "max_grid", None) is not None:
                 if render_rgb:
                     raise ValueError("grid worlds cannot be combined with render_rgb: wall colours are defined by box and face")
-                if objectnav_metrics:
-                    raise ValueError("grid worlds cannot be combined with objectnav_metrics: the geodesic fields hold at most "
-                                     "141 rectangles")
+        # geodesic: what the metrics measure path lengths with -- "graph": the visibility graph over the inflated rectangles (at
+        # most 141 of them: no grid worlds); "lattice": the 16-connected metric lattice with integer costs, for every kind of world
+        # (csrc/lattice_geodesic.hip; within [0.9838, 1.05] of the graph's lengths in the rooms world).  Same keys either way
+        check_geodesic_backend(geodesic, self.objectnav_metrics, worlds)
+        self.geodesic_backend = geodesic
         # render_rgb: the step's RGB frames are the camera's view of the world the depth frame shows (RoomsRenderer.cast_worlds_rgb /
         # cast_cameras_rgb: depth, ids, stats and colours from ONE launch) instead of the pool's noise -- what the transport hop,
         # BLIP-2, the detector and the segmenter then see; they stay readable as ``live.rgb``.  Off: every step is the step it was
@@ -339,7 +342,7 @@ class BatchedEpisodes:
             self.tf_table = np.stack([np.stack([pose_to_tf(x, y, yaw) for (x, y, yaw) in row]) for row in self.pose_table])
         # closed loop: the simulator -- where the robots are, their worlds, objects and episodes (worlds.LiveWorld); else None
         self.live = LiveWorld(self.rooms, self.env_ids, self.targets, world_objects, worlds, objectnav_metrics,
-                              render_rgb) if self.closed_loop else None
+                              render_rgb, geodesic) if self.closed_loop else None
         self.last_poses = self.last_world_actions = None     # closed loop: the poses the last step observed from, its actions
         # of a controller with act_on_map (MapPlannerController): plans = ok + unreachable + too_long + invalid (off the map)
         self.planner_stats = {k: np.zeros(n_envs, np.int64) for k in ("plans", "ok", "unreachable", "too_long", "invalid")}

@@ -675,11 +675,13 @@ def _edge_weights(a, b) -> np.ndarray:
     return np.sqrt(dx * dx + dy * dy)
 
 
-def goal_viewpoints(target_box, rects, success_distance: float, max_points: int = GEODESIC_MAX_SOURCES) -> np.ndarray:
+def goal_viewpoints(target_box, rects, success_distance: float, max_points: int = GEODESIC_MAX_SOURCES, boxes=None,
+                    grid=None) -> np.ndarray:
     """[S,2] f64, the sources of a geodesic field: the points (0.25 i, 0.25 j), i and j integers, with
     dx*dx + dy*dy <= r*r for `rect_distance`'s clamped offsets (dx, dy) to ``target_box[:4]`` and r = ``success_distance``,
     that `step_poses`' CLOSED test against the inflated rectangles ``rects`` does not block -- where a robot can stand and
-    have succeeded.  Ordered by (i, j).  More than ``max_points`` of them: ValueError."""
+    have succeeded.  Ordered by (i, j).  More than ``max_points`` of them: ValueError.  ``boxes`` [B,4] (NOT inflated) and
+    ``grid`` (a GridPlan): walls that block as well, by the same closed test with STEP_MARGIN (`_within`, `grid_blocked`)."""
     x0, y0, x1, y1 = (float(v) for v in np.asarray(target_box, np.float64).reshape(-1)[:4])
     r = float(success_distance)
     i = np.arange(int(np.floor((x0 - r) / 0.25)), int(np.ceil((x1 + r) / 0.25)) + 1, dtype=np.float64)
@@ -690,6 +692,11 @@ def goal_viewpoints(target_box, rects, success_distance: float, max_points: int 
     dy = np.maximum(np.maximum(y0 - py, 0.0), py - y1)
     keep = dx * dx + dy * dy <= r * r
     keep &= ~_within(px, py, np.asarray(rects, np.float64).reshape(-1, 4), 0.0)     # (inflated already: e - 0.0 is e)
+    if boxes is not None:
+        keep &= ~_within(px, py, np.asarray(boxes, np.float64).reshape(-1, 4), STEP_MARGIN)
+    if grid is not None:
+        for i in np.flatnonzero(keep):
+            keep[i] = not grid_blocked(grid, px[i], py[i], STEP_MARGIN)
     pts = np.stack([px[keep], py[keep]], axis=1)
     if len(pts) > max_points:
         raise ValueError(f"goal_viewpoints: {len(pts)} view points, at most {max_points} fit a geodesic field")
@@ -1207,6 +1214,189 @@ class GridWorlds:
 
     def layout(self, env_id: int, episode: int, robot_xy):
         return _layout_over_spots(self.world(env_id, episode).spots, env_id, episode, robot_xy)
+
+
+# ---------------------------------------------------------------------------------------------- Lattice geodesic
+# The ObjectNav metrics' second backend: the geodesic on a metric LATTICE with integer costs, for worlds the visibility graph
+# cannot hold (grid worlds: tens of thousands of occupied cells; box worlds beyond 141 rectangles).  This section is the HOST
+# STATEMENT; the device (csrc/lattice_geodesic.hip: vlfm_lattice_free / vlfm_lattice_fields / vlfm_lattice_query) matches it
+# bit for bit.  Everything is integers except the free test and the query, which are f64 with one rounding per operation.
+#
+#   lattice    n = cells_per_metre, an int and a multiple of 4 (every multiple of 0.25 m -- robot starts, grid_spots, view
+#              points -- is a node).  Node (a, b), global integers, sits at (a / n, b / n): true f64 divisions.  A field covers
+#              a0 .. a0 + na - 1 by b0 .. b0 + nb - 1 (`lattice_extent`: the hull of the world's boxes, the plan's extent and the
+#              valid object footprints, widened by STEP_MARGIN + pad_m, floor / ceil of the bound times n); na, nb <= 1024.
+#              Nodes outside the lattice do not exist.
+#   free       the obstacles of the visibility-graph rule -- the world's boxes, its occupied grid cells, the valid object
+#              footprints --, each inflated by STEP_MARGIN with `step_poses`' expressions, each an OPEN set: node (x, y) is
+#              blocked iff some obstacle has lo_x < x < hi_x and lo_y < y < hi_y.  Grid cells: edge - m and edge + m are monotone
+#              in the edge, so the cells passing each strict comparison are a run of indices, found by binary search; the node
+#              is blocked iff any cell of that block of the plan is occupied.
+#   moves      16-connected: 5 straight, 7 diagonal, 11 for a knight move (+-2, +-1) / (+-1, +-2).  Both ends free, and the
+#              intermediate nodes: a diagonal needs the two nodes that share an edge with both ends; a knight move (2s, t) from
+#              (a, b) needs (a + s, b) and (a + s, b + t); (s, 2t) needs (a, b + t) and (a + s, b + t).  Symmetric.
+#   sources    `goal_viewpoints`' points, each the node round(0.25 i * n); cost 0 if that node is free (a closed-free point is
+#              open-free, so every view point is a source).  A source outside the lattice or on a blocked node is ignored.
+#   field      uint16 [nb][na]: the least cost over move sequences from a source; 0xFFFF: none, or above ``max_cost`` (<= 65534).
+#   query      p = (x, y): fa = floor(x * n), fb = floor(y * n); over the four nodes (fa | fa + 1, fb | fb + 1) that lie in the
+#              lattice and hold a cost: d = min fl(sqrt(dx*dx + dy*dy) + cost / (5.0 * n)), dx = x - a / n, dy = y - b / n;
+#              inf if none qualifies.  No visibility test: p and the node are less than a cell apart.
+#
+# Known looseness: the chamfer is not Euclidean -- in free space cost / (5 n) over the true length lies in
+# [5.5 / (5 sqrt(1.25)), 5.2 / (5 sqrt(1.04))] = [0.98387, 1.01980], plus O(1/n) at corners and at the query; paths cannot leave
+# the padded lattice; a point inside an obstacle but within a cell of its border may get a finite value (robots never stand
+# there).  Against the visibility-graph rule in the rooms world: tests/test_lattice_geodesic_cpu.py.
+LATTICE_MAX_NODES = 1024
+LATTICE_NONE = 0xFFFF
+LATTICE_MAX_COST = 65534
+LATTICE_MOVES = tuple([(dx, dy, 5) for dx, dy in ((1, 0), (-1, 0), (0, 1), (0, -1))] +
+                      [(dx, dy, 7) for dx in (1, -1) for dy in (1, -1)] +
+                      [(2 * s, t, 11) for s in (1, -1) for t in (1, -1)] + [(s, 2 * t, 11) for s in (1, -1) for t in (1, -1)])
+
+
+def _lattice_n(cells_per_metre) -> int:
+    n = int(cells_per_metre)
+    if n != cells_per_metre or n < 4 or n % 4:
+        raise ValueError("lattice geodesic: cells_per_metre must be a positive multiple of 4 (every 0.25 m is a node)")
+    return n
+
+
+def _valid_footprints(objects) -> np.ndarray:
+    """[K,4] f64: the footprints of ``objects`` -- [K,8] ray-caster records (valid: column 6 non-zero), [K,4] / [K,6] boxes, None."""
+    if objects is None or not len(objects):
+        return np.zeros((0, 4))
+    o = np.asarray(objects, np.float64)
+    o = o.reshape(-1, o.shape[-1])
+    return (o[o[:, 6] != 0.0] if o.shape[1] == 8 else o)[:, :4]
+
+
+def lattice_extent(boxes=None, grid=None, objects=None, cells_per_metre: int = 20, pad_m: float = 1.0):
+    """(a0, b0, na, nb): the nodes a lattice field covers -- the hull of the walls ``boxes`` (None: BOXES), of ``grid``'s extent and
+    of the valid footprints of ``objects``, widened by STEP_MARGIN + pad_m; floor / ceil of the bound times n (an empty hull is
+    the origin).  ValueError when na or nb exceeds LATTICE_MAX_NODES."""
+    n = _lattice_n(cells_per_metre)
+    b = np.concatenate([_walls_of(boxes), _valid_footprints(objects)])
+    if grid is not None:
+        b = np.concatenate([b, [[grid.xs[0], grid.ys[0], grid.xs[-1], grid.ys[-1]]]])
+    if not len(b):
+        b = np.zeros((1, 4))
+    if not np.all(np.isfinite(b)) or not np.isfinite(pad_m) or pad_m < 0.0:
+        raise ValueError("lattice_extent: finite boxes and pad_m >= 0")
+    w = STEP_MARGIN + float(pad_m)
+    a0, b0 = int(np.floor((b[:, 0].min() - w) * n)), int(np.floor((b[:, 1].min() - w) * n))
+    a1, b1 = int(np.ceil((b[:, 2].max() + w) * n)), int(np.ceil((b[:, 3].max() + w) * n))
+    na, nb = a1 - a0 + 1, b1 - b0 + 1
+    if na > LATTICE_MAX_NODES or nb > LATTICE_MAX_NODES:
+        raise ValueError(f"lattice_extent: {na} x {nb} nodes, a lattice field holds at most {LATTICE_MAX_NODES} a side "
+                         f"(fewer cells_per_metre, or a smaller pad_m)")
+    return a0, b0, na, nb
+
+
+def lattice_free_numpy(extent, boxes=None, grid=None, objects=None, cells_per_metre: int = 20,
+                       margin: float = STEP_MARGIN) -> np.ndarray:
+    """bool [nb, na]: the free nodes of the lattice ``extent`` = (a0, b0, na, nb) (the rule above): not strictly inside a wall of
+    ``boxes`` (None: BOXES), an occupied cell of ``grid`` or a valid footprint of ``objects``, each inflated by ``margin``."""
+    n, m = _lattice_n(cells_per_metre), float(margin)
+    a0, b0, na, nb = (int(v) for v in extent)
+    x = np.arange(a0, a0 + na, dtype=np.float64) / float(n)
+    y = np.arange(b0, b0 + nb, dtype=np.float64) / float(n)
+    blocked = np.zeros((nb, na), bool)
+    for (x0, y0, x1, y1) in np.concatenate([_walls_of(boxes), _valid_footprints(objects)]):
+        blocked |= ((y0 - m < y) & (y < y1 + m))[:, None] & ((x0 - m < x) & (x < x1 + m))[None, :]
+    if grid is not None:
+        i0, i1 = np.searchsorted(grid.xs[1:] + m, x, side="right"), np.searchsorted(grid.xs[:-1] - m, x, side="left")
+        j0, j1 = np.searchsorted(grid.ys[1:] + m, y, side="right"), np.searchsorted(grid.ys[:-1] - m, y, side="left")
+        area = np.zeros((grid.ny + 1, grid.nx + 1), np.int64)      # occ[j0:j1, i0:i1].any() of every node, from one summed table
+        area[1:, 1:] = np.cumsum(np.cumsum(grid.occ, axis=0, dtype=np.int64), axis=1)
+        i1, j1 = np.maximum(i0, i1), np.maximum(j0, j1)
+        J0, J1, I0, I1 = j0[:, None], j1[:, None], i0[None, :], i1[None, :]
+        blocked |= (area[J1, I1] - area[J0, I1] - area[J1, I0] + area[J0, I0]) > 0
+    return ~blocked
+
+
+def lattice_sources(points, cells_per_metre: int = 20) -> np.ndarray:
+    """int64 [S,2]: the nodes (a, b) = round(p * n) of the view points ``points`` [S,2] (multiples of 0.25 m)."""
+    return np.rint(np.asarray(points, np.float64).reshape(-1, 2) * float(_lattice_n(cells_per_metre))).astype(np.int64)
+
+
+def lattice_move_masks(free) -> np.ndarray:
+    """bool [16, nb, na], in the order of LATTICE_MOVES: may the move leave node (b, a) (both ends and the intermediate nodes
+    free, the target inside the lattice)."""
+    free = np.asarray(free, bool)
+    nb, na = free.shape
+    fp = np.zeros((nb + 4, na + 4), bool)
+    fp[2:-2, 2:-2] = free
+    at = lambda dx, dy: fp[2 + dy:2 + dy + nb, 2 + dx:2 + dx + na]      # noqa: E731  free at (a + dx, b + dy)
+    out = np.zeros((len(LATTICE_MOVES), nb, na), bool)
+    for k, (dx, dy, c) in enumerate(LATTICE_MOVES):
+        ok = free & at(dx, dy)
+        if c == 7:
+            ok = ok & at(dx, 0) & at(0, dy)
+        elif c == 11 and abs(dx) == 2:
+            ok = ok & at(dx // 2, 0) & at(dx // 2, dy)
+        elif c == 11:
+            ok = ok & at(0, dy // 2) & at(dx, dy // 2)
+        out[k] = ok
+    return out
+
+
+def lattice_field_numpy(free, sources, origin=(0, 0), max_cost: int = LATTICE_MAX_COST) -> np.ndarray:
+    """uint16 [nb, na]: the field of the rule above over the free mask ``free`` [nb, na] of a lattice whose node [0, 0] is
+    ``origin`` = (a0, b0), around the source nodes ``sources`` [S,2] (global a, b), by Dial's level sets: level d is what a
+    straight move reaches from level d - 5, a diagonal from d - 7, a knight move from d - 11 and nothing settled earlier."""
+    free = np.asarray(free, bool)
+    nb, na = free.shape
+    max_cost = int(max_cost)
+    if not 0 <= max_cost <= LATTICE_MAX_COST:
+        raise ValueError(f"lattice_field_numpy: max_cost in [0, {LATTICE_MAX_COST}]")
+    dist = np.full(nb * na, LATTICE_NONE, np.uint16)
+    s = np.asarray(sources, np.int64).reshape(-1, 2) - np.asarray(origin, np.int64)
+    s = s[(s[:, 0] >= 0) & (s[:, 0] < na) & (s[:, 1] >= 0) & (s[:, 1] < nb)]
+    s = np.unique(s[:, 1] * na + s[:, 0])
+    s = s[free.reshape(-1)[s]]
+    dist[s] = 0
+    ok = lattice_move_masks(free).reshape(len(LATTICE_MOVES), -1)
+    levels = {0: s}
+    empty = 0 if len(s) else 11
+    d = 0
+    while d < max_cost and empty < 11:
+        d += 1
+        new = []
+        for k, (dx, dy, c) in enumerate(LATTICE_MOVES):
+            src = levels.get(d - c)
+            if src is not None and len(src):
+                new.append(src[ok[k][src]] + (dy * na + dx))
+        levels.pop(d - 12, None)
+        got = np.unique(np.concatenate(new)) if new else np.zeros(0, np.int64)
+        got = got[dist[got] == LATTICE_NONE]
+        dist[got] = d
+        levels[d] = got
+        empty = 0 if len(got) else empty + 1
+    return dist.reshape(nb, na)
+
+
+def lattice_query_numpy(dist, origin, points, cells_per_metre: int = 20) -> np.ndarray:
+    """f64 [m]: the query of the rule above for the ``points`` [m,2] in the field ``dist`` uint16 [nb, na] whose node [0, 0] is
+    ``origin`` = (a0, b0).  inf: none of the four nodes around the point is in the lattice with a cost."""
+    n = float(_lattice_n(cells_per_metre))
+    dist = np.asarray(dist, np.uint16)
+    nb, na = dist.shape
+    a0, b0 = (int(v) for v in origin)
+    p = np.asarray(points, np.float64).reshape(-1, 2)
+    with np.errstate(over="ignore"):
+        fa, fb = np.floor(p[:, 0] * n), np.floor(p[:, 1] * n)
+    out = np.full(len(p), np.inf)
+    for ua in (0.0, 1.0):
+        for ub in (0.0, 1.0):
+            a, b = fa + ua, fb + ub
+            inside = (a >= a0) & (a <= a0 + na - 1) & (b >= b0) & (b <= b0 + nb - 1)       # (False for a NaN)
+            ia, ib = np.where(inside, a - a0, 0.0).astype(np.int64), np.where(inside, b - b0, 0.0).astype(np.int64)
+            cost = dist[ib, ia]
+            with np.errstate(invalid="ignore", over="ignore"):                             # (points at infinity: not inside)
+                dx, dy = p[:, 0] - a / n, p[:, 1] - b / n
+                d = np.sqrt(dx * dx + dy * dy) + cost.astype(np.float64) / (5.0 * n)
+            out = np.where(inside & (cost != LATTICE_NONE), np.minimum(out, d), out)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- map planner

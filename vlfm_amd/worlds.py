@@ -13,7 +13,7 @@ from . import _lib
 from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TURN_RIGHT, BOXES, MAX_DEPTH, MIN_DEPTH, YAWS, \
     camera_intrinsics, integrate, GEODESIC_MAX_SOURCES, STEP_MARGIN, WORLD_MAX_BOXES, WORLD_MAX_OBJECTS, goal_viewpoints, \
     inflated_rects, object_layout, plan_actions, rect_distance, soft_spl, spl, step_poses, tf_of, OBJECT_COLOURS, WORLD_PALETTE, \
-    GRID_MAX_CELLS, GridPlan
+    GRID_MAX_CELLS, GridPlan, LATTICE_MAX_COST, lattice_extent, lattice_sources
 
 
 @dataclass(frozen=True)
@@ -90,6 +90,58 @@ class GeodesicFields:
         idx = torch.from_numpy(rows).to(self.rects.device)
         for name in ("rects", "nodes", "dist", "counts", "sources", "source_counts"):
             getattr(self, name).index_copy_(0, idx, getattr(other, name))
+        self.has_target[rows] = other.has_target
+
+
+@dataclass
+class LatticeFields:
+    """Device handle of ``n`` lattice geodesic fields (RoomsRenderer.lattice_fields_worlds) of ``cells_per_metre`` nodes per
+    metre, with the strides of include/vlfm_amd.h ("Lattice geodesic"): every plane holds max_nb x max_na nodes, field i uses
+    the ``dims[i]`` = (a0, b0, na, nb) of them.  ``dims_host``: the same on the host; ``has_target`` [n] bool on the host:
+    False for a field built without a target (no source).  ``residence``: where the last launch kept its bit planes
+    (_lib.LATTICE_IN_LDS / LATTICE_IN_SCRATCH / LATTICE_ALL_IN_SCRATCH; None: nothing was launched)."""
+    n: int
+    cells_per_metre: int
+    bits: torch.Tensor           # [n,max_nb,ceil(max_na / 32)] int32: the free planes
+    dist: torch.Tensor           # [n,max_nb,max_na] int16 holding the uint16 costs, 0xFFFF for none (``costs``)
+    dims: torch.Tensor           # [n,4] int32
+    dims_host: np.ndarray        # [n,4] int32
+    has_target: np.ndarray
+    residence: Optional[int] = None
+
+    def costs(self, i: int) -> np.ndarray:
+        """uint16 [nb, na] on the host: the field ``i`` within its dims (a read-back)."""
+        _, _, na, nb = (int(v) for v in self.dims_host[i])
+        return self.dist[i, :nb, :na].contiguous().cpu().numpy().view(np.uint16)
+
+    def free(self, i: int) -> np.ndarray:
+        """bool [nb, na] on the host: the free nodes of field ``i`` within its dims (a read-back)."""
+        _, _, na, nb = (int(v) for v in self.dims_host[i])
+        words = self.bits[i, :nb].cpu().numpy().view(np.uint32)
+        return np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :na].astype(bool)
+
+    def assign(self, rows, other: "LatticeFields") -> None:
+        """Overwrite the fields ``rows`` of this handle with the fields of ``other`` (len(rows) == other.n), on the device.
+        The planes of this handle grow to ``other``'s strides where those are larger."""
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        if len(rows) != other.n or other.cells_per_metre != self.cells_per_metre:
+            raise ValueError("LatticeFields.assign: the other handle must hold one field of the same spacing per row")
+        if np.any((rows < 0) | (rows >= self.n)):
+            raise ValueError("LatticeFields.assign: row out of range")
+        if not len(rows):
+            return
+        for name in ("bits", "dist"):
+            mine, theirs = getattr(self, name), getattr(other, name)
+            if theirs.shape[1] > mine.shape[1] or theirs.shape[2] > mine.shape[2]:
+                grown = torch.full((self.n, max(mine.shape[1], theirs.shape[1]), max(mine.shape[2], theirs.shape[2])),
+                                   -1 if name == "dist" else 0, dtype=mine.dtype, device=mine.device)   # (0xFFFF: no cost)
+                grown[:, :mine.shape[1], :mine.shape[2]] = mine
+                setattr(self, name, grown)
+                mine = grown
+            idx = torch.from_numpy(rows).to(mine.device)
+            mine[idx, :theirs.shape[1], :theirs.shape[2]] = theirs
+        self.dims.index_copy_(0, torch.from_numpy(rows).to(self.dims.device), other.dims)
+        self.dims_host[rows] = other.dims_host
         self.has_target[rows] = other.has_target
 
 
@@ -441,6 +493,109 @@ class RoomsRenderer:
                                                       handle.max_sources, out.data_ptr(), stream), "geodesic_query")
         return out
 
+    @torch.no_grad()
+    def lattice_fields_worlds(self, table: WorldTable, world_of, objects: np.ndarray, targets_boxes, success_distance: float,
+                              cells_per_metre: int = 20, pad_m: float = 1.0, max_cost: int = LATTICE_MAX_COST,
+                              max_sources: int = GEODESIC_MAX_SOURCES) -> LatticeFields:
+        """``geodesic_fields_worlds`` on the metric lattice (synthetic.py, "Lattice geodesic"), for worlds of any number of
+        boxes and for grid worlds: TWO launches on the current stream -- vlfm_lattice_free builds the bit-packed free plane of
+        every field from the table's rows (boxes and grids) and the records ``objects`` [n,8,8], bit for bit
+        synthetic.lattice_free_numpy; vlfm_lattice_fields grows the uint16 cost fields from the view points, bit for bit
+        synthetic.lattice_field_numpy.  Extents (synthetic.lattice_extent) and view points (synthetic.goal_viewpoints, the
+        table's grid included) are worked out on the host; the source nodes, their counts, the dims and world_of cross in one
+        copy, the records in another.  A field wider than 1024 nodes, or more than ``max_sources`` view points: ValueError
+        before anything is launched."""
+        objects = np.ascontiguousarray(objects, np.float64)
+        if objects.ndim != 3 or objects.shape[1:] != (WORLD_MAX_OBJECTS, 8):
+            raise ValueError(f"lattice_fields_worlds: objects must be [n, {WORLD_MAX_OBJECTS}, 8]")
+        n, cpm, max_cost = len(objects), int(cells_per_metre), int(max_cost)
+        dev = self.device
+        if table.device != dev:
+            raise ValueError(f"lattice_fields_worlds: the world table must live on {dev}")
+        if not 0 <= max_cost <= LATTICE_MAX_COST:
+            raise ValueError(f"lattice_fields_worlds: max_cost in [0, {LATTICE_MAX_COST}]")
+        world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
+        if len(world_of) != n or np.any((world_of < 0) | (world_of >= table.n_worlds)):
+            raise ValueError("lattice_fields_worlds: world_of must name one world of the table per field")
+        boxes = np.asarray(targets_boxes, np.float64).reshape(n, -1)[:, :4] if n else np.zeros((0, 4))
+        # source nodes [n][max_sources][2], counts [n], dims [n][4], world_of [n]: one int32 buffer
+        blob = np.zeros(n * (2 * max_sources + 6), np.int32)
+        src = blob[:2 * n * max_sources].reshape(n, max_sources, 2)
+        cnt = blob[2 * n * max_sources:][:n]
+        dims = blob[2 * n * max_sources + n:][:4 * n].reshape(n, 4)
+        blob[2 * n * max_sources + 5 * n:] = world_of
+        has = np.zeros(n, bool)
+        lattice_extent(np.zeros((0, 4)), None, None, cpm, pad_m)            # (the spacing and the pad, checked even for n == 0)
+        for e in range(n):
+            walls, grid = table.world(world_of[e]), table.grids[world_of[e]]
+            dims[e] = lattice_extent(walls, grid, objects[e], cpm, pad_m)
+            if np.all(np.isfinite(boxes[e])):
+                pts = goal_viewpoints(boxes[e], inflated_rects(objects[e], STEP_MARGIN, walls), success_distance, max_sources,
+                                      grid=grid)
+                src[e, :len(pts)], cnt[e], has[e] = lattice_sources(pts, cpm), len(pts), True
+        max_na, max_nb = (int(dims[:, 2].max()), int(dims[:, 3].max())) if n else (1, 1)
+        h = LatticeFields(n, cpm, torch.empty((n, max_nb, (max_na + 31) // 32), dtype=torch.int32, device=dev),
+                          torch.empty((n, max_nb, max_na), dtype=torch.int16, device=dev),
+                          torch.empty((n, 4), dtype=torch.int32, device=dev), dims.copy(), has)
+        if n == 0:
+            return h
+        with torch.cuda.device(dev):
+            L = _lib.lib()
+            d_obj = torch.from_numpy(objects).to(dev)
+            d_blob = torch.from_numpy(blob).to(dev)
+            p = d_blob.data_ptr()
+            p_cnt, p_dims, p_world = p + 8 * n * max_sources, p + 8 * n * max_sources + 4 * n, p + 8 * n * max_sources + 20 * n
+            h.dims.copy_(d_blob[2 * n * max_sources + n:][:4 * n].view(n, 4))
+            g_bits, g_edges, g_dims, g_ny, g_nx = None, None, None, 0, 0
+            if table.max_grid is not None:
+                g_bits, g_edges, g_dims = table.d_grid_bits.data_ptr(), table.d_grid_edges.data_ptr(), table.d_grid_dims.data_ptr()
+                g_ny, g_nx = table.max_grid
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.check(L.vlfm_lattice_free(table.d_boxes.data_ptr(), table.d_counts.data_ptr(), table.n_worlds, table.max_boxes,
+                                           g_bits, g_edges, g_dims, g_nx, g_ny, p_world, STEP_MARGIN, d_obj.data_ptr(), p_dims, n,
+                                           cpm, max_nb, max_na, h.bits.data_ptr(), stream), "lattice_free")
+            h.residence = self._launch_lattice_fields(h, p, p_cnt, max_sources, max_cost)
+        return h
+
+    def _launch_lattice_fields(self, h: LatticeFields, d_sources: int, d_source_counts: int, max_sources: int,
+                             max_cost: int = LATTICE_MAX_COST) -> int:
+        """vlfm_lattice_fields over the free planes ``h.bits`` and ``h.dims`` as they stand -- whatever wrote them --, into
+        ``h.dist``, on the current stream: ``d_sources`` / ``d_source_counts`` are device addresses of int32 [n][max_sources][2]
+        global nodes and [n] counts.  Returns where the bit planes lived (_lib.LATTICE_IN_LDS / LATTICE_IN_SCRATCH / LATTICE_ALL_IN_SCRATCH)."""
+        L = _lib.lib()
+        max_nb, max_na = h.dist.shape[1:]
+        need = L.vlfm_lattice_scratch_bytes(h.n, max_nb, max_na)
+        scratch = torch.empty((need,), dtype=torch.uint8, device=self.device) if need else None
+        return _lib.check(L.vlfm_lattice_fields(h.bits.data_ptr(), h.dims.data_ptr(), h.n, max_nb, max_na, d_sources,
+                                                d_source_counts, max_sources, max_cost, h.dist.data_ptr(),
+                                                scratch.data_ptr() if need else None, need,
+                                                torch.cuda.current_stream().cuda_stream), "lattice_fields")
+
+    @torch.no_grad()
+    def lattice_distances(self, handle: LatticeFields, field_of, xy) -> torch.Tensor:
+        """f64 [m] on the device: the lattice geodesic distance to the goal of the points ``xy`` [m,2], point i in the field
+        ``field_of[i]`` of ``handle`` (-1: no field, the answer is NaN), ONE launch on the current stream (vlfm_lattice_query,
+        bit for bit synthetic.lattice_query_numpy).  inf: no way to the goal."""
+        xy = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
+        m = len(xy)
+        field_of = np.ascontiguousarray(np.asarray(field_of).reshape(-1), np.int32)
+        if len(field_of) != m or np.any((field_of < -1) | (field_of >= handle.n)):
+            raise ValueError("lattice_distances: field_of must name one field of the handle (or -1) per point")
+        dev = self.device
+        out = torch.empty((m,), dtype=torch.float64, device=dev)
+        if m == 0:
+            return out
+        with torch.cuda.device(dev):
+            blob = np.concatenate([xy.reshape(-1), np.zeros((m + 1) // 2, np.float64)])     # points and field_of: one copy
+            blob[2 * m:].view(np.int32)[:m] = field_of
+            d_blob = torch.from_numpy(blob).to(dev)
+            p = d_blob.data_ptr()
+            max_nb, max_na = handle.dist.shape[1:]
+            _lib.check(_lib.lib().vlfm_lattice_query(p, p + 16 * m, m, handle.n, handle.dist.data_ptr(), handle.dims.data_ptr(),
+                                                     max_nb, max_na, handle.cells_per_metre, out.data_ptr(),
+                                                     torch.cuda.current_stream().cuda_stream), "lattice_query")
+        return out
+
     def prepare(self, t0: int, n: int) -> None:
         self.window = torch.stack([self.render((t0 + i) % self.L) for i in range(n)])
         self.window_t0 = t0
@@ -451,19 +606,35 @@ class RoomsRenderer:
         return self.render(t)
 
 
+def check_geodesic_backend(geodesic, objectnav_metrics: bool, worlds) -> None:
+    """What ``LiveWorld`` and ``BatchedEpisodes`` refuse about ``geodesic`` before any device is touched: a name that is neither
+    backend, "lattice" without the metrics it serves, and grid worlds scored by the visibility graph."""
+    if geodesic not in ("graph", "lattice"):
+        raise ValueError(f'geodesic must be "graph" or "lattice", not {geodesic!r}')
+    if geodesic == "lattice" and not objectnav_metrics:
+        raise ValueError('geodesic="lattice" is a backend of objectnav_metrics: it needs objectnav_metrics=True')
+    if objectnav_metrics and geodesic == "graph" and getattr(worlds, "max_grid", None) is not None:
+        raise ValueError('grid worlds cannot be combined with objectnav_metrics over the visibility graph: the geodesic fields '
+                         'hold at most 141 rectangles; geodesic="lattice" scores them')
+
+
 class LiveWorld:
     """The closed-loop world of ``BatchedEpisodes(closed_loop=True)`` (its ``live``): E robots that stand where their actions
     took them.  ``observe()`` ray-casts what they see -- one launch of ``renderer`` (a RoomsRenderer) -- and ``advance()``
     moves them (synthetic.step_poses).  ``worlds``: every environment in its own floor plan, a row of ``table`` each, else all
     in the renderer's rooms world; ``world_objects``: objects stand in the worlds and the environments run ObjectNav episodes
     (``start_episodes`` / ``end_episodes``, scored in ``objectnav_stats``; ``objectnav_metrics``: also SPL, SoftSPL, geodesic
-    distance); ``render_rgb``: the colour view too.  Every attribute exists in every mode; what a mode does not use is None."""
+    distance -- ``geodesic``: "graph", the visibility graph over at most 141 rectangles (GeodesicFields), or "lattice", the
+    metric lattice that also holds grid worlds (LatticeFields)); ``render_rgb``: the colour view too.  Every attribute exists
+    in every mode; what a mode does not use is None."""
 
     def __init__(self, renderer, env_ids, targets, world_objects: Optional[WorldObjects] = None, worlds=None,
-                 objectnav_metrics: bool = False, render_rgb: bool = False) -> None:
+                 objectnav_metrics: bool = False, render_rgb: bool = False, geodesic: str = "graph") -> None:
         self.renderer, self.env_ids, self.targets = renderer, list(env_ids), list(targets)
         self.world_objects, self.worlds = world_objects, worlds
         self.objectnav_metrics, self.render_rgb = bool(objectnav_metrics), bool(render_rgb)
+        check_geodesic_backend(geodesic, self.objectnav_metrics, worlds)
+        self.geodesic_backend = geodesic
         E = self.E = len(self.env_ids)
         z = lambda dt: np.zeros(E, dt)   # noqa: E731
         # an episode starts at the environment's open-loop start pose (diverse, in free space), with ``worlds`` at its world's
@@ -590,15 +761,22 @@ class LiveWorld:
         envs = np.array(envs, np.int64)
         slots = self.target_slot[envs]
         boxes = np.where((slots >= 0)[:, None], self.objects[envs, np.maximum(slots, 0), :4], np.nan)
-        fresh = self.renderer.geodesic_fields_worlds(self.table, self.world_of[envs], self.objects[envs], boxes, wo.success_distance)
+        fields = self.renderer.lattice_fields_worlds if self.geodesic_backend == "lattice" else self.renderer.geodesic_fields_worlds
+        fresh = fields(self.table, self.world_of[envs], self.objects[envs], boxes, wo.success_distance)
         if self.geodesic is None:               # (the first call starts every environment's episode)
             assert len(envs) == self.E and np.array_equal(envs, np.arange(self.E))
             self.geodesic = fresh
         else:
             self.geodesic.assign(envs, fresh)
         field_of = np.where(fresh.has_target, np.arange(len(envs)), -1)
-        self.ep_geodesic[envs] = self.renderer.geodesic_distances(fresh, field_of, self.xy[envs]).cpu().numpy()
+        self.ep_geodesic[envs] = self._distances(fresh, field_of, self.xy[envs])
         self.distance_to_goal[envs] = self.ep_geodesic[envs]
+
+    def _distances(self, fields, field_of, xy) -> np.ndarray:
+        """f64 on the host: the distance to the goal of each point in its field, by the backend's query: one launch, one read-back."""
+        r = self.renderer
+        ask = r.lattice_distances if self.geodesic_backend == "lattice" else r.geodesic_distances
+        return ask(fields, field_of, xy).cpu().numpy()
 
     def _score(self, e: int, outcome: str) -> None:
         st = self.objectnav_stats
@@ -624,7 +802,7 @@ class LiveWorld:
         self.ep_clock += 1                          # this step is taken
         if self.objectnav_metrics:
             field_of = np.where(self.geodesic.has_target, np.arange(self.E), -1)
-            self.distance_to_goal = self.renderer.geodesic_distances(self.geodesic, field_of, self.xy).cpu().numpy()
+            self.distance_to_goal = self._distances(self.geodesic, field_of, self.xy)
         for e in range(self.E):
             navigating = bool(modes) and modes[e] == "navigate"
             exploring = bool(modes) and modes[e] == "explore"
