@@ -1093,6 +1093,34 @@ int vlfm_lattice_fields(const uint32_t* d_free, const int32_t* d_dims, int n, in
 int vlfm_lattice_query(const double* d_points, const int32_t* d_field_of, int m, int n_fields, const uint16_t* d_dist,
                        const int32_t* d_dims, int max_nb, int max_na, int cells_per_metre, double* d_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Depth sensor (ABI 27, csrc/depth_sensor.hip): what a depth camera makes of the exact frames vlfm_worlds_raycast writes --
+ * axial noise, disparity quantisation, holes -- for n frames in ONE launch on `stream`, bit for bit
+ * vlfm_amd.synthetic.depth_sensor_numpy (f32, one rounding per operation, no fused multiply-add).  Per frame i, with
+ * kf = d_keys[i] (synthetic.DepthSensor.frame_keys: the hash of seed, environment and clock, made on the host),
+ * lo = d_range[i][0], hi = d_range[i][1], span = hi - lo, p = r * W + u, mix32 the mixer of world_render.hip:
+ *   metres    z = lo + d * span
+ *   invalid   any of: min_range_m > 0 or max_range_m < inf, and not (z >= min_range_m and z <= max_range_m);
+ *             edge_m > 0 and |z_n - z| > edge_m for a neighbour above, below, left or right inside the frame;
+ *             mix32(kf, p, 55) < drop_threshold;  mix32(kf, (r >> 3) * ((W + 7) >> 3) + (u >> 3), 56) < patch_threshold
+ *             (a threshold of 0: the stage is off).  An invalid pixel is written as 0.0f.
+ *   noise     (sigma0_m or sigma2_per_m not 0)  h1 = mix32(kf, p, 53), h2 = mix32(kf, p, 54),
+ *             nf = f32((h1 & 0xFFFF) + (h1 >> 16) + (h2 & 0xFFFF) + (h2 >> 16) - 131070) * f32(1 / sqrt(1431655765)),
+ *             z1 = z + (sigma0_m + sigma2_per_m * (z * z)) * nf
+ *   quantise  (disparity_k > 0)  z1 = z1 < 1e-3f ? 1e-3f : z1;  m = rint(k / z1);  m = m < 1 ? 1 : m;  z1 = k / m
+ *   output    v = (z1 - lo) / span;  v < 1e-3f ? 1e-3f : (v > 1 ? 1 : v)
+ *   With noise and quantisation both off a valid pixel is the input value, bit for bit (nothing is computed for it).
+ * d_clean, d_out: f32 [n][H][W]; they must not overlap (the edge stage reads clean neighbours).  d_keys uint32 [n], d_range
+ * f32 [n][2].  d_invalid: NULL, or int32 [n] that receives the invalid pixels of each frame (zeroed by a memset on `stream`
+ * first).  band_rows: rows per workgroup, 0: planned by the library (the ray caster's plan, rounded up to whole 8-row blocks).
+ * With W % 4 == 0 and both planes 16-byte aligned a lane moves its four columns with one 16-byte load and one 16-byte store;
+ * any other width or alignment takes scalar loads and stores.
+ * NULL planes (or keys, ranges) with n > 0, n < 0 or n > 65535, H < 1, W < 1, H * W >= 2^31, band_rows < 0, a negative or NaN
+ * scalar, or overlapping planes: VLFM_ERR_INVALID, nothing launched, nothing written.  n == 0: VLFM_OK without a launch. */
+int vlfm_depth_sensor(const float* d_clean, float* d_out, int n, int H, int W, const uint32_t* d_keys, const float* d_range,
+                      float sigma0_m, float sigma2_per_m, float disparity_k, uint32_t drop_threshold, uint32_t patch_threshold,
+                      float edge_m, float min_range_m, float max_range_m, int32_t* d_invalid, int band_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

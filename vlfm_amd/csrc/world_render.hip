@@ -26,6 +26,7 @@
 
 #include "../../include/vlfm_amd.h"
 #include "profile.h"
+#include "row_bands.h"
 #include "status.h"
 #include "world_table.h"
 
@@ -33,7 +34,6 @@ namespace vlfm {
 namespace world {
 
 constexpr int THREADS = 256;
-constexpr int MIN_BAND_ROWS = 4;
 
 struct CameraRec {      // 64 bytes, vlfm_amd.h
     double x, y, c, s, height, fx, lo, hi;
@@ -603,21 +603,7 @@ __global__ void rooms_stats_init_kernel(int32_t* __restrict__ stats, int total, 
     stats[i] = f == 0 ? 0 : (f == 1 ? W : (f == 3 ? H : -1));
 }
 
-// ---- launch geometry (host) -------------------------------------------------------------------------------------------------
-struct Bands {
-    int band, grid_x;                         // rows per workgroup, workgroups per camera
-};
-
-// row bands: enough workgroups for four per compute unit, never fewer than MIN_BAND_ROWS rows each and never more than `max_rows`
-static Bands plan_bands(int n, int H, int max_rows) {
-    const long long want = 4LL * device_cu_count();
-    long long bands = (want + n - 1) / n;
-    const long long most = (H + MIN_BAND_ROWS - 1) / MIN_BAND_ROWS, least = ((long long)H + max_rows - 1) / max_rows;
-    bands = bands < least ? least : (bands > most ? most : bands);
-    const int band = (int)((H + bands - 1) / bands);
-    return Bands{band, (H + band - 1) / band};
-}
-
+// ---- launch geometry (host): the row bands are row_bands.h's ----------------------------------------------------------------------
 // LDS of the three kernels for `wp` padded columns and a band of `band` rows: each adds its tables to the one before
 static size_t walls_lds(int max_boxes, size_t wp, int band) { return (size_t)max_boxes * 32 + wp * 4 + (size_t)band * 4; }
 static size_t objects_lds(int max_boxes, size_t wp, int band) {

@@ -33,12 +33,13 @@ from . import _lib
 from .mapping.base_map import require_gpu
 from .mapping.value_map import ValueMapBatch
 from .synthetic import MAX_DEPTH, MIN_DEPTH, BangBangController, ReplayController, Trajectory, camera_intrinsics, depth_frame, \
-    ProceduralWorlds, pose_to_tf, rgb_frame, PLAN_INVALID, PLAN_OK, PLAN_TOO_LONG, PLAN_UNREACHABLE, GridWorlds, _mix32  # noqa: F401
+    ProceduralWorlds, pose_to_tf, rgb_frame, PLAN_INVALID, PLAN_OK, PLAN_TOO_LONG, PLAN_UNREACHABLE, GridWorlds, _mix32, DepthSensor  # noqa: F401
 from .worlds import GeodesicFields, LatticeFields, LiveWorld, RoomsRenderer, WorldObjects, WorldTable, check_geodesic_backend, \
     objectnav_outcome, sightings_from_stats  # noqa: F401  (the worlds' names stay importable from here)
 
 PROMPT = "Seems like there is a target_object ahead."  # vlfm/policy/base_objectnav_policy.py:377
 TARGETS = ["chair", "bed", "potted plant", "toilet", "tv", "couch"]  # HM3D ObjectNav categories
+OBSTACLE_HOLE_AREA_THRESH = 100000   # the harness's obstacle maps fill small depth holes (the reference's default); -1: they would not
 
 
 class ScriptedSightings:
@@ -195,7 +196,7 @@ class BatchedEpisodes:
                  controller=None, world_objects: Optional[WorldObjects] = None, batch_object_maps: bool = True,
                  device_object_clouds: bool = True, objectnav_metrics: bool = False,
                  worlds: Optional[Union[ProceduralWorlds, GridWorlds]] = None, render_rgb: bool = False,
-                 geodesic: str = "graph") -> None:
+                 geodesic: str = "graph", depth_sensor: Optional[DepthSensor] = None) -> None:
         # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
         # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -277,6 +278,25 @@ class BatchedEpisodes:
                 raise ValueError("render_rgb needs closed_loop=True: the frames are rendered from where the robot is")
             if rig is not None:
                 raise ValueError("render_rgb renders the robot's own camera: it cannot be combined with a camera rig")
+        # depth_sensor: a synthetic.DepthSensor between the ray caster and everything that reads the step's depth frames (both
+        # maps, the object clouds, PointNav, the planner): noise, quantisation and holes, one more launch per step
+        # (RoomsRenderer.sense_depth); ``live.clean_frames`` keeps the exact ranges.  Off: every step is the step it was
+        self.depth_sensor = depth_sensor
+        if depth_sensor is not None:
+            if not isinstance(depth_sensor, DepthSensor):
+                raise ValueError("depth_sensor must be a synthetic.DepthSensor")
+            if not self.closed_loop:
+                raise ValueError("depth_sensor needs closed_loop=True: it senses the frames rendered from where the robot is")
+            if rig is not None:
+                raise ValueError("depth_sensor senses the robot's own camera: it cannot be combined with a camera rig")
+            from .mapping.obstacle_map import ObstacleMapBatch
+
+            # isolated invalid pixels are one contour each for fill_small_holes, whose scratch holds HOLE_CAP_CONTOURS of them
+            bound = ObstacleMapBatch.HOLE_CAP_CONTOURS / 2
+            if OBSTACLE_HOLE_AREA_THRESH != -1 and depth_sensor.dropout * height * width > bound:
+                raise ValueError(f"depth_sensor: dropout * height * width = {depth_sensor.dropout * height * width:.0f} exceeds "
+                                 f"ObstacleMapBatch.HOLE_CAP_CONTOURS / 2 = {bound:.0f} contours of the obstacle map's hole filling: "
+                                 f"at {width} x {height} dropout <= {bound / (height * width):.3f}")
         self.device = require_gpu(device)
         # rig: K cameras per environment (CameraRig) fused into the environment's maps by ONE ingest_cameras / update_cameras per
         # step (step() -> _step_rig()); None = one camera at the robot pose, the step as it always was
@@ -342,7 +362,7 @@ class BatchedEpisodes:
             self.tf_table = np.stack([np.stack([pose_to_tf(x, y, yaw) for (x, y, yaw) in row]) for row in self.pose_table])
         # closed loop: the simulator -- where the robots are, their worlds, objects and episodes (worlds.LiveWorld); else None
         self.live = LiveWorld(self.rooms, self.env_ids, self.targets, world_objects, worlds, objectnav_metrics,
-                              render_rgb, geodesic) if self.closed_loop else None
+                              render_rgb, geodesic, depth_sensor) if self.closed_loop else None
         self.last_poses = self.last_world_actions = None     # closed loop: the poses the last step observed from, its actions
         # of a controller with act_on_map (MapPlannerController): plans = ok + unreachable + too_long + invalid (off the map)
         self.planner_stats = {k: np.zeros(n_envs, np.int64) for k in ("plans", "ok", "unreachable", "too_long", "invalid")}
@@ -359,7 +379,8 @@ class BatchedEpisodes:
             from .mapping.obstacle_map import ObstacleMapBatch
 
             self.obstacles = ObstacleMapBatch(n_envs, min_height=0.61, max_height=0.88, agent_radius=0.18,
-                                              area_thresh=1.5, size=map_size, device=self.device)
+                                              area_thresh=1.5, hole_area_thresh=OBSTACLE_HOLE_AREA_THRESH, size=map_size,
+                                              device=self.device)
             if sync_explored:
                 self.values.explored_bits = self.obstacles.explored_bits
         # The obstacle pipeline is a handful of latency-bound workgroups per environment: it runs on its own HIP

@@ -3,6 +3,7 @@ scripted trajectories and stub values.  Used by bench.py, the harness and the pa
 oracle are fed from here, so they see identical inputs)."""
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import NamedTuple
 
 import numpy as np
@@ -1553,3 +1554,157 @@ class MapPlannerController:
             lx, ly = c * d[:, 0] - s * d[:, 1], s * d[:, 0] + c * d[:, 1]
             rt[idx[use]] = np.stack([np.hypot(lx, ly), np.arctan2(ly, lx)], axis=1)
         return self.inner.act(modes, rt, stops, collided)
+
+
+# ---------------------------------------------------------------------------------------------- depth sensor
+# What a depth CAMERA makes of the exact ranges the ray caster writes: axial noise, disparity quantisation, holes (single
+# pixels, 8 x 8 blocks, silhouettes, out of range).  `depth_sensor_numpy` is the HOST STATEMENT of the rule; the device
+# (csrc/depth_sensor.hip: vlfm_depth_sensor, behind RoomsRenderer.sense_depth) matches it bit for bit.  A frame is a pure
+# function of (sensor, env_id, clock, clean frame): the randomness is `_mix32` of those, there is no generator state.
+DEPTH_SENSOR_BLOCK = 8                                              # patch dropout: blocks of 8 x 8 pixels
+DEPTH_SENSOR_NOISE_SCALE = np.float32(1.0 / np.sqrt(1431655765.0))  # 1 / std of a sum of four uniform 16-bit integers
+
+
+@dataclass(frozen=True)
+class DepthSensor:
+    """The depth camera of ``LiveWorld(depth_sensor=...)`` / ``BatchedEpisodes(closed_loop=True, depth_sensor=...)``.  Every
+    default means "this stage is off"; a ``DepthSensor()`` returns its input.
+
+    ``sigma0_m``, ``sigma2_per_m``: axial noise of sigma(z) = sigma0 + sigma2 * z * z metres.  ``disparity_k`` > 0: z becomes
+    k / rint(k / z), k = baseline x focal length x sub-pixel steps in metres.  ``dropout``: probability that a pixel is invalid,
+    ``patch_dropout``: that an 8 x 8 block is (both within [0, 0.5]).  ``edge_m`` > 0: invalid where a 4-neighbour inside the frame
+    differs by more than ``edge_m`` metres in the clean frame.  ``min_range_m``, ``max_range_m``: a clean z outside [min, max] is
+    invalid (off at 0 and inf).  Negative or non-finite values are refused here, before any device is touched."""
+    seed: int = 0
+    sigma0_m: float = 0.0
+    sigma2_per_m: float = 0.0
+    disparity_k: float = 0.0
+    dropout: float = 0.0
+    patch_dropout: float = 0.0
+    edge_m: float = 0.0
+    min_range_m: float = 0.0
+    max_range_m: float = float("inf")
+
+    def __post_init__(self) -> None:
+        if isinstance(self.seed, bool) or not isinstance(self.seed, (int, np.integer)) or not 0 <= self.seed < 2 ** 32:
+            raise ValueError("DepthSensor: seed must be an integer in [0, 2**32)")
+        for name in ("sigma0_m", "sigma2_per_m", "disparity_k", "dropout", "patch_dropout", "edge_m", "min_range_m"):
+            v = getattr(self, name)
+            if not (isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v) and v >= 0):
+                raise ValueError(f"DepthSensor: {name} must be finite and not negative")
+            if not np.isfinite(np.float32(v)):
+                raise ValueError(f"DepthSensor: {name} does not fit an f32")
+        m = self.max_range_m
+        if not (isinstance(m, (int, float, np.integer, np.floating)) and not np.isnan(m) and m >= 0):
+            raise ValueError("DepthSensor: max_range_m must not be negative (inf: no limit)")
+        for name in ("dropout", "patch_dropout"):
+            if getattr(self, name) > 0.5:
+                raise ValueError(f"DepthSensor: {name} must lie in [0, 0.5]")
+
+    @property
+    def computes(self) -> bool:
+        """Noise or quantisation is on: a valid pixel is computed through metres instead of passed through."""
+        return self.sigma0_m != 0 or self.sigma2_per_m != 0 or self.disparity_k != 0
+
+    @property
+    def range_on(self) -> bool:
+        return self.min_range_m > 0 or self.max_range_m < np.inf
+
+    def thresholds(self):
+        """(T_drop, T_patch): a hash below T makes a pixel / a block invalid; T = min(int(p * 2**32), 2**32 - 1)."""
+        return tuple(min(int(float(p) * 2.0 ** 32), 2 ** 32 - 1) for p in (self.dropout, self.patch_dropout))
+
+    def frame_keys(self, env_ids, clocks) -> np.ndarray:
+        """uint32 [n]: kf = _mix32(_mix32(seed, env_id, 51), clock, 52) of each frame (env_id and clock taken modulo 2**32)."""
+        env_ids = np.asarray(env_ids, np.int64).reshape(-1)
+        clocks = np.asarray(clocks, np.int64).reshape(-1)
+        return np.array([_mix32(_mix32(int(self.seed), int(e) & 0xFFFFFFFF, 51), int(c) & 0xFFFFFFFF, 52)
+                         for e, c in zip(env_ids, clocks)], np.uint32).reshape(-1)
+
+
+def _mix32_array(a: int, b, salt: int) -> np.ndarray:
+    """`_mix32(a, b[i], salt)` for an array ``b`` of values below 2**32: uint64 arithmetic, masked to 32 bits."""
+    m = np.uint64(0xFFFFFFFF)
+    h = (np.asarray(b, np.uint64) * np.uint64(40503) + np.uint64((a * 2654435761 + salt * 97 + 0x9E3779B9) & 0xFFFFFFFF)) & m
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x85EBCA6B)) & m
+    h ^= h >> np.uint64(13)
+    h = (h * np.uint64(0xC2B2AE35)) & m
+    return h ^ (h >> np.uint64(16))
+
+
+def depth_sensor_noise(kf: int, H: int, W: int) -> np.ndarray:
+    """f32 [H,W]: the unit-variance noise nf of the frame with key ``kf`` -- per pixel the sum of the four 16-bit halves of two
+    hashes, centred (- 131070) and scaled by DEPTH_SENSOR_NOISE_SCALE: mean 0, variance 1 by construction, |nf| <= 3.47."""
+    p = np.arange(H * W, dtype=np.uint64).reshape(H, W)
+    h1, h2 = _mix32_array(kf, p, 53), _mix32_array(kf, p, 54)
+    m16 = np.uint64(0xFFFF)
+    n = ((h1 & m16) + (h1 >> np.uint64(16)) + (h2 & m16) + (h2 >> np.uint64(16))).astype(np.int64) - 131070
+    return n.astype(np.float32) * DEPTH_SENSOR_NOISE_SCALE
+
+
+def depth_sensor_numpy(clean, lo, hi, sensor: DepthSensor, env_id: int, clock: int):
+    """(f32 [H,W], invalid pixel count): what ``sensor`` makes of the normalised frame ``clean`` [H,W] (as the ray caster writes
+    it) of a camera with the range [lo, hi] metres, for environment ``env_id`` at sensor clock ``clock``.  Whole-array NumPy; all
+    arithmetic is f32 with one rounding per operation, the expressions exactly as written here, no fused multiply-add.
+
+      keys     kf = _mix32(_mix32(seed, env_id, 51), clock, 52); with p = r * W + u (u32):
+               h1 = _mix32(kf, p, 53), h2 = _mix32(kf, p, 54), hd = _mix32(kf, p, 55),
+               hb = _mix32(kf, (r >> 3) * ((W + 7) >> 3) + (u >> 3), 56)
+      metres   span = hi - lo;  z = lo + d * span
+      invalid  any of: the range stage is on (min_range > 0 or max_range < inf) and not (z >= min_range and z <= max_range) -- a
+               NaN is invalid there; with the stage off nothing is compared and a NaN passes like any other value --;
+               the edge stage is on and |z_n - z| > edge_m for a neighbour above, below, left or right inside the frame (a NaN
+               difference is not greater: a NaN pixel invalidates no neighbour);  hd < T_drop;  hb < T_patch
+               (`DepthSensor.thresholds`; T == 0: the stage is off and its hash is not evaluated).  An invalid pixel is 0.0f.
+      noise    n = (h1 & 0xFFFF) + (h1 >> 16) + (h2 & 0xFFFF) + (h2 >> 16) - 131070;  nf = f32(n) * DEPTH_SENSOR_NOISE_SCALE;
+               z1 = z + (sigma0 + sigma2 * (z * z)) * nf
+      quantise (k > 0)  z1 = z1 < 1e-3f ? 1e-3f : z1;  m = rint(k / z1), half to even;  m = m < 1 ? 1 : m;  z1 = k / m
+      output   v = (z1 - lo) / span;  v < 1e-3f ? 1e-3f : (v > 1 ? 1 : v)
+               (the selects are max / clip for every number and keep a NaN a NaN, which pins what max and clip leave open)
+      pass-through  with noise and quantisation both off (sigma0 == sigma2 == k == 0) a valid pixel is the INPUT value, bit for
+               bit: the trip through metres is not the identity, so it is not made."""
+    f = np.float32
+    d = np.ascontiguousarray(clean, np.float32)
+    if d.ndim != 2:
+        raise ValueError("depth_sensor_numpy: clean must be [H,W]")
+    H, W = d.shape
+    lo, hi = f(lo), f(hi)
+    span = f(hi - lo)
+    t_drop, t_patch = sensor.thresholds()
+    kf = int(sensor.frame_keys([env_id], [clock])[0])
+    rows, cols = np.arange(H, dtype=np.uint64)[:, None], np.arange(W, dtype=np.uint64)[None, :]
+    p = rows * np.uint64(W) + cols
+    invalid = np.zeros((H, W), bool)
+    with np.errstate(all="ignore"):
+        z = lo + d * span
+        if sensor.range_on:
+            invalid |= ~((z >= f(sensor.min_range_m)) & (z <= f(sensor.max_range_m)))
+        if sensor.edge_m > 0:
+            e = f(sensor.edge_m)
+            dv, dh = np.abs(z[1:] - z[:-1]) > e, np.abs(z[:, 1:] - z[:, :-1]) > e
+            invalid[1:] |= dv
+            invalid[:-1] |= dv
+            invalid[:, 1:] |= dh
+            invalid[:, :-1] |= dh
+        if t_drop:
+            invalid |= _mix32_array(kf, p, 55) < np.uint64(t_drop)
+        if t_patch:
+            block = (rows >> np.uint64(3)) * np.uint64((W + 7) >> 3) + (cols >> np.uint64(3))
+            invalid |= _mix32_array(kf, block, 56) < np.uint64(t_patch)
+        if not sensor.computes:
+            out = d
+        else:
+            z1 = z
+            if sensor.sigma0_m != 0 or sensor.sigma2_per_m != 0:
+                z1 = z + (f(sensor.sigma0_m) + f(sensor.sigma2_per_m) * (z * z)) * depth_sensor_noise(kf, H, W)
+            if sensor.disparity_k > 0:
+                k = f(sensor.disparity_k)
+                z1 = np.where(z1 < f(1e-3), f(1e-3), z1)
+                m = np.rint(k / z1)
+                m = np.where(m < f(1.0), f(1.0), m)
+                z1 = k / m
+            v = (z1 - lo) / span
+            out = np.where(v < f(1e-3), f(1e-3), np.where(v > f(1.0), f(1.0), v))
+        out = np.where(invalid, f(0.0), out).astype(np.float32)
+    return out, int(invalid.sum())

@@ -13,7 +13,7 @@ from . import _lib
 from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TURN_RIGHT, BOXES, MAX_DEPTH, MIN_DEPTH, YAWS, \
     camera_intrinsics, integrate, GEODESIC_MAX_SOURCES, STEP_MARGIN, WORLD_MAX_BOXES, WORLD_MAX_OBJECTS, goal_viewpoints, \
     inflated_rects, object_layout, plan_actions, rect_distance, soft_spl, spl, step_poses, tf_of, OBJECT_COLOURS, WORLD_PALETTE, \
-    GRID_MAX_CELLS, GridPlan, LATTICE_MAX_COST, lattice_extent, lattice_sources
+    GRID_MAX_CELLS, GridPlan, LATTICE_MAX_COST, lattice_extent, lattice_sources, DepthSensor
 
 
 @dataclass(frozen=True)
@@ -406,6 +406,61 @@ class RoomsRenderer:
         return self._raycast("cast_cameras_rgb", tf, self.table, self._rooms_world_of(tf), objects, env_of, hfov, min_depth,
                              max_depth, out, True, colours, palette, rgb_out)
 
+    @torch.no_grad()
+    def sense_depth(self, clean: torch.Tensor, sensor: DepthSensor, env_ids, clocks, min_depth=None, max_depth=None,
+                    out: Optional[torch.Tensor] = None, invalid_out: Optional[torch.Tensor] = None, band_rows: int = 0):
+        """What the depth camera ``sensor`` makes of the clean frames ``clean`` (contiguous f32 [n,H,W] on the renderer's device,
+        as the ``cast_*`` methods write them): frame i belongs to environment ``env_ids[i]`` at sensor clock ``clocks[i]`` and to
+        a camera of the range ``min_depth[i]`` .. ``max_depth[i]`` (None = 0.5 / 5 m).  ONE launch on the current stream
+        (vlfm_depth_sensor), bit for bit synthetic.depth_sensor_numpy per frame; the frames' keys and ranges cross in one small
+        host-to-device copy.  Returns (frames f32 [n,H,W], invalid int32 [n]: the invalid pixels of each frame), both on the
+        device.  ``out`` / ``invalid_out``: tensors to write into; ``out`` must not share storage with ``clean`` (the edge stage
+        reads clean neighbours).  ``band_rows``: rows per workgroup (0: planned).  Everything is checked before the launch."""
+        dev = self.device
+        if not isinstance(sensor, DepthSensor):
+            raise ValueError("sense_depth: sensor must be a synthetic.DepthSensor")
+        if not isinstance(clean, torch.Tensor) or clean.dtype != torch.float32 or clean.dim() != 3 or \
+                tuple(clean.shape[1:]) != (self.H, self.W) or not clean.is_contiguous() or clean.device != dev:
+            raise ValueError(f"sense_depth: clean must be a contiguous f32 [n,{self.H},{self.W}] tensor on {dev}")
+        n = clean.shape[0]
+        if n > 65535:
+            raise ValueError("sense_depth: at most 65535 frames per call")
+        env_ids, clocks = np.asarray(env_ids).reshape(-1), np.asarray(clocks).reshape(-1)
+        if len(env_ids) != n or len(clocks) != n or (n > 0 and (env_ids.dtype.kind not in "iu" or clocks.dtype.kind not in "iu")):
+            raise ValueError("sense_depth: env_ids and clocks must hold one integer per frame")
+        rng = np.empty((n, 2), np.float32)
+        rng[:, 0] = MIN_DEPTH if min_depth is None else np.asarray(min_depth, np.float64)
+        rng[:, 1] = MAX_DEPTH if max_depth is None else np.asarray(max_depth, np.float64)
+        if not np.all(rng[:, 1] > rng[:, 0]):
+            raise ValueError("sense_depth: every camera needs max_depth > min_depth")
+        band_rows = int(band_rows)
+        if band_rows < 0:
+            raise ValueError("sense_depth: band_rows must not be negative")
+        if out is None:
+            out = torch.empty_like(clean)
+        elif not isinstance(out, torch.Tensor) or out.shape != clean.shape or out.dtype != torch.float32 or \
+                not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"sense_depth: out must be a contiguous f32 [{n},{self.H},{self.W}] tensor on {dev}")
+        elif out is clean or (n > 0 and out.untyped_storage().data_ptr() == clean.untyped_storage().data_ptr()):
+            raise ValueError("sense_depth: out must not share storage with clean (the edge stage reads clean neighbours)")
+        if invalid_out is None:
+            invalid_out = torch.empty((n,), dtype=torch.int32, device=dev)
+        elif not isinstance(invalid_out, torch.Tensor) or tuple(invalid_out.shape) != (n,) or invalid_out.dtype != torch.int32 or \
+                not invalid_out.is_contiguous() or invalid_out.device != dev:
+            raise ValueError(f"sense_depth: invalid_out must be a contiguous int32 [{n}] tensor on {dev}")
+        if n == 0:
+            return out, invalid_out
+        t_drop, t_patch = sensor.thresholds()
+        blob = np.concatenate([sensor.frame_keys(env_ids, clocks), rng.reshape(-1).view(np.uint32)]).view(np.int32)      # keys [n], ranges [n][2]
+        with torch.cuda.device(dev):
+            d_blob = torch.from_numpy(blob).to(dev)
+            p = d_blob.data_ptr()
+            _lib.check(_lib.lib().vlfm_depth_sensor(
+                clean.data_ptr(), out.data_ptr(), n, self.H, self.W, p, p + 4 * n, sensor.sigma0_m, sensor.sigma2_per_m,
+                sensor.disparity_k, t_drop, t_patch, sensor.edge_m, sensor.min_range_m, sensor.max_range_m,
+                invalid_out.data_ptr(), band_rows, torch.cuda.current_stream().cuda_stream), "depth_sensor")
+        return out, invalid_out
+
     def geodesic_fields(self, objects: np.ndarray, targets_boxes, success_distance: float,
                         max_sources: int = GEODESIC_MAX_SOURCES) -> GeodesicFields:
         """``geodesic_fields_worlds`` for the rooms world: every field stands in the renderer's own table."""
@@ -626,11 +681,15 @@ class LiveWorld:
     (``start_episodes`` / ``end_episodes``, scored in ``objectnav_stats``; ``objectnav_metrics``: also SPL, SoftSPL, geodesic
     distance -- ``geodesic``: "graph", the visibility graph over at most 141 rectangles (GeodesicFields), or "lattice", the
     metric lattice that also holds grid worlds (LatticeFields)); ``render_rgb``: the colour view too.  Every attribute exists
-    in every mode; what a mode does not use is None."""
+    in every mode; what a mode does not use is None.  ``depth_sensor``: a synthetic.DepthSensor between the ray caster and every
+    reader of ``frames`` (``clean_frames`` keeps the exact ranges)."""
 
     def __init__(self, renderer, env_ids, targets, world_objects: Optional[WorldObjects] = None, worlds=None,
-                 objectnav_metrics: bool = False, render_rgb: bool = False, geodesic: str = "graph") -> None:
+                 objectnav_metrics: bool = False, render_rgb: bool = False, geodesic: str = "graph",
+                 depth_sensor: Optional[DepthSensor] = None) -> None:
         self.renderer, self.env_ids, self.targets = renderer, list(env_ids), list(targets)
+        if depth_sensor is not None and not isinstance(depth_sensor, DepthSensor):
+            raise ValueError("depth_sensor must be a synthetic.DepthSensor")
         self.world_objects, self.worlds = world_objects, worlds
         self.objectnav_metrics, self.render_rgb = bool(objectnav_metrics), bool(render_rgb)
         check_geodesic_backend(geodesic, self.objectnav_metrics, worlds)
@@ -652,6 +711,10 @@ class LiveWorld:
         self.frames = self.ids = self.seen_stats = self.sightings = self.rgb = self.objects = self.object_classes = self.target_slot = None
         self.ep_index = self.ep_clock = self.ep_path = self.ep_first = self.objectnav_stats = None
         self.distance_to_goal = self.ep_geodesic = self.geodesic = None   # objectnav_metrics: now; at the episode's start; the fields
+        # depth_sensor: ``frames`` is what the depth camera makes of ``clean_frames``, the ray caster's (and painter's) output;
+        # ``sensor_clock`` [E]: the noted observations of each environment so far; ``sensor_invalid``: the last counts (device)
+        self.depth_sensor, self.clean_frames, self.sensor_invalid = depth_sensor, None, None
+        self.sensor_clock = None if depth_sensor is None else z(np.int64)
         if world_objects is not None:
             self.objects, self.sightings = np.zeros((E, WORLD_MAX_OBJECTS, 8)), []
             self.object_classes: List[List[str]] = [[] for _ in range(E)]
@@ -677,12 +740,18 @@ class LiveWorld:
         their classes, else mid grey).  ``tf``: what ``poses_tf()`` returns for the CURRENT poses, from a caller that already holds
         it (nothing checks that; None: computed here).  With objects it notes what the ray caster saw (``ids``, ``seen_stats``,
         ``sightings``: the one extra D2H copy of that mode); without, ``painter(t_ep, frames)`` paints scripted ones in.
-        ``fresh``: new buffers, nothing noted, no colours."""
+        ``fresh``: new buffers, nothing noted, no colours.  ``depth_sensor``: the ray caster (and the painter) write
+        ``clean_frames`` and the sensor -- one more launch -- writes ``frames``, which is what is returned; ids, statistics and
+        colours stay what the ray caster saw.  A noted observation advances ``sensor_clock``; a ``fresh`` one is sensed with the
+        clock the next noted one will use."""
         r, wo = self.renderer, self.world_objects
         tf = self.poses_tf()[1] if tf is None else tf
         if self.frames is None and not fresh:
             self.frames = torch.empty((self.E, r.H, r.W), dtype=torch.float32, device=r.device)
-        out = None if fresh else self.frames
+        sensor = self.depth_sensor
+        if sensor is not None and self.clean_frames is None and not fresh:
+            self.clean_frames = torch.empty((self.E, r.H, r.W), dtype=torch.float32, device=r.device)
+        out = None if fresh else (self.frames if sensor is None else self.clean_frames)
         objects, env_of = (None, None) if wo is None else (self.objects, np.arange(self.E))
         if self.render_rgb and not fresh:
             if self.rgb is None:
@@ -697,15 +766,25 @@ class LiveWorld:
             seen = r.cast_worlds(tf, self.table, self.world_of, objects, env_of, out=out)
             d, ids, stats = (seen, None, None) if wo is None else seen
         if wo is None:
-            return painter(t_ep, d) if painter is not None else d
-        if not fresh:
+            d = painter(t_ep, d) if painter is not None else d
+        elif not fresh:
             self.ids, self.seen_stats = ids, stats.cpu().numpy()
             self.sightings = sightings_from_stats(self.seen_stats, self.object_classes, wo.min_pixels, wo.confidence,
                                                   wo.faint_confidence)
             for (e, _, conf, _, k) in self.sightings:
                 if k == self.target_slot[e] and conf == wo.confidence and self.ep_first[e] < 0:
                     self.ep_first[e] = self.ep_clock[e]
-        return d
+        return d if sensor is None else self._sense(d, fresh)
+
+    def _sense(self, clean: torch.Tensor, fresh: bool) -> torch.Tensor:
+        """The depth camera's view of the ``clean`` frames of this observation (RoomsRenderer.sense_depth: one launch, nothing
+        read back): into ``frames`` and noted, or ``fresh``: new buffers at the clock the next noted observation will use."""
+        sensed, invalid = self.renderer.sense_depth(clean, self.depth_sensor, self.env_ids, self.sensor_clock,
+                                                    out=None if fresh else self.frames)
+        if not fresh:
+            self.clean_frames, self.sensor_invalid = clean, invalid
+            self.sensor_clock += 1
+        return sensed
 
     def advance(self, actions, ended) -> np.ndarray:
         """The step's ``actions`` [E] move the robots (synthetic.step_poses: refused by their worlds' walls and the objects'
@@ -820,6 +899,8 @@ class LiveWorld:
         """The robots return to their start poses; objects: running episodes end as timeouts, everybody starts the next."""
         self.xy, self.k = self.start_xy.copy(), self.start_k.copy()
         self.collided[:] = False
+        if self.sensor_clock is not None:
+            self.sensor_clock[:] = 0
         if self.world_objects is not None:
             running = np.flatnonzero(self.ep_clock > 0)
             for e in running:
