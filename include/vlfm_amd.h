@@ -1121,6 +1121,29 @@ int vlfm_depth_sensor(const float* d_clean, float* d_out, int n, int H, int W, c
                       float sigma0_m, float sigma2_per_m, float disparity_k, uint32_t drop_threshold, uint32_t patch_threshold,
                       float edge_m, float min_range_m, float max_range_m, int32_t* d_invalid, int band_rows, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Depth filter (ABI 28, csrc/depth_filter.hip): the holes of n depth frames (zeros, NaN, negatives) filled from the nearest valid
+ * pixels of their row and column, in two launches on `stream` (a row pass, a column pass) and the memset of the counts; bit for
+ * bit vlfm_amd.synthetic.depth_filter_numpy.  Values are only selected, never computed.  The rule is this project's own: it
+ * follows the contract of depth_camera_filtering.filter_depth ("fills zero pixels from valid neighbours, optionally restores
+ * originally non-zero pixels") and claims no arithmetic parity with that library, whose source is pinned nowhere.  Per pixel d:
+ *   positive   d > 0 (NaN, +0.0, -0.0 and negatives are not)
+ *   source     positive, and with clip_far > 0 not (d > clip_far): a value equal to clip_far stays a source
+ *   kept       recover_nonzero ? positive : source.  A kept pixel leaves with its input bits; every other pixel is a hole
+ *   candidate  per direction left, right, up, down: the value of the nearest source of d_in in that direction inside the frame,
+ *              if reach_px == 0 or it is at most reach_px steps away.  Candidates are input pixels: a fill never feeds a fill
+ *   hole       the maximum (fill == 0, "far") or minimum (fill == 1, "near") of its candidates; without one: set_black ?
+ *              black_value : 0.0f
+ * d_in, d_out: f32 [n][H][W]; they must not overlap.  d_counts: NULL, or int32 [n][2] that receives per frame the holes that had
+ * a candidate and the holes that had none (zeroed by a memset on `stream` first).  band_rows: rows per workgroup of the column
+ * pass, 0: planned by the library; the result is the same for every value.  With W % 4 == 0 and both planes 16-byte aligned a
+ * lane moves its four columns 16 bytes at a time; any other width or alignment takes scalar loads and stores.
+ * NULL planes with n > 0, n < 0 or n > 65535, H < 1, W < 1, H * W >= 2^31, band_rows < 0, fill not 0 or 1, reach_px outside
+ * [0, 65535], a negative or non-finite clip_far, a non-finite black_value, or overlapping planes: VLFM_ERR_INVALID, nothing
+ * launched, nothing written.  n == 0: VLFM_OK without a launch. */
+int vlfm_depth_filter(const float* d_in, float* d_out, int n, int H, int W, int fill, int reach_px, float clip_far,
+                      int recover_nonzero, int set_black, float black_value, int32_t* d_counts, int band_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

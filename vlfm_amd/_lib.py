@@ -13,7 +13,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlfm_amd.so")
-SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "qformer_attention.hip", "detect_ops.hip", "object_cloud.hip", "cloud_query.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "world_render.hip", "depth_sensor.hip", "geodesic.hip", "map_planner.hip", "lattice_geodesic.hip", "host.cpp"]
+SOURCES = ["value_map.hip", "depth_ingest.hip", "depth_holes.hip", "obstacle_map.hip", "vlm_ops.hip", "vit_attention.hip", "qformer_attention.hip", "detect_ops.hip", "object_cloud.hip", "cloud_query.hip", "gemm_f16.hip", "gemm_f32.hip", "conv_nhwc.hip", "sam_ops.hip", "map_render.hip", "jpeg_codec.hip", "jpeg_entropy.hip", "jpeg_decode.hip", "world_render.hip", "depth_sensor.hip", "depth_filter.hip", "geodesic.hip", "map_planner.hip", "lattice_geodesic.hip", "host.cpp"]
 
 VLFM_OK = 0
 VLFM_ERR_INVALID = -1
@@ -258,6 +258,7 @@ def lib() -> ctypes.CDLL:
         L.vlfm_lattice_query.argtypes = [vp, vp, ci, ci, vp, vp, ci, ci, ci, vp, vp]
         u32 = ctypes.c_uint32
         L.vlfm_depth_sensor.argtypes = [vp, vp, ci, ci, ci, vp, vp, cf, cf, cf, u32, u32, cf, cf, cf, vp, ci, vp]
+        L.vlfm_depth_filter.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, cf, vp, ci, vp]
         _lib = L
     return _lib
 

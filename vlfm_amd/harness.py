@@ -33,7 +33,7 @@ from . import _lib
 from .mapping.base_map import require_gpu
 from .mapping.value_map import ValueMapBatch
 from .synthetic import MAX_DEPTH, MIN_DEPTH, BangBangController, ReplayController, Trajectory, camera_intrinsics, depth_frame, \
-    ProceduralWorlds, pose_to_tf, rgb_frame, PLAN_INVALID, PLAN_OK, PLAN_TOO_LONG, PLAN_UNREACHABLE, GridWorlds, _mix32, DepthSensor  # noqa: F401
+    ProceduralWorlds, pose_to_tf, rgb_frame, PLAN_INVALID, PLAN_OK, PLAN_TOO_LONG, PLAN_UNREACHABLE, GridWorlds, _mix32, DepthSensor, DepthFilter  # noqa: F401
 from .worlds import GeodesicFields, LatticeFields, LiveWorld, RoomsRenderer, WorldObjects, WorldTable, check_geodesic_backend, \
     objectnav_outcome, sightings_from_stats  # noqa: F401  (the worlds' names stay importable from here)
 
@@ -196,7 +196,8 @@ class BatchedEpisodes:
                  controller=None, world_objects: Optional[WorldObjects] = None, batch_object_maps: bool = True,
                  device_object_clouds: bool = True, objectnav_metrics: bool = False,
                  worlds: Optional[Union[ProceduralWorlds, GridWorlds]] = None, render_rgb: bool = False,
-                 geodesic: str = "graph", depth_sensor: Optional[DepthSensor] = None) -> None:
+                 geodesic: str = "graph", depth_sensor: Optional[DepthSensor] = None,
+                 depth_filter: Optional[DepthFilter] = None) -> None:
         # text_prompt: "|"-separated prompts, one value-map channel each (itm_policy.py:50-54); exploration_thresh: ITMPolicyV3's
         # frontier rule over the two channels "target | exploration" (itm_policy.py:270-317).  Checked before the device is.
         self.env_ids = [env_offset + e for e in range(n_envs)]
@@ -281,6 +282,17 @@ class BatchedEpisodes:
         # depth_sensor: a synthetic.DepthSensor between the ray caster and everything that reads the step's depth frames (both
         # maps, the object clouds, PointNav, the planner): noise, quantisation and holes, one more launch per step
         # (RoomsRenderer.sense_depth); ``live.clean_frames`` keeps the exact ranges.  Off: every step is the step it was
+        # depth_filter: a synthetic.DepthFilter after the sensor (without one: after the ray caster) and before every reader: the
+        # holes are filled from the nearest valid pixels of their row and column, two more launches per step
+        # (RoomsRenderer.filter_depth); ``live.sensed_frames`` keeps what went in.  Off: every step is the step it was
+        self.depth_filter = depth_filter
+        if depth_filter is not None:
+            if not isinstance(depth_filter, DepthFilter):
+                raise ValueError("depth_filter must be a synthetic.DepthFilter")
+            if not self.closed_loop:
+                raise ValueError("depth_filter needs closed_loop=True: it filters the frames rendered from where the robot is")
+            if rig is not None:
+                raise ValueError("depth_filter filters the robot's own camera: it cannot be combined with a camera rig")
         self.depth_sensor = depth_sensor
         if depth_sensor is not None:
             if not isinstance(depth_sensor, DepthSensor):
@@ -293,7 +305,16 @@ class BatchedEpisodes:
 
             # isolated invalid pixels are one contour each for fill_small_holes, whose scratch holds HOLE_CAP_CONTOURS of them
             bound = ObstacleMapBatch.HOLE_CAP_CONTOURS / 2
-            if OBSTACLE_HOLE_AREA_THRESH != -1 and depth_sensor.dropout * height * width > bound:
+            if depth_filter is not None:
+                # a hole the filter leaves has no source within reach in any direction, so (reach_px >= 1) its four neighbours
+                # inside the frame are holes too: dropout alone leaves at most the pixels dropped together with all four
+                left = depth_sensor.dropout ** 5 * height * width
+                if OBSTACLE_HOLE_AREA_THRESH != -1 and left > bound:
+                    raise ValueError(f"depth_sensor with depth_filter: dropout**5 * height * width = {left:.0f} (the pixels dropped "
+                                     f"together with their four neighbours, all the filter can leave) exceeds "
+                                     f"ObstacleMapBatch.HOLE_CAP_CONTOURS / 2 = {bound:.0f} contours of the obstacle map's hole "
+                                     f"filling: at {width} x {height} dropout <= {(bound / (height * width)) ** 0.2:.3f}")
+            elif OBSTACLE_HOLE_AREA_THRESH != -1 and depth_sensor.dropout * height * width > bound:
                 raise ValueError(f"depth_sensor: dropout * height * width = {depth_sensor.dropout * height * width:.0f} exceeds "
                                  f"ObstacleMapBatch.HOLE_CAP_CONTOURS / 2 = {bound:.0f} contours of the obstacle map's hole filling: "
                                  f"at {width} x {height} dropout <= {bound / (height * width):.3f}")
@@ -362,7 +383,7 @@ class BatchedEpisodes:
             self.tf_table = np.stack([np.stack([pose_to_tf(x, y, yaw) for (x, y, yaw) in row]) for row in self.pose_table])
         # closed loop: the simulator -- where the robots are, their worlds, objects and episodes (worlds.LiveWorld); else None
         self.live = LiveWorld(self.rooms, self.env_ids, self.targets, world_objects, worlds, objectnav_metrics,
-                              render_rgb, geodesic, depth_sensor) if self.closed_loop else None
+                              render_rgb, geodesic, depth_sensor, depth_filter) if self.closed_loop else None
         self.last_poses = self.last_world_actions = None     # closed loop: the poses the last step observed from, its actions
         # of a controller with act_on_map (MapPlannerController): plans = ok + unreachable + too_long + invalid (off the map)
         self.planner_stats = {k: np.zeros(n_envs, np.int64) for k in ("plans", "ok", "unreachable", "too_long", "invalid")}

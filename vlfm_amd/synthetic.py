@@ -4,7 +4,7 @@ oracle are fed from here, so they see identical inputs)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -1708,3 +1708,100 @@ def depth_sensor_numpy(clean, lo, hi, sensor: DepthSensor, env_id: int, clock: i
             out = np.where(v < f(1e-3), f(1e-3), np.where(v > f(1.0), f(1.0), v))
         out = np.where(invalid, f(0.0), out).astype(np.float32)
     return out, int(invalid.sum())
+
+
+# ---------------------------------------------------------------------------------------------- depth filter
+# What stands between the depth camera and every reader of its frames: the holes (zeros, NaN, negatives) are filled from the
+# nearest valid pixels of their row and column.  `depth_filter_numpy` is the HOST STATEMENT of the rule; the device
+# (csrc/depth_filter.hip: vlfm_depth_filter, behind utils.depth_filter.filter_depth_batch / RoomsRenderer.filter_depth) matches
+# it bit for bit.  The rule is this project's own: it follows the contract of depth_camera_filtering.filter_depth as SURVEY B4
+# words it, and claims no arithmetic parity with that library, whose source is pinned nowhere.
+DEPTH_FILTER_MAX_REACH = 65535
+
+
+@dataclass(frozen=True)
+class DepthFilter:
+    """The hole filling of ``LiveWorld(depth_filter=...)`` / ``BatchedEpisodes(closed_loop=True, depth_filter=...)`` and of
+    ``utils.depth_filter.filter_depth_batch``.
+
+    ``fill``: a hole becomes the farthest ("far", the maximum) or the nearest ("near", the minimum) of its candidates -- the
+    nearest source pixel to its left, right, above and below.  ``reach_px``: a candidate counts only within that many steps (None:
+    no limit).  ``clip_far_thresh`` > 0: a value above it is no source.  ``recover_nonzero``: every positive input pixel keeps its
+    value (False: only the sources do; a clipped pixel becomes a hole).  ``set_black_value``: what a hole without a candidate
+    becomes (None: 0.0).  Refused here, before any device is touched: anything else."""
+    fill: str = "far"
+    reach_px: Optional[int] = None
+    clip_far_thresh: float = 0.0
+    recover_nonzero: bool = True
+    set_black_value: Optional[float] = None
+
+    def __post_init__(self) -> None:
+        if self.fill not in ("far", "near"):
+            raise ValueError('DepthFilter: fill must be "far" or "near"')
+        r = self.reach_px
+        if r is not None and (isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= r <= DEPTH_FILTER_MAX_REACH):
+            raise ValueError(f"DepthFilter: reach_px must be None or an integer in [1, {DEPTH_FILTER_MAX_REACH}]")
+        c = self.clip_far_thresh
+        if isinstance(c, bool) or not (isinstance(c, (int, float, np.integer, np.floating)) and np.isfinite(c) and c >= 0):
+            raise ValueError("DepthFilter: clip_far_thresh must be finite and not negative")
+        with np.errstate(over="ignore"):
+            if not np.isfinite(np.float32(c)):
+                raise ValueError("DepthFilter: clip_far_thresh does not fit an f32")
+        if not isinstance(self.recover_nonzero, (bool, np.bool_)):
+            raise ValueError("DepthFilter: recover_nonzero must be a bool")
+        b = self.set_black_value
+        if b is not None:
+            if isinstance(b, bool) or not (isinstance(b, (int, float, np.integer, np.floating)) and np.isfinite(b)):
+                raise ValueError("DepthFilter: set_black_value must be None or finite")
+            with np.errstate(over="ignore"):
+                if not np.isfinite(np.float32(b)):
+                    raise ValueError("DepthFilter: set_black_value does not fit an f32")
+
+
+def _nearest_source_before(frame: np.ndarray, src: np.ndarray, reach):
+    """Along axis 1, towards lower indices: (value of the nearest ``src`` pixel at or before each pixel, whether there is one
+    within ``reach`` steps).  Whole-array: a running maximum of the source indices."""
+    cols = np.arange(frame.shape[1], dtype=np.int64)[None, :]
+    last = np.maximum.accumulate(np.where(src, cols, -1), axis=1)
+    ok = last >= 0
+    if reach is not None:
+        ok &= cols - last <= int(reach)
+    return np.take_along_axis(frame, np.maximum(last, 0), axis=1), ok
+
+
+def depth_filter_numpy(frame, flt: DepthFilter):
+    """(f32 [H,W], filled, left): what ``flt`` makes of the frame ``frame`` [H,W].  Whole-array NumPy; values are only selected,
+    never computed, so nothing depends on rounding.
+
+      positive   pos = frame > 0 (NaN, +0.0, -0.0 and negatives are not)
+      sources    src = pos, and with clip_far_thresh > 0 also not (frame > f32(clip_far_thresh)): a value equal to it stays one
+      kept       keep = pos if recover_nonzero else src; a kept pixel leaves with its input bits, every other pixel is a hole
+      candidates per direction left, right, up, down: the value of the nearest src pixel in that direction inside the frame, if
+                 it is at most reach_px steps away (None: any distance).  They come from INPUT pixels only: a filled value never
+                 feeds another fill
+      fill       a hole with candidates becomes their maximum ("far") or minimum ("near"); one without becomes
+                 set_black_value, else 0.0f
+      counts     filled: the holes that had a candidate; left: those that had none (whatever they were then set to)"""
+    f = np.float32
+    d = np.ascontiguousarray(frame, np.float32)
+    if d.ndim != 2:
+        raise ValueError("depth_filter_numpy: frame must be [H,W]")
+    if not isinstance(flt, DepthFilter):
+        raise ValueError("depth_filter_numpy: flt must be a DepthFilter")
+    with np.errstate(invalid="ignore"):
+        pos = d > 0
+        src = pos & ~(d > f(flt.clip_far_thresh)) if flt.clip_far_thresh > 0 else pos
+    keep = pos if flt.recover_nonzero else src
+    far = flt.fill == "far"
+    best, has = np.zeros_like(d), np.zeros(d.shape, bool)
+    views = (lambda a: a, lambda a: a[:, ::-1], lambda a: a.T, lambda a: a.T[:, ::-1])      # left, right, up, down
+    for view in views:
+        val, ok = _nearest_source_before(view(d), view(src), flt.reach_px)
+        b, h = view(best), view(has)                                                        # (views: written through)
+        better = ok & (~h | ((val > b) if far else (val < b)))
+        b[better] = val[better]
+        h |= ok
+    hole = ~keep
+    black = f(0.0) if flt.set_black_value is None else f(flt.set_black_value)
+    out = np.where(keep, d, np.where(has, best, black)).astype(np.float32)
+    return out, int((hole & has).sum()), int((hole & ~has).sum())

@@ -13,7 +13,7 @@ from . import _lib
 from .synthetic import ACTION_FORWARD, ACTION_STOP, ACTION_TURN_LEFT, ACTION_TURN_RIGHT, BOXES, MAX_DEPTH, MIN_DEPTH, YAWS, \
     camera_intrinsics, integrate, GEODESIC_MAX_SOURCES, STEP_MARGIN, WORLD_MAX_BOXES, WORLD_MAX_OBJECTS, goal_viewpoints, \
     inflated_rects, object_layout, plan_actions, rect_distance, soft_spl, spl, step_poses, tf_of, OBJECT_COLOURS, WORLD_PALETTE, \
-    GRID_MAX_CELLS, GridPlan, LATTICE_MAX_COST, lattice_extent, lattice_sources, DepthSensor
+    GRID_MAX_CELLS, GridPlan, LATTICE_MAX_COST, lattice_extent, lattice_sources, DepthSensor, DepthFilter
 
 
 @dataclass(frozen=True)
@@ -461,6 +461,17 @@ class RoomsRenderer:
                 invalid_out.data_ptr(), band_rows, torch.cuda.current_stream().cuda_stream), "depth_sensor")
         return out, invalid_out
 
+    def filter_depth(self, frames: torch.Tensor, flt: DepthFilter, out: Optional[torch.Tensor] = None,
+                     counts_out: Optional[torch.Tensor] = None):
+        """The holes of ``frames`` (contiguous f32 [n,H,W] on the renderer's device) filled by ``flt``, a synthetic.DepthFilter:
+        utils.depth_filter.filter_depth_batch (vlfm_depth_filter: two launches on the current stream, nothing read back, bit for
+        bit synthetic.depth_filter_numpy per frame).  Returns (frames, counts int32 [n,2]: filled, left), both on the device."""
+        from .utils.depth_filter import filter_depth_batch
+
+        if not isinstance(frames, torch.Tensor) or frames.device != self.device or tuple(frames.shape[1:]) != (self.H, self.W):
+            raise ValueError(f"filter_depth: frames must be a contiguous f32 [n,{self.H},{self.W}] tensor on {self.device}")
+        return filter_depth_batch(frames, flt, out=out, counts_out=counts_out)
+
     def geodesic_fields(self, objects: np.ndarray, targets_boxes, success_distance: float,
                         max_sources: int = GEODESIC_MAX_SOURCES) -> GeodesicFields:
         """``geodesic_fields_worlds`` for the rooms world: every field stands in the renderer's own table."""
@@ -682,14 +693,17 @@ class LiveWorld:
     distance -- ``geodesic``: "graph", the visibility graph over at most 141 rectangles (GeodesicFields), or "lattice", the
     metric lattice that also holds grid worlds (LatticeFields)); ``render_rgb``: the colour view too.  Every attribute exists
     in every mode; what a mode does not use is None.  ``depth_sensor``: a synthetic.DepthSensor between the ray caster and every
-    reader of ``frames`` (``clean_frames`` keeps the exact ranges)."""
+    reader of ``frames`` (``clean_frames`` keeps the exact ranges).  ``depth_filter``: a synthetic.DepthFilter after the sensor (or,
+    without one, after the ray caster): ``frames`` is then the filter's output and ``sensed_frames`` its input."""
 
     def __init__(self, renderer, env_ids, targets, world_objects: Optional[WorldObjects] = None, worlds=None,
                  objectnav_metrics: bool = False, render_rgb: bool = False, geodesic: str = "graph",
-                 depth_sensor: Optional[DepthSensor] = None) -> None:
+                 depth_sensor: Optional[DepthSensor] = None, depth_filter: Optional[DepthFilter] = None) -> None:
         self.renderer, self.env_ids, self.targets = renderer, list(env_ids), list(targets)
         if depth_sensor is not None and not isinstance(depth_sensor, DepthSensor):
             raise ValueError("depth_sensor must be a synthetic.DepthSensor")
+        if depth_filter is not None and not isinstance(depth_filter, DepthFilter):
+            raise ValueError("depth_filter must be a synthetic.DepthFilter")
         self.world_objects, self.worlds = world_objects, worlds
         self.objectnav_metrics, self.render_rgb = bool(objectnav_metrics), bool(render_rgb)
         check_geodesic_backend(geodesic, self.objectnav_metrics, worlds)
@@ -715,6 +729,9 @@ class LiveWorld:
         # ``sensor_clock`` [E]: the noted observations of each environment so far; ``sensor_invalid``: the last counts (device)
         self.depth_sensor, self.clean_frames, self.sensor_invalid = depth_sensor, None, None
         self.sensor_clock = None if depth_sensor is None else z(np.int64)
+        # depth_filter: ``frames`` is what the filter makes of ``sensed_frames`` -- the sensor's output, or without a sensor the
+        # ray caster's (and painter's) --, a buffer the world keeps; ``filter_counts`` [E,2]: the last filled / left counts (device)
+        self.depth_filter, self.sensed_frames, self.filter_counts = depth_filter, None, None
         if world_objects is not None:
             self.objects, self.sightings = np.zeros((E, WORLD_MAX_OBJECTS, 8)), []
             self.object_classes: List[List[str]] = [[] for _ in range(E)]
@@ -743,15 +760,20 @@ class LiveWorld:
         ``fresh``: new buffers, nothing noted, no colours.  ``depth_sensor``: the ray caster (and the painter) write
         ``clean_frames`` and the sensor -- one more launch -- writes ``frames``, which is what is returned; ids, statistics and
         colours stay what the ray caster saw.  A noted observation advances ``sensor_clock``; a ``fresh`` one is sensed with the
-        clock the next noted one will use."""
+        clock the next noted one will use.  ``depth_filter``: last of all the filter -- two more launches -- fills the holes of
+        ``sensed_frames`` (the sensor's output, else the ray caster's and painter's) into ``frames``; ``fresh``: into new buffers."""
         r, wo = self.renderer, self.world_objects
         tf = self.poses_tf()[1] if tf is None else tf
         if self.frames is None and not fresh:
             self.frames = torch.empty((self.E, r.H, r.W), dtype=torch.float32, device=r.device)
-        sensor = self.depth_sensor
+        sensor, flt = self.depth_sensor, self.depth_filter
         if sensor is not None and self.clean_frames is None and not fresh:
             self.clean_frames = torch.empty((self.E, r.H, r.W), dtype=torch.float32, device=r.device)
+        if flt is not None and self.sensed_frames is None and not fresh:
+            self.sensed_frames = torch.empty((self.E, r.H, r.W), dtype=torch.float32, device=r.device)
         out = None if fresh else (self.frames if sensor is None else self.clean_frames)
+        if flt is not None and sensor is None and not fresh:
+            out = self.sensed_frames
         objects, env_of = (None, None) if wo is None else (self.objects, np.arange(self.E))
         if self.render_rgb and not fresh:
             if self.rgb is None:
@@ -774,17 +796,28 @@ class LiveWorld:
             for (e, _, conf, _, k) in self.sightings:
                 if k == self.target_slot[e] and conf == wo.confidence and self.ep_first[e] < 0:
                     self.ep_first[e] = self.ep_clock[e]
-        return d if sensor is None else self._sense(d, fresh)
+        d = d if sensor is None else self._sense(d, fresh)
+        return d if flt is None else self._filter(d, fresh)
 
     def _sense(self, clean: torch.Tensor, fresh: bool) -> torch.Tensor:
         """The depth camera's view of the ``clean`` frames of this observation (RoomsRenderer.sense_depth: one launch, nothing
-        read back): into ``frames`` and noted, or ``fresh``: new buffers at the clock the next noted observation will use."""
+        read back): into ``frames`` (with a ``depth_filter``: ``sensed_frames``) and noted, or ``fresh``: new buffers at the clock
+        the next noted observation will use."""
+        keep = self.frames if self.depth_filter is None else self.sensed_frames
         sensed, invalid = self.renderer.sense_depth(clean, self.depth_sensor, self.env_ids, self.sensor_clock,
-                                                    out=None if fresh else self.frames)
+                                                    out=None if fresh else keep)
         if not fresh:
             self.clean_frames, self.sensor_invalid = clean, invalid
             self.sensor_clock += 1
         return sensed
+
+    def _filter(self, sensed: torch.Tensor, fresh: bool) -> torch.Tensor:
+        """The holes of this observation's ``sensed`` frames filled (RoomsRenderer.filter_depth: two launches, nothing read back):
+        into ``frames`` and noted, or ``fresh``: new buffers, nothing noted."""
+        filled, counts = self.renderer.filter_depth(sensed, self.depth_filter, out=None if fresh else self.frames)
+        if not fresh:
+            self.sensed_frames, self.filter_counts = sensed, counts
+        return filled
 
     def advance(self, actions, ended) -> np.ndarray:
         """The step's ``actions`` [E] move the robots (synthetic.step_poses: refused by their worlds' walls and the objects'
