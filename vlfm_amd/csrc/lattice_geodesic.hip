@@ -11,11 +11,9 @@
 //
 // lattice_fields_kernel: one 1024-thread workgroup per field.  With integer costs the field is a sequence of level sets,
 //     L[d] = (straight(L[d-5]) | diagonal(L[d-7]) | knight(L[d-11])) & free & ~settled,
-// and on bit-packed rows a level is word shifts with carries from the neighbouring words, ANDs and ORs:
-//     straight     up | down | (a << 1 | left >> 31) | (a >> 1 | right << 31)
-//     diagonal     target (x, y), source (x - dx, y - dy): the source AND the side node (x - dx, y) are one AND of the source's
-//                  row of L[d-7] with the target's row of `free` BEFORE the shift, the side node (x, y - dy) one AND with the
-//                  source's row of `free` after it (map_planner.hip's form)
+// swept level by level in this kernel's loop; the straight and diagonal moves on bit-packed rows, the bands (here a ring of
+// sixteen, sweeps widened by two rows), the order of a level and why its one barrier is enough are stated once, in level_sets.h.
+// The knight moves are this file's own:
 //     knight 2s,t  source (x - 2s, y - t): both intermediate nodes stand in column x - s, in the source's and in the target's
 //                  row: shift by one, AND with both rows of `free`, shift by one more.  Two bits cross a word boundary: the
 //                  second shift's carry is the top (bottom) bit of the neighbouring word's intermediate, built from that word
@@ -27,10 +25,8 @@
 // stay in LDS while two planes fit (up to about 780 x 780; the rooms world's 449 x 449: 62 KB) and the ring goes to a per-field
 // global scratch (L2-resident): a word's first question -- has it an open bit -- is then answered without a trip to L2, and the
 // level loads go out together; beyond that all fourteen live in the scratch.  One template over the three layouts.
-// Bands: every level records the first and last row it set (LDS atomics, a ring of sixteen); level d sweeps only the rows of its
-// three source levels widened by two, plus the rows L[d-12] left in the slot it overwrites; a level whose three source levels
-// are empty only clears that slot.  One barrier per level.  The search ends after eleven empty levels in a row (nothing can
-// follow: every source level of every later level is among them) or past max_cost.
+// A level whose three source levels are empty only clears the slot it overwrites.  The search ends after eleven empty levels in
+// a row (level_sets.h) or past max_cost.
 // dist: uint16 [max_nb][max_na] per field in global memory, preset to 0xFFFF by a memset in front of the kernel; each node is
 // stored once, by the level that settles it, with ordinary vector stores.
 // lattice_query_kernel: one lane per point, four nodes each; f64, one rounding per operation (-ffp-contract=off).
@@ -38,23 +34,21 @@
 #include <stdint.h>
 
 #include "../../include/vlfm_amd.h"
+#include "level_sets.h"
 #include "profile.h"
 #include "status.h"
 #include "world_table.h"
 
 namespace vlfm {
 namespace lattice {
+using namespace levels;                 // (THREADS: the fields kernel's)
 
-constexpr int THREADS = 1024;           // fields kernel: 16 waves, the one workgroup a CU gets
 constexpr int SMALL_THREADS = 256;      // free and query kernels
 constexpr int PLANES = 14;              // free, open, twelve level planes
 constexpr int RING = 12;
-constexpr int HEADER_WORDS = 32;        // LDS in front of the planes: the band ring (lo[16], hi[16])
 constexpr int MAX_NODES = VLFM_LATTICE_MAX_NODES;
 constexpr int MAX_OBJECTS = 8;          // vlfm_amd.h: objects per environment
 constexpr int OBJ_REC = 8;              // doubles per object record: x0 y0 x1 y1 z0 z1 valid pad
-constexpr size_t LDS_BYTES_MAX = 160 * 1024;
-constexpr int NONE = 0x7FFFFFFF;
 
 // words of one plane that holds any lattice of at most max_nb x max_na nodes: the row's words and the two zero words, nb + 4 rows
 __host__ __device__ inline size_t plane_words(int max_nb, int max_na) {
@@ -151,19 +145,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void lattice_free_kernel(
 }
 
 // ---- fields -------------------------------------------------------------------------------------------------------------------
-// what the moves of one cost reach in the target word c (pitch P), before `& open`
-__device__ __forceinline__ unsigned straight_into(const unsigned* A, int c, int P) {
-    const unsigned a = A[c];
-    return A[c - P] | A[c + P] | (a << 1) | (A[c - 1] >> 31) | (a >> 1) | (A[c + 1] << 31);
-}
-
-// diagonals out of the source row at c + S (S = -P: the row above, +P: below), F the free plane
-__device__ __forceinline__ unsigned diagonal_into(const unsigned* B, const unsigned* F, int c, int S) {
-    const unsigned l = B[c + S - 1] & F[c - 1], m = B[c + S] & F[c], r = B[c + S + 1] & F[c + 1];
-    return ((m << 1) | (l >> 31) | (m >> 1) | (r << 31)) & F[c + S];
-}
-
-// knight moves (2s, t) out of the source row at c + S: two columns along the row
+// knight moves (2s, t) out of the source row at c + S (S = -P: the row above, +P: below): two columns along the row
 __device__ __forceinline__ unsigned knight_wide_into(const unsigned* C, const unsigned* F, int c, int S) {
     const unsigned cl = C[c + S - 1], cm = C[c + S], cr = C[c + S + 1];
     const unsigned gl = F[c + S - 1] & F[c - 1], gm = F[c + S] & F[c], gr = F[c + S + 1] & F[c + 1];
@@ -231,7 +213,7 @@ __global__ __launch_bounds__(THREADS) void lattice_fields_kernel(
     }
     __syncthreads();
 
-    // ---- levels.  Everything read at the top of level d was written before the barrier that ended level d - 1.
+    // ---- levels (the order of a level: level_sets.h)
     int run = 0, sd = 0;                            // empty levels in a row; d % 12
     for (int d = 1; d <= max_cost; ++d) {
         sd = sd == RING - 1 ? 0 : sd + 1;

@@ -4,19 +4,14 @@
 //
 // One 1024-thread workgroup per job.  With costs 2 (E/N/W/S) and 3 (diagonals) the field is a sequence of level sets,
 //     L[d] = (orthogonal step from L[d-2]  |  diagonal step from L[d-3])  &  free  &  not yet settled,
-// and on bit-packed rows a level is word shifts, ANDs and ORs:
-//     orthogonal   up | down | (a << 1 | left >> 31) | (a >> 1 | right << 31)            over the words of L[d-2]
-//     diagonal     target (x, y), source (x - dx, y - dy): the source AND the side cell (x - dx, y) are one AND of the source's
-//                  row of L[d-3] with the target's row of `free` BEFORE the shift; the side cell (x, y - dy) is one AND with
-//                  the source's row of `free` after it.  Shift-with-carry distributes over AND, so that is two ANDs per row.
+// swept level by level in this kernel's loop; the moves on bit-packed rows, the bands (here a ring of eight, sweeps widened by
+// one row), the order of a level and why its one barrier is enough are stated once, in level_sets.h.
 // Six planes per job: `free`, `open` (free and not yet settled) and a ring of four level planes -- level d writes slot d & 3
 // while it reads d - 2 and d - 3, and d - 1 must survive for the next level.  Each plane covers the job's window, word-aligned
 // to the map's words (no bit shifting on the way in), with one zero word left and right of every row and one zero row above and
 // below: no bounds test anywhere, in the sweep or in the descent.  The planes live in LDS when six planes of the call's
 // field_h x field_w bound fit 160 KB (a 400 x 400 window: 151 KB), else in a per-job global scratch (L2-resident); the code is
 // the same template over the two pointer kinds.
-// Bands: every level records the first and last row it set (LDS atomics, a ring of eight); level d sweeps only the rows of
-// L[d-2] and L[d-3] widened by one, plus the rows L[d-4] left in the slot it overwrites.  One barrier per level.
 // dist: a uint16 plane in global memory (the caller's field, else scratch), preset to 0xFFFF by a memset node in front of the
 // kernel; each cell is stored once, by the level that settles it.  The descent is a single-lane walk behind a release fence, a
 // workgroup barrier and an acquire fence.
@@ -27,18 +22,16 @@
 
 #include "../../include/vlfm_amd.h"
 #include "bitmap.h"
+#include "level_sets.h"
 #include "profile.h"
 #include "status.h"
 
 namespace vlfm {
 namespace planner {
+using namespace levels;
 
-constexpr int THREADS = 1024;
 constexpr int PLANES = 6;               // free, open, four level planes
-constexpr int HEADER_WORDS = 32;        // LDS in front of the planes: band ring (lo[8], hi[8]), the level that settled `start`
 constexpr int MAX_RADIUS = 4096;        // vlfm_amd.h: free radii
-constexpr size_t LDS_BYTES_MAX = 160 * 1024;
-constexpr int NONE = 0x7FFFFFFF;
 
 // words of one plane that holds any window of at most field_h x field_w cells: a run of w columns touches at most
 // (w + 30) / 32 + 1 words, plus the two zero words; field_h + 2 rows
@@ -126,7 +119,7 @@ __global__ __launch_bounds__(THREADS) void plan_paths_kernel(
     }
     __syncthreads();
 
-    // ---- levels.  Everything read at the top of level d was written before the barrier that ended level d - 1.
+    // ---- levels (the order of a level: level_sets.h)
     int too_long = 0;
     const int last = max_cost + 3;      // a cell beyond max_cost shows in one of the three levels after it
     for (int d = 1;; ++d) {
@@ -161,14 +154,7 @@ __global__ __launch_bounds__(THREADS) void plan_paths_kernel(
             const int c = (r + 1) * P + k + 1;
             unsigned out = 0u, u = 0u;
             if (r >= n0 && r <= n1 && (u = U[c]) != 0u) {
-                const unsigned a = A[c];
-                const unsigned orth = A[c - P] | A[c + P] | (a << 1) | (A[c - 1] >> 31) | (a >> 1) | (A[c + 1] << 31);
-                const unsigned fl = F[c - 1], fm = F[c], fr = F[c + 1];
-                const unsigned ul = B[c - P - 1] & fl, um = B[c - P] & fm, ur = B[c - P + 1] & fr;
-                const unsigned dl = B[c + P - 1] & fl, dm = B[c + P] & fm, dr = B[c + P + 1] & fr;
-                const unsigned from_up = ((um << 1) | (ul >> 31) | (um >> 1) | (ur << 31)) & F[c - P];
-                const unsigned from_dn = ((dm << 1) | (dl >> 31) | (dm >> 1) | (dr << 31)) & F[c + P];
-                out = (orth | from_up | from_dn) & u;
+                out = (straight_into(A, c, P) | diagonal_into(B, F, c, -P) | diagonal_into(B, F, c, P)) & u;
             }
             Ld[c] = out;
             if (out) {

@@ -1320,25 +1320,40 @@ def lattice_sources(points, cells_per_metre: int = 20) -> np.ndarray:
     return np.rint(np.asarray(points, np.float64).reshape(-1, 2) * float(_lattice_n(cells_per_metre))).astype(np.int64)
 
 
+def _through(dx: int, dy: int):
+    """The offsets, besides its two ends, of the cells the move (dx, dy) needs free: none for a straight move; for a diagonal the
+    two cells that share an edge with both ends; for a knight move the two intermediate nodes, next to the source and to the
+    target along the long axis."""
+    if dx == 0 or dy == 0:
+        return ()
+    if abs(dx) == abs(dy):
+        return ((dx, 0), (0, dy))
+    return ((dx // 2, 0), (dx // 2, dy)) if abs(dx) == 2 else ((0, dy // 2), (dx, dy // 2))
+
+
+def _move_masks(free, moves, through) -> np.ndarray:
+    """bool [len(moves), h, w]: may the move ``moves[k]`` = (dx, dy) leave cell [y, x] of ``free`` [h, w] -- both ends and the
+    cells at the offsets ``through[k]`` free, everything outside ``free`` blocked.  The one statement behind
+    lattice_move_masks and plan_allowed_moves."""
+    free = np.asarray(free, bool)
+    h, w = free.shape
+    pad = max(max(abs(dx), abs(dy)) for dx, dy in moves)
+    f = np.zeros((h + 2 * pad, w + 2 * pad), bool)
+    f[pad:pad + h, pad:pad + w] = free
+    at = lambda dx, dy: f[pad + dy:pad + dy + h, pad + dx:pad + dx + w]      # noqa: E731  free[y + dy, x + dx]
+    out = np.zeros((len(moves), h, w), bool)
+    for k, (dx, dy) in enumerate(moves):
+        out[k] = free & at(dx, dy)
+        for ox, oy in through[k]:
+            out[k] &= at(ox, oy)
+    return out
+
+
 def lattice_move_masks(free) -> np.ndarray:
     """bool [16, nb, na], in the order of LATTICE_MOVES: may the move leave node (b, a) (both ends and the intermediate nodes
     free, the target inside the lattice)."""
-    free = np.asarray(free, bool)
-    nb, na = free.shape
-    fp = np.zeros((nb + 4, na + 4), bool)
-    fp[2:-2, 2:-2] = free
-    at = lambda dx, dy: fp[2 + dy:2 + dy + nb, 2 + dx:2 + dx + na]      # noqa: E731  free at (a + dx, b + dy)
-    out = np.zeros((len(LATTICE_MOVES), nb, na), bool)
-    for k, (dx, dy, c) in enumerate(LATTICE_MOVES):
-        ok = free & at(dx, dy)
-        if c == 7:
-            ok = ok & at(dx, 0) & at(0, dy)
-        elif c == 11 and abs(dx) == 2:
-            ok = ok & at(dx // 2, 0) & at(dx // 2, dy)
-        elif c == 11:
-            ok = ok & at(0, dy // 2) & at(dx, dy // 2)
-        out[k] = ok
-    return out
+    steps = [(dx, dy) for dx, dy, _ in LATTICE_MOVES]
+    return _move_masks(free, steps, [_through(dx, dy) for dx, dy in steps])
 
 
 def lattice_field_numpy(free, sources, origin=(0, 0), max_cost: int = LATTICE_MAX_COST) -> np.ndarray:
@@ -1431,17 +1446,8 @@ def plan_jobs_array(jobs) -> np.ndarray:
 
 def plan_allowed_moves(free: np.ndarray) -> np.ndarray:
     """[8,h,w] bool: is the move with chain code s out of cell (x, y) = [s, y, x] of the window's ``free`` [h,w] allowed."""
-    h, w = free.shape
-    f = np.zeros((h + 2, w + 2), bool)              # everything outside the window is blocked
-    f[1:-1, 1:-1] = free
-    at = lambda dx, dy: f[1 + dy:1 + dy + h, 1 + dx:1 + dx + w]   # noqa: E731  free[y + dy, x + dx]
-    out = np.zeros((8, h, w), bool)
-    for s in range(8):
-        dx, dy = PLAN_CODE_DX[s], PLAN_CODE_DY[s]
-        out[s] = free & at(dx, dy)
-        if s & 1:                                   # a diagonal: the two cells that share an edge with both ends
-            out[s] &= at(dx, 0) & at(0, dy)
-    return out
+    steps = list(zip(PLAN_CODE_DX, PLAN_CODE_DY))
+    return _move_masks(free, steps, [_through(dx, dy) for dx, dy in steps])
 
 
 def plan_paths_numpy(free_or_navigable, jobs, lookahead: int = 15, max_cost: int = 65534):

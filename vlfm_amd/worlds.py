@@ -279,9 +279,7 @@ class RoomsRenderer:
         dev = self.device
         if table.device != dev:
             raise ValueError(f"{who}: the world table must live on {dev}")
-        world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
-        if len(world_of) != n or np.any((world_of < 0) | (world_of >= table.n_worlds)):
-            raise ValueError(f"{who}: world_of must name one world of the table per camera")
+        world_of = self._checked_world_of(who, table, world_of, n, "camera")
         ints = [world_of]
         with_grids = table.max_grid is not None
         if with_grids and rgb:
@@ -340,10 +338,7 @@ class RoomsRenderer:
                 d_blob = torch.from_numpy(blob).to(dev)
                 p = d_blob.data_ptr()
                 p_ints = p + 8 * (rec.size + objects.size)          # world_of [n], env_of [n], colours, palette
-                g_bits, g_edges, g_dims, g_ny, g_nx = None, None, None, 0, 0
-                if with_grids:
-                    g_bits, g_edges, g_dims = table.d_grid_bits.data_ptr(), table.d_grid_edges.data_ptr(), table.d_grid_dims.data_ptr()
-                    g_ny, g_nx = table.max_grid
+                g_bits, g_edges, g_dims, g_nx, g_ny = self._grid_pointers(table)
                 _lib.check(_lib.lib().vlfm_worlds_raycast_grids(
                     p, n, table.d_boxes.data_ptr(), table.d_counts.data_ptr(), table.n_worlds, table.max_boxes, p_ints,
                     p + 8 * rec.size if with_objects else None, p_ints + 4 * n if with_objects else None, len(objects),
@@ -352,6 +347,40 @@ class RoomsRenderer:
                     rgb_out.data_ptr() if rgb else None, g_bits, g_edges, g_dims, g_nx, g_ny,
                     torch.cuda.current_stream().cuda_stream), "worlds_raycast")
         return out, ids, stats, rgb_out
+
+    @staticmethod
+    def _checked_world_of(who: str, table: WorldTable, world_of, n: int, per: str) -> np.ndarray:
+        """int32 [n]: ``world_of`` as the library takes it, one world of ``table`` per ``per`` ("camera", "field")."""
+        world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
+        if len(world_of) != n or np.any((world_of < 0) | (world_of >= table.n_worlds)):
+            raise ValueError(f"{who}: world_of must name one world of the table per {per}")
+        return world_of
+
+    @staticmethod
+    def _grid_pointers(table: WorldTable):
+        """(d_grid_bits, d_grid_edges, d_grid_dims, max_nx, max_ny) as the library's grid arguments: NULLs and zeros for a
+        table without grids."""
+        if table.max_grid is None:
+            return None, None, None, 0, 0
+        g_ny, g_nx = table.max_grid
+        return table.d_grid_bits.data_ptr(), table.d_grid_edges.data_ptr(), table.d_grid_dims.data_ptr(), g_nx, g_ny
+
+    def _points_and_fields(self, who: str, handle, field_of, xy):
+        """(m, out, d_blob) of a ``*_distances`` call: the number of points ``xy`` [m,2], the empty f64 [m] answer on the device,
+        and -- for m > 0 -- the points followed by their int32 ``field_of`` (one field of ``handle``, or -1, each), sent in ONE
+        copy: the points at the buffer's address, field_of 16 * m bytes behind it."""
+        xy = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
+        m = len(xy)
+        field_of = np.ascontiguousarray(np.asarray(field_of).reshape(-1), np.int32)
+        if len(field_of) != m or np.any((field_of < -1) | (field_of >= handle.n)):
+            raise ValueError(f"{who}: field_of must name one field of the handle (or -1) per point")
+        out = torch.empty((m,), dtype=torch.float64, device=self.device)
+        if m == 0:
+            return m, out, None
+        with torch.cuda.device(self.device):
+            blob = np.concatenate([xy.reshape(-1), np.zeros((m + 1) // 2, np.float64)])
+            blob[2 * m:].view(np.int32)[:m] = field_of
+            return m, out, torch.from_numpy(blob).to(self.device)
 
     def _rooms_world_of(self, tf) -> np.ndarray:
         """The rooms world: every camera of ``tf`` stands in row 0 of the renderer's own table."""
@@ -496,9 +525,7 @@ class RoomsRenderer:
         dev = self.device
         if table.device != dev:
             raise ValueError(f"geodesic_fields_worlds: the world table must live on {dev}")
-        world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
-        if len(world_of) != n or np.any((world_of < 0) | (world_of >= table.n_worlds)):
-            raise ValueError("geodesic_fields_worlds: world_of must name one world of the table per field")
+        world_of = self._checked_world_of("geodesic_fields_worlds", table, world_of, n, "field")
         boxes = np.asarray(targets_boxes, np.float64).reshape(n, -1)[:, :4] if n else np.zeros((0, 4))
         # sources, their counts and world_of in one host buffer: [n][max_sources][2] doubles, then two int32 lists
         pad = (n + 1) // 2
@@ -537,19 +564,10 @@ class RoomsRenderer:
         """f64 [m] on the device: the geodesic distance to the goal of the points ``xy`` [m,2], point i in the field
         ``field_of[i]`` of ``handle`` (-1: no field, the answer is NaN), ONE launch on the current stream
         (vlfm_geodesic_query, bit for bit synthetic.geodesic_query_numpy).  inf: no way to the goal."""
-        xy = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
-        m = len(xy)
-        field_of = np.ascontiguousarray(np.asarray(field_of).reshape(-1), np.int32)
-        if len(field_of) != m or np.any((field_of < -1) | (field_of >= handle.n)):
-            raise ValueError("geodesic_distances: field_of must name one field of the handle (or -1) per point")
-        dev = self.device
-        out = torch.empty((m,), dtype=torch.float64, device=dev)
+        m, out, d_blob = self._points_and_fields("geodesic_distances", handle, field_of, xy)
         if m == 0:
             return out
-        with torch.cuda.device(dev):
-            blob = np.concatenate([xy.reshape(-1), np.zeros((m + 1) // 2, np.float64)])     # points and field_of: one copy
-            blob[2 * m:].view(np.int32)[:m] = field_of
-            d_blob = torch.from_numpy(blob).to(dev)
+        with torch.cuda.device(self.device):
             p = d_blob.data_ptr()
             stream = torch.cuda.current_stream().cuda_stream
             n_boxes = handle.rects.shape[1] - WORLD_MAX_OBJECTS     # the stride the handle was built with (walls + 8)
@@ -580,9 +598,7 @@ class RoomsRenderer:
             raise ValueError(f"lattice_fields_worlds: the world table must live on {dev}")
         if not 0 <= max_cost <= LATTICE_MAX_COST:
             raise ValueError(f"lattice_fields_worlds: max_cost in [0, {LATTICE_MAX_COST}]")
-        world_of = np.ascontiguousarray(np.asarray(world_of).reshape(-1), np.int32)
-        if len(world_of) != n or np.any((world_of < 0) | (world_of >= table.n_worlds)):
-            raise ValueError("lattice_fields_worlds: world_of must name one world of the table per field")
+        world_of = self._checked_world_of("lattice_fields_worlds", table, world_of, n, "field")
         boxes = np.asarray(targets_boxes, np.float64).reshape(n, -1)[:, :4] if n else np.zeros((0, 4))
         # source nodes [n][max_sources][2], counts [n], dims [n][4], world_of [n]: one int32 buffer
         blob = np.zeros(n * (2 * max_sources + 6), np.int32)
@@ -612,10 +628,7 @@ class RoomsRenderer:
             p = d_blob.data_ptr()
             p_cnt, p_dims, p_world = p + 8 * n * max_sources, p + 8 * n * max_sources + 4 * n, p + 8 * n * max_sources + 20 * n
             h.dims.copy_(d_blob[2 * n * max_sources + n:][:4 * n].view(n, 4))
-            g_bits, g_edges, g_dims, g_ny, g_nx = None, None, None, 0, 0
-            if table.max_grid is not None:
-                g_bits, g_edges, g_dims = table.d_grid_bits.data_ptr(), table.d_grid_edges.data_ptr(), table.d_grid_dims.data_ptr()
-                g_ny, g_nx = table.max_grid
+            g_bits, g_edges, g_dims, g_nx, g_ny = self._grid_pointers(table)
             stream = torch.cuda.current_stream().cuda_stream
             _lib.check(L.vlfm_lattice_free(table.d_boxes.data_ptr(), table.d_counts.data_ptr(), table.n_worlds, table.max_boxes,
                                            g_bits, g_edges, g_dims, g_nx, g_ny, p_world, STEP_MARGIN, d_obj.data_ptr(), p_dims, n,
@@ -642,19 +655,10 @@ class RoomsRenderer:
         """f64 [m] on the device: the lattice geodesic distance to the goal of the points ``xy`` [m,2], point i in the field
         ``field_of[i]`` of ``handle`` (-1: no field, the answer is NaN), ONE launch on the current stream (vlfm_lattice_query,
         bit for bit synthetic.lattice_query_numpy).  inf: no way to the goal."""
-        xy = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
-        m = len(xy)
-        field_of = np.ascontiguousarray(np.asarray(field_of).reshape(-1), np.int32)
-        if len(field_of) != m or np.any((field_of < -1) | (field_of >= handle.n)):
-            raise ValueError("lattice_distances: field_of must name one field of the handle (or -1) per point")
-        dev = self.device
-        out = torch.empty((m,), dtype=torch.float64, device=dev)
+        m, out, d_blob = self._points_and_fields("lattice_distances", handle, field_of, xy)
         if m == 0:
             return out
-        with torch.cuda.device(dev):
-            blob = np.concatenate([xy.reshape(-1), np.zeros((m + 1) // 2, np.float64)])     # points and field_of: one copy
-            blob[2 * m:].view(np.int32)[:m] = field_of
-            d_blob = torch.from_numpy(blob).to(dev)
+        with torch.cuda.device(self.device):
             p = d_blob.data_ptr()
             max_nb, max_na = handle.dist.shape[1:]
             _lib.check(_lib.lib().vlfm_lattice_query(p, p + 16 * m, m, handle.n, handle.dist.data_ptr(), handle.dims.data_ptr(),
